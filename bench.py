@@ -3,18 +3,26 @@
 the configuration BASELINE.json's metric is quoted on -- configs[2]: N = 65 536 particles, T = 3000, m = 512 basis
 functions (nLin = 515), fp64 -- plus the smoother wall-clock of the same configuration.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one time step of particleFilter (src/particleFilter.m:100-218) over all particles: resample-gather,
 dynModel, measModel, importance weights, normalisation and the Kalman map update.  `value` = particle-steps/s over the K
 timed steps with all inputs resident in HBM.  The total particle count is fixed ("scaling": "strong"): --gpus N shards
-the 65 536 particles over N ranks (multigpu.ShardedFilterSession).  One JSON line is printed by rank 0.
+the 65 536 particles over N ranks (multigpu.ShardedFilterSession).  One JSON line is printed by rank 0.  When K + W
+exceed --T, the synthetic trajectory is generated with T = K + W time steps, so that K steps are always timed.
+
+A plain run measures the headline and nothing else: set-up, W warm-up steps, the K timed steps, the roofline of those
+steps (HIP events inside the library), the outputs if --dump-outputs is given, the line.  --full adds every other leg:
+the HBM counter passes, the smoothers, the other configurations, the complete T-step filter run, the CPU baseline and,
+with --gpus N, the synchronised diagnostic pass and the sharded smoothers.  --dump-outputs DIR writes what the timed run
+returns as of its last step (the reference's outputs of particleFilter.m:220-233 and the final particle states; a fixed,
+seeded sample of the particles' linear states) as DIR/<name>.npy in float64.
 
 roofline: `achieved` = bytes the run's schedule has to move per launch of the step kernel (rbpf_timing
 .scheduled_bytes_per_launch: the stored covariance is read every step and rewritten every lazy_depth-th step) / mean launch
 time from HIP events on the library's stream; `frac` = achieved / 8 TB/s (<= 1 by construction).  The ratio against
 SURVEY 8(d)'s full read + write per step is reported separately as `algorithmic_GBps` / `algorithmic_ratio` (it exceeds
-the HBM peak when the lazy update elides writes, so it is not a roofline fraction).  `traffic` is measured in THIS run:
+the HBM peak when the lazy update elides writes, so it is not a roofline fraction).  `traffic` is measured in THIS run (--full):
 two child runs of the same workload under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, FETCH x2 on
 gfx950 per MI355X_MICROARCH.md), null when rocprofv3 is unavailable.  See DESIGN.md "Measurement".
 """
@@ -37,6 +45,11 @@ sys.path.insert(0, ROOT)
 
 THETA_MAG = [650.0, 1.2, 200.0, 10.0]                       # examples/slam-dense-mag/main.m:23
 HBM_PEAK_GBPS = 8000.0                                       # MI355X_MICROARCH.md: HBM3E 8 TB/s
+# --dump-outputs: the outputs fetched after the timed steps (one GPU / sharded), the particles of final_xl kept, the size cap
+DUMP_WANT = ("traj_max", "traj_mean", "traj_sample_iwmax", "xl_max", "xl_mean", "P_max", "P_mean", "final_xn", "final_xl")
+DUMP_WANT_SHARDED = ("traj_max", "traj_mean", "xl_max", "xl_mean", "P_max", "P_mean")
+DUMP_XL_PARTICLES = 2048
+DUMP_MAX_BYTES = 64 << 20
 
 
 def q_mag():
@@ -111,10 +124,11 @@ def roofline_of(tm, storage="fp64"):
                     "symmetric storage, the lazy update and the shared reads all elide bytes)"}
 
 
-def filter_leg(pkg, datagen, N, m, T, K, W, seed, lazy_depth, inplace, storage, keep_history=True):
+def filter_leg(pkg, datagen, N, m, T, K, W, seed, lazy_depth, inplace, storage, keep_history=True, want=None):
     """One single-GPU filter run: W warm-up steps, K timed steps.  keep_history: the state history and the ancestor table
     (particleFilter.m:117-118,233: xn_traj / traj_sample_iwmax) are written inside the timed steps, so the run could return the
-    reference's full output set."""
+    reference's full output set.  want: the outputs to fetch after the timed steps (default: the two the finiteness check
+    reads).  Returns (result, data, model, x0_lin, P0, R, covariance banks the library chose, outputs)."""
     import numpy as np
     Q = q_mag()
     data = datagen.bean_6D(T, Q, THETA_MAG, 0.01, seed=seed)
@@ -130,13 +144,37 @@ def filter_leg(pkg, datagen, N, m, T, K, W, seed, lazy_depth, inplace, storage, 
         sess.sync()
         dt_s = time.perf_counter() - t0
         tm = sess.timing(reset=True)
-        chk = sess.finish(want=("traj_mean", "traj_sample_iwmax") if keep_history else ("traj_mean",))
+        banks = sess.banks
+        chk = sess.finish(want=want or (("traj_mean", "traj_sample_iwmax") if keep_history else ("traj_mean",)))
     if not np.all(np.isfinite(chk["traj_mean"][:, :W + K])):
         raise RuntimeError("non-finite filter output")
     if keep_history and not np.all(np.isfinite(chk["traj_sample_iwmax"][:, :W + K])):
         raise RuntimeError("non-finite back-traced trajectory")
     return {"value": N * K / dt_s, "unit": "particle-steps/s", "steps": K, "warmup": W, "ms_per_step": dt_s / K * 1e3,
-            "roofline": roofline_of(tm, storage)}, data, model, x0_lin, P0, R
+            "roofline": roofline_of(tm, storage)}, data, model, x0_lin, P0, R, banks, chk
+
+
+def dump_outputs(out_dir, outs, t_done):
+    """--dump-outputs: every array of `outs` (FilterSession / ShardedFilterSession.finish) as out_dir/<name>.npy in float64.
+    Trajectories are cut to the t_done steps that ran; final_xl [nLin x N] keeps DUMP_XL_PARTICLES particles drawn with a
+    fixed seed (final_xl_particles.npy holds their indices)."""
+    import numpy as np
+    arrays = {}
+    for k, v in outs.items():
+        a = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        if k.startswith("traj_"):
+            a = a[:, :t_done]
+        if k == "final_xl" and a.shape[1] > DUMP_XL_PARTICLES:
+            idx = np.sort(np.random.RandomState(0).choice(a.shape[1], DUMP_XL_PARTICLES, replace=False))
+            a = a[:, idx]
+            arrays["final_xl_particles"] = idx.astype(np.float64)
+        arrays[k] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def bank_bytes_per_particle(n, storage):
@@ -552,7 +590,11 @@ def main():
     ap.add_argument("--particles", type=int, default=65536, help="particles: the total (strong scaling) or per GPU (--scaling weak)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"])
     ap.add_argument("--m", type=int, default=512)
-    ap.add_argument("--T", type=int, default=3000)
+    ap.add_argument("--T", type=int, default=3000, help="time steps of the synthetic trajectory (raised to --steps + --warmup when they exceed it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed run computed (its outputs as of the last timed step) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also run every leg besides the headline (counter passes, smoothers, other configurations, "
+                    "complete filter run, CPU baseline; with --gpus N the diagnostic pass and the sharded smoothers); the --no-* options switch "
+                    "single legs of it off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-smoother", action="store_true", help="skip every smoother leg")
     ap.add_argument("--no-smoother-full", action="store_true", help="skip the complete T=3000 smoother run of the per-GPU share (about a minute)")
@@ -598,12 +640,13 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run")
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU: the RBPF path has no CPU fallback")
-    torch.cuda.set_device(local_rank)
-    dist = None
+    dist = torch = None
     sharded = world > 1 or args.force_sharded
+    if sharded:                                # torch carries the process group; a single process needs the library alone
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a GPU: the RBPF path has no CPU fallback")
+        torch.cuda.set_device(local_rank)
     # RCCL prints a version banner to STDOUT when its first communicator comes up; the contract is ONE JSON line on stdout, so the
     # process's stdout (file descriptor 1) points at stderr until that line is printed
     saved_stdout = None
@@ -625,9 +668,10 @@ def main():
 
     pkg = importlib.import_module("rao-blackwellized-slam-smoothing_amd")
     datagen = importlib.import_module("rao-blackwellized-slam-smoothing_amd.datagen")
+    if pkg.device_count() < 1:
+        raise SystemExit("bench.py needs a GPU: the RBPF path has no CPU fallback")
+    args.T = max(args.T, args.steps + args.warmup)             # the counter passes' child runs read args.T too
     K, W, T = args.steps, args.warmup, args.T
-    if K + W > T:
-        raise SystemExit(f"--steps + --warmup must be <= T={T}")
     if args.scaling == "strong":
         if args.particles % world:
             raise SystemExit("--particles must be a multiple of --gpus")
@@ -637,6 +681,8 @@ def main():
     Q = q_mag()
 
     def barrier():
+        if torch is None:                                      # one process: every leg ends in a device synchronisation of its own
+            return
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -664,41 +710,42 @@ def main():
         tt = torch.tensor([dt_s], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt_s = float(tt.item())
-        chk = sess.finish(want=("traj_mean",))
+        chk = sess.finish(want=DUMP_WANT_SHARDED if args.dump_outputs else ("traj_mean",))
         if not np.all(np.isfinite(chk["traj_mean"][:, :W + K])):
             raise SystemExit("non-finite filter output")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, chk, W + K)
         shard_stats = dict(getattr(sess, "stats", None) or {})
         shard_stats.pop("phase_s", None)                  # host enqueue times only: the timed run has one sync per step
         sess.close()
-        # diagnostic pass (not timed into `value`): the same steps with a stream synchronisation after every phase, so that
-        # the first multi-GPU run shows where a step's time goes (gather / normalise+plan / exchange / step kernel)
-        diag_steps = min(24, K)
-        try:
-            sess = mg.ShardedFilterSession(model, data["dx"], data["y"], data["initState"], x0_lin, P0, Q, R,
-                                           N_local, 0.01, rng=pkg.PhiloxRNG(args.seed), rank=rank, world=world,
-                                           lazy_depth=args.lazy_depth, storage=args.storage, sync_phases=True, force_collectives=(world == 1))
-            sess.advance(6)
-            sess.sync()
-            sess.stats["phase_s"] = dict(gather=0.0, normalise=0.0, plan=0.0, exchange=0.0, step=0.0)
-            sess.stats["steps"] = 0
-            barrier()
-            sess.advance(diag_steps)
-            sess.sync()
-            ph = sess.stats.get("phase_s", {})
-            shard_stats["phase_ms_per_step_synchronised"] = {k: round(v / max(diag_steps, 1) * 1e3, 4) for k, v in ph.items()}
-            sess.close()
-        except Exception as exc:                                   # the diagnostic must never cost the measurement
-            shard_stats["phase_ms_per_step_synchronised"] = {"error": f"{type(exc).__name__}: {exc}"}
+        if args.full:
+            # diagnostic pass (not timed into `value`): the same steps with a stream synchronisation after every phase, so that
+            # the first multi-GPU run shows where a step's time goes (gather / normalise+plan / exchange / step kernel)
+            diag_steps = min(24, K)
+            try:
+                sess = mg.ShardedFilterSession(model, data["dx"], data["y"], data["initState"], x0_lin, P0, Q, R,
+                                               N_local, 0.01, rng=pkg.PhiloxRNG(args.seed), rank=rank, world=world,
+                                               lazy_depth=args.lazy_depth, storage=args.storage, sync_phases=True, force_collectives=(world == 1))
+                sess.advance(6)
+                sess.sync()
+                sess.stats["phase_s"] = dict(gather=0.0, normalise=0.0, plan=0.0, exchange=0.0, step=0.0)
+                sess.stats["steps"] = 0
+                barrier()
+                sess.advance(diag_steps)
+                sess.sync()
+                ph = sess.stats.get("phase_s", {})
+                shard_stats["phase_ms_per_step_synchronised"] = {k: round(v / max(diag_steps, 1) * 1e3, 4) for k, v in ph.items()}
+                sess.close()
+            except Exception as exc:                                   # the diagnostic must never cost the measurement
+                shard_stats["phase_ms_per_step_synchronised"] = {"error": f"{type(exc).__name__}: {exc}"}
         head = {"value": N_total * K / dt_s, "ms_per_step": dt_s / K * 1e3, "roofline": roofline_of(tm, args.storage)}
         single_bank = False
     else:
-        barrier()
-        head, data, model, x0_lin, P0, R = filter_leg(pkg, datagen, N_local, args.m, T, K, W, args.seed, args.lazy_depth,
-                                                     args.inplace, args.storage)
-        _free_b, tot_b = torch.cuda.mem_get_info()
-        n_ = model.nLin
-        single_bank = args.inplace > 0 or (args.inplace == 0 and args.lazy_depth >= 2 and
-                                           2.0 * N_local * bank_bytes_per_particle(n_, args.storage) > 0.85 * tot_b)
+        head, data, model, x0_lin, P0, R, banks, outs = filter_leg(pkg, datagen, N_local, args.m, T, K, W, args.seed, args.lazy_depth,
+                                                                   args.inplace, args.storage, want=DUMP_WANT if args.dump_outputs else None)
+        single_bank = banks == 1
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outs, W + K)
 
     inlib = None
     if args.driver == "inlib":
@@ -738,8 +785,8 @@ def main():
             line["config"]["sharding"] = shard_stats
         if inlib is not None:
             line["inlib_driver"] = inlib
-        solo = world == 1 and not args.force_sharded
-        if solo and not args.no_traffic:
+        full_solo = args.full and world == 1 and not args.force_sharded          # the legs of --full on one GPU
+        if full_solo and not args.no_traffic:
             tr, why = measure_traffic(args, args.lazy_depth)
             if tr:
                 line["roofline"]["traffic"] = tr["bytes_per_launch"]
@@ -749,7 +796,7 @@ def main():
                 line["roofline"]["frac_hbm_counters"] = line["roofline"]["hbm_counter_GBps"] / HBM_PEAK_GBPS
             else:
                 line["roofline"]["traffic_note"] = why
-        if solo and not args.no_smoother:
+        if full_solo and not args.no_smoother:
             sm = {"reference_size": guarded(smoother_reference_size, pkg, datagen),
                   "kernel_roofline_in_smoother": guarded(smoother_kernel_in_smoother, args),
                   "kernel_roofline": guarded(smoother_kernel_roofline, pkg),
@@ -778,7 +825,7 @@ def main():
             if not args.no_large:
                 sm["radio_N65536"] = guarded(smoother_radio_large, pkg, datagen)
             line["smoother"] = sm
-        if solo and not args.no_large:
+        if full_solo and not args.no_large:
             def extra(N, m, Kx, Wx, lazy, storage):
                 r, *_ = filter_leg(pkg, datagen, N, m, 3000, Kx, Wx, args.seed, lazy, 0, storage)
                 r["workload"] = workload_string(N, 3000, m, m + 3, storage, lazy, 1, 2.0 * N * bank_bytes_per_particle(m + 3, storage) > 0.85 * 288e9)
@@ -797,17 +844,17 @@ def main():
             # full-square fp32 storage it replaces
             line["configs4_share_filter"] = guarded(extra, 32768, 1024, 32, 4, 4, "fp32sym")
             line["configs4_share_filter_full_square"] = guarded(extra, 32768, 1024, 30, 4, 2, "fp32")
-        if solo and not args.no_filter_full:
+        if full_solo and not args.no_filter_full:
             line["filter_full_T"] = guarded(lambda: filter_full_run(pkg, datagen, N_local, args.m, T, args.seed, args.lazy_depth, args.inplace, args.storage))
             if "seconds" in line["filter_full_T"]:
                 line["filter_full_T_s"] = line["filter_full_T"]["seconds"]
-        if solo and not args.no_smoother and not args.no_smoother_full and args.smoother_32k:
+        if full_solo and not args.no_smoother and not args.no_smoother_full and args.smoother_32k:
             sm_storage = args.storage if args.storage in ("fp64", "fp64sym") and args.m == 512 else "fp64"
             r32 = guarded(lambda: smoother_share_full(pkg, datagen, 32768, 3000, 512, 2, args.seed, lazy_depth=3, storage=sm_storage))
             line["smoother"]["N32768_library_defaults"] = r32
             if "seconds" in r32:
                 line["smoother_wall_clock_N32768_defaults_s"] = r32["seconds"]
-        if solo and not args.no_smoother and not args.no_smoother_full and not args.no_smoother_largest:
+        if full_solo and not args.no_smoother and not args.no_smoother_full and not args.no_smoother_largest:
             # THE METRIC'S FULL SMOOTHER ON ONE GPU: N_P = 65 536, T = 3000, m = 512, N_K = 2.  What makes it fit (r05): the carried factors need
             # no information matrix once they are never refactorised (chol_refresh >= N_T: 2999 sweeps on end; ancestor probabilities 1.5e-9
             # from the from-scratch arithmetic at N_P = 8192 over T = 3000, every index identical: profiles/r05_refresh_free_vs_fresh_*.jsonl),
@@ -825,7 +872,7 @@ def main():
                 if "seconds" in r64:
                     line["smoother_wall_clock_N65536_1gpu_s"] = r64["seconds"]
                     line["smoother_wall_clock_N65536_1gpu_workload"] = r64["workload"] + ", lazy_depth 3"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(pkg, data, model, x0_lin, P0, R, args.m)
             except Exception as exc:                                  # report, never hide
@@ -833,7 +880,7 @@ def main():
                                         "sample": f"failed: {exc}"}
     else:
         line = None
-    if sharded and not args.no_smoother:
+    if sharded and args.full and not args.no_smoother:
         # The smoother as the N-GPU job runs it.  Every rank takes part (collectives), so the leg runs under a watchdog: if it
         # does not come back in time, rank 0 prints the line it already has (the filter measurement) and every rank leaves.
         import threading

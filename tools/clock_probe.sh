@@ -1,7 +1,7 @@
 #!/bin/bash
 # Shader / memory clocks and power while the complete T = 3000 filter run of the headline configuration is in flight (sampled every 2 s).
 # Run on the GPU box:  bash tools/clock_probe.sh > gpurun_out/clock_probe.txt
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-smoother --no-large --no-traffic > /tmp/clk_bench.json 2> /tmp/clk_bench.err &
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-smoother --no-large --no-traffic > /tmp/clk_bench.json 2> /tmp/clk_bench.err &
 BP=$!
 for i in $(seq 1 30); do
   sleep 2
