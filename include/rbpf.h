@@ -176,8 +176,9 @@ typedef struct {
                           * -1: off.  On block-lower storage (eight / sixteen tile rows) the single bank keeps   *
                           * the shared flush: one writer per parent with children, the first writer of a stored  *
                           * matrix overwrites it in place after its readers (results to rounding, as two banks). */
-  int32_t storage;       /* dense-mag filter (also sharded): 0 = the covariance banks hold fp64 (the reference's precision); 1 = fp32     *
-                          * STORAGE of the banks (BASELINE.json configs[4]): half the HBM traffic and memory, all     *
+  int32_t storage;       /* 0 = the covariance banks hold fp64 (the reference's precision); 1 = fp32 STORAGE of the banks, for the  *
+                          * filter of a dense model with n_y = 3 (dense-mag, also sharded, or a generic model;       *
+                          * BASELINE.json configs[4]): half the HBM traffic and memory, all                          *
                           * arithmetic and every other state stay fp64.  Results then agree with the fp64 run to     *
                           * ~1e-6 relative per step (not to 1e-9) and resampling indices may differ.                 *
                           * 2 = fp64, SYMMETRIC storage: particleFilter.m:198 keeps P_i symmetric up to rounding, so only the   *
@@ -185,13 +186,15 @@ typedef struct {
                           * 515, i.e. 0.56 x the HBM traffic and memory of storage 0; read-only steps of lazy_depth apply the  *
                           * pending sets as P H' - KS (K' H') instead of element-wise.  Same algebra: results within 1e-9 of  *
                           * storage 0 (P(r,c) and P(c,r), which differ by rounding in the reference's plain form, are one     *
-                          * stored value).  Dense families with n_y = 3 and 515 <= n_lin <= 639 (BASELINE.json configs[2]) or      *
-                          * 259 <= n_lin <= 383: filter and both smoothers, single-GPU and sharded; 1024 <= n_lin <= 1151       *
-                          * (sixteen tile rows, BASELINE.json configs[4]'s basis size): the filter; dense-radio (n_y = 1) with   *
-                          * n_lin = 128 (two tile rows: 0.75 x the bytes): filter and both smoothers; RBPF_ERR_UNSUPPORTED       *
+                          * stored value).  Dense models with n_y = 3 and 512 <= n_lin <= 639 (BASELINE.json configs[2]) or      *
+                          * 256 <= n_lin <= 383: filter and both smoothers, single-GPU and sharded (generic models: single-GPU); *
+                          * 1024 <= n_lin <= 1151 (sixteen tile rows, BASELINE.json configs[4]'s basis size): the filter; n_y = 1 *
+                          * with n_lin = 128 (dense-radio; two tile rows: 0.75 x the bytes): filter and both smoothers.  The     *
+                          * generic (host-callback) family takes the same sizes as the built-in ones.  RBPF_ERR_UNSUPPORTED      *
                           * elsewhere.                                                                                          *
                           * 3 = fp32 tiles of the lower block triangle (storage 1's rounding on storage 2's layout: 0.28 x the   *
-                          * bytes of storage 0): the filter with 515 <= n_lin <= 639 or 1027 <= n_lin <= 1151, lazy_depth <= 4.  */
+                          * bytes of storage 0): the filter with n_y = 3 and 512 <= n_lin <= 639 or 1024 <= n_lin <= 1151,      *
+                          * lazy_depth <= 4.                                                                                    */
   int32_t chol_variant;  /* smoothers: kernel of the ancestor-weight factorisation (particleSmoother.m:221,                   *
                           * particleSmootherInformationForm.m:228).  0: by matrix size (default); 16 / 64 / 648 / 644 / 1 /             *
                           * (a non-zero value with chol_refresh = 0 selects the from-scratch factorisation, chol_refresh = 1)           *

@@ -233,15 +233,15 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     // symmetric storage (lower block triangle, rbpf_step_sym.hip): the filter of the ny = 3 dense families at the
     // sizes its wave decomposition takes (eight 64-row tile rows: 512 <= nLin - nb < 640)
     if (sparse || !sym_supported(prob->n_lin, prob->n_y)) {
-      set_error("symmetric storage (options.storage = 2 / 3): dense filter / smoothers (single-GPU or sharded) with ny = 3 and nLin in 259..383 or 515..639, dense filter with nLin in 1027..1151, dense-radio (ny = 1) with nLin = 128 only"); return RBPF_ERR_UNSUPPORTED;
+      set_error("symmetric storage (options.storage = 2 / 3): dense filter / smoothers (built-in or generic models) with ny = 3 and nLin in 256..383 or 512..639, dense filter with ny = 3 and nLin in 1024..1151, ny = 1 with nLin = 128 only"); return RBPF_ERR_UNSUPPORTED;
     }
     c->lay = make_layout_sym(prob->n_lin, prob->n_y, c->fp32 ? 1 : 0);
     c->lay_low = c->lay;
     if (c->lay.CH64 == 16 && smoother) { set_error("symmetric storage at sixteen tile rows (nLin >= 1027): the filter only"); return RBPF_ERR_UNSUPPORTED; }
-    if (c->fp32 && c->lay.CH64 == 4) { set_error("fp32 tiles (options.storage = 3): nLin in 515..639 or 1027..1151"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->fp32 && c->lay.CH64 == 4) { set_error("fp32 tiles (options.storage = 3): nLin in 512..639 or 1024..1151"); return RBPF_ERR_UNSUPPORTED; }
   }
   if (c->fp32 && (smoother || sparse || prob->n_y != 3)) {
-    set_error("fp32 storage of the covariance banks: dense-mag filter only"); return RBPF_ERR_UNSUPPORTED;
+    set_error("fp32 storage of the covariance banks: the filter of a dense model with ny = 3 only (dense-mag or generic)"); return RBPF_ERR_UNSUPPORTED;
   }
   {
     const int cv = c->opt.chol_variant;
