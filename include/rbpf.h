@@ -173,7 +173,8 @@ typedef struct {
                           * every flush (the first child of a stored matrix overwrites it after its siblings    *
                           * were written to dead slots) instead of ping-pong banks -- halves the memory, same    *
                           * results bit for bit.  0: automatic (when two banks do not fit the device), 1: on,    *
-                          * -1: off.  On block-lower storage (eight / sixteen tile rows) the single bank keeps   *
+                          * -1: off.  On block-lower storage (eight / sixteen tile rows; elsewhere the per-child  *
+                          * in-place flush) the single bank keeps                                                *
                           * the shared flush: one writer per parent with children, the first writer of a stored  *
                           * matrix overwrites it in place after its readers (results to rounding, as two banks). */
   int32_t storage;       /* 0 = the covariance banks hold fp64 (the reference's precision); 1 = fp32 STORAGE of the banks, for the  *
@@ -186,14 +187,15 @@ typedef struct {
                           * 515, i.e. 0.56 x the HBM traffic and memory of storage 0; read-only steps of lazy_depth apply the  *
                           * pending sets as P H' - KS (K' H') instead of element-wise.  Same algebra: results within 1e-9 of  *
                           * storage 0 (P(r,c) and P(c,r), which differ by rounding in the reference's plain form, are one     *
-                          * stored value).  Dense models with n_y = 3 and 512 <= n_lin <= 639 (BASELINE.json configs[2]) or      *
-                          * 256 <= n_lin <= 383: filter and both smoothers, single-GPU and sharded (generic models: single-GPU); *
-                          * 1024 <= n_lin <= 1151 (sixteen tile rows, BASELINE.json configs[4]'s basis size): the filter; n_y = 1 *
+                          * stored value).  Dense models with n_y = 3 and 256 <= n_lin <= 1151 (4 to 16 tile rows of 64, the     *
+                          * core rows 64 * floor(n_lin / 128) * 2): the filter, single-GPU and sharded, lazy_depth <= 4 off     *
+                          * eight tile rows; both smoothers at 256 <= n_lin <= 767 (single-GPU; sharded at 256..383 and          *
+                          * 512..639 only); the smoothers are refused from n_lin = 768 on.  n_y = 1                               *
                           * with n_lin = 128 (dense-radio; two tile rows: 0.75 x the bytes): filter and both smoothers.  The     *
                           * generic (host-callback) family takes the same sizes as the built-in ones.  RBPF_ERR_UNSUPPORTED      *
                           * elsewhere.                                                                                          *
                           * 3 = fp32 tiles of the lower block triangle (storage 1's rounding on storage 2's layout: 0.28 x the   *
-                          * bytes of storage 0): the filter with n_y = 3 and 512 <= n_lin <= 639 or 1024 <= n_lin <= 1151,      *
+                          * bytes of storage 0): the filter with n_y = 3 and 384 <= n_lin <= 1151 (not at four tile rows),      *
                           * lazy_depth <= 4.                                                                                    */
   int32_t chol_variant;  /* smoothers: kernel of the ancestor-weight factorisation (particleSmoother.m:221,                   *
                           * particleSmootherInformationForm.m:228).  0: by matrix size (default); 16 / 64 / 648 / 644 / 1 /             *

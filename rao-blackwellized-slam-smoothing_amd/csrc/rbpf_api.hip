@@ -230,15 +230,17 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
   c->fp32 = c->opt.storage == 1 || c->opt.storage == 3;
   if (c->opt.storage < 0 || c->opt.storage > 3) { set_error("options.storage must be 0 (fp64), 1 (fp32), 2 (fp64, symmetric) or 3 (fp32, symmetric)"); return RBPF_ERR_INVALID_ARG; }
   if (c->opt.storage == 2 || c->opt.storage == 3) {
-    // symmetric storage (lower block triangle, rbpf_step_sym.hip): the filter of the ny = 3 dense families at the
-    // sizes its wave decomposition takes (eight 64-row tile rows: 512 <= nLin - nb < 640)
+    // symmetric storage (lower block triangle, rbpf_step_sym.hip): the ny = 3 dense families at the sizes its wave decomposition
+    // takes (4 to 16 tile rows of 64: 256 <= nLin - nb < 1024 + 128), ny = 1 at nLin = 128
     if (sparse || !sym_supported(prob->n_lin, prob->n_y)) {
-      set_error("symmetric storage (options.storage = 2 / 3): dense filter / smoothers (built-in or generic models) with ny = 3 and nLin in 256..383 or 512..639, dense filter with ny = 3 and nLin in 1024..1151, ny = 1 with nLin = 128 only"); return RBPF_ERR_UNSUPPORTED;
+      set_error("symmetric storage (options.storage = 2 / 3): dense filter (built-in or generic models) with ny = 3 and nLin in 256..1151, dense smoothers with ny = 3 and nLin in 256..767, ny = 1 with nLin = 128 only"); return RBPF_ERR_UNSUPPORTED;
     }
     c->lay = make_layout_sym(prob->n_lin, prob->n_y, c->fp32 ? 1 : 0);
     c->lay_low = c->lay;
-    if (c->lay.CH64 == 16 && smoother) { set_error("symmetric storage at sixteen tile rows (nLin >= 1027): the filter only"); return RBPF_ERR_UNSUPPORTED; }
-    if (c->fp32 && c->lay.CH64 == 4) { set_error("fp32 tiles (options.storage = 3): nLin in 512..639 or 1024..1151"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->lay.CH64 == 16 && smoother) { set_error("symmetric storage at sixteen tile rows (nLin >= 1024): the filter only"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->lay.CH64 >= 12 && smoother) { set_error("symmetric storage at twelve or fourteen tile rows (nLin 768..1023): the filter only (smoothers: nLin 256..767)"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->fp32 && c->lay.CH64 == 4) { set_error("fp32 tiles (options.storage = 3): nLin in 384..1151"); return RBPF_ERR_UNSUPPORTED; }
+    if (ex && smoother && (c->lay.CH64 == 6 || c->lay.CH64 == 10)) { set_error("the sharded smoother on symmetric storage: nLin in 256..383 or 512..639 (at 384..511 and 640..767 the single-GPU smoothers)"); return RBPF_ERR_UNSUPPORTED; }
   }
   if (c->fp32 && (smoother || sparse || prob->n_y != 3)) {
     set_error("fp32 storage of the covariance banks: the filter of a dense model with ny = 3 only (dense-mag or generic)"); return RBPF_ERR_UNSUPPORTED;
@@ -387,7 +389,7 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
   }
   // shared flush: with ping-pong banks the children of one parent store ONE copy of their (identical) flushed matrix
   c->share_flush = c->lazy_depth >= 2 && !c->inplace && !ex && c->lay.sym && (c->lay.CH64 == 8 || c->lay.CH64 == 16);   // (smoothers: the information form)
-  if (const size_t sd = sym_strip_doubles(c->lay, d)) {     // sixteen tile rows: the step kernel's column strips live in global memory
+  if (const size_t sd = sym_strip_doubles(c->lay, d + (smoother ? 1 : 0))) {   // 6, 10, 12, 14, 16 tile rows: the step kernel's column strips live in global memory (information form: one more right-hand side)
     RB_TRY(dmalloc(&c->d_strip_ws, (size_t)N * sd));
     c->strip_ws_stride = sd;
   }
@@ -397,7 +399,7 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     HIPCHK(hipMemset(c->d_share_writers, 0, sizeof(unsigned long long)));
   }
   if (c->lazy_depth >= 2) {
-    if (L.CH < 1 || L.CPL < 1 || L.CPL > 2) { set_error("lazy_depth >= 2 needs 128 <= nLin with at most two row chunks per wave"); return RBPF_ERR_UNSUPPORTED; }
+    if (!L.sym && (L.CH < 1 || L.CPL < 1 || L.CPL > 2)) { set_error("lazy_depth >= 2 needs 128 <= nLin with at most two row chunks per wave (full-square storage; block-lower storage, options.storage = 2, takes nLin 384..511)"); return RBPF_ERR_UNSUPPORTED; }
     if (!L.sym && step_lds_bytes(c->mdl, c->lay, smoother ? 1 : 0, c->lazy_depth) > 160 * 1024) { set_error("lazy_depth too large for the LDS plan"); return RBPF_ERR_UNSUPPORTED; }
     if (L.sym && step_sym_lds_bytes(c->mdl, c->lay, c->lazy_depth, 1, smoother ? 1 : 0) > 160 * 1024) { set_error("lazy_depth too large for the LDS plan"); return RBPF_ERR_UNSUPPORTED; }
     for (int b = 0; b <= c->lazy_depth; ++b) {            // entry N of every bank stays zero (fresh lineages)

@@ -1421,7 +1421,7 @@ extern "C" int rbpf_particle_smoother(const rbpf_model* model, const rbpf_proble
     // say what would fit: the information-form state without stored information matrices and with one covariance bank
     const double n = (double)prob->n_lin, mb = (8.0 * (0.57 * n * n + 2.0 * 0.52 * (n + 1) * (n + 1))) / 1e6;
     set_error(std::string(rbpf_last_error()) + " -- the information-form smoother did not fit this device with these options.  Its smallest "
-              "footprint: storage = 2 (where supported), lazy_depth >= 2, inplace = 1 and chol_refresh >= N_T (or info_rebuild = 1): about " +
+              "footprint: storage = 2 (nLin 256..767), lazy_depth >= 2, inplace = 1 and chol_refresh >= N_T (or info_rebuild = 1): about " +
               std::to_string((int)(mb * 10) / 10.0).substr(0, 4) + " MB of state per particle at this nLin (include/rbpf.h, rbpf_options)");
   }
   if (!c) return st;

@@ -35,8 +35,12 @@
 //   the vector memory path is bound by load instructions, not bytes), all arithmetic fp64, a flush rounds once on the way out -- as
 //   storage = 1 does for the full square.  Filter only.
 //
-// Supported: dense families with ny = 3; fp64: 512 <= mc < 640 core rows (nLin = 515: BASELINE.json configs[2]) or four tile rows
-// (nLin = 259), filter and both smoothers, single-GPU and sharded; sixteen tile rows (nLin = 1027) and fp32 tiles: the filter.
+// * 6, 10, 12 and 14 tile rows (nLin 384..511, 640..1023): one instantiation per (TS, NS, WR, E) for the four counts (CH = 0, the count
+//   from the layout): a wave per row pair, CH / 2 waves, the column strips in the global workspace as at sixteen tile rows, eight wave
+//   loads per quad round (no scratch).
+//
+// Supported: dense families with ny = 3 and 4 to 16 tile rows (256 <= nLin < 1152): the filter in fp64 tiles, single-GPU and sharded;
+// fp32 tiles from six tile rows on; both smoothers (fp64 tiles) at 4, 6, 8 and 10 tile rows (sharded: 4 and 8).  ny = 1 at nLin = 128.
 #include <type_traits>
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
@@ -81,18 +85,25 @@ constexpr int kSymRows = 2;            // tile rows per wave: rows rp and CH - 1
 constexpr int kSymRed = 64;            // doubles per wave of the block-reduction scratch (up to 7 * 3 * 3 = 63 values)
 constexpr int kSymStage = 32;          // columns of pending column factors a wave keeps in LDS at a time (flush)
 
+// 6, 10, 12 and 14 tile rows (nLin 384..511 and 640..1023): ONE instantiation per (TS, NS, WR, E) serves the four counts -- CH = 0
+// in the template, the count read from the layout at run time.  A wave per row pair (CH / 2 waves: the rows {w, CH - 1 - w}, CH + 1
+// tiles each), the quad mapping in the read-only steps, the column strips in the global workspace as at sixteen tile rows.
+__host__ __device__ constexpr bool sym_rt(int ch) { return ch == 6 || ch == 10 || ch == 12 || ch == 14; }
+constexpr int kSymRtWaves = 7;          // waves of the largest runtime count (fourteen tile rows): the launch bound of CH = 0
+
 bool sym_supported(int n, int d) {
   const int mc = (n / kChunkRows) * kChunkRows;
   const int ch = mc / kSymChunk;
   if (d == 1) return ch == 2 && n == mc;             // dense-radio (n_y = 1, nLin = m = 128: two tile rows, no border rows)
-  return d == 3 && (ch == 8 || ch == 4 || ch == 16);
+  return d == 3 && (ch == 8 || ch == 4 || ch == 16 || sym_rt(ch));
 }
 
-// sixteen tile rows: doubles of the global column-strip workspace per workgroup (the seven strips of row pairs 1..7)
-size_t sym_strip_doubles(const Layout& lay, int d) {
-  if (!lay.sym || lay.CH64 != 16) return 0;
+// sixteen tile rows and the runtime counts: doubles of the global column-strip workspace per workgroup (the strips of row pairs
+// 1 .. CH / 2 - 1), de = D + E right-hand sides
+size_t sym_strip_doubles(const Layout& lay, int de) {
+  if (!lay.sym || (lay.CH64 != 16 && !sym_rt(lay.CH64))) return 0;
   size_t o = 0;
-  for (int rp = 1; rp < lay.CH64 / 2; ++rp) o += (size_t)d * kSymChunk * (lay.CH64 - 1 - rp);
+  for (int rp = 1; rp < lay.CH64 / 2; ++rp) o += (size_t)de * kSymChunk * (lay.CH64 - 1 - rp);
   return o;
 }
 
@@ -113,8 +124,9 @@ __host__ __device__ inline int sym_ld_col(int ch, int rp) { return kSymChunk * (
 __host__ __device__ inline int sym_off_col(int off_col1, int D, int ch, int rp) { return off_col1 + D * kSymChunk * ((rp - 1) * (ch - 1) - (rp - 1) * rp / 2); }
 
 __host__ __device__ inline int sym_even(int x) { return (x + 1) & ~1; }
-// waves of a workgroup = row pairs x column phases: four (CH = 8: four row pairs; CH = 4: two row pairs x two phases), eight at CH = 16
-__host__ __device__ constexpr int sym_waves(int ch) { return ch == 16 ? 8 : kWaves; }
+// waves of a workgroup = row pairs x column phases: four (CH = 8: four row pairs; CH = 4: two row pairs x two phases), eight at CH = 16,
+// CH / 2 at the runtime counts (ch = 0: the most of them, the launch bound)
+__host__ __device__ constexpr int sym_waves(int ch) { return ch == 16 ? 8 : (ch == 0 ? kSymRtWaves : (sym_rt(ch) ? ch / 2 : kWaves)); }
 // column phases = waves that share a row pair and split its column pairs: CH / 2 row pairs x phases = waves
 __host__ __device__ constexpr int sym_phases(int ch) { return ch == 4 ? 2 : (ch == 2 ? 4 : 1); }
 
@@ -126,7 +138,7 @@ __host__ __device__ inline SymPlan sym_plan(int n, int D, int ldx, int ktot, int
   p.off_xl = o;  o += xl_lds ? ldx : 0;
   p.off_PHt = o; o += D * ldx;
   p.off_col1 = o;
-  if (ch == 16) o += waves * D * kSymChunk;        // sixteen tile rows: one block column of column sums per wave (the strips are global)
+  if (ch == 16 || sym_rt(ch)) o += waves * D * kSymChunk;   // sixteen tile rows, runtime counts: one block column of column sums per wave (the strips are global)
   else for (int rp = 1; rp < ch / 2; ++rp) o += D * sym_ld_col(ch, rp);
   p.off_row = o;  o += (sym_phases(ch) - 1) * D * ch * kSymChunk;
   p.off_tab = o;  o += sym_even(2 * (ktot > 0 ? ktot : 1));
@@ -138,7 +150,7 @@ __host__ __device__ inline SymPlan sym_plan(int n, int D, int ldx, int ktot, int
 }
 
 size_t step_sym_lds_bytes(const ModelDev& m, const Layout& lay, int n_sets, int write_base, int extra) {
-  const int xl_lds = ((RBPF_SYM_LIGHT_WGS > 2 && !write_base && extra == 0) || lay.CH64 == 16) ? 0 : 1;
+  const int xl_lds = ((RBPF_SYM_LIGHT_WGS > 2 && !write_base && extra == 0) || lay.CH64 == 16 || sym_rt(lay.CH64)) ? 0 : 1;
   return (size_t)sym_plan(lay.n, m.d + extra, lay.ldx, m.ktot, write_base ? n_sets * m.d : 0, lay.CH64, xl_lds).total * sizeof(double);
 }
 
@@ -426,7 +438,7 @@ __device__ __forceinline__ void sym_block(const TS* const (&src)[kSymRows], TS* 
 #ifndef RBPF_SYM_BUTTERFLY
 #define RBPF_SYM_BUTTERFLY 1
 #endif
-template <typename TS, int D, int DE, int NACT, bool DIAG, int Q0>
+template <typename TS, int D, int DE, int NACT, bool DIAG, int Q0, int QL = RBPF_SYM_QUAD_LOADS>
 __device__ __forceinline__ void sym_block_quad(const TS* const (&src)[kSymRows], const double* __restrict__ Hc,
                                                const double (&hown)[kSymRows][4][DE], double (&accr)[kSymRows][4][DE],
                                                double* __restrict__ colp, int ldc, int lane) {
@@ -434,7 +446,7 @@ __device__ __forceinline__ void sym_block_quad(const TS* const (&src)[kSymRows],
   constexpr bool kCol = !(DIAG && NACT == 1);           // any off-diagonal tile in this block column?
   // quads per round: RBPF_SYM_QUAD_LOADS wave loads in flight whatever the active rows (information form, DE = 4: eight -- its
   // four more row-sum and four more H registers per row do not leave room for sixteen)
-  constexpr int TQ = ((DE > 3 ? 8 : RBPF_SYM_QUAD_LOADS) / 4) / NACT;
+  constexpr int TQ = ((DE > 3 ? 8 : QL) / 4) / NACT;
   // one quad of column pairs (4 t .. 4 t + 3; this lane: pair 4 t + g), vq: its rows r16 + 16 rq of the active tile rows
   auto quad = [&](const dbl2s (&vq)[NACT][4], const int t) {
       double h0[DE], h1[DE];
@@ -595,10 +607,11 @@ __device__ __forceinline__ void sym_block_quad_f4(const float* const (&src)[kSym
 // sharing a stored matrix -- and measured it 0.4-0.8 ms per step SLOWER than this kernel: removed in r05, see commit 4711b84 and
 // DESIGN_NOTEBOOK.md 10.)
 template <typename TS, int D, int NS, bool WR, int E, int CH>
-__global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0) ? RBPF_SYM_LIGHT_WGS : 2)) void step_sym_kernel(const StepArgs a) {
-  constexpr int NW = sym_waves(CH), NT = 64 * NW;              // CH = 16: eight waves, one workgroup per CU (the same eight waves per CU as 2 x 4)
-  constexpr int NPH = sym_phases(CH);                          // column phases (waves per row pair)
-  constexpr bool kGStrip = (CH == 16);                         // column strips in the global workspace, one block column staged in LDS
+__global__ __launch_bounds__(64 * sym_waves(CH), (CH == 16 || CH == 0) ? 1 : ((!WR && E == 0) ? RBPF_SYM_LIGHT_WGS : 2)) void step_sym_kernel(const StepArgs a) {
+  const int chv = CH ? CH : a.lay.CH64;                        // tile rows (CH = 0: 6, 10, 12 or 14, from the layout)
+  const int NW = sym_waves(chv), NT = 64 * NW;                 // CH = 16: eight waves, one workgroup per CU (the same eight waves per CU as 2 x 4)
+  constexpr int NPH = sym_phases(CH);                          // column phases (waves per row pair; CH = 0: one)
+  constexpr bool kGStrip = (CH == 16 || CH == 0);              // column strips in the global workspace, one block column staged in LDS
   extern __shared__ double smem[];
   constexpr int DE = D + E, ND = NS * D, NDA = ND > 0 ? ND : 1, NSA = NS > 0 ? NS : 1;
   // more than four pending sets in a flush: the wave's two tile rows go through every block column one after the other, so that
@@ -613,7 +626,7 @@ __global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0)
   const int i = pre_i[0];
   const int dslot = WR ? pre_i[4] : i;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const SymPlan lp = sym_plan(n, DE, ldx, M.ktot, WR ? ND : 0, CH, ((RBPF_SYM_LIGHT_WGS > 2 && !WR && E == 0) || CH == 16) ? 0 : 1);
+  const SymPlan lp = sym_plan(n, DE, ldx, M.ktot, WR ? ND : 0, chv, ((RBPF_SYM_LIGHT_WGS > 2 && !WR && E == 0) || kGStrip) ? 0 : 1);
   double* Hs = smem + lp.off_H + ((nb * DE) & 1);             // [H | ivec] of column c at Hs[c * DE ..): core pairs 16-byte aligned
   double* xls = smem + lp.off_xl;
   double* PHt = smem + lp.off_PHt;                            // [DE][ldx]
@@ -646,7 +659,7 @@ __global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0)
   RBPF_SYM_KSTAMP(0);
   // ---- A: propagated state (propagate_kernel ran first), prior mean ----
   if (tid < kPreDoubles) misc[tid] = a.pre_d[(size_t)pos * kPreDoubles + tid];
-  constexpr bool kXlLds = !(RBPF_SYM_LIGHT_WGS > 2 && !WR && E == 0) && CH != 16;   // three workgroups per CU: no room for the prior mean in LDS
+  constexpr bool kXlLds = !(RBPF_SYM_LIGHT_WGS > 2 && !WR && E == 0) && !kGStrip;   // three workgroups per CU: no room for the prior mean in LDS
   if (kXlLds) for (int c = tid; c < n; c += NT) xls[c] = srcX[c];
   double Riy[D];                                               // R^-1 y (:292)
   if (E > 0) {
@@ -691,9 +704,11 @@ __global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0)
   RBPF_SYM_KSTAMP(3);
   {
   // ---- D: stream the stored tiles once ----
-  const int rp = (NPH == 1) ? wave : (wave % (CH / 2)), cp = (NPH == 1) ? 0 : (wave / (CH / 2));   // row pair, column phase
-  const int rows[kSymRows] = {rp, CH - 1 - rp};                // ascending
+  const int rp = (NPH == 1) ? wave : (wave % (chv / 2)), cp = (NPH == 1) ? 0 : (wave / (chv / 2));   // row pair, column phase
+  const int rows[kSymRows] = {rp, chv - 1 - rp};               // ascending
   constexpr bool kQuad = RBPF_SYM_QUAD && !WR && NPH == 1 && E <= RBPF_SYM_QUAD_EMAX;   // read-only steps at CH = 8: sym_block_quad
+  // wave loads in flight per quad round: runtime counts eight (sixteen spilled 4-5 registers there: 256 VGPRs; eight: 202, none)
+  constexpr int kQL = CH == 0 ? 8 : RBPF_SYM_QUAD_LOADS;
   double accr[kSymRows][DE], hown[kSymRows][DE], ks[kSplit ? 1 : kSymRows][NDA];
   double accq[kQuad ? kSymRows : 1][4][DE], hq[kQuad ? kSymRows : 1][4][DE];
   if constexpr (kQuad) {
@@ -731,10 +746,10 @@ __global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0)
   {
     TS* dT = reinterpret_cast<TS*>(a.Pt_new) + (size_t)dslot * Ly.szT;
     double* kst = smem + lp.off_kst + (size_t)wave * kSymStage * ND;
-    double* colw = (rp == 0) ? PHt + nb : (kGStrip ? smem + lp.off_col1 + (size_t)wave * DE * kSymChunk : smem + sym_off_col(lp.off_col1, DE, CH, rp));
-    const int ldc = (rp == 0) ? ldx : (kGStrip ? kSymChunk : sym_ld_col(CH, rp));
-    // sixteen tile rows: this wave's strip in the global workspace
-    double* gstrip = kGStrip ? a.strip_ws + (size_t)blockIdx.x * a.strip_ws_stride + sym_off_col(0, DE, CH, rp) : nullptr;
+    double* colw = (rp == 0) ? PHt + nb : (kGStrip ? smem + lp.off_col1 + (size_t)wave * DE * kSymChunk : smem + sym_off_col(lp.off_col1, DE, chv, rp));
+    const int ldc = (rp == 0) ? ldx : (kGStrip ? kSymChunk : sym_ld_col(chv, rp));
+    // sixteen tile rows, runtime counts: this wave's strip in the global workspace
+    double* gstrip = kGStrip ? a.strip_ws + (size_t)blockIdx.x * a.strip_ws_stride + sym_off_col(0, DE, chv, rp) : nullptr;
     const double* Hcore = Hs + (size_t)nb * DE;
     // column factors K(c, .) of kSymStage columns of every pending set -> the wave's LDS stage [pair][k][e] (lane = column;
     // wave-private: program order is the only synchronisation; the fetch latency is paid once per 32 columns and hidden by the
@@ -777,10 +792,10 @@ __global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0)
           else if (J < last) sym_block_quad_f4<D, DE, 1, false, 1>(srq, Hc, hq, accq, colp, ldc, lane);
           else sym_block_quad_f4<D, DE, 1, true, 1>(srq, Hc, hq, accq, colp, ldc, lane);
         } else {
-        if (J < rows[0]) sym_block_quad<TS, D, DE, 2, false, 0>(srq, Hc, hq, accq, colp, ldc, lane);
-        else if (J == rows[0]) sym_block_quad<TS, D, DE, 2, true, 0>(srq, Hc, hq, accq, colp, ldc, lane);
-        else if (J < last) sym_block_quad<TS, D, DE, 1, false, 1>(srq, Hc, hq, accq, colp, ldc, lane);
-        else sym_block_quad<TS, D, DE, 1, true, 1>(srq, Hc, hq, accq, colp, ldc, lane);
+        if (J < rows[0]) sym_block_quad<TS, D, DE, 2, false, 0, kQL>(srq, Hc, hq, accq, colp, ldc, lane);
+        else if (J == rows[0]) sym_block_quad<TS, D, DE, 2, true, 0, kQL>(srq, Hc, hq, accq, colp, ldc, lane);
+        else if (J < last) sym_block_quad<TS, D, DE, 1, false, 1, kQL>(srq, Hc, hq, accq, colp, ldc, lane);
+        else sym_block_quad<TS, D, DE, 1, true, 1, kQL>(srq, Hc, hq, accq, colp, ldc, lane);
         }
       } else if constexpr (!kSplit) {
         for (int pbeg = 0; pbeg < kSymChunk / 2; pbeg += kSymStage / 2) {
@@ -817,7 +832,7 @@ __global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0)
         // the block column's sums leave the stage: rows k of the strip, 64 consecutive columns each (the stage is wave-private: program
         // order is the only synchronisation, as for kst)
 #pragma unroll
-        for (int k = 0; k < DE; ++k) gstrip[(size_t)k * sym_ld_col(CH, rp) + J * kSymChunk + lane] = colw[k * kSymChunk + lane];
+        for (int k = 0; k < DE; ++k) gstrip[(size_t)k * sym_ld_col(chv, rp) + J * kSymChunk + lane] = colw[k * kSymChunk + lane];
       }
     }
   }
@@ -859,11 +874,11 @@ __global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0)
     }
   }
   if (NPH > 1 && cp > 0) {                                     // the other column phases: their row sums go through LDS
-    double* rowp = smem + lp.off_row + (size_t)(cp - 1) * DE * CH * kSymChunk;
+    double* rowp = smem + lp.off_row + (size_t)(cp - 1) * DE * chv * kSymChunk;
 #pragma unroll
     for (int q = 0; q < kSymRows; ++q)
 #pragma unroll
-      for (int k = 0; k < DE; ++k) rowp[(size_t)k * (CH * kSymChunk) + rows[q] * kSymChunk + lane] = accr[q][k];
+      for (int k = 0; k < DE; ++k) rowp[(size_t)k * (chv * kSymChunk) + rows[q] * kSymChunk + lane] = accr[q][k];
   }
   __syncthreads();
   // combine, by the lane (of the first column phase) that owns the row: row part incl. the border columns (registers) + the other
@@ -895,17 +910,17 @@ __global__ __launch_bounds__(64 * sym_waves(CH), CH == 16 ? 1 : ((!WR && E == 0)
       if (NPH > 1) {
 #pragma unroll
         for (int ph = 1; ph < NPH; ++ph) {                     // phases in order: a fixed summation order
-          const double* rowp = smem + lp.off_row + (size_t)(ph - 1) * DE * CH * kSymChunk;
+          const double* rowp = smem + lp.off_row + (size_t)(ph - 1) * DE * chv * kSymChunk;
 #pragma unroll
-          for (int k = 0; k < DE; ++k) s[k] += rowp[(size_t)k * (CH * kSymChunk) + rc];
+          for (int k = 0; k < DE; ++k) s[k] += rowp[(size_t)k * (chv * kSymChunk) + rc];
         }
       }
 #pragma unroll
-      for (int w = 0; w < CH / 2; ++w) {
-        if (rows[q] < CH - 1 - w) {                           // row pair w holds off-diagonal tiles in this block column
-          const double* cw = (w == 0) ? PHt + nb : (kGStrip ? a.strip_ws + (size_t)blockIdx.x * a.strip_ws_stride + sym_off_col(0, DE, CH, w)
-                                                            : smem + sym_off_col(lp.off_col1, DE, CH, w));
-          const int ldw = (w == 0) ? ldx : sym_ld_col(CH, w);
+      for (int w = 0; w < chv / 2; ++w) {
+        if (rows[q] < chv - 1 - w) {                          // row pair w holds off-diagonal tiles in this block column
+          const double* cw = (w == 0) ? PHt + nb : (kGStrip ? a.strip_ws + (size_t)blockIdx.x * a.strip_ws_stride + sym_off_col(0, DE, chv, w)
+                                                            : smem + sym_off_col(lp.off_col1, DE, chv, w));
+          const int ldw = (w == 0) ? ldx : sym_ld_col(chv, w);
 #pragma unroll
           for (int k = 0; k < DE; ++k) s[k] += cw[(size_t)k * ldw + rc];
         }
@@ -1134,13 +1149,16 @@ static hipError_t launch_sym_kc(const StepArgs& a, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
   if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&step_sym_kernel<TS, D, NS, WR, E, CH>), 160 * 1024, attr_done)) return e;
   const size_t lds = step_sym_lds_bytes(a.mdl, a.lay, NS, WR ? 1 : 0, E);
-  if (CH == 16 && (!a.strip_ws || lds > 160 * 1024)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((step_sym_kernel<TS, D, NS, WR, E, CH>), dim3(a.N), dim3(64 * sym_waves(CH)), lds, s, a);
+  if ((CH == 16 || CH == 0) && (!a.strip_ws || lds > 160 * 1024)) return hipErrorInvalidValue;
+  if (CH == 0 && !sym_rt(a.lay.CH64)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((step_sym_kernel<TS, D, NS, WR, E, CH>), dim3(a.N), dim3(64 * sym_waves(CH ? CH : a.lay.CH64)), lds, s, a);
   return hipGetLastError();
 }
 
 template <typename TS, int D, int NS, bool WR, int E>
 static hipError_t launch_sym_k(const StepArgs& a, hipStream_t s) {
+  // 6, 10, 12 and 14 tile rows: one runtime-count kernel (fp64 and fp32 tiles; filter and information form), lazy_depth <= 4
+  if constexpr (NS <= 4) { if (sym_rt(a.lay.CH64)) return launch_sym_kc<TS, D, NS, WR, E, 0>(a, s); }
   if constexpr (std::is_same<TS, double>::value) {
     if (a.lay.CH64 == 8) return launch_sym_kc<TS, D, NS, WR, E, 8>(a, s);
     if constexpr (NS <= 4) { if (a.lay.CH64 == 4) return launch_sym_kc<TS, D, NS, WR, E, 4>(a, s); }      // four tile rows: lazy_depth <= 4
@@ -1223,7 +1241,7 @@ static hipError_t launch_step_sym_radio(const StepArgs& a, hipStream_t s) {
 
 hipError_t launch_step_sym(const StepArgs& a, hipStream_t s) {
   if (a.lay.sym && a.mdl.d == 1) return launch_step_sym_radio(a, s);
-  if (!a.lay.sym || a.mdl.d != 3 || (a.lay.CH64 != 8 && a.lay.CH64 != 4 && a.lay.CH64 != 16)) return hipErrorInvalidValue;
+  if (!a.lay.sym || a.mdl.d != 3 || (a.lay.CH64 != 8 && a.lay.CH64 != 4 && a.lay.CH64 != 16 && !sym_rt(a.lay.CH64))) return hipErrorInvalidValue;
   if (a.fp32) return a.info ? hipErrorInvalidValue : launch_step_sym_filter<float>(a, s);
   if (a.info) {                                            // information form: lazy_depth <= 3
     if (a.write_base) {
