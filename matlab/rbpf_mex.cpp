@@ -283,7 +283,10 @@ void fill_nan(mxArray* a) { double* p = mxGetPr(a); const size_t n = mxGetNumber
 
 // Options that change the schedule or the arithmetic, not the interface (include/rbpf.h `rbpf_options`): they cannot travel in
 // the reference's signatures, so they are session state of the gateway, set once by  rbpf_mex('options', struct(...))  (see
-// matlab/rbpf_options.m) and applied to every later filter / smoother call.  All zero = the reference's behaviour.
+// matlab/rbpf_options.m) and applied to every later filter / smoother call.  All zero = the library's defaults.  That is the
+// reference's arithmetic except in the information-form smoother: chol_refresh = 0 is automatic and carries the ancestor-weight
+// factors (K = 32) for the recognised dense family at 128 <= nLin <= 575; chol_refresh = 1 factorises from scratch at every step
+// as the reference does.
 struct SessionOptions {
   int lazy_depth = 0, chol_refresh = 0, chol_variant = 0, storage = 0, inplace = 0, fix_p_mean = 0, n_devices = 0, rng_mode = 0, info_rebuild = 0;
   double jitter = 0.0, rng_seed = 0.0;

@@ -381,14 +381,14 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     HIPCHK(hipMemsetAsync(c->xl[b], 0, c->bank_cap * L.ldx * sizeof(double), c->stream));
   }
   if (c->inplace) RB_TRY(dmalloc(&c->d_ip, (size_t)8 * N));
-  c->share_inplace = c->inplace && c->lazy_depth >= 2 && !ex && c->lay.sym && (c->lay.CH64 == 8 || c->lay.CH64 == 16);
+  c->share_inplace = c->inplace && c->lazy_depth >= 2 && !ex && layout_shares_flush(c->lay);
   if (const char* e = tuning_env("RBPF_SHARE_INPLACE")) c->share_inplace = c->share_inplace && atoi(e) != 0;   // diagnostic builds: the per-child in-place flush
   if (c->share_inplace) {
     RB_TRY(dmalloc(&c->d_share_writers, 1));
     HIPCHK(hipMemset(c->d_share_writers, 0, sizeof(unsigned long long)));
   }
   // shared flush: with ping-pong banks the children of one parent store ONE copy of their (identical) flushed matrix
-  c->share_flush = c->lazy_depth >= 2 && !c->inplace && !ex && c->lay.sym && (c->lay.CH64 == 8 || c->lay.CH64 == 16);   // (smoothers: the information form)
+  c->share_flush = c->lazy_depth >= 2 && !c->inplace && !ex && layout_shares_flush(c->lay);   // (smoothers: the information form)
   if (const size_t sd = sym_strip_doubles(c->lay, d + (smoother ? 1 : 0))) {   // 6, 10, 12, 14, 16 tile rows: the step kernel's column strips live in global memory (information form: one more right-hand side)
     RB_TRY(dmalloc(&c->d_strip_ws, (size_t)N * sd));
     c->strip_ws_stride = sd;
@@ -591,6 +591,142 @@ int ctx_call_on_step(rbpf_ctx* c, int t, bool is_smoother) {
   return RBPF_OK;
 }
 
+bool layout_shares_flush(const Layout& L) { return L.sym && (L.CH64 == 8 || L.CH64 == 16); }
+bool step_shares_flush(const StepArgs& a) { return a.n_sets >= 1 && a.n_sets <= (a.info ? 3 : 7); }
+
+StepBanks ctx_step_args(rbpf_ctx* c, int t, int k_iter, const double* xref_t, const InfoStep* info, int N, StepArgs& a) {
+  const Layout& L = c->lay;
+  const int d = c->mdl.d, nw = c->mdl.nw;
+  const bool lazy = c->lazy_depth >= 2;
+  // multi-step lazy update: sets produced at steps t-ell .. t-1 are pending; every C-th step rewrites the matrices
+  const LazySched sc = lazy_for_step(c->lazy_depth, t);
+  StepBanks bk;
+  bk.flush = sc.flush;
+  bk.ob = c->cur; bk.nb = (t == 0) ? 0 : (sc.flush ? c->cur ^ 1 : c->cur);   // bank the stored covariances are written to (if at all)
+  bk.xo = c->xcur; bk.xn = (t == 0) ? 0 : (c->xcur ^ 1);
+  bk.told = c->tcur; bk.tnew = c->tcur ^ 1;
+  a = StepArgs{};
+  a.mdl = c->mdl; a.lay = (sc.ell >= 3) ? c->lay_low : L;
+  a.N = N; a.t = t; a.propagate = (t > 0);
+  a.n_sets = sc.ell; a.write_base = sc.flush ? 1 : 0;
+  a.zero_set_idx = N;
+  a.phase = -1;                                            // (every slot; the flushes in several launches go by phase)
+  if (lazy) {
+    for (int q = 0; q < sc.ell; ++q) {
+      a.fset[q] = c->Fb[sc.bank(q)];
+      a.fset_idx_old[q] = c->fidx[bk.told] + (size_t)sc.bank(q) * N;
+      a.fset_idx_new[q] = c->fidx[bk.tnew] + (size_t)sc.bank(q) * N;
+    }
+    a.fself_idx_new = c->fidx[bk.tnew] + (size_t)sc.self_bank() * N;
+    a.base_old = (t > 0) ? c->base[bk.told] : nullptr;
+    a.base_new = c->base[bk.tnew];
+  }
+  if (t == 0) {                                            // x0_lin and P0, broadcast (strides 0)
+    a.xl_old = c->d_x0l;
+    a.Pt_old = c->d_P0t; a.Pb_old = c->d_P0b;
+  } else {
+    a.xl_old = c->xl[bk.xo]; a.xl_old_stride = (size_t)L.ldx;
+    a.F_old = lazy ? nullptr : c->F[bk.ob];
+    a.Pt_old = c->Pt[bk.ob]; a.Pb_old = c->Pb[bk.ob]; a.Pt_old_stride = L.szT; a.Pb_old_stride = L.szB;
+  }
+  a.xl_new = c->xl[bk.xn]; a.F_new = lazy ? c->Fb[sc.self_bank()] : c->F[bk.nb];
+  a.Pt_new = c->Pt[bk.nb]; a.Pb_new = c->Pb[bk.nb];
+  a.fp32 = c->fp32 ? 1 : 0;
+  a.strip_ws = c->d_strip_ws; a.strip_ws_stride = c->strip_ws_stride;
+  a.rng_mode = c->rng_mode; a.k_iter = k_iter; a.seed = c->seed;
+  a.odo = c->d_odo + (size_t)(t > 0 ? t - 1 : 0) * c->mdl.nodo;
+  a.cholQ = c->d_cholQ + (size_t)((c->chol_pages > 1 && t > 0) ? t - 1 : 0) * nw * nw;
+  a.y = c->d_y + (size_t)t * d;
+  a.xref = xref_t;
+  a.status = c->d_flags;
+  a.pre_i = c->d_pre_i; a.pre_d = c->d_pre_d;
+  a.info = info ? 1 : 0;
+  if (info) {
+    a.ivec_old = info->ivec_old; a.ivec_old_stride = info->ivec_old_stride; a.ivec_new = info->ivec_new;
+    a.hld_old = info->hld_old; a.hld_old_stride = info->hld_old_stride; a.hld_new = info->hld_new;
+    a.qf_new = info->qf_new; a.Hb_new = info->Hb_new;
+  }
+  return bk;
+}
+
+int ctx_launch_step(rbpf_ctx* c, StepArgs& a, const StepBanks& bk, FlushMode mode) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (c->timing_on) {
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, c->stream));
+  }
+  const bool shared = mode == FlushMode::Shared || mode == FlushMode::InPlaceShared;
+  StepArgs rd = a;
+  rd.phase = 0; rd.write_base = 0;                         // shared flushes: the read-only variant with the same pending sets
+  switch (mode) {
+    case FlushMode::Plain:
+      HIPCHK(launch_step(a, c->stream));
+      break;
+    case FlushMode::Shared:
+      // Writers (the flush variant, one per parent with children) first, then their read-only siblings (they point at their writer's
+      // new entry), one after the other.  (Measured r05 with diagnostic builds of commit 31144f4: both side by side on
+      // two streams 11.39 against 11.24 ms per step; one step of a STAGGERED flush -- a quarter of the families flushing beside three
+      // quarters of read-only particles -- 12.2 ms whether serial or concurrent, against the lock-step schedule's 11.66: DESIGN.md 9.)
+      a.phase = 1; HIPCHK(launch_step(a, c->stream));
+      HIPCHK(launch_step(rd, c->stream));
+      break;
+    case FlushMode::InPlace:
+      a.phase = 0; HIPCHK(launch_step(a, c->stream));
+      a.phase = 1; HIPCHK(launch_step(a, c->stream));
+      break;
+    case FlushMode::InPlaceShared:
+      HIPCHK(launch_step(rd, c->stream));                  // readers over the old matrices
+      a.phase = 1; HIPCHK(launch_step(a, c->stream));      // writers into entries nobody refers to
+      a.phase = 2; HIPCHK(launch_step(a, c->stream));      // first writers, in place
+      break;
+  }
+  if (c->timing_on) {
+    if (shared) c->share_flush_particles += a.N;
+    HIPCHK(hipEventRecord(e1, c->stream)); c->events.emplace_back(e0, e1);
+    ctx_account_launch(c, a);                              // (the writers' arguments: write_base as scheduled)
+  }
+  const bool lazy = c->lazy_depth >= 2;
+  c->cur = bk.nb;
+  c->xcur = lazy ? bk.xn : bk.nb;
+  if (lazy) c->tcur = bk.tnew;
+  c->t = a.t + 1;
+  return RBPF_OK;
+}
+
+// Diagnostic builds only (-DRBPF_TUNING, -DRBPF_STAMPS): drop or check the processing order, print the kernels' time stamps.
+static int ctx_step_diagnostics(rbpf_ctx* c, StepArgs& a, const int* A_t) {
+  const int t = a.t, N = a.N;
+  static const int no_order = tuning_env("RBPF_NO_ORDER") ? 1 : 0;      // tuning / debugging only
+  static const int dbg_order = tuning_env("RBPF_DEBUG_ORDER") ? 1 : 0;
+  if (no_order) a.order = nullptr;
+#ifdef RBPF_STAMPS
+  if (t >= 100 && t <= 103) {
+    unsigned long long ks[8];
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(ks, c->d_counts + 2 * N + 32, sizeof(ks), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[rbpf kstamps] step %d (prev launch): A %.1f B %.1f C %.1f D(stream) %.1f comb %.1f E %.1f F %.1f us\n", t - 1, (ks[1]-ks[0])*0.01, (ks[2]-ks[1])*0.01, (ks[3]-ks[2])*0.01, (ks[4]-ks[3])*0.01, 0.0, (ks[5]-ks[4])*0.01, (ks[6]-ks[5])*0.01);
+  }
+  if (t == 100) {
+    unsigned long long st[8];
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(st, c->d_counts + 2 * N, sizeof(st), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[rbpf stamps] normalise %.1f us, search %.1f us, order %.1f us\n", (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01);
+    fprintf(stderr, "[rbpf stamps] shader clock during the kernel: %.0f MHz\n", (double)(st[7] - st[4]) / ((st[3] - st[0]) * 0.01));
+  }
+#endif
+  if (dbg_order && a.order && (t == 5 || t == 50)) {
+    std::vector<int> ho(N), ha(N);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(ho.data(), c->d_order, (size_t)N * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ha.data(), A_t, (size_t)N * 4, hipMemcpyDeviceToHost));
+    long bad = 0; std::vector<char> seen(N, 0); long dup = 0;
+    for (int b = 0; b < N; ++b) { if (ho[b] < 0 || ho[b] >= N || seen[ho[b]]) ++dup; else seen[ho[b]] = 1; }
+    for (int b = 1; b < N; ++b) if (ha[ho[b]] < ha[ho[b - 1]]) ++bad;
+    fprintf(stderr, "[rbpf debug] t=%d order: %ld inversions, %ld duplicates/out-of-range; first anc %d %d %d %d\n", t, bad, dup, ha[ho[0]], ha[ho[1]], ha[ho[2]], ha[ho[3]]);
+  }
+  return RBPF_OK;
+}
+
 // One time step of particleFilter.m:100-218 / particleSmoother.m:124-341 (iteration k_iter).
 // xref != nullptr: slot N-1 is the conditioned reference trajectory (its ancestor index has
 // already been written to A_t[N-1] by the ancestor-sampling kernels).
@@ -650,167 +786,52 @@ int ctx_step(rbpf_ctx* c, int k_iter, const double* xref_t, int n_draw, const In
     c->t = t + 1;
     return RBPF_OK;
   }
-  StepArgs a;
-  a.mdl = c->mdl; a.lay = L; a.N = N; a.t = t; a.propagate = (t > 0);
-  a.ai = (t > 0) ? A_t : nullptr;
-  a.ai_bank = nullptr; a.slot_offset = 0; a.xn_old_stride = (size_t)N; a.xn_new_stride = (size_t)N;
-  a.order = ((pre_drawn || c->order_step == t) && t > 0) ? c->d_order : nullptr;
-  a.zero_set_idx = N;
-  a.slot_ids = nullptr; a.n_bank_local = 0; a.rec = nullptr; a.rec_stride = 0; a.rec_off_B = a.rec_off_F = a.rec_off_X = 0;
-  a.rec_off_I = a.rec_off_hld = 0;
-  {
-    static const int no_order = tuning_env("RBPF_NO_ORDER") ? 1 : 0;      // tuning / debugging only
-    static const int dbg_order = tuning_env("RBPF_DEBUG_ORDER") ? 1 : 0;
-    if (no_order) a.order = nullptr;
-#ifdef RBPF_STAMPS
-    if (t >= 100 && t <= 103) {
-      unsigned long long ks[8];
-      HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(hipMemcpy(ks, c->d_counts + 2 * N + 32, sizeof(ks), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[rbpf kstamps] step %d (prev launch): A %.1f B %.1f C %.1f D(stream) %.1f comb %.1f E %.1f F %.1f us\n", t - 1, (ks[1]-ks[0])*0.01, (ks[2]-ks[1])*0.01, (ks[3]-ks[2])*0.01, (ks[4]-ks[3])*0.01, 0.0, (ks[5]-ks[4])*0.01, (ks[6]-ks[5])*0.01);
-    }
-    if (t == 100) {
-      unsigned long long st[8];
-      HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(hipMemcpy(st, c->d_counts + 2 * N, sizeof(st), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[rbpf stamps] normalise %.1f us, search %.1f us, order %.1f us\n", (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01);
-      fprintf(stderr, "[rbpf stamps] shader clock during the kernel: %.0f MHz\n", (double)(st[7] - st[4]) / ((st[3] - st[0]) * 0.01));
-    }
-#endif
-    if (dbg_order && a.order && (t == 5 || t == 50)) {
-      std::vector<int> ho(N), ha(N);
-      HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(hipMemcpy(ho.data(), c->d_order, (size_t)N * 4, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(ha.data(), A_t, (size_t)N * 4, hipMemcpyDeviceToHost));
-      long bad = 0; std::vector<char> seen(N, 0); long dup = 0;
-      for (int b = 0; b < N; ++b) { if (ho[b] < 0 || ho[b] >= N || seen[ho[b]]) ++dup; else seen[ho[b]] = 1; }
-      for (int b = 1; b < N; ++b) if (ha[ho[b]] < ha[ho[b - 1]]) ++bad;
-      fprintf(stderr, "[rbpf debug] t=%d order: %ld inversions, %ld duplicates/out-of-range; first anc %d %d %d %d\n", t, bad, dup, ha[ho[0]], ha[ho[1]], ha[ho[2]], ha[ho[3]]);
-    }
-  }
-  a.xn_old = X_old; a.xn_new = X_new;
   const bool lazy = c->lazy_depth >= 2;
-  const int ob = c->cur;
-  int nb = (t == 0) ? 0 : (c->cur ^ 1);          // bank the stored covariances are written to (if at all)
-  const int xo = c->xcur, xn = (t == 0) ? 0 : (c->xcur ^ 1);
-  const int told = c->tcur, tnew = c->tcur ^ 1;
-  bool flush = true;
-  for (int q = 0; q < kMaxSets; ++q) { a.fset[q] = nullptr; a.fset_idx_old[q] = nullptr; a.fset_idx_new[q] = nullptr; }
-  a.fself_idx_new = nullptr; a.base_old = nullptr; a.base_new = nullptr;
-  a.dst_slot = nullptr; a.phase_of = nullptr; a.phase = -1; a.share_flush = 0;
-  a.fp32 = c->fp32 ? 1 : 0;
-  a.strip_ws = c->d_strip_ws; a.strip_ws_stride = c->strip_ws_stride;
+  StepArgs a{};
+  const StepBanks bk = ctx_step_args(c, t, k_iter, xref_t, info, N, a);
+  // what one GPU does differently from a rank of a sharded session: ancestors, states and weights are the context's own arrays,
+  // indexed by slot; the fused resample kernel of step t-1 left a processing order (and takes this step's uniforms for step t+1)
+  a.ai = (t > 0) ? A_t : nullptr;
+  a.order = ((pre_drawn || c->order_step == t) && t > 0) ? c->d_order : nullptr;
+  a.xn_old = X_old; a.xn_old_stride = (size_t)N; a.xn_new = X_new; a.xn_new_stride = (size_t)N;
+  if (t == 0 && c->x0_lin_cols > 1) a.xl_old_stride = (size_t)L.ldx;      // one x0_lin per particle
+  a.logw = c->logw + tr;
+  a.Z = (c->d_Z && t > 0) ? c->d_Z + (rng_page + (size_t)(t - 1) * N) * nw : nullptr;
+  a.xref_gslot = N - 1;
+  a.stamps = reinterpret_cast<unsigned long long*>(c->d_counts + 2 * N + 32);
+  // fused fast path with the device generator: the uniforms of step t+1 are produced here, in parallel
+  a.u_next = (c->fuse_resample && c->rng_mode == RBPF_RNG_PHILOX && t + 1 < c->T) ? c->d_unext : nullptr;
   a.xn_ext = c->ext_xn; a.H_ext = c->ext_H;
+  RB_TRY(ctx_step_diagnostics(c, a, A_t));
   if (c->mdl.kind == RBPF_MODEL_GENERIC_DENSE && (!a.xn_ext || !a.H_ext)) {
     set_error("generic (host-callback) model: advance with rbpf_filter_step_external"); return RBPF_ERR_STATE;
   }
-  a.n_sets = (t > 0) ? 1 : 0; a.write_base = 1;
-  if (lazy) {
-    // multi-step lazy update: sets produced at steps t-ell .. t-1 are pending; every C-th step rewrites the matrices
-    const int C = c->lazy_depth, B = C + 1;
-    const int ell = (t == 0) ? 0 : ((t - 1) % C) + 1;
-    flush = (t == 0) || (ell == C);
-    a.n_sets = ell; a.write_base = flush ? 1 : 0;
-    if (ell >= 3) a.lay = c->lay_low;
-    for (int q = 0; q < ell; ++q) {
-      const int bank = (t - ell + q) % B;
-      a.fset[q] = c->Fb[bank];
-      a.fset_idx_old[q] = c->fidx[told] + (size_t)bank * N;
-      a.fset_idx_new[q] = c->fidx[tnew] + (size_t)bank * N;
-    }
-    a.fself_idx_new = c->fidx[tnew] + (size_t)(t % B) * N;
-    a.base_old = (t > 0) ? c->base[told] : nullptr;
-    a.base_new = c->base[tnew];
-    if (!flush) nb = ob;
-  }
-  if (t == 0) {
-    a.xl_old = c->d_x0l; a.xl_old_stride = (c->x0_lin_cols > 1) ? (size_t)L.ldx : 0;
-    a.F_old = nullptr;
-    a.Pt_old = c->d_P0t; a.Pb_old = c->d_P0b; a.Pt_old_stride = 0; a.Pb_old_stride = 0;
-  } else {
-    a.xl_old = c->xl[xo]; a.xl_old_stride = (size_t)L.ldx;
-    a.F_old = lazy ? nullptr : c->F[ob];
-    a.Pt_old = c->Pt[ob]; a.Pb_old = c->Pb[ob]; a.Pt_old_stride = L.szT; a.Pb_old_stride = L.szB;
-  }
-  a.xl_new = c->xl[xn]; a.F_new = lazy ? c->Fb[t % (c->lazy_depth + 1)] : c->F[nb];
-  a.Pt_new = c->Pt[nb]; a.Pb_new = c->Pb[nb];
-  a.logw = c->logw + tr;
-  a.rng_mode = c->rng_mode; a.k_iter = k_iter; a.seed = c->seed;
-  a.Z = (c->d_Z && t > 0) ? c->d_Z + (rng_page + (size_t)(t - 1) * N) * nw : nullptr;
-  a.odo = c->d_odo + (size_t)(t > 0 ? t - 1 : 0) * c->mdl.nodo;
-  a.cholQ = c->d_cholQ + (size_t)((c->chol_pages > 1 && t > 0) ? t - 1 : 0) * nw * nw;
-  a.y = c->d_y + (size_t)t * d;
-  a.xref = xref_t; a.xref_gslot = N - 1;
-  a.status = c->d_flags;
-  a.stamps = reinterpret_cast<unsigned long long*>(c->d_counts + 2 * N + 32);
-  a.pre_i = c->d_pre_i; a.pre_d = c->d_pre_d;
-  // fused fast path with the device generator: the uniforms of step t+1 are produced here, in parallel
-  a.u_next = (c->fuse_resample && c->rng_mode == RBPF_RNG_PHILOX && t + 1 < c->T) ? c->d_unext : nullptr;
-  a.info = info ? 1 : 0;
-  a.ivec_old = nullptr; a.ivec_old_stride = 0; a.ivec_new = nullptr; a.hld_old = nullptr; a.hld_old_stride = 0;
-  a.hld_new = nullptr; a.qf_new = nullptr; a.Hb_new = nullptr;
-  if (info) {
-    a.ivec_old = info->ivec_old; a.ivec_old_stride = info->ivec_old_stride; a.ivec_new = info->ivec_new;
-    a.hld_old = info->hld_old; a.hld_old_stride = info->hld_old_stride; a.hld_new = info->hld_new;
-    a.qf_new = info->qf_new; a.Hb_new = info->Hb_new;
-  }
-  const bool two_phase = c->inplace && lazy && flush && t > 0;
-  const bool sip = two_phase && c->share_inplace && a.n_sets >= 1 && a.n_sets <= (info ? 3 : 7);
-  if (sip) {
-    // single bank, shared flush: one writer per parent with children; the first writer of a stored matrix overwrites it in place
-    // after everything else has read it (launch_share_inplace_plan)
+  // a flush (the pending sets applied for good) may take several launches, planned here
+  const bool flushing = lazy && bk.flush && t > 0;
+  // shared: the children of one parent flush to ONE entry, one writer per parent with children; its siblings only read
+  const bool share = flushing && step_shares_flush(a) && (c->inplace ? c->share_inplace : c->share_flush);
+  FlushMode mode = FlushMode::Plain;
+  if (flushing && c->inplace) {
+    // single bank: siblings move to dead entries first, then the first child of every stored matrix overwrites it (launch_inplace_plan);
+    // shared, the first writer of a stored matrix overwrites it after everything else has read it (launch_share_inplace_plan).
+    // Either plan comes from the ancestor-sorted order of the fused resample kernel.
     if (!a.order) { set_error("in-place flush without a processing order"); return RBPF_ERR_STATE; }
-    int* dst = c->d_ip; int* ph = c->d_ip + N;
-    HIPCHK(launch_share_inplace_plan(N, a.order, A_t, c->base[told], dst, ph, c->d_ip + 2 * (size_t)N, c->timing_on ? c->d_share_writers : nullptr, c->stream));
-    a.dst_slot = dst; a.phase_of = ph; a.share_flush = 1;
-  } else if (two_phase) {
-    // single-bank flush: siblings move to dead entries first (launch 0), then the first child of every stored
-    // matrix overwrites it (launch 1); the plan comes from the ancestor-sorted order of the fused resample kernel
-    if (!a.order) { set_error("in-place flush without a processing order"); return RBPF_ERR_STATE; }
-    int* dst = c->d_ip; int* ph = c->d_ip + N;
-    HIPCHK(launch_inplace_plan(N, a.order, A_t, c->base[told], dst, ph, c->d_ip + 2 * (size_t)N, c->stream));
+    int* dst = c->d_ip; int* ph = c->d_ip + N; int* scratch = c->d_ip + 2 * (size_t)N;
+    if (share) HIPCHK(launch_share_inplace_plan(N, a.order, A_t, c->base[bk.told], dst, ph, scratch, c->timing_on ? c->d_share_writers : nullptr, c->stream));
+    else HIPCHK(launch_inplace_plan(N, a.order, A_t, c->base[bk.told], dst, ph, scratch, c->stream));
     a.dst_slot = dst; a.phase_of = ph;
-  }
-  const bool share = c->share_flush && lazy && flush && t > 0 && !two_phase && a.n_sets >= 1 && a.n_sets <= (info ? 3 : 7);
-  if (share) {
-    // the children of one parent flush to ONE entry (launch_share_plan): the smallest child stores it, its siblings only read
+    mode = share ? FlushMode::InPlaceShared : FlushMode::InPlace;
+  } else if (share) {
+    // ping-pong banks (launch_share_plan): the smallest child stores the matrix
     int* lead = c->d_share; int* dst = c->d_share + N; int* ph = c->d_share + 2 * (size_t)N;
     HIPCHK(launch_share_plan(N, N, A_t, lead, dst, ph, c->timing_on ? c->d_share_writers : nullptr, c->stream));
-    a.dst_slot = dst; a.phase_of = ph; a.share_flush = 1;
+    a.dst_slot = dst; a.phase_of = ph;
+    mode = FlushMode::Shared;
   }
+  a.share_flush = share ? 1 : 0;
   RB_TRY(ctx_arm_distinct(c, a, (size_t)N + 1));
   HIPCHK(launch_propagate(a, c->stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->timing_on) {
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, c->stream));
-  }
-  if (sip) {
-    StepArgs rd = a;
-    rd.phase = 0; rd.write_base = 0; HIPCHK(launch_step(rd, c->stream));   // readers over the old matrices
-    a.phase = 1; HIPCHK(launch_step(a, c->stream));                        // writers into entries nobody refers to
-    a.phase = 2; HIPCHK(launch_step(a, c->stream));                        // first writers, in place
-    if (c->timing_on) c->share_flush_particles += N;
-  } else if (two_phase) {
-    a.phase = 0; HIPCHK(launch_step(a, c->stream));
-    a.phase = 1; HIPCHK(launch_step(a, c->stream));
-  } else if (share) {
-    // Writers (the flush variant, one per parent with children) first, then their read-only siblings (the same pending sets; they
-    // point at their writer's new entry), one after the other.  (Measured r05 with diagnostic builds of commit 31144f4: both side by side on
-    // two streams 11.39 against 11.24 ms per step; one step of a STAGGERED flush -- a quarter of the families flushing beside three
-    // quarters of read-only particles -- 12.2 ms whether serial or concurrent, against the lock-step schedule's 11.66: DESIGN.md 9.)
-    a.phase = 1; HIPCHK(launch_step(a, c->stream));                 // writers: the flush variant
-    StepArgs rd = a;
-    rd.phase = 0; rd.write_base = 0;                                // readers: the read-only variant with the same pending sets
-    HIPCHK(launch_step(rd, c->stream));
-    if (c->timing_on) c->share_flush_particles += N;
-  } else {
-    HIPCHK(launch_step(a, c->stream));
-  }
-  if (c->timing_on) {
-    HIPCHK(hipEventRecord(e1, c->stream)); c->events.emplace_back(e0, e1);
-    ctx_account_launch(c, a);
-  }
+  RB_TRY(ctx_launch_step(c, a, bk, mode));
 
   NormArgs nm;
   nm.N = N; nm.nN = nN; nm.t = t; nm.logw = c->logw + tr; nm.w = c->w + tr; nm.wc = c->wc; nm.xn = X_new;
@@ -829,19 +850,15 @@ int ctx_step(rbpf_ctx* c, int k_iter, const double* xref_t, int n_draw, const In
     s.approx = 1; s.ambiguous = c->d_flags + 4; s.w = c->w + tr; s.wc_exact = c->wc;
     // sort key of the next step: the slot of the stored matrix each ancestor's lineage refers to
     if (N > kSingleWgResampleMaxN)
-      HIPCHK(launch_resample_pipeline(nm, &s, c->d_order, c->d_counts, lazy ? c->base[tnew] : nullptr, c->d_rs, c->stream));
+      HIPCHK(launch_resample_pipeline(nm, &s, c->d_order, c->d_counts, lazy ? c->base[bk.tnew] : nullptr, c->d_rs, c->stream));
     else
-      HIPCHK(launch_normalise_resample(nm, s, c->d_order, c->d_counts, c->stream, lazy ? c->base[tnew] : nullptr));
+      HIPCHK(launch_normalise_resample(nm, s, c->d_order, c->d_counts, c->stream, lazy ? c->base[bk.tnew] : nullptr));
     c->ready_step = t + 1;
   } else if (N > kSingleWgResampleMaxN) {
     HIPCHK(launch_resample_pipeline(nm, nullptr, nullptr, nullptr, nullptr, c->d_rs, c->stream));
   } else {
     HIPCHK(launch_normalise_scan(nm, c->stream));
   }
-  c->cur = nb;
-  c->xcur = lazy ? xn : nb;
-  if (lazy) c->tcur = tnew;
-  c->t = t + 1;
   return RBPF_OK;
 }
 
@@ -854,14 +871,8 @@ int ctx_unpack(rbpf_ctx* c, const int* d_index, int count, double* d_out) {
                            c->fp32 ? 1 : 0));
     return RBPF_OK;
   }
-  const int C = c->lazy_depth, B = C + 1, t = c->t;          // state after step t-1
-  const int ell = (t == 0) ? 0 : ((t - 1) % C) + 1;
-  const double* fset[kMaxSets]; const int* fidx[kMaxSets];
-  for (int q = 0; q < ell; ++q) {
-    const int bank = (t - ell + q) % B;
-    fset[q] = c->Fb[bank]; fidx[q] = c->fidx[c->tcur] + (size_t)bank * N;
-  }
-  HIPCHK(launch_unpack_P_sets(L, d, c->Pt[c->cur], c->Pb[c->cur], ell, fset, fidx, c->base[c->tcur], d_index, count, d_out, c->stream,
+  const PendingSets ps = ctx_pending_sets(c, N);
+  HIPCHK(launch_unpack_P_sets(L, d, c->Pt[c->cur], c->Pb[c->cur], ps.n, ps.fset, ps.fidx, c->base[c->tcur], d_index, count, d_out, c->stream,
                               c->fp32 ? 1 : 0));
   return RBPF_OK;
 }

@@ -10,8 +10,8 @@
 // O(n^2) flop and one read + one write of the factor), the augmented row carrying the forward solve along.  Every K-th step
 // the factor is recomputed from the exactly carried Imat by the factorisation kernels above ("refresh"), which bounds the
 // drift.  This changes the ARITHMETIC of the ancestor weights (not the algebra): the weights agree with the fresh
-// factorisation to the tolerance stated in DESIGN.md / tests/test_gpu_chol_carry.py; it is therefore an option, off by
-// default.
+// factorisation to the tolerance stated in DESIGN.md / tests/test_gpu_chol_carry.py.  It is the default (chol_refresh = 0 resolves
+// to K = 32) for the recognised dense family at 128 <= nLin <= 575; chol_refresh = 1 asks for the reference's own arithmetic.
 //
 // Sweep layout of a factor (per particle): rows 0..n-1 and the augmented row n, padded to NS slots of 64 rows; column k
 // keeps the slots k/64 .. NS-1 only (the rows above its diagonal block are zero), slot q at row 64 q + lane:

@@ -142,6 +142,50 @@ int generic_finish_inputs(rbpf_ctx* c, const double* xref_host);
 int ctx_call_on_step(rbpf_ctx* c, int t, bool is_smoother);
 void ctx_account_launch(rbpf_ctx* c, const StepArgs& a);
 int ctx_arm_distinct(rbpf_ctx* c, StepArgs& a, size_t keys);
+
+// Schedule of the multi-step lazy update (lazy_depth = C; C = 1 is the plain schedule, one pending set rewritten every step): with
+// t steps done the sets produced at steps t-ell .. t-1 are pending, set q in factor bank bank(q) of the C + 1; the step that finds
+// C of them rewrites the stored matrices (`flush`), and every step leaves its own set in self_bank().
+struct LazySched {
+  int ell, first, B;
+  bool flush;
+  int bank(int q) const { return (first + q) % B; }
+  int self_bank() const { return (first + ell) % B; }
+};
+// the sets pending FOR step t: what it applies
+inline LazySched lazy_for_step(int lazy_depth, int t) {
+  const int C = lazy_depth, ell = (t == 0) ? 0 : ((t - 1) % C) + 1;
+  return {ell, t - ell, C + 1, t == 0 || ell == C};
+}
+// the sets pending AFTER the last finished step, c->t - 1: what unpacking or packing the state as it stands has to apply
+inline LazySched lazy_after_last_step(const rbpf_ctx* c) { return lazy_for_step(c->lazy_depth, c->t); }
+// ... and where they are: set q of particle j is entry fidx[q][j] of fset[q] (N: particles of this context's banks)
+struct PendingSets { int n; const double* fset[kMaxSets]; const int* fidx[kMaxSets]; };
+inline PendingSets ctx_pending_sets(const rbpf_ctx* c, int N) {
+  const LazySched sc = lazy_after_last_step(c);
+  PendingSets p{};
+  p.n = sc.ell;
+  for (int q = 0; q < sc.ell; ++q) { p.fset[q] = c->Fb[sc.bank(q)]; p.fidx[q] = c->fidx[c->tcur] + (size_t)sc.bank(q) * N; }
+  return p;
+}
+
+// The shared flush (the children of one parent store ONE copy of their identical flushed matrix): the layouts whose step kernel
+// has the writer / reader variants, and the steps that can use them.
+bool layout_shares_flush(const Layout& L);
+bool step_shares_flush(const StepArgs& a);
+
+// What ctx_step (one GPU) and shard_step_impl (one rank of a sharded session) have in common.
+struct StepBanks { int ob, nb, xo, xn, told, tnew; bool flush; };   // covariance / mean / index-table banks read (old) and written (new) by a step
+// Everything of step t's StepArgs that does not depend on where the particles' states and ancestors live (N: local particles).
+StepBanks ctx_step_args(rbpf_ctx* c, int t, int k_iter, const double* xref_t, const InfoStep* info, int N, StepArgs& a);
+enum class FlushMode {
+  Plain,            // one launch
+  Shared,           // writers (phase 1), then their read-only siblings (phase 0)
+  InPlace,          // single bank: phases 0, 1
+  InPlaceShared     // single bank, shared: readers (phase 0), then phases 1 and 2
+};
+// The step launches after launch_propagate (timed when timing_on) and the commit of the banks and of t.
+int ctx_launch_step(rbpf_ctx* c, StepArgs& a, const StepBanks& bk, FlushMode mode);
 int ctx_unpack(rbpf_ctx* c, const int* d_index, int count, double* d_out);
 void smoother_free(rbpf_ctx* c);
 // in-library multi-device driver (rbpf_multi.hip): rbpf_options.n_devices

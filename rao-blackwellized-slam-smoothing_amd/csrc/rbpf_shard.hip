@@ -250,11 +250,9 @@ int rbpf_shard_pack(rbpf_ctx* c, const int32_t* idx_host, int32_t count) {
   const int ob = c->cur;
   if (c->lazy_depth >= 2) {
     // state after step t-1: ell pending sets per lineage; apply them while packing
-    const int C = c->lazy_depth, B = C + 1, t = c->t, N = s->Nloc;
-    const int ell = (t == 0) ? 0 : ((t - 1) % C) + 1;
-    const double* fset[kMaxSets]; const int* fidx[kMaxSets];
-    for (int q = 0; q < ell; ++q) { const int bank = (t - ell + q) % B; fset[q] = c->Fb[bank]; fidx[q] = c->fidx[c->tcur] + (size_t)bank * N; }
-    HIPCHK(launch_pack_records_flushed(c->lay, c->mdl.d, idx, count, c->Pt[ob], c->Pb[ob], ell, fset, fidx, c->base[c->tcur], N,
+    const int N = s->Nloc;
+    const PendingSets ps = ctx_pending_sets(c, N);
+    HIPCHK(launch_pack_records_flushed(c->lay, c->mdl.d, idx, count, c->Pt[ob], c->Pb[ob], ps.n, ps.fset, ps.fidx, c->base[c->tcur], N,
                                        s->recv_rec, s->recsz, c->xl[c->xcur], s->send_rec, c->stream, c->fp32 ? 1 : 0));
   } else {
     HIPCHK(launch_pack_records(c->lay, c->mdl.d, idx, count, c->Pt[ob], c->Pb[ob], c->F[ob], c->xl[ob], s->send_rec,
@@ -287,42 +285,17 @@ int rbpf::shard_step_impl(rbpf_ctx* c, const int32_t* anc_bank_host, const int32
   }
   if (t == 0 && (anc_bank_host || slot_ids_host)) { set_error("anc_bank / slot_ids must be NULL at t = 0"); return RBPF_ERR_INVALID_ARG; }
   const Layout& L = c->lay;
-  StepArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.mdl = c->mdl; a.lay = L; a.N = N; a.t = t; a.propagate = (t > 0);
-  a.n_sets = (t > 0) ? 1 : 0; a.write_base = 1;          // one pending set, rewritten every step
+  const bool lazy = c->lazy_depth >= 2;
+  if (lazy && t > 0 && !dev_plan) { set_error("lazy_depth >= 2 in the sharded filter needs the device planner"); return RBPF_ERR_UNSUPPORTED; }
+  StepArgs a{};
+  const StepBanks bk = ctx_step_args(c, t, k_iter, xref_t, info, N, a);
+  // what a rank does differently from one GPU: its slots are a window of the global particles (logical ids, global ancestor and
+  // state arrays), an ancestor may sit in a received record, and states + weights go out through fwd_local for the next collective
   a.slot_offset = s->rank * N;
   a.xn_new = s->fwd_local; a.xn_new_stride = (size_t)N;
   a.logw = s->fwd_local + (size_t)nN * N;
-  const bool lazy = c->lazy_depth >= 2;
-  if (lazy && t > 0 && !dev_plan) { set_error("lazy_depth >= 2 in the sharded filter needs the device planner"); return RBPF_ERR_UNSUPPORTED; }
-  const int ob = c->cur;
-  int nb = (t == 0) ? 0 : (c->cur ^ 1);
-  const int xo = c->xcur, xn = (t == 0) ? 0 : (c->xcur ^ 1);
-  const int told = c->tcur, tnew = c->tcur ^ 1;
-  bool flush = true;
-  a.zero_set_idx = N;
-  if (lazy) {
-    const int C = c->lazy_depth, B = C + 1;
-    const int ell = (t == 0) ? 0 : ((t - 1) % C) + 1;
-    flush = (t == 0) || (ell == C);
-    a.n_sets = ell; a.write_base = flush ? 1 : 0;
-    if (ell >= 3) a.lay = c->lay_low;
-    for (int q = 0; q < ell; ++q) {
-      const int bank = (t - ell + q) % B;
-      a.fset[q] = c->Fb[bank];
-      a.fset_idx_old[q] = c->fidx[told] + (size_t)bank * N;
-      a.fset_idx_new[q] = c->fidx[tnew] + (size_t)bank * N;
-    }
-    a.fself_idx_new = c->fidx[tnew] + (size_t)(t % B) * N;
-    a.base_old = (t > 0) ? c->base[told] : nullptr;
-    a.base_new = c->base[tnew];
-    if (!flush) nb = ob;
-  }
   if (t == 0) {
     a.xn_old = c->X; a.xn_old_stride = (size_t)N;           // filled with x0 by ctx_reset
-    a.xl_old = c->d_x0l; a.xl_old_stride = 0; a.F_old = nullptr;
-    a.Pt_old = c->d_P0t; a.Pb_old = c->d_P0b; a.Pt_old_stride = 0; a.Pb_old_stride = 0;
   } else {
     if (dev_plan) {
       a.slot_ids = s->pb.slot_ids;
@@ -335,8 +308,6 @@ int rbpf::shard_step_impl(rbpf_ctx* c, const int32_t* anc_bank_host, const int32
     }
     a.ai = s->ai_glob;                                       // indexed by logical slot id
     a.xn_old = s->xn_glob; a.xn_old_stride = (size_t)s->Nglob;
-    a.xl_old = c->xl[xo]; a.xl_old_stride = (size_t)L.ldx; a.F_old = lazy ? nullptr : c->F[ob];
-    a.Pt_old = c->Pt[ob]; a.Pb_old = c->Pb[ob]; a.Pt_old_stride = L.szT; a.Pb_old_stride = L.szB;
     a.n_bank_local = N;
     a.rec = s->recv_rec; a.rec_stride = s->recsz;
     const size_t per = c->fp32 ? 2 : 1;                      // stored elements per double in the covariance blocks
@@ -344,28 +315,10 @@ int rbpf::shard_step_impl(rbpf_ctx* c, const int32_t* anc_bank_host, const int32
     a.rec_off_I = s->rec_off_I; a.rec_off_hld = s->rec_off_hld;
     // the host places the new generation in ancestor order, so physical order is already cache-friendly
   }
-  a.xl_new = c->xl[xn]; a.F_new = lazy ? c->Fb[t % (c->lazy_depth + 1)] : c->F[nb];
-  a.Pt_new = c->Pt[nb]; a.Pb_new = c->Pb[nb];
-  a.fp32 = c->fp32 ? 1 : 0;
-  a.strip_ws = c->d_strip_ws; a.strip_ws_stride = c->strip_ws_stride;
-  a.rng_mode = c->rng_mode; a.k_iter = k_iter; a.seed = c->seed;
   a.Z = (c->d_Z && t > 0) ? c->d_Z + ((size_t)k_iter * std::max(c->T - 1, 0) + (size_t)(t - 1)) * s->Nglob * nw : nullptr;
-  a.xref = xref_t; a.xref_gslot = s->Nglob - 1;
-  a.info = info ? 1 : 0;
-  if (info) {
-    a.ivec_old = info->ivec_old; a.ivec_old_stride = info->ivec_old_stride; a.ivec_new = info->ivec_new;
-    a.hld_old = info->hld_old; a.hld_old_stride = info->hld_old_stride; a.hld_new = info->hld_new;
-    a.qf_new = info->qf_new; a.Hb_new = info->Hb_new;
-  }
-  a.odo = c->d_odo + (size_t)(t > 0 ? t - 1 : 0) * c->mdl.nodo;
-  a.cholQ = c->d_cholQ + (size_t)((c->chol_pages > 1 && t > 0) ? t - 1 : 0) * nw * nw;
-  a.y = c->d_y + (size_t)t * d;
-  a.status = c->d_flags;
-  a.stamps = nullptr;
-  a.pre_i = c->d_pre_i; a.pre_d = c->d_pre_d; a.u_next = nullptr;
-  a.phase = -1;                                            // (every slot; the shared flush below launches by phase)
+  a.xref_gslot = s->Nglob - 1;
   // shared flush (see ctx_step): the children of one parent -- one bank entry or one received record -- store ONE flushed matrix
-  const bool share = lazy && flush && t > 0 && dev_plan && L.sym && (L.CH64 == 8 || L.CH64 == 16) && a.n_sets >= 1 && a.n_sets <= (info ? 3 : 7);
+  const bool share = lazy && bk.flush && t > 0 && dev_plan && layout_shares_flush(L) && step_shares_flush(a);
   if (share) {
     const size_t keys = (size_t)N + s->recv_cap;
     if (s->share_keys < keys) {
@@ -381,18 +334,7 @@ int rbpf::shard_step_impl(rbpf_ctx* c, const int32_t* anc_bank_host, const int32
   }
   RB_TRY(ctx_arm_distinct(c, a, (size_t)N + s->recv_cap + 1));
   HIPCHK(launch_propagate(a, c->stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->timing_on) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, c->stream)); }
-  if (share) {
-    a.phase = 1; HIPCHK(launch_step(a, c->stream));                 // writers: the flush variant
-    StepArgs rd = a;
-    rd.phase = 0; rd.write_base = 0;                                // readers: the read-only variant with the same pending sets
-    HIPCHK(launch_step(rd, c->stream));
-    if (c->timing_on) c->share_flush_particles += N;
-  } else {
-    HIPCHK(launch_step(a, c->stream));
-  }
-  if (c->timing_on) { HIPCHK(hipEventRecord(e1, c->stream)); c->events.emplace_back(e0, e1); ctx_account_launch(c, a); }
+  RB_TRY(ctx_launch_step(c, a, bk, share ? FlushMode::Shared : FlushMode::Plain));
   // fwd_local feeds the next collective; host arrays (anc_bank / slot_ids) are caller memory behind asynchronous copies
   if (!s->async || anc_bank_host || slot_ids_host) HIPCHK(hipStreamSynchronize(c->stream));
   if (t > 0 && !dev_plan) s->host_planned = true;           // placement unknown to the library from here on (rbpf_shard_finish)
@@ -404,15 +346,11 @@ int rbpf::shard_step_impl(rbpf_ctx* c, const int32_t* anc_bank_host, const int32
   }
   if (lazy) {
     // records received for this step stay alive (imported lineages keep them as base) until the next flush
-    s->rec_used = flush ? 0 : s->rec_used + s->plan_recv;
+    s->rec_used = bk.flush ? 0 : s->rec_used + s->plan_recv;
     for (int q = 0; q < s->world; ++q)
-      s->rec_used_all[q] = flush ? 0 : s->rec_used_all[q] + (dev_plan ? (int)s->counts_pin[2 * s->world + 1 + q] : 0);
+      s->rec_used_all[q] = bk.flush ? 0 : s->rec_used_all[q] + (dev_plan ? (int)s->counts_pin[2 * s->world + 1 + q] : 0);
     s->plan_recv = 0;
-    c->tcur = tnew;
   }
-  c->cur = nb;
-  c->xcur = lazy ? xn : nb;
-  c->t = t + 1;
   return RBPF_OK;
 }
 
@@ -544,14 +482,11 @@ int rbpf::shard_unpack_particle(rbpf_ctx* c, int idx, double* dP) {
   RB_TRY(dmalloc(&didx, 1));
   hipError_t e = hipMemcpyAsync(didx, &idx, sizeof(int), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && c->lazy_depth >= 2) {
-    const int C = c->lazy_depth, B = C + 1, t = c->t;
-    const int ell = (t == 0) ? 0 : ((t - 1) % C) + 1;
-    const double* fset[kMaxSets]; const int* fidx[kMaxSets];
-    for (int q = 0; q < ell; ++q) { const int bank = (t - ell + q) % B; fset[q] = c->Fb[bank]; fidx[q] = c->fidx[c->tcur] + (size_t)bank * N; }
+    const PendingSets ps = ctx_pending_sets(c, N);
     double* rec = nullptr;
     int st = dmalloc(&rec, s->recsz);
     if (st != RBPF_OK) { hipFree(didx); return st; }
-    e = launch_pack_records_flushed(L, d, didx, 1, c->Pt[c->cur], c->Pb[c->cur], ell, fset, fidx, c->base[c->tcur], N, s->recv_rec,
+    e = launch_pack_records_flushed(L, d, didx, 1, c->Pt[c->cur], c->Pb[c->cur], ps.n, ps.fset, ps.fidx, c->base[c->tcur], N, s->recv_rec,
                                     s->recsz, c->xl[c->xcur], rec, c->stream, c->fp32 ? 1 : 0);
     const size_t per = c->fp32 ? 2 : 1;
     if (e == hipSuccess) e = launch_unpack_P(L, d, rec, rec + L.szT / per, nullptr, nullptr, 1, dP, c->stream, c->fp32 ? 1 : 0);
