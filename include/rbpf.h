@@ -304,7 +304,8 @@ typedef struct {
 int rbpf_abi_version(void);
 /* sizeof of the library's own view of an interface struct -- a binding in another language (ctypes, MEX, a MATLAB loadlibrary
  * prototype file) compares its mirror against it once at load time.  which: 0 rbpf_model, 1 rbpf_problem, 2 rbpf_rng, 3 rbpf_options,
- * 4 rbpf_filter_out, 5 rbpf_smoother_out, 6 rbpf_timing, 7 rbpf_callbacks, 8 rbpf_view; -1 for any other value.               */
+ * 4 rbpf_filter_out, 5 rbpf_smoother_out, 6 rbpf_timing, 7 rbpf_callbacks, 8 rbpf_view, 9 rbpf_loc_map, 10 rbpf_loc_problem,
+ * 11 rbpf_loc_out; -1 for any other value.                                                                                  */
 int rbpf_abi_sizeof(int32_t which);
 const char* rbpf_status_string(int status);
 /* Thread-local text of the last error raised on this thread (HIP error string, argument name). */
@@ -581,6 +582,77 @@ int rbpf_quat_helpers(int32_t op, int32_t n, const double* in, double* out);
  * folds + DPP row rotations) on its own, for the kernel-level test: in [4][64] (four values per lane of one wave64) -> out [4],
  * out[v] = sum over the 64 lanes of in[v][.] in the kernel's fixed association order.                                    */
 int rbpf_probe_wave_reduce(const double* in, double* out);
+
+/* ---- localisation in a fixed GP map (examples/mag-localization-mapping) --------------------------
+ * particleFilterLocalization.m:84-132 with the closures of run_localization.m:241-281: a particle filter over the
+ * 7 non-linear states (pos3 + quat4) that carries no map state.  The map is a posterior N(mean, P) over the n = m + 3
+ * coefficients of the dense-mag basis, handed over as the mean and a lower-triangular factor V with V'V = P.  Per step and
+ * particle i, with G_c(i) = row c of [e_c, d_c Phi(p_i)]:
+ *     dEft(i,c) = G_c(i) mean,   var(i,c) = |V G_c(i)'|^2   (or var_table(i,c), the reference's literal reading: quirk Q10),
+ *     w(i) = sum_c normpdf(y_t(c), (Rnb_i' dEft(i,:)')(c), sqrt(var(i,c) + sigma2))       -- a SUM of three densities
+ * dynModel (:274-281): pos + dx + sqrt(dt Q(1:3,1:3)) randn(3,1) with the ELEMENT-WISE square root, orientation
+ * qLeft(qRight(q) dq) expq(sqrt(dt Q(4:6,4:6)) randn(3,1)).  R of the reference signature is not used (:19).
+ * These structs are additions to ABI 9: each starts with its own struct_size (0 is accepted as in rbpf_options). */
+typedef struct {
+  int32_t struct_size;       /* sizeof(rbpf_loc_map) = rbpf_abi_sizeof(9)                                */
+  int32_t m_basis;           /* m; n = m + 3, 4 <= n <= 1151                                             */
+  const int32_t* NN;         /* [m x 3] column-major index table (domain_cartesian_dx.m:36-43)           */
+  double L[3];               /* domain half-widths                                                       */
+  const double* mean;        /* [n] posterior mean (`foo`, run_localization.m:151)                       */
+  const double* V;           /* [n x n] column-major, lower triangle read: V'V = P.  May be NULL         */
+  double sigma2;             /* measurement noise variance (theta(4))                                    */
+  const double* var_table;   /* [N_P x 3] column-major: slot i uses row i (run_localization.m:261-263,270). May be NULL; *
+                              * exactly one of V / var_table is set for the filter entry points          */
+} rbpf_loc_map;
+
+typedef struct {
+  int32_t struct_size;       /* sizeof(rbpf_loc_problem) = rbpf_abi_sizeof(10)                           */
+  int32_t N_P, N_T;          /* particles; time steps = size(y,1)                                        */
+  int32_t x0_cols;           /* 1 or N_P   (particleFilterLocalization.m:55-59)                          */
+  int32_t q_pages;           /* 1 or >= N_T-1  (:66-68)                                                  */
+  int32_t dt_len;            /* 1 or >= N_T-1  (:71-73)                                                  */
+  int32_t odo_ld;            /* leading dimension of odometry                                            */
+  const double* odometry;    /* [>= N_T-1 x 7]                                                           */
+  const double* y;           /* [N_T x 3]                                                                */
+  const double* x0_nonlin;   /* [7 x x0_cols]                                                            */
+  const double* Q;           /* [6 x 6 x q_pages]                                                        */
+  const double* dt;          /* [dt_len]                                                                 */
+} rbpf_loc_problem;
+
+/* Outputs of particleFilterLocalization (:1, :25-26) as of the last finished step (T_done columns are filled).  NULL
+ * pointers are skipped.                                                                                  */
+typedef struct {
+  int32_t struct_size;       /* sizeof(rbpf_loc_out) = rbpf_abi_sizeof(11)                               */
+  int32_t first_degenerate_step; /* OUT: -1, or the first 0-based t with sum(w) <= 1e-12 (:113-115)      */
+  double* traj_max;          /* [7 x N_T]                                                                */
+  double* traj_mean;         /* [7 x N_T] (quaternion rows included, not renormalised: :123)             */
+  /* extras */
+  double* trace_logw;        /* [N_P x N_T] log of the unnormalised weights (needs trace)                */
+  double* trace_w;           /* [N_P x N_T] (needs trace)                                                */
+  int32_t* trace_ai;         /* [N_P x N_T] 0-based, column 0 unused (needs keep_history)                */
+  double* final_xn;          /* [7 x N_P]                                                                */
+  double* xn_traj;           /* [7 x N_P x N_T] (needs keep_history): :101-104, traced back on request   */
+  double* log_sum_w;         /* [N_T] log(sum(w)) before the normalisation of :118                       */
+} rbpf_loc_out;
+
+/* One shot.  Of `opt` only struct_size, keep_history, trace, on_step / on_step_user are read (jitter is ignored); any
+ * other non-zero field is RBPF_ERR_UNSUPPORTED (n_devices > 1 included).  on_step: view->ctx is valid for rbpf_loc_finish. */
+int rbpf_particle_filter_localization(const rbpf_loc_map* map, const rbpf_loc_problem* prob, const rbpf_rng* rng,
+                                      const rbpf_options* opt, rbpf_loc_out* out);
+/* Resident form: rbpf_sync, rbpf_filter_tell and rbpf_destroy work on the context.                      */
+int rbpf_loc_create(const rbpf_loc_map* map, const rbpf_loc_problem* prob, const rbpf_rng* rng, const rbpf_options* opt,
+                    rbpf_ctx** ctx);
+int rbpf_loc_advance(rbpf_ctx* ctx, int32_t n_steps);
+int rbpf_loc_finish(rbpf_ctx* ctx, rbpf_loc_out* out);
+/* Bytes of device memory such a context needs (no device access).                                       */
+int rbpf_loc_workspace_bytes(const rbpf_loc_map* map, const rbpf_loc_problem* prob, const rbpf_options* opt, size_t* bytes);
+/* The prediction kernel on its own: xn [7 x n_pred] -> dEft [3 x n_pred], var [3 x n_pred] (var and map->V may be NULL:
+ * means only; map->var_table is not read).  reps >= 1 repeats the launch; *ms (may be NULL) = median kernel time.       */
+int rbpf_loc_predict(const rbpf_loc_map* map, int32_t n_pred, const double* xn, double* dEft, double* var, int32_t reps,
+                     double* ms);
+/* dynModel of run_localization.m:274-281 with injected normals: xn [7 x n_p], odo [7], z [6 x n_p] -> xn_next [7 x n_p]. */
+int rbpf_loc_dyn_model(int32_t n_p, const double* xn, const double* odo, double dt, const double* Q, const double* z,
+                       double* xn_next);
 
 #ifdef __cplusplus
 }

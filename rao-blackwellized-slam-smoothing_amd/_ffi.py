@@ -99,8 +99,35 @@ class rbpf_timing(C.Structure):
                 ("algorithmic_bytes_per_launch", C.c_double), ("scheduled_bytes_per_launch", C.c_double)]
 
 
+class _SizedStructure(C.Structure):
+    """The localisation structs start with their own struct_size (include/rbpf.h)."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_size" not in kw and not args:
+            self.struct_size = C.sizeof(type(self))
+
+
+class rbpf_loc_map(_SizedStructure):
+    _fields_ = [("struct_size", C.c_int32), ("m_basis", C.c_int32), ("NN", c_int32_p), ("L", C.c_double * 3),
+                ("mean", c_double_p), ("V", c_double_p), ("sigma2", C.c_double), ("var_table", c_double_p)]
+
+
+class rbpf_loc_problem(_SizedStructure):
+    _fields_ = [("struct_size", C.c_int32), ("N_P", C.c_int32), ("N_T", C.c_int32), ("x0_cols", C.c_int32),
+                ("q_pages", C.c_int32), ("dt_len", C.c_int32), ("odo_ld", C.c_int32), ("odometry", c_double_p),
+                ("y", c_double_p), ("x0_nonlin", c_double_p), ("Q", c_double_p), ("dt", c_double_p)]
+
+
+class rbpf_loc_out(_SizedStructure):
+    _fields_ = [("struct_size", C.c_int32), ("first_degenerate_step", C.c_int32), ("traj_max", c_double_p),
+                ("traj_mean", c_double_p), ("trace_logw", c_double_p), ("trace_w", c_double_p), ("trace_ai", c_int32_p),
+                ("final_xn", c_double_p), ("xn_traj", c_double_p), ("log_sum_w", c_double_p)]
+
+
 # rbpf_abi_sizeof(which): the mirrors in the order of its `which` argument
-ABI_STRUCTS = [rbpf_model, rbpf_problem, rbpf_rng, rbpf_options, rbpf_filter_out, rbpf_smoother_out, rbpf_timing, rbpf_callbacks, rbpf_view]
+ABI_STRUCTS = [rbpf_model, rbpf_problem, rbpf_rng, rbpf_options, rbpf_filter_out, rbpf_smoother_out, rbpf_timing, rbpf_callbacks, rbpf_view,
+               rbpf_loc_map, rbpf_loc_problem, rbpf_loc_out]
 
 # every symbol include/rbpf.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTS = [
@@ -117,6 +144,8 @@ EXPORTS = [
     "rbpf_shard_smoother_normalise", "rbpf_shard_smoother_anc_weights", "rbpf_shard_smoother_anc_sample",
     "rbpf_shard_smoother_refresh_begin", "rbpf_shard_smoother_refresh_pack", "rbpf_shard_smoother_refresh_end",
     "rbpf_shard_smoother_step", "rbpf_shard_smoother_end",
+    "rbpf_particle_filter_localization", "rbpf_loc_create", "rbpf_loc_advance", "rbpf_loc_finish", "rbpf_loc_workspace_bytes",
+    "rbpf_loc_predict", "rbpf_loc_dyn_model",
 ]
 
 ABI_VERSION = 9            # RBPF_ABI_VERSION of include/rbpf.h this mirror was written against
@@ -211,6 +240,16 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_quat_helpers.argtypes = [C.c_int32, C.c_int32, c_double_p, c_double_p]
     lib.rbpf_chol_refresh_resolve.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.rbpf_chol_refresh_resolve.restype = C.c_int32
+    lib.rbpf_particle_filter_localization.argtypes = [C.POINTER(rbpf_loc_map), C.POINTER(rbpf_loc_problem), C.POINTER(rbpf_rng),
+                                                      C.POINTER(rbpf_options), C.POINTER(rbpf_loc_out)]
+    lib.rbpf_loc_create.argtypes = [C.POINTER(rbpf_loc_map), C.POINTER(rbpf_loc_problem), C.POINTER(rbpf_rng),
+                                    C.POINTER(rbpf_options), C.POINTER(C.c_void_p)]
+    lib.rbpf_loc_advance.argtypes = [C.c_void_p, C.c_int32]
+    lib.rbpf_loc_finish.argtypes = [C.c_void_p, C.POINTER(rbpf_loc_out)]
+    lib.rbpf_loc_workspace_bytes.argtypes = [C.POINTER(rbpf_loc_map), C.POINTER(rbpf_loc_problem), C.POINTER(rbpf_options),
+                                             C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_predict.argtypes = [C.POINTER(rbpf_loc_map), C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_dyn_model.argtypes = [C.c_int32, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p]
     _lib = lib
     return lib
 

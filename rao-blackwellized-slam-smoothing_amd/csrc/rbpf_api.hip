@@ -483,6 +483,7 @@ void ctx_free(rbpf_ctx* c) {
   hipFree(c->traj_max); hipFree(c->traj_mean); hipFree(c->d_scal); hipFree(c->d_flags); hipFree(c->d_order); hipFree(c->d_counts); hipFree(c->d_pre_i); hipFree(c->d_pre_d); hipFree(c->d_unext); hipFree(c->d_rs);
   smoother_free(c);
   shard_free(c);
+  loc_free(c);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -958,6 +959,9 @@ int rbpf_abi_sizeof(int32_t which) {
     case 6: return (int)sizeof(rbpf_timing);
     case 7: return (int)sizeof(rbpf_callbacks);
     case 8: return (int)sizeof(rbpf_view);
+    case 9: return (int)sizeof(rbpf_loc_map);
+    case 10: return (int)sizeof(rbpf_loc_problem);
+    case 11: return (int)sizeof(rbpf_loc_out);
     default: return -1;
   }
 }

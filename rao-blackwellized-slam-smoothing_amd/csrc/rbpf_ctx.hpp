@@ -21,6 +21,7 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 
 struct SmootherState;   // rbpf_smoother.hip
 struct ShardState;      // rbpf_shard.hip
+struct LocState;        // rbpf_loc.hip
 
 // extra capacity requested by the sharded filter
 struct CreateExtras {
@@ -111,6 +112,7 @@ struct rbpf_ctx {
   double sched_bytes = 0.0;  // bytes the timed launches had to move (rbpf_timing.scheduled_bytes_per_launch)
   rbpf::SmootherState* sm = nullptr;
   rbpf::ShardState* sh = nullptr;
+  rbpf::LocState* loc = nullptr;   // localisation in a fixed map (rbpf_loc_*): the map and the per-step noise factors
   double* d_rs = nullptr;    // scratch of the multi-workgroup resample pipeline
   double* d_unext = nullptr; // [N] Philox resampling uniforms of the next step (written by propagate_kernel)
   int* d_pre_i = nullptr;   // [N][kPreInts]  per-workgroup descriptors of the step kernel
@@ -207,5 +209,6 @@ int multi_particle_filter(const rbpf_model* model, const rbpf_problem* prob, con
 int multi_particle_smoother(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng, const rbpf_options* opt,
                             int32_t N_K, int32_t info_form, rbpf_smoother_out* out);
 void shard_free(rbpf_ctx* c);
+void loc_free(rbpf_ctx* c);
 
 }  // namespace rbpf

@@ -240,6 +240,8 @@ hipError_t launch_share_plan(int N, int nkeys, const int* ai, int* lead, int* ds
 size_t resample_scratch_doubles(int N);
 hipError_t launch_resample_pipeline(const NormArgs& nm, const SearchArgs* sa, int* order, int* counts, const int* remap,
                                     double* scratch, hipStream_t s);
+// log(sum(exp(logw))) of the pipeline's last normalisation, from its scratch (what rs_weights_kernel subtracted)
+hipError_t launch_resample_lse(int N, const double* scratch, double* out, hipStream_t s);
 constexpr int kMaxParticles = 1024 * 1024;     // largest global particle count (rs_offsets_kernel: <= 1024 blocks of 1024)
 constexpr int kSingleWgResampleMaxN = 8192;   // above this the multi-workgroup pipeline is used
 // exact re-draw of every slot with the strict left-to-right cumsum if any draw was flagged ambiguous

@@ -219,6 +219,19 @@ hipError_t launch_resample_pipeline(const NormArgs& nm, const SearchArgs* sa, in
   return e;
 }
 
+__global__ void rs_lse_kernel(int B, const double* __restrict__ pmax, const double* __restrict__ psum, double* __restrict__ out) {
+  double c = -INFINITY, t = 0.0;
+  for (int b = 0; b < B; ++b) c = fmax(c, pmax[b]);
+  for (int b = 0; b < B; ++b) t += psum[b];                                     // the order of rs_weights_kernel
+  *out = c + log(t);
+}
+
+hipError_t launch_resample_lse(int N, const double* scratch, double* out, hipStream_t s) {
+  const int B = (N + kRB - 1) / kRB;
+  hipLaunchKernelGGL(rs_lse_kernel, dim3(1), dim3(1), 0, s, B, scratch, scratch + B, out);
+  return hipGetLastError();
+}
+
 // counting sort of n_slots slots by remap[key[i]] over `range` key values, multi-workgroup (histogram, scan, scatter);
 // counts: >= range ints of scratch
 hipError_t launch_order_large(int n_slots, int range, const int* key, const int* remap, int* order, int* counts, hipStream_t s) {

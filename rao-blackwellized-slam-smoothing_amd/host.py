@@ -934,3 +934,298 @@ class FilterSession:
 
     def __exit__(self, *a):
         self.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# localisation in a fixed GP map: examples/mag-localization-mapping
+# ------------------------------------------------------------------------------------------------
+def _grad_rows(NN, L, x):
+    """Rows of [e_c, d_c Phi(x)] for c = x, y, z: three [N x (m + 3)] arrays (run_localization.m:135-142; per-axis tables
+    instead of tools/domain_cartesian_dx.m:146-170's m x d loops, same products)."""
+    NN = np.asarray(NN, dtype=np.int64)
+    L = np.asarray(L, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    S, Cc, D = [], [], []
+    for a in range(3):
+        arg = np.pi * NN[None, :, a] * (x[:, a:a + 1] + L[a]) / (2.0 * L[a])
+        S.append(1.0 / math.sqrt(L[a]) * np.sin(arg))
+        Cc.append(np.pi * NN[None, :, a] / (2.0 * L[a] * math.sqrt(L[a])) * np.cos(arg))
+    N, m = x.shape[0], NN.shape[0]
+    rows = []
+    for c in range(3):
+        v = np.ones((N, m))
+        for a in range(3):
+            v = v * (Cc[a] if a == c else S[a])
+        lin = np.zeros((N, 3))
+        lin[:, c] = 1.0
+        rows.append(np.hstack((lin, v)))
+    return rows
+
+
+class DenseMagMap:
+    """A fixed map of the dense-mag family: the posterior N(mean, V'V) over the m + 3 basis coefficients, as the SLAM filter /
+    smoothers return it (xl_max, P_max / XLK, PK) or as the batch regression of run_localization.m:134-151 computes it.  Its
+    `dynModel` / `measModel` are the closures of run_localization.m:274-281 / :241-272 and are recognised by
+    particleFilterLocalization.
+
+    var_points=None: every particle gets the predictive variance at its own position (the evident intent of :261-263).
+    var_points=[>= N_P x 3]: the reference's literal behaviour (quirk Q10): the variances at those points are computed once on
+    the device and particle slot i uses row i."""
+
+    def __init__(self, model, mean, V, sigma2, var_points=None):
+        if not isinstance(model, DenseMagModel):
+            raise TypeError("DenseMagMap needs a DenseMagModel")
+        self.model = model
+        n = model.nLin
+        self.mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).ravel())
+        self.V = np.asfortranarray(np.tril(np.asarray(V, dtype=np.float64)))
+        self.sigma2 = float(sigma2)
+        if self.mean.size != n or self.V.shape != (n, n):
+            raise ValueError("mean must be [m + 3] and V [(m + 3) x (m + 3)]")
+        self.var_points = None if var_points is None else np.asarray(var_points, dtype=np.float64).reshape(-1, 3)
+        self._var_table = None
+        self.dynModel = _Handle(self, "dynModel")
+        self.measModel = _Handle(self, "measModel")
+
+    @classmethod
+    def from_posterior(cls, model, xl, P, sigma2, var_points=None):
+        """From a map posterior (mean xl, covariance P).  V = lower factor with V'V = P: the transposed Cholesky factor of the
+        index-reversed matrix, reversed back."""
+        P = np.asarray(P, dtype=np.float64)
+        P = 0.5 * (P + P.T)
+        try:
+            Cr = np.linalg.cholesky(P[::-1, ::-1])
+        except np.linalg.LinAlgError as exc:
+            raise ValueError("P is not positive definite") from exc
+        return cls(model, xl, Cr.T[::-1, ::-1], sigma2, var_points)
+
+    @classmethod
+    def from_data(cls, model, x, y, theta, var_points=None):
+        """Batch GP regression of run_localization.m:119-151: x [N x 3] positions (domain coordinates), y [N x 3] field
+        measurements in the navigation frame, theta = (linSigma2, lengthScale, magnSigma2, sigma2)."""
+        linSigma2, lengthScale, magnSigma2, sigma2 = (float(t) for t in np.asarray(theta).ravel())
+        lam = eigenval(model.NN, model.L)
+        k = np.concatenate(([linSigma2] * 3, magnSigma2 * math.sqrt(2 * math.pi) ** 3 * lengthScale ** 3 * np.exp(-lam * lengthScale ** 2 / 2)))
+        Phi = np.vstack(_grad_rows(model.NN, model.L, x))                                   # :145
+        y = np.asarray(y, dtype=np.float64).reshape(-1, 3)
+        Phiy = Phi.T @ y.reshape(-1, order="F")                                              # :147
+        Lc = np.linalg.cholesky(Phi.T @ Phi + np.diag(sigma2 / k))                           # :150
+        import scipy.linalg as sla
+        foo = sla.solve_triangular(Lc.T, sla.solve_triangular(Lc, Phiy, lower=True), lower=False)   # :151
+        V = math.sqrt(sigma2) * sla.solve_triangular(Lc, np.eye(Lc.shape[0]), lower=True)   # dVarft = sigma2 |L \ g|^2 (:261)
+        return cls(model, foo, V, sigma2, var_points)
+
+    def _map_struct(self, table=None, with_V=True):
+        mp = _ffi.rbpf_loc_map()
+        mp.m_basis = self.model.m
+        self._nn_f = np.asfortranarray(self.model.NN)
+        mp.NN = _ip(self._nn_f)
+        for a in range(3):
+            mp.L[a] = float(self.model.L[a])
+        mp.mean = _dp(self.mean)
+        mp.sigma2 = self.sigma2
+        if table is not None:
+            mp.var_table = _dp(table)
+        elif with_V:
+            mp.V = _dp(self.V)
+        return mp
+
+    def predict(self, xn, reps=1, want_var=True):
+        """The prediction kernel on its own (rbpf_loc_predict): xn [7 x n_pred] (or [3 x n_pred] positions) ->
+        (dEft [n_pred x 3], var [n_pred x 3], median kernel ms)."""
+        lib = load_library()
+        xn = np.asarray(xn, dtype=np.float64)
+        if xn.shape[0] == 3:
+            xn = np.vstack((xn.reshape(3, -1), np.tile(np.array([[1.0], [0.0], [0.0], [0.0]]), (1, xn.reshape(3, -1).shape[1]))))
+        xn = np.asfortranarray(xn.reshape(7, -1))
+        npred = xn.shape[1]
+        dE = np.empty((3, npred), order="F")
+        var = np.empty((3, npred), order="F") if want_var else None
+        ms = C.c_double(0.0)
+        mp = self._map_struct(with_V=want_var)
+        check(lib.rbpf_loc_predict(C.byref(mp), npred, _dp(xn), _dp(dE), _dp(var) if want_var else None, int(reps), C.byref(ms)))
+        return dE.T.copy(), (var.T.copy() if want_var else None), ms.value
+
+    def _loc_map(self, N_P):
+        """rbpf_loc_map for a run with N_P particles (the variance table of var_points is computed here, once)."""
+        if self.var_points is None:
+            return self._map_struct()
+        if self.var_points.shape[0] < N_P:
+            raise ValueError(f"var_points has {self.var_points.shape[0]} rows, fewer than N_P = {N_P} (index out of bounds in the reference)")
+        _, var, _ = self.predict(self.var_points[:N_P].T)
+        self._var_table = np.asfortranarray(var)                                            # [N_P x 3]
+        return self._map_struct(table=self._var_table)
+
+    def _evaluate(self, role, *args):
+        if role == "dynModel":
+            xn, dx, dt, Q, z = args
+            lib = load_library()
+            xn = np.asfortranarray(np.asarray(xn, dtype=np.float64).reshape(7, -1))
+            npar = xn.shape[1]
+            z = np.asfortranarray(np.asarray(z, dtype=np.float64).reshape(6, npar))
+            dx = np.ascontiguousarray(np.asarray(dx, dtype=np.float64).ravel())
+            Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(6, 6))
+            out = np.empty_like(xn)
+            check(lib.rbpf_loc_dyn_model(npar, _dp(xn), _dp(dx), float(dt), _dp(Q), _dp(z), _dp(out)))
+            return out[:, 0] if npar == 1 else out
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "the localisation measModel is only evaluated inside particleFilterLocalization")
+
+
+class _LocProblem:
+    def __init__(self, odometry, y, x0_nonLin, Q, N_P, dt):
+        y = np.asarray(y, dtype=np.float64)
+        self.N_T, self.N_P = y.shape[0], int(N_P)
+        if y.ndim != 2 or y.shape[1] != 3:
+            raise ValueError("y must be [N_T x 3]")
+        self.y = np.asfortranarray(y)
+        odo = np.asarray(odometry, dtype=np.float64)
+        self.odo = np.asfortranarray(odo.reshape(1, -1) if odo.ndim == 1 else odo)
+        x0 = np.asarray(x0_nonLin, dtype=np.float64)
+        self.x0 = np.asfortranarray(x0.reshape(7, -1))
+        if self.x0.shape[1] not in (1, self.N_P):
+            raise ValueError("x0_nonLin must be [7] or [7 x N_P]")
+        Q = np.asarray(Q, dtype=np.float64)
+        self.Q = np.asfortranarray(Q[:, :, None] if Q.ndim == 2 else Q)
+        self.dt = np.ascontiguousarray(np.atleast_1d(np.asarray(dt, dtype=np.float64)).ravel())
+        if self.Q.shape[:2] != (6, 6):
+            raise ValueError("Q must be [6 x 6] or [6 x 6 x >= N_T-1]")
+        if self.N_T > 1 and (self.odo.shape[0] < self.N_T - 1 or self.odo.shape[1] != 7):
+            raise ValueError("odometry must be [>= N_T-1 x 7]")
+        p = _ffi.rbpf_loc_problem()
+        p.N_P, p.N_T, p.x0_cols, p.q_pages, p.dt_len = self.N_P, self.N_T, self.x0.shape[1], self.Q.shape[2], self.dt.size
+        p.odo_ld = self.odo.shape[0]
+        p.odometry, p.y, p.x0_nonlin, p.Q, p.dt = _dp(self.odo), _dp(self.y), _dp(self.x0), _dp(self.Q), _dp(self.dt)
+        self.c = p
+
+
+def _recognise_map(dynModel, measModel):
+    mp = getattr(dynModel, "model", None)
+    if not isinstance(mp, DenseMagMap) or getattr(measModel, "model", None) is not mp:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleFilterLocalization runs the handles of a DenseMagMap; a host-callback "
+                        "family for arbitrary localisation handles is not implemented")
+    return mp
+
+
+def _loc_out(N, T, Td, extras, hist=True, trace=True):
+    o = _ffi.rbpf_loc_out()
+    b = dict(traj_max=np.full((7, T), np.nan, order="F"), traj_mean=np.full((7, T), np.nan, order="F"))
+    if extras:
+        b.update(final_xn=np.empty((7, N), order="F"), log_sum_w=np.empty(Td))
+        if trace:
+            b.update(trace_logw=np.empty((N, Td), order="F"), trace_w=np.empty((N, Td), order="F"))
+        if hist:
+            b.update(trace_ai=np.zeros((N, Td), dtype=np.int32, order="F"), xn_traj=np.empty((7, N, Td), order="F"))
+    for k, v in b.items():
+        setattr(o, k, _ip(v) if v.dtype == np.int32 else _dp(v))
+    return o, b
+
+
+def particleFilterLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, dt, makePlots=None, *, rng=None,
+                               extras=False, n_devices=0, lazy_depth=0):
+    """Mirror of examples/mag-localization-mapping/particleFilterLocalization.m:1-2 -> (traj_max, traj_mean[, extras]).
+    dynModel / measModel are the handles of a DenseMagMap; R is accepted and not used (:19).  makePlots(xn, traj_max, yhattraj,
+    xn_traj, traj_mean) is called after every step (:129-131).  A step whose weights sum to <= 1e-12 raises a RuntimeWarning
+    with the reference's text (:113-115) and the run carries on."""
+    import warnings
+    mp = _recognise_map(dynModel, measModel)
+    lib = load_library()
+    prob = _LocProblem(odometry, y, x0_nonLin, Q, N_P, dt)
+    N, T = prob.N_P, prob.N_T
+    if lib.rbpf_device_count() < 1:
+        raise RBPFError(_ffi.RBPF_ERR_NO_DEVICE, "no HIP device: the localisation filter has no CPU fallback")
+    opt = _ffi.rbpf_options(keep_history=1, trace=1 if extras else 0, n_devices=int(n_devices), lazy_depth=int(lazy_depth))
+    if opt.n_devices or opt.lazy_depth:
+        mstruct = mp._map_struct()                                   # refused by the library before anything is computed
+    else:
+        mstruct = mp._loc_map(N)
+    blk, _keep = _rng_block(rng, N, T, 6, 1)
+    hook_error = []
+    if makePlots is not None:
+        def on_step(view_p, _user):
+            try:
+                v = view_p.contents
+                t = int(v.t)
+                o, b = _loc_out(N, T, t + 1, True, trace=False)
+                check(lib.rbpf_loc_finish(C.c_void_p(v.ctx), C.byref(o)))
+                xn_traj = np.zeros((7, N, T))
+                xn_traj[:, :, :t + 1] = b["xn_traj"]
+                makePlots(b["final_xn"], b["traj_max"], np.full((3, T), np.nan), xn_traj, b["traj_mean"])
+                return 0
+            except Exception as exc:                                                      # noqa: BLE001
+                hook_error.append(exc)
+                return 1
+        hook = _ffi.ON_STEP_FN(on_step)
+        opt.on_step = hook
+    ctx = C.c_void_p()
+    check(lib.rbpf_loc_create(C.byref(mstruct), C.byref(prob.c), C.byref(blk), C.byref(opt), C.byref(ctx)))
+    try:
+        try:
+            check(lib.rbpf_loc_advance(ctx, T))
+        except RBPFError as exc:
+            if exc.status == _ffi.RBPF_ERR_CALLBACK and hook_error:
+                raise hook_error[0] from exc
+            raise
+        o, b = _loc_out(N, T, T, extras)
+        check(lib.rbpf_loc_finish(ctx, C.byref(o)))
+    finally:
+        lib.rbpf_destroy(ctx)
+    if o.first_degenerate_step >= 0:
+        warnings.warn(f"Weights filter close to zero at t={o.first_degenerate_step + 1} !!!", RuntimeWarning, stacklevel=2)
+    if extras:
+        ex = dict(logw=b["trace_logw"].T.copy(), w=b["trace_w"].T.copy(), ai=b["trace_ai"].T.copy(), xn=b["final_xn"],
+                  xn_traj=b["xn_traj"], log_sum_w=b["log_sum_w"], first_degenerate_step=int(o.first_degenerate_step))
+        return b["traj_max"], b["traj_mean"], ex
+    return b["traj_max"], b["traj_mean"]
+
+
+def loc_workspace_bytes(map_struct, prob_struct, opt=None):
+    """rbpf_loc_workspace_bytes (no device access)."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_workspace_bytes(C.byref(map_struct), C.byref(prob_struct), C.byref(opt) if opt is not None else None,
+                                       C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+class LocalizationSession:
+    """rbpf_loc_create / advance / sync / finish / destroy: the counterpart of FilterSession for the localisation filter."""
+
+    def __init__(self, loc_map, odometry, y, x0_nonLin, Q, N_P, dt, rng=None, keep_history=False, trace=False):
+        self.lib = load_library()
+        self.map = loc_map
+        self.prob = _LocProblem(odometry, y, x0_nonLin, Q, N_P, dt)
+        self.mstruct = loc_map._loc_map(self.prob.N_P)
+        self.blk, self._rng = _rng_block(rng, self.prob.N_P, self.prob.N_T, 6, 1)
+        self.opt = _ffi.rbpf_options(keep_history=1 if keep_history else 0, trace=1 if trace else 0)
+        self.hist = bool(keep_history)
+        self.ctx = C.c_void_p()
+        check(self.lib.rbpf_loc_create(C.byref(self.mstruct), C.byref(self.prob.c), C.byref(self.blk), C.byref(self.opt),
+                                       C.byref(self.ctx)))
+
+    def advance(self, n_steps):
+        check(self.lib.rbpf_loc_advance(self.ctx, int(n_steps)))
+
+    def sync(self):
+        check(self.lib.rbpf_sync(self.ctx))
+
+    def tell(self):
+        t = C.c_int32(0)
+        check(self.lib.rbpf_filter_tell(self.ctx, C.byref(t)))
+        return t.value
+
+    def finish(self, extras=False):
+        o, b = _loc_out(self.prob.N_P, self.prob.N_T, self.tell(), extras, self.hist, bool(self.opt.trace))
+        check(self.lib.rbpf_loc_finish(self.ctx, C.byref(o)))
+        b["first_degenerate_step"] = int(o.first_degenerate_step)
+        return b
+
+    def close(self):
+        if self.ctx:
+            self.lib.rbpf_destroy(self.ctx)
+            self.ctx = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
