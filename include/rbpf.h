@@ -312,6 +312,9 @@ const char* rbpf_status_string(int status);
 const char* rbpf_last_error(void);
 /* Number of visible gfx950 devices (0 when none; never touches a device).                        */
 int rbpf_device_count(void);
+/* Bytes of device memory this process's sessions and calls own right now: back to its earlier value once they are destroyed /
+ * have returned, successfully or not (a leak check that does not depend on what else runs on the device).                   */
+int64_t rbpf_device_bytes_live(void);
 
 /* ---- one-shot entry points: what the MEX gateway binds ----------------------------------------- */
 /* Replaces src/particleFilter.m:1-3 for the recognised model families (dense branch).             */

@@ -131,7 +131,7 @@ ABI_STRUCTS = [rbpf_model, rbpf_problem, rbpf_rng, rbpf_options, rbpf_filter_out
 
 # every symbol include/rbpf.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTS = [
-    "rbpf_abi_version", "rbpf_abi_sizeof", "rbpf_status_string", "rbpf_last_error", "rbpf_device_count",
+    "rbpf_abi_version", "rbpf_abi_sizeof", "rbpf_status_string", "rbpf_last_error", "rbpf_device_count", "rbpf_device_bytes_live",
     "rbpf_particle_filter", "rbpf_particle_smoother",
     "rbpf_filter_create", "rbpf_filter_workspace_bytes", "rbpf_filter_advance", "rbpf_filter_reset", "rbpf_sync",
     "rbpf_filter_finish", "rbpf_filter_tell", "rbpf_filter_schedule", "rbpf_plan_refresh", "rbpf_chol_refresh_resolve", "rbpf_shard_smoother_refresh_reserve", "rbpf_shard_xn_traj", "rbpf_filter_ancestors", "rbpf_filter_step_external", "rbpf_timing_enable", "rbpf_timing_read", "rbpf_destroy",
@@ -203,6 +203,7 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_status_string.restype = C.c_char_p
     lib.rbpf_status_string.argtypes = [C.c_int]
     lib.rbpf_last_error.restype = C.c_char_p
+    lib.rbpf_device_bytes_live.restype = C.c_int64
     lib.rbpf_particle_filter.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem), C.POINTER(rbpf_rng),
                                          C.POINTER(rbpf_options), C.POINTER(rbpf_filter_out)]
     lib.rbpf_particle_smoother.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem), C.POINTER(rbpf_rng),

@@ -30,7 +30,7 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line) {
   return (e == hipErrorOutOfMemory) ? RBPF_ERR_OUT_OF_MEMORY : RBPF_ERR_HIP;
 }
 
-static bool chol_lower_host(const double* A, int n, int lda, double* Lc, int ldl) {
+bool chol_lower_host(const double* A, int n, int lda, double* Lc, int ldl) {
   for (int j = 0; j < n; ++j) {
     double s = A[j + (size_t)lda * j];
     for (int k = 0; k < j; ++k) s -= Lc[j + (size_t)ldl * k] * Lc[j + (size_t)ldl * k];
@@ -188,23 +188,6 @@ static int validate_problem(const rbpf_problem* p) {
   return RBPF_OK;
 }
 
-template <typename T>
-static int dmalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) return RBPF_OK;
-  hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-  if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-  return RBPF_OK;
-}
-
-#define RB_TRY(x) do { int _s = (x); if (_s != RBPF_OK) return _s; } while (0)
-
-
-static bool have_device() {
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
 static size_t bank_bytes(const Layout& L, int d, int N) {
   return ((size_t)N * (L.szT + L.szB) + (size_t)N * 2 * d * L.ldx + (size_t)N * L.ldx) * sizeof(double);
 }
@@ -255,8 +238,8 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
       c->cb = *model->callbacks; c->has_cb = true;
       if (!c->cb.dyn_model || !c->cb.meas_model) { set_error("generic model: callbacks need dyn_model and meas_model"); return RBPF_ERR_INVALID_ARG; }
     } else if (smoother) { set_error("generic (host-callback) smoothers need rbpf_model.callbacks"); return RBPF_ERR_INVALID_ARG; }
-    RB_TRY(dmalloc(&c->d_xn_ext, (size_t)prob->n_nonlin * prob->N_P));
-    RB_TRY(dmalloc(&c->d_H_ext, (size_t)prob->N_P * prob->n_y * c->lay.ldx));
+    RB_TRY(c->pool.alloc(&c->d_xn_ext, (size_t)prob->n_nonlin * prob->N_P));
+    RB_TRY(c->pool.alloc(&c->d_H_ext, (size_t)prob->N_P * prob->n_y * c->lay.ldx));
     c->h_odo.assign((size_t)std::max(prob->N_T - 1, 1) * prob->n_odo, 0.0);
     for (int t = 0; t < prob->N_T - 1; ++t) for (int k = 0; k < prob->n_odo; ++k) c->h_odo[(size_t)t * prob->n_odo + k] = prob->odometry[t + (size_t)prob->odo_ld * k];
     c->h_Q.assign(prob->Q, prob->Q + (size_t)prob->n_w * prob->n_w * prob->q_pages);
@@ -284,26 +267,24 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
   }
 
   // ---- model / problem constants ----
-  RB_TRY(dmalloc(&c->d_NN, nn.size()));
-  if (!nn.empty()) HIPCHK(hipMemcpy(c->d_NN, nn.data(), nn.size() * sizeof(int), hipMemcpyHostToDevice));
+  RB_TRY(c->pool.upload(&c->d_NN, nn.data(), nn.size()));
   c->mdl.NN = c->d_NN;
   if (sparse) {
-    RB_TRY(dmalloc(&c->d_R, (size_t)d * d));
-    HIPCHK(hipMemcpy(c->d_R, prob->R, (size_t)d * d * sizeof(double), hipMemcpyHostToDevice));
+    RB_TRY(c->pool.upload(&c->d_R, prob->R, (size_t)d * d));
     c->mdl.Rdev = c->d_R;
   }
   {
     std::vector<double> yt((size_t)T * d), od((size_t)std::max(T - 1, 1) * nodo, 0.0);
     for (int t = 0; t < T; ++t) for (int k = 0; k < d; ++k) yt[(size_t)t * d + k] = prob->y[t + (size_t)T * k];
     for (int t = 0; t < T - 1; ++t) for (int k = 0; k < nodo; ++k) od[(size_t)t * nodo + k] = prob->odometry[t + (size_t)prob->odo_ld * k];
-    RB_TRY(dmalloc(&c->d_y, yt.size()));
-    RB_TRY(dmalloc(&c->d_odo, od.size()));
+    RB_TRY(c->pool.alloc(&c->d_y, yt.size()));
+    RB_TRY(c->pool.alloc(&c->d_odo, od.size()));
     HIPCHK(hipMemcpy(c->d_y, yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->d_odo, od.data(), od.size() * sizeof(double), hipMemcpyHostToDevice));
     std::vector<double> blk, full;
     RB_TRY(build_chol_factors(model, prob, blk, full, c->chol_pages, &c->cholQfull_ok));
-    RB_TRY(dmalloc(&c->d_cholQ, blk.size()));
-    RB_TRY(dmalloc(&c->d_cholQfull, full.size()));
+    RB_TRY(c->pool.alloc(&c->d_cholQ, blk.size()));
+    RB_TRY(c->pool.alloc(&c->d_cholQfull, full.size()));
     HIPCHK(hipMemcpy(c->d_cholQ, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->d_cholQfull, full.data(), full.size() * sizeof(double), hipMemcpyHostToDevice));
   }
@@ -313,25 +294,19 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     for (int j = 0; j < prob->x0_lin_cols; ++j)
       for (int r = 0; r < n; ++r) x0l[(size_t)j * L.ldx + r] = prob->x0_lin[r + (size_t)n * j];
     c->x0_lin_cols = prob->x0_lin_cols;
-    RB_TRY(dmalloc(&c->d_x0l, x0l.size()));
-    HIPCHK(hipMemcpy(c->d_x0l, x0l.data(), x0l.size() * sizeof(double), hipMemcpyHostToDevice));
+    RB_TRY(c->pool.upload(&c->d_x0l, x0l.data(), x0l.size()));
     c->h_x0n.assign(prob->x0_nonlin, prob->x0_nonlin + nN);
     c->h_P0.assign(prob->P0_lin, prob->P0_lin + (size_t)n * n);
     c->h_x0l.assign(prob->x0_lin, prob->x0_lin + (size_t)n * prob->x0_lin_cols);
     c->h_R.assign(prob->R, prob->R + (size_t)d * d);
     c->h_y.assign(prob->y, prob->y + (size_t)T * d);
-    double* tmp = nullptr;
-    RB_TRY(dmalloc(&tmp, (size_t)n * n));
-    hipError_t e = hipMemcpy(tmp, prob->P0_lin, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-      int s1 = dmalloc(&c->d_P0t, std::max<size_t>(L.szT, 1));
-      int s2 = dmalloc(&c->d_P0b, std::max<size_t>(L.szB, 1));
-      if (s1 != RBPF_OK || s2 != RBPF_OK) { hipFree(tmp); return s1 != RBPF_OK ? s1 : s2; }
-      e = launch_pack_P(L, tmp, 0, c->d_P0t, c->d_P0b, 1, c->stream, c->fp32 ? 1 : 0);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    hipFree(tmp);
-    HIPCHK(e);
+    DevicePool tmp;
+    double* P0 = nullptr;
+    RB_TRY(tmp.upload(&P0, prob->P0_lin, (size_t)n * n));
+    RB_TRY(c->pool.alloc(&c->d_P0t, std::max<size_t>(L.szT, 1)));
+    RB_TRY(c->pool.alloc(&c->d_P0b, std::max<size_t>(L.szB, 1)));
+    HIPCHK(launch_pack_P(L, P0, 0, c->d_P0t, c->d_P0b, 1, c->stream, c->fp32 ? 1 : 0));
+    HIPCHK(hipStreamSynchronize(c->stream));
   }
   // ---- RNG block ----
   if (rng->mode == RBPF_RNG_REPLAY) {
@@ -340,8 +315,8 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     if (rng->n_iter < iters) { set_error("replay RNG has fewer pages than iterations"); return RBPF_ERR_INVALID_ARG; }
     if (smoother && !rng->Ufin) { set_error("replay RNG needs Ufin for the smoother"); return RBPF_ERR_INVALID_ARG; }
     const size_t nu = c->rng_slots * std::max(T - 1, 0) * iters;
-    RB_TRY(dmalloc(&c->d_U, nu));
-    RB_TRY(dmalloc(&c->d_Z, nu * nw));
+    RB_TRY(c->pool.alloc(&c->d_U, nu));
+    RB_TRY(c->pool.alloc(&c->d_Z, nu * nw));
     if (nu) {
       HIPCHK(hipMemcpy(c->d_U, rng->U, nu * sizeof(double), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(c->d_Z, rng->Z, nu * nw * sizeof(double), hipMemcpyHostToDevice));
@@ -372,30 +347,30 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     if (b == 1 && c->inplace) { c->Pt[1] = c->Pt[0]; c->Pb[1] = c->Pb[0]; }
     else {
       // (counts in doubles; a float bank needs half of them)
-      RB_TRY(dmalloc(&c->Pt[b], c->fp32 ? (c->bank_cap * L.szT + 1) / 2 : c->bank_cap * L.szT));
-      RB_TRY(dmalloc(&c->Pb[b], c->fp32 ? (c->bank_cap * L.szB + 1) / 2 : c->bank_cap * L.szB));
+      RB_TRY(c->pool.alloc(&c->Pt[b], c->fp32 ? (c->bank_cap * L.szT + 1) / 2 : c->bank_cap * L.szT));
+      RB_TRY(c->pool.alloc(&c->Pb[b], c->fp32 ? (c->bank_cap * L.szB + 1) / 2 : c->bank_cap * L.szB));
     }
-    RB_TRY(dmalloc(&c->F[b], c->bank_cap * 2 * d * L.ldx));
-    RB_TRY(dmalloc(&c->xl[b], c->bank_cap * L.ldx));
+    RB_TRY(c->pool.alloc(&c->F[b], c->bank_cap * 2 * d * L.ldx));
+    RB_TRY(c->pool.alloc(&c->xl[b], c->bank_cap * L.ldx));
     HIPCHK(hipMemsetAsync(c->F[b], 0, c->bank_cap * 2 * d * L.ldx * sizeof(double), c->stream));
     HIPCHK(hipMemsetAsync(c->xl[b], 0, c->bank_cap * L.ldx * sizeof(double), c->stream));
   }
-  if (c->inplace) RB_TRY(dmalloc(&c->d_ip, (size_t)8 * N));
+  if (c->inplace) RB_TRY(c->pool.alloc(&c->d_ip, (size_t)8 * N));
   c->share_inplace = c->inplace && c->lazy_depth >= 2 && !ex && layout_shares_flush(c->lay);
   if (const char* e = tuning_env("RBPF_SHARE_INPLACE")) c->share_inplace = c->share_inplace && atoi(e) != 0;   // diagnostic builds: the per-child in-place flush
   if (c->share_inplace) {
-    RB_TRY(dmalloc(&c->d_share_writers, 1));
+    RB_TRY(c->pool.alloc(&c->d_share_writers, 1));
     HIPCHK(hipMemset(c->d_share_writers, 0, sizeof(unsigned long long)));
   }
   // shared flush: with ping-pong banks the children of one parent store ONE copy of their (identical) flushed matrix
   c->share_flush = c->lazy_depth >= 2 && !c->inplace && !ex && layout_shares_flush(c->lay);   // (smoothers: the information form)
   if (const size_t sd = sym_strip_doubles(c->lay, d + (smoother ? 1 : 0))) {   // 6, 10, 12, 14, 16 tile rows: the step kernel's column strips live in global memory (information form: one more right-hand side)
-    RB_TRY(dmalloc(&c->d_strip_ws, (size_t)N * sd));
+    RB_TRY(c->pool.alloc(&c->d_strip_ws, (size_t)N * sd));
     c->strip_ws_stride = sd;
   }
   if (c->share_flush) {
-    RB_TRY(dmalloc(&c->d_share, (size_t)3 * N));
-    RB_TRY(dmalloc(&c->d_share_writers, 1));
+    RB_TRY(c->pool.alloc(&c->d_share, (size_t)3 * N));
+    RB_TRY(c->pool.alloc(&c->d_share_writers, 1));
     HIPCHK(hipMemset(c->d_share_writers, 0, sizeof(unsigned long long)));
   }
   if (c->lazy_depth >= 2) {
@@ -403,32 +378,32 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     if (!L.sym && step_lds_bytes(c->mdl, c->lay, smoother ? 1 : 0, c->lazy_depth) > 160 * 1024) { set_error("lazy_depth too large for the LDS plan"); return RBPF_ERR_UNSUPPORTED; }
     if (L.sym && step_sym_lds_bytes(c->mdl, c->lay, c->lazy_depth, 1, smoother ? 1 : 0) > 160 * 1024) { set_error("lazy_depth too large for the LDS plan"); return RBPF_ERR_UNSUPPORTED; }
     for (int b = 0; b <= c->lazy_depth; ++b) {            // entry N of every bank stays zero (fresh lineages)
-      RB_TRY(dmalloc(&c->Fb[b], (size_t)(N + 1) * 2 * d * L.ldx));
+      RB_TRY(c->pool.alloc(&c->Fb[b], (size_t)(N + 1) * 2 * d * L.ldx));
       HIPCHK(hipMemsetAsync(c->Fb[b], 0, (size_t)(N + 1) * 2 * d * L.ldx * sizeof(double), c->stream));
     }
     for (int b = 0; b < 2; ++b) {
-      RB_TRY(dmalloc(&c->fidx[b], (size_t)(c->lazy_depth + 1) * N));
-      RB_TRY(dmalloc(&c->base[b], (size_t)N));
+      RB_TRY(c->pool.alloc(&c->fidx[b], (size_t)(c->lazy_depth + 1) * N));
+      RB_TRY(c->pool.alloc(&c->base[b], (size_t)N));
     }
   }
   c->hist_slabs = c->opt.keep_history ? T : 2;
-  RB_TRY(dmalloc(&c->X, (size_t)c->hist_slabs * nN * N));
-  RB_TRY(dmalloc(&c->A, (size_t)(c->opt.keep_history ? T : 1) * N));
+  RB_TRY(c->pool.alloc(&c->X, (size_t)c->hist_slabs * nN * N));
+  RB_TRY(c->pool.alloc(&c->A, (size_t)(c->opt.keep_history ? T : 1) * N));
   HIPCHK(hipMemsetAsync(c->A, 0, (size_t)(c->opt.keep_history ? T : 1) * N * sizeof(int), c->stream));
   const size_t tr = c->opt.trace ? (size_t)T : 1;
-  RB_TRY(dmalloc(&c->logw, tr * N));
-  RB_TRY(dmalloc(&c->w, tr * N));
-  RB_TRY(dmalloc(&c->wc, (size_t)N));
-  RB_TRY(dmalloc(&c->traj_max, (size_t)T * nN));
-  RB_TRY(dmalloc(&c->traj_mean, (size_t)T * nN));
-  RB_TRY(dmalloc(&c->d_scal, 64));
-  RB_TRY(dmalloc(&c->d_rs, resample_scratch_doubles(std::max<size_t>((size_t)N, c->rng_slots))));
-  RB_TRY(dmalloc(&c->d_unext, (size_t)N));
-  RB_TRY(dmalloc(&c->d_pre_i, (size_t)N * kPreInts));
-  RB_TRY(dmalloc(&c->d_pre_d, (size_t)N * kPreDoubles));
-  RB_TRY(dmalloc(&c->d_order, (size_t)N));
-  RB_TRY(dmalloc(&c->d_counts, (size_t)2 * N + 128));
-  RB_TRY(dmalloc(&c->d_flags, 16));
+  RB_TRY(c->pool.alloc(&c->logw, tr * N));
+  RB_TRY(c->pool.alloc(&c->w, tr * N));
+  RB_TRY(c->pool.alloc(&c->wc, (size_t)N));
+  RB_TRY(c->pool.alloc(&c->traj_max, (size_t)T * nN));
+  RB_TRY(c->pool.alloc(&c->traj_mean, (size_t)T * nN));
+  RB_TRY(c->pool.alloc(&c->d_scal, 64));
+  RB_TRY(c->pool.alloc(&c->d_rs, resample_scratch_doubles(std::max<size_t>((size_t)N, c->rng_slots))));
+  RB_TRY(c->pool.alloc(&c->d_unext, (size_t)N));
+  RB_TRY(c->pool.alloc(&c->d_pre_i, (size_t)N * kPreInts));
+  RB_TRY(c->pool.alloc(&c->d_pre_d, (size_t)N * kPreDoubles));
+  RB_TRY(c->pool.alloc(&c->d_order, (size_t)N));
+  RB_TRY(c->pool.alloc(&c->d_counts, (size_t)2 * N + 128));
+  RB_TRY(c->pool.alloc(&c->d_flags, 16));
   HIPCHK(hipMemsetAsync(c->d_flags, 0, 16 * sizeof(int), c->stream));
   RB_TRY(ctx_reset(c));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -470,17 +445,7 @@ void ctx_free(rbpf_ctx* c) {
   if (!c) return;
   if (c->stream) hipStreamSynchronize(c->stream);
   for (auto& ev : c->events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-  hipFree(c->d_R); hipFree(c->d_xn_ext); hipFree(c->d_H_ext);
-  hipFree(c->d_NN); hipFree(c->d_y); hipFree(c->d_odo); hipFree(c->d_cholQ); hipFree(c->d_cholQfull);
-  hipFree(c->d_x0l); hipFree(c->d_P0t); hipFree(c->d_P0b); hipFree(c->d_U); hipFree(c->d_Z);
-  if (c->inplace) { c->Pt[1] = nullptr; c->Pb[1] = nullptr; }     // aliases of bank 0
-  hipFree(c->d_strip_ws);
-  hipFree(c->d_ip); hipFree(c->d_share); hipFree(c->d_share_writers); hipFree(c->d_distinct_mark); hipFree(c->d_distinct_counter);
-  for (int b = 0; b < 2; ++b) { hipFree(c->Pt[b]); hipFree(c->Pb[b]); hipFree(c->F[b]); hipFree(c->xl[b]); }
-  hipFree(c->X); hipFree(c->A); hipFree(c->logw); hipFree(c->w); hipFree(c->wc);
-  for (int b = 0; b <= kMaxSets; ++b) hipFree(c->Fb[b]);
-  for (int b = 0; b < 2; ++b) { hipFree(c->fidx[b]); hipFree(c->base[b]); }
-  hipFree(c->traj_max); hipFree(c->traj_mean); hipFree(c->d_scal); hipFree(c->d_flags); hipFree(c->d_order); hipFree(c->d_counts); hipFree(c->d_pre_i); hipFree(c->d_pre_d); hipFree(c->d_unext); hipFree(c->d_rs);
+  c->pool.clear();                                     // the device buffers go first and the stream last, as they always have
   smoother_free(c);
   shard_free(c);
   loc_free(c);
@@ -561,13 +526,13 @@ int ctx_arm_distinct(rbpf_ctx* c, StepArgs& a, size_t keys) {
   if (!c->timing_on || a.t == 0) return RBPF_OK;
   if (c->distinct_keys < keys) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    hipFree(c->d_distinct_mark); c->d_distinct_mark = nullptr;
-    HIPCHK(hipMalloc(&c->d_distinct_mark, keys * sizeof(int)));
+    c->pool.release(c->d_distinct_mark);
+    RB_TRY(c->pool.alloc(&c->d_distinct_mark, keys));
     HIPCHK(hipMemset(c->d_distinct_mark, 0, keys * sizeof(int)));
     c->distinct_keys = keys;
   }
   if (!c->d_distinct_counter) {
-    HIPCHK(hipMalloc(&c->d_distinct_counter, sizeof(unsigned long long)));
+    RB_TRY(c->pool.alloc(&c->d_distinct_counter, 1));
     HIPCHK(hipMemset(c->d_distinct_counter, 0, sizeof(unsigned long long)));
   }
   a.distinct_mark = c->d_distinct_mark; a.distinct_counter = c->d_distinct_counter; a.distinct_tag = ++c->distinct_epoch;
@@ -903,30 +868,24 @@ __global__ void iota_kernel(int count, int first, int* out) {
 static int accumulate_p_mean(rbpf_ctx* c, const double* w_last, const std::vector<double>& xl_mean_h, double* P_mean_host) {
   const int N = c->N, n = c->mdl.n, ldx = c->lay.ldx, cur = c->xcur;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)N, ((size_t)64 << 20) / ((size_t)n * n * sizeof(double))));
+  DevicePool tmp;
   double *dP = nullptr, *dacc = nullptr, *dmean = nullptr; int* didx = nullptr;
-  int st = dmalloc(&dP, (size_t)chunk * n * n);
-  if (st == RBPF_OK) st = dmalloc(&dacc, (size_t)n * n);
-  if (st == RBPF_OK) st = dmalloc(&dmean, (size_t)n);
-  if (st == RBPF_OK) st = dmalloc(&didx, (size_t)chunk);
-  hipError_t e = hipSuccess;
-  if (st == RBPF_OK) {
-    e = hipMemsetAsync(dacc, 0, (size_t)n * n * sizeof(double), c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dmean, xl_mean_h.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    for (int i0 = 0; i0 < N && e == hipSuccess && st == RBPF_OK; i0 += chunk) {
-      const int count = std::min(chunk, N - i0);
-      hipLaunchKernelGGL(iota_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, count, i0, didx);
-      st = ctx_unpack(c, didx, count, dP);
-      if (st != RBPF_OK) break;
-      hipLaunchKernelGGL(p_mean_accum_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, c->stream, n, ldx, i0,
-                         count, dP, c->xl[cur], dmean, w_last, dacc);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess && st == RBPF_OK) e = hipMemcpyAsync(P_mean_host, dacc, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && st == RBPF_OK) e = hipStreamSynchronize(c->stream);
+  RB_TRY(tmp.alloc(&dP, (size_t)chunk * n * n));
+  RB_TRY(tmp.alloc(&dacc, (size_t)n * n));
+  RB_TRY(tmp.alloc(&dmean, (size_t)n));
+  RB_TRY(tmp.alloc(&didx, (size_t)chunk));
+  HIPCHK(hipMemsetAsync(dacc, 0, (size_t)n * n * sizeof(double), c->stream));
+  HIPCHK(hipMemcpyAsync(dmean, xl_mean_h.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  for (int i0 = 0; i0 < N; i0 += chunk) {
+    const int count = std::min(chunk, N - i0);
+    hipLaunchKernelGGL(iota_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, count, i0, didx);
+    RB_TRY(ctx_unpack(c, didx, count, dP));
+    hipLaunchKernelGGL(p_mean_accum_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, c->stream, n, ldx, i0,
+                       count, dP, c->xl[cur], dmean, w_last, dacc);
+    HIPCHK(hipGetLastError());
   }
-  hipFree(dP); hipFree(dacc); hipFree(dmean); hipFree(didx);
-  if (st != RBPF_OK) return st;
-  HIPCHK(e);
+  HIPCHK(hipMemcpyAsync(P_mean_host, dacc, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return RBPF_OK;
 }
 
@@ -981,6 +940,8 @@ const char* rbpf_status_string(int s) {
 }
 
 const char* rbpf_last_error(void) { return g_last_error.c_str(); }
+
+int64_t rbpf_device_bytes_live(void) { return (int64_t)g_device_bytes_live.load(); }
 
 int rbpf_device_count(void) {
   int n = 0;
@@ -1174,73 +1135,61 @@ int rbpf_filter_finish(rbpf_ctx* c, rbpf_filter_out* o) {
   if (o->xl_max) HIPCHK(hipMemcpy(o->xl_max, c->xl[cur] + (size_t)iw * L.ldx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   std::vector<double> xl_mean;
   if (o->xl_mean || o->P_mean) {
+    DevicePool tmp;
     double* dm = nullptr;
-    RB_TRY(dmalloc(&dm, (size_t)n));
-    hipError_t e = launch_weighted_mean_xl(N, n, L.ldx, c->xl[cur], w_last, dm, c->stream);
+    RB_TRY(tmp.alloc(&dm, (size_t)n));
+    HIPCHK(launch_weighted_mean_xl(N, n, L.ldx, c->xl[cur], w_last, dm, c->stream));
     xl_mean.resize(n);
-    if (e == hipSuccess) e = hipMemcpyAsync(xl_mean.data(), dm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(dm);
-    HIPCHK(e);
+    HIPCHK(hipMemcpyAsync(xl_mean.data(), dm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     if (o->xl_mean) std::memcpy(o->xl_mean, xl_mean.data(), (size_t)n * sizeof(double));
   }
   if (o->P_max || o->P_mean) {
+    DevicePool tmp;
     double* dP = nullptr; int* didx = nullptr;
-    RB_TRY(dmalloc(&dP, (size_t)n * n));
-    int s2 = dmalloc(&didx, 1);
-    if (s2 != RBPF_OK) { hipFree(dP); return s2; }
-    hipError_t e = hipSuccess;
+    RB_TRY(tmp.alloc(&dP, (size_t)n * n));
+    RB_TRY(tmp.alloc(&didx, 1));
     if (o->P_max) {
-      e = hipMemcpy(didx, &iw, sizeof(int), hipMemcpyHostToDevice);
-      if (e == hipSuccess && ctx_unpack(c, didx, 1, dP) != RBPF_OK) e = hipErrorUnknown;
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e == hipSuccess) e = hipMemcpy(o->P_max, dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost);
+      HIPCHK(hipMemcpy(didx, &iw, sizeof(int), hipMemcpyHostToDevice));
+      RB_TRY(ctx_unpack(c, didx, 1, dP));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(o->P_max, dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost));
     }
-    if (e == hipSuccess && o->P_mean) {
-      if (c->opt.fix_p_mean) {
-        hipFree(dP); hipFree(didx);
-        return accumulate_p_mean(c, w_last, xl_mean, o->P_mean);   // consciously fixed quirk Q3 (option, not the default)
-      }
+    if (o->P_mean && !c->opt.fix_p_mean) {
       // quirk Q3 (particleFilter.m:228-230): P_mean = w(N)*(P(:,:,N) + (xl_mean-xl(:,N))*(...)')
       const int last = N - 1;
       std::vector<double> Pl((size_t)n * n), xll(n);
       double wl = 0.0;
-      e = hipMemcpy(didx, &last, sizeof(int), hipMemcpyHostToDevice);
-      if (e == hipSuccess && ctx_unpack(c, didx, 1, dP) != RBPF_OK) e = hipErrorUnknown;
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e == hipSuccess) e = hipMemcpy(Pl.data(), dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(xll.data(), c->xl[cur] + (size_t)last * L.ldx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(&wl, w_last + last, sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess)
-        for (int cc = 0; cc < n; ++cc)
-          for (int r = 0; r < n; ++r)
-            o->P_mean[r + (size_t)n * cc] = wl * (Pl[r + (size_t)n * cc] + (xl_mean[r] - xll[r]) * (xl_mean[cc] - xll[cc]));
+      HIPCHK(hipMemcpy(didx, &last, sizeof(int), hipMemcpyHostToDevice));
+      RB_TRY(ctx_unpack(c, didx, 1, dP));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(Pl.data(), dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(xll.data(), c->xl[cur] + (size_t)last * L.ldx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&wl, w_last + last, sizeof(double), hipMemcpyDeviceToHost));
+      for (int cc = 0; cc < n; ++cc)
+        for (int r = 0; r < n; ++r)
+          o->P_mean[r + (size_t)n * cc] = wl * (Pl[r + (size_t)n * cc] + (xl_mean[r] - xll[r]) * (xl_mean[cc] - xll[cc]));
     }
-    hipFree(dP); hipFree(didx);
-    HIPCHK(e);
   }
+  if (o->P_mean && c->opt.fix_p_mean) RB_TRY(accumulate_p_mean(c, w_last, xl_mean, o->P_mean));   // consciously fixed quirk Q3 (option, not the default)
   if (o->traj_sample_iwmax || o->xn_traj) {
     if (!c->opt.keep_history) { set_error("traj_sample_iwmax / xn_traj need keep_history=1"); return RBPF_ERR_STATE; }
     if (o->traj_sample_iwmax) {
+      DevicePool tmp;
       double* dout = nullptr; int* didx = nullptr;
-      RB_TRY(dmalloc(&dout, (size_t)nN * Tdone));
-      int s2 = dmalloc(&didx, 1);
-      if (s2 != RBPF_OK) { hipFree(dout); return s2; }
-      hipError_t e = hipMemcpy(didx, &iw, sizeof(int), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = launch_backtrace(N, nN, Tdone, c->X, c->A, didx, 1, dout, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e == hipSuccess) e = hipMemcpy(o->traj_sample_iwmax, dout, (size_t)nN * Tdone * sizeof(double), hipMemcpyDeviceToHost);
-      hipFree(dout); hipFree(didx);
-      HIPCHK(e);
+      RB_TRY(tmp.alloc(&dout, (size_t)nN * Tdone));
+      RB_TRY(tmp.upload(&didx, &iw, 1));
+      HIPCHK(launch_backtrace(N, nN, Tdone, c->X, c->A, didx, 1, dout, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(o->traj_sample_iwmax, dout, (size_t)nN * Tdone * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (o->xn_traj) {
+      DevicePool tmp;
       double* dout = nullptr;
-      RB_TRY(dmalloc(&dout, (size_t)nN * N * Tdone));
-      hipError_t e = launch_backtrace(N, nN, Tdone, c->X, c->A, nullptr, N, dout, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e == hipSuccess) e = hipMemcpy(o->xn_traj, dout, (size_t)nN * N * Tdone * sizeof(double), hipMemcpyDeviceToHost);
-      hipFree(dout);
-      HIPCHK(e);
+      RB_TRY(tmp.alloc(&dout, (size_t)nN * N * Tdone));
+      HIPCHK(launch_backtrace(N, nN, Tdone, c->X, c->A, nullptr, N, dout, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(o->xn_traj, dout, (size_t)nN * N * Tdone * sizeof(double), hipMemcpyDeviceToHost));
     }
   }
   if (o->trace_logw || o->trace_w || o->trace_ai) {
@@ -1253,32 +1202,29 @@ int rbpf_filter_finish(rbpf_ctx* c, rbpf_filter_out* o) {
     }
   }
   if (o->final_xn) {
+    DevicePool tmp;
     double* dout = nullptr;
-    RB_TRY(dmalloc(&dout, (size_t)nN * N));
+    RB_TRY(tmp.alloc(&dout, (size_t)nN * N));
     const double* Xl = c->X + (size_t)(c->opt.keep_history ? Tdone - 1 : ((Tdone - 1) & 1)) * nN * N;
-    hipError_t e = launch_transpose_soa(N, nN, Xl, dout, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(o->final_xn, dout, (size_t)nN * N * sizeof(double), hipMemcpyDeviceToHost);
-    hipFree(dout);
-    HIPCHK(e);
+    HIPCHK(launch_transpose_soa(N, nN, Xl, dout, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(o->final_xn, dout, (size_t)nN * N * sizeof(double), hipMemcpyDeviceToHost));
   }
   if (o->final_xl) {
+    DevicePool tmp;
     double* dout = nullptr;
-    RB_TRY(dmalloc(&dout, (size_t)n * N));
-    hipError_t e = launch_gather_xl(N, n, L.ldx, c->xl[cur], dout, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(o->final_xl, dout, (size_t)n * N * sizeof(double), hipMemcpyDeviceToHost);
-    hipFree(dout);
-    HIPCHK(e);
+    RB_TRY(tmp.alloc(&dout, (size_t)n * N));
+    HIPCHK(launch_gather_xl(N, n, L.ldx, c->xl[cur], dout, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(o->final_xl, dout, (size_t)n * N * sizeof(double), hipMemcpyDeviceToHost));
   }
   if (o->final_P) {
+    DevicePool tmp;
     double* dout = nullptr;
-    RB_TRY(dmalloc(&dout, (size_t)n * n * N));
-    hipError_t e = (ctx_unpack(c, nullptr, N, dout) == RBPF_OK) ? hipSuccess : hipErrorUnknown;
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(o->final_P, dout, (size_t)n * n * N * sizeof(double), hipMemcpyDeviceToHost);
-    hipFree(dout);
-    HIPCHK(e);
+    RB_TRY(tmp.alloc(&dout, (size_t)n * n * N));
+    RB_TRY(ctx_unpack(c, nullptr, N, dout));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(o->final_P, dout, (size_t)n * n * N * sizeof(double), hipMemcpyDeviceToHost));
   }
   return RBPF_OK;
 }
@@ -1301,38 +1247,22 @@ int rbpf_philox_fill(uint64_t seed, int32_t k_iter, int32_t N, int32_t T, int32_
   if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   if (nw > 8 || N < 1 || T < 1) { set_error("bad sizes"); return RBPF_ERR_INVALID_ARG; }
   const size_t nu = (size_t)N * (T - 1);
+  DevicePool tmp;
   double *dU = nullptr, *dZ = nullptr, *dF = nullptr;
-  RB_TRY(dmalloc(&dU, std::max<size_t>(nu, 1)));
-  int s = dmalloc(&dZ, std::max<size_t>(nu * nw, 1));
-  if (s == RBPF_OK) s = dmalloc(&dF, 1);
-  hipError_t e = hipSuccess;
-  if (s == RBPF_OK) {
-    e = launch_philox_fill(seed, k_iter, N, T, nw, dU, dZ, dF, 0);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && U && nu) e = hipMemcpy(U, dU, nu * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && Z && nu) e = hipMemcpy(Z, dZ, nu * nw * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && Ufin) e = hipMemcpy(Ufin, dF, sizeof(double), hipMemcpyDeviceToHost);
-  }
-  hipFree(dU); hipFree(dZ); hipFree(dF);
-  if (s != RBPF_OK) return s;
-  HIPCHK(e);
+  RB_TRY(tmp.alloc(&dU, std::max<size_t>(nu, 1)));
+  RB_TRY(tmp.alloc(&dZ, std::max<size_t>(nu * nw, 1)));
+  RB_TRY(tmp.alloc(&dF, 1));
+  HIPCHK(launch_philox_fill(seed, k_iter, N, T, nw, dU, dZ, dF, 0));
+  HIPCHK(hipDeviceSynchronize());
+  if (U && nu) HIPCHK(hipMemcpy(U, dU, nu * sizeof(double), hipMemcpyDeviceToHost));
+  if (Z && nu) HIPCHK(hipMemcpy(Z, dZ, nu * nw * sizeof(double), hipMemcpyDeviceToHost));
+  if (Ufin) HIPCHK(hipMemcpy(Ufin, dF, sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
 }  // extern "C"
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  int alloc(size_t bytes) {
-    hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-    return RBPF_OK;
-  }
-  template <typename T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
-static int model_for_helpers(const rbpf_model* model, int nN, int nw, int nodo, ModelDev& M, DevBuf& nnbuf) {
+static int model_for_helpers(const rbpf_model* model, int nN, int nw, int nodo, ModelDev& M, DevicePool& tmp) {
   int n = 0, d = 0;
   if (!model) { set_error("model is NULL"); return RBPF_ERR_INVALID_ARG; }
   if (model->kind == RBPF_MODEL_DENSE_MAG_6D) { n = model->m_basis + 3; d = 3; }
@@ -1340,9 +1270,9 @@ static int model_for_helpers(const rbpf_model* model, int nN, int nw, int nodo, 
   else { set_error("unknown model family"); return RBPF_ERR_UNSUPPORTED; }
   std::vector<int> nn;
   RB_TRY(fill_model_dev(model, nN, n, d, nw, nodo, nullptr, 0.0, M, nn));
-  RB_TRY(nnbuf.alloc(nn.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(nnbuf.p, nn.data(), nn.size() * sizeof(int), hipMemcpyHostToDevice));
-  M.NN = nnbuf.as<int>();
+  int* d_nn = nullptr;
+  RB_TRY(tmp.upload(&d_nn, nn.data(), nn.size()));
+  M.NN = d_nn;
   return RBPF_OK;
 }
 
@@ -1358,14 +1288,13 @@ int rbpf_meas_model(const rbpf_model* model, int32_t n_nonlin, int32_t n_pred, c
   if (!xn || !dy || n_pred < 1) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }
   int nN, nw, nodo; default_dims(model, nN, nw, nodo);
   if (n_nonlin != nN) { set_error("n_nonlin does not match the model family"); return RBPF_ERR_INVALID_ARG; }
-  ModelDev M; DevBuf nnb, dx, dd;
-  RB_TRY(model_for_helpers(model, nN, nw, nodo, M, nnb));
-  RB_TRY(dx.alloc((size_t)nN * n_pred * sizeof(double)));
-  RB_TRY(dd.alloc((size_t)M.d * M.n * n_pred * sizeof(double)));
-  HIPCHK(hipMemcpy(dx.p, xn, (size_t)nN * n_pred * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(launch_meas_model(M, n_pred, dx.as<double>(), dd.as<double>(), 0));
+  ModelDev M; DevicePool tmp; double *dx = nullptr, *dd = nullptr;
+  RB_TRY(model_for_helpers(model, nN, nw, nodo, M, tmp));
+  RB_TRY(tmp.upload(&dx, xn, (size_t)nN * n_pred));
+  RB_TRY(tmp.alloc(&dd, (size_t)M.d * M.n * n_pred));
+  HIPCHK(launch_meas_model(M, n_pred, dx, dd, 0));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(dy, dd.p, (size_t)M.d * M.n * n_pred * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(dy, dd, (size_t)M.d * M.n * n_pred * sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
@@ -1384,19 +1313,16 @@ int rbpf_dyn_model(const rbpf_model* model, int32_t n_nonlin, int32_t n_w, int32
   if (!xn || !odo || !Q || !z || !xn_next || n_p < 1) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }
   int nN, nw, nodo; default_dims(model, nN, nw, nodo);
   if (n_nonlin != nN || n_w != nw || n_odo != nodo) { set_error("dims do not match the model family"); return RBPF_ERR_INVALID_ARG; }
-  ModelDev M; DevBuf nnb, dx, dodo, dL, dz, dout;
-  RB_TRY(model_for_helpers(model, nN, nw, nodo, M, nnb));
+  ModelDev M; DevicePool tmp; double *dx = nullptr, *dodo = nullptr, *dL = nullptr, *dz = nullptr, *dout = nullptr;
+  RB_TRY(model_for_helpers(model, nN, nw, nodo, M, tmp));
   std::vector<double> blk, full;
   RB_TRY(chol_for_helper(model, nw, dt, Q, blk, full));
-  RB_TRY(dx.alloc((size_t)nN * n_p * 8)); RB_TRY(dodo.alloc((size_t)nodo * 8)); RB_TRY(dL.alloc((size_t)nw * nw * 8));
-  RB_TRY(dz.alloc((size_t)nw * n_p * 8)); RB_TRY(dout.alloc((size_t)nN * n_p * 8));
-  HIPCHK(hipMemcpy(dx.p, xn, (size_t)nN * n_p * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dodo.p, odo, (size_t)nodo * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dL.p, blk.data(), (size_t)nw * nw * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dz.p, z, (size_t)nw * n_p * 8, hipMemcpyHostToDevice));
-  HIPCHK(launch_dyn_model(M, n_p, dx.as<double>(), dodo.as<double>(), dL.as<double>(), dz.as<double>(), dout.as<double>(), 0));
+  RB_TRY(tmp.upload(&dx, xn, (size_t)nN * n_p)); RB_TRY(tmp.upload(&dodo, odo, (size_t)nodo));
+  RB_TRY(tmp.upload(&dL, blk.data(), (size_t)nw * nw));
+  RB_TRY(tmp.upload(&dz, z, (size_t)nw * n_p)); RB_TRY(tmp.alloc(&dout, (size_t)nN * n_p));
+  HIPCHK(launch_dyn_model(M, n_p, dx, dodo, dL, dz, dout, 0));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(xn_next, dout.p, (size_t)nN * n_p * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(xn_next, dout, (size_t)nN * n_p * 8, hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
@@ -1408,21 +1334,17 @@ int rbpf_dyn_res_norm(const rbpf_model* model, int32_t n_nonlin, int32_t n_w, in
   if (n_nonlin != nN || n_odo != nodo) { set_error("dims do not match the model family"); return RBPF_ERR_INVALID_ARG; }
   if (!model->use_dyn_res_norm) nw = nN;    // additive default: residual over all non-linear states
   if (n_w != nw) { set_error("n_w does not match"); return RBPF_ERR_INVALID_ARG; }
-  ModelDev M; DevBuf nnb, dk, dx, dodo, dL, dout;
-  RB_TRY(model_for_helpers(model, nN, model->use_dyn_res_norm ? nw : (model->kind == RBPF_MODEL_DENSE_MAG_6D ? 6 : 1), nodo, M, nnb));
+  ModelDev M; DevicePool tmp; double *dk = nullptr, *dx = nullptr, *dodo = nullptr, *dL = nullptr, *dout = nullptr;
+  RB_TRY(model_for_helpers(model, nN, model->use_dyn_res_norm ? nw : (model->kind == RBPF_MODEL_DENSE_MAG_6D ? 6 : 1), nodo, M, tmp));
   M.nw = nw;
   std::vector<double> Lf((size_t)nw * nw, 0.0), A((size_t)nw * nw);
   for (int q = 0; q < nw * nw; ++q) A[q] = dt * Q[q];
   if (!chol_lower_host(A.data(), nw, nw, Lf.data(), nw)) { set_error("chol(dt*Q) failed"); return RBPF_ERR_CHOL_FAILED; }
-  RB_TRY(dk.alloc((size_t)nN * 8)); RB_TRY(dx.alloc((size_t)nN * n_p * 8)); RB_TRY(dodo.alloc((size_t)nodo * 8));
-  RB_TRY(dL.alloc((size_t)nw * nw * 8)); RB_TRY(dout.alloc((size_t)nw * n_p * 8));
-  HIPCHK(hipMemcpy(dk.p, xnk_t, (size_t)nN * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dx.p, xn, (size_t)nN * n_p * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dodo.p, odo, (size_t)nodo * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dL.p, Lf.data(), (size_t)nw * nw * 8, hipMemcpyHostToDevice));
-  HIPCHK(launch_dyn_res_norm(M, n_p, dk.as<double>(), dx.as<double>(), dodo.as<double>(), dL.as<double>(), dout.as<double>(), 0));
+  RB_TRY(tmp.upload(&dk, xnk_t, (size_t)nN)); RB_TRY(tmp.upload(&dx, xn, (size_t)nN * n_p)); RB_TRY(tmp.upload(&dodo, odo, (size_t)nodo));
+  RB_TRY(tmp.upload(&dL, Lf.data(), (size_t)nw * nw)); RB_TRY(tmp.alloc(&dout, (size_t)nw * n_p));
+  HIPCHK(launch_dyn_res_norm(M, n_p, dk, dx, dodo, dL, dout, 0));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(e_dyn, dout.p, (size_t)nw * n_p * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(e_dyn, dout, (size_t)nw * n_p * 8, hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
@@ -1431,19 +1353,17 @@ int rbpf_sample(int32_t N, const double* w, int32_t n_draws, const double* u, in
   if (!w || !u || !ind || N < 1 || n_draws < 1) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }
   // reuse normalise_scan's cumsum by feeding log(w): instead run the dedicated path: upload w as
   // already-normalised weights through logw = log(w) would re-normalise; so scan directly.
-  DevBuf dw, dwc, du, di, dlog, dx, dflag;
-  RB_TRY(dw.alloc((size_t)N * 8)); RB_TRY(dwc.alloc((size_t)N * 8)); RB_TRY(du.alloc((size_t)n_draws * 8));
-  RB_TRY(di.alloc((size_t)n_draws * 4)); RB_TRY(dflag.alloc(16));
-  HIPCHK(hipMemcpy(dw.p, w, (size_t)N * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(du.p, u, (size_t)n_draws * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(dflag.p, 0, 16));
-  HIPCHK(launch_cumsum(N, dw.as<double>(), dwc.as<double>(), 0));
+  DevicePool tmp; double *dw = nullptr, *dwc = nullptr, *du = nullptr; int *di = nullptr, *dflag = nullptr;
+  RB_TRY(tmp.upload(&dw, w, (size_t)N)); RB_TRY(tmp.alloc(&dwc, (size_t)N)); RB_TRY(tmp.upload(&du, u, (size_t)n_draws));
+  RB_TRY(tmp.alloc(&di, (size_t)n_draws)); RB_TRY(tmp.alloc(&dflag, 4));
+  HIPCHK(hipMemset(dflag, 0, 16));
+  HIPCHK(launch_cumsum(N, dw, dwc, 0));
   SearchArgs s;
-  s.N = N; s.n_draw = n_draws; s.t = 0; s.wc = dwc.as<double>(); s.rng_mode = 0; s.k_iter = 0; s.U = du.as<double>();
-  s.seed = 0; s.ai = di.as<int>(); s.overflow = dflag.as<int>();
+  s.N = N; s.n_draw = n_draws; s.t = 0; s.wc = dwc; s.rng_mode = 0; s.k_iter = 0; s.U = du;
+  s.seed = 0; s.ai = di; s.overflow = dflag;
   HIPCHK(launch_search(s, 0));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(ind, di.p, (size_t)n_draws * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ind, di, (size_t)n_draws * 4, hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
@@ -1451,39 +1371,34 @@ int rbpf_quat_helpers(int32_t op, int32_t n, const double* in, double* out) {
   if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   if (op < 0 || op > 8 || n < 1 || !in || !out) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }
   static const int nin_of[9] = {3, 3, 4, 4, 4, 4, 4, 4, 3}, nout_of[9] = {4, 4, 3, 3, 16, 16, 4, 9, 9};
-  DevBuf di, dout;
-  RB_TRY(di.alloc((size_t)n * nin_of[op] * 8)); RB_TRY(dout.alloc((size_t)n * nout_of[op] * 8));
-  HIPCHK(hipMemcpy(di.p, in, (size_t)n * nin_of[op] * 8, hipMemcpyHostToDevice));
-  HIPCHK(launch_quat_helpers(op, n, di.as<double>(), dout.as<double>(), 0));
+  DevicePool tmp; double *di = nullptr, *dout = nullptr;
+  RB_TRY(tmp.upload(&di, in, (size_t)n * nin_of[op])); RB_TRY(tmp.alloc(&dout, (size_t)n * nout_of[op]));
+  HIPCHK(launch_quat_helpers(op, n, di, dout, 0));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, dout.p, (size_t)n * nout_of[op] * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, dout, (size_t)n * nout_of[op] * 8, hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
 int rbpf_probe_wave_reduce(const double* in, double* out) {
   if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   if (!in || !out) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }
-  DevBuf di, dout;
-  RB_TRY(di.alloc(256 * 8)); RB_TRY(dout.alloc(4 * 8));
-  HIPCHK(hipMemcpy(di.p, in, 256 * 8, hipMemcpyHostToDevice));
-  HIPCHK(launch_probe_wave_reduce(di.as<double>(), dout.as<double>(), 0));
+  DevicePool tmp; double *di = nullptr, *dout = nullptr;
+  RB_TRY(tmp.upload(&di, in, 256)); RB_TRY(tmp.alloc(&dout, 4));
+  HIPCHK(launch_probe_wave_reduce(di, dout, 0));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, dout.p, 4 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, dout, 4 * 8, hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
 int rbpf_jacobian_phi3d(const rbpf_model* model, int32_t n_p, const double* x, const double* lower, const double* upper, double* J) {
   if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   if (!model || model->kind != RBPF_MODEL_DENSE_MAG_6D || !x || !lower || !upper || !J || n_p < 1) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }
-  ModelDev M; DevBuf nnb, dx, dlo, dup, dj;
-  RB_TRY(model_for_helpers(model, 7, 6, 7, M, nnb));
-  RB_TRY(dx.alloc((size_t)3 * n_p * 8)); RB_TRY(dlo.alloc(24)); RB_TRY(dup.alloc(24)); RB_TRY(dj.alloc((size_t)9 * M.m * n_p * 8));
-  HIPCHK(hipMemcpy(dx.p, x, (size_t)3 * n_p * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dlo.p, lower, 24, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dup.p, upper, 24, hipMemcpyHostToDevice));
-  HIPCHK(launch_jacobian_phi3d(M, n_p, dx.as<double>(), dlo.as<double>(), dup.as<double>(), dj.as<double>(), 0));
+  ModelDev M; DevicePool tmp; double *dx = nullptr, *dlo = nullptr, *dup = nullptr, *dj = nullptr;
+  RB_TRY(model_for_helpers(model, 7, 6, 7, M, tmp));
+  RB_TRY(tmp.upload(&dx, x, (size_t)3 * n_p)); RB_TRY(tmp.upload(&dlo, lower, 3)); RB_TRY(tmp.upload(&dup, upper, 3)); RB_TRY(tmp.alloc(&dj, (size_t)9 * M.m * n_p));
+  HIPCHK(launch_jacobian_phi3d(M, n_p, dx, dlo, dup, dj, 0));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(J, dj.p, (size_t)9 * M.m * n_p * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(J, dj, (size_t)9 * M.m * n_p * 8, hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
+#include "rbpf_devmem.hpp"
 
 #include <memory>
 #include <string>
@@ -18,6 +19,14 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
     hipError_t _e = (expr);                                                   \
     if (_e != hipSuccess) return ::rbpf::hip_fail(_e, #expr, __FILE__, __LINE__); \
   } while (0)
+#define RB_TRY(x) do { int _s = (x); if (_s != RBPF_OK) return _s; } while (0)
+
+inline bool have_device() {
+  int n = 0;
+  return hipGetDeviceCount(&n) == hipSuccess && n > 0;
+}
+// lower Cholesky factor of the leading n x n of A (column-major, leading dimensions lda / ldl); false: not positive definite
+bool chol_lower_host(const double* A, int n, int lda, double* Lc, int ldl);
 
 struct SmootherState;   // rbpf_smoother.hip
 struct ShardState;      // rbpf_shard.hip
@@ -41,6 +50,7 @@ struct InfoStep {
 struct rbpf_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  rbpf::DevicePool pool;    // owns every device buffer below (Pt[1] / Pb[1] of a single-bank session alias bank 0)
   rbpf::ModelDev mdl;
   rbpf::Layout lay;
   rbpf::Layout lay_low;     // same HBM layout, 2 x 2 wave decomposition (lazy variants with >= 3 pending sets)

@@ -350,6 +350,7 @@ __global__ void loc_fill_x0_kernel(int N, int cols, const double* __restrict__ x
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 struct LocState {
+  DevicePool pool;                 // owns the device buffers below; the context-level arrays of a localisation session are in rbpf_ctx::pool
   int n = 0;
   double sigma2 = 0.0;
   double *d_mean = nullptr, *d_V = nullptr, *d_vartab = nullptr, *d_S = nullptr, *d_lse = nullptr, *d_x0 = nullptr;
@@ -359,16 +360,8 @@ struct LocState {
 void loc_free(rbpf_ctx* c) {
   if (!c || !c->loc) return;
   LocState* L = c->loc;
-  hipFree(L->d_mean); hipFree(L->d_V); hipFree(L->d_vartab); hipFree(L->d_S); hipFree(L->d_lse); hipFree(L->d_x0);
   delete L;
   c->loc = nullptr;
-}
-
-#define LOC_TRY(x) do { int _s = (x); if (_s != RBPF_OK) return _s; } while (0)
-
-static bool loc_have_device() {
-  int nd = 0;
-  return hipGetDeviceCount(&nd) == hipSuccess && nd > 0;
 }
 
 template <typename T>
@@ -384,7 +377,7 @@ static int loc_size_ok(const T* p, const char* name) {
 
 // filter = true: exactly one of V / var_table; false (rbpf_loc_predict): V optional, var_table not read
 static int loc_validate_map(const rbpf_loc_map* map, bool filter) {
-  LOC_TRY(loc_size_ok(map, "rbpf_loc_map"));
+  RB_TRY(loc_size_ok(map, "rbpf_loc_map"));
   if (map->m_basis < 1 || map->m_basis + 3 > kLocMaxN) { set_error("rbpf_loc_map: n = m_basis + 3 must be in 4 .. 1151"); return RBPF_ERR_INVALID_ARG; }
   if (!map->NN || !map->mean) { set_error("rbpf_loc_map: NN / mean is NULL"); return RBPF_ERR_INVALID_ARG; }
   if (filter && ((map->V != nullptr) == (map->var_table != nullptr))) { set_error("rbpf_loc_map: exactly one of V and var_table must be set"); return RBPF_ERR_INVALID_ARG; }
@@ -393,7 +386,7 @@ static int loc_validate_map(const rbpf_loc_map* map, bool filter) {
 }
 
 static int loc_validate_problem(const rbpf_loc_problem* p) {
-  LOC_TRY(loc_size_ok(p, "rbpf_loc_problem"));
+  RB_TRY(loc_size_ok(p, "rbpf_loc_problem"));
   if (p->N_P < 1 || p->N_T < 1) { set_error("N_P and N_T must be >= 1"); return RBPF_ERR_INVALID_ARG; }
   if (p->N_P > kMaxParticles) { set_error("N_P above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
   if (!p->y || !p->x0_nonlin || !p->Q || !p->dt) { set_error("a required problem array is NULL"); return RBPF_ERR_INVALID_ARG; }
@@ -405,7 +398,7 @@ static int loc_validate_problem(const rbpf_loc_problem* p) {
 }
 
 static int loc_validate_options(const rbpf_options* o) {
-  LOC_TRY(options_ok(o));
+  RB_TRY(options_ok(o));
   if (!o) return RBPF_OK;
   if (o->fix_p_mean || o->lazy_depth || o->inplace || o->storage || o->chol_variant || o->chol_refresh || o->exchange_capacity ||
       o->n_devices || o->device_ids || o->info_rebuild) {
@@ -441,19 +434,11 @@ static int loc_model_dev(const rbpf_loc_map* map, ModelDev& M, std::vector<int>&
   std::memset(&md, 0, sizeof(md));
   md.kind = RBPF_MODEL_DENSE_MAG_6D; md.m_basis = map->m_basis; md.dim = 3; md.NN = map->NN;
   for (int a = 0; a < 3; ++a) md.L[a] = map->L[a];
-  LOC_TRY(fill_model_dev(&md, 7, map->m_basis + 3, 3, 6, 7, nullptr, 0.0, M, nn));
+  RB_TRY(fill_model_dev(&md, 7, map->m_basis + 3, 3, 6, 7, nullptr, 0.0, M, nn));
   if (loc_lds_bytes(M.ktot, true) > (size_t)kLocLdsLimit) {
     set_error("rbpf_loc_map: the per-axis index range of NN (" + std::to_string(M.ktot) + " table entries per particle) exceeds the 96 the prediction kernel keeps in LDS");
     return RBPF_ERR_UNSUPPORTED;
   }
-  return RBPF_OK;
-}
-
-template <typename T>
-static int loc_upload(T** dst, const T* src, size_t count) {
-  *dst = nullptr;
-  HIPCHK(hipMalloc((void**)dst, std::max<size_t>(count, 1) * sizeof(T)));
-  if (count) HIPCHK(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
   return RBPF_OK;
 }
 
@@ -529,9 +514,9 @@ extern "C" {
 
 int rbpf_loc_workspace_bytes(const rbpf_loc_map* map, const rbpf_loc_problem* prob, const rbpf_options* opt, size_t* bytes) {
   if (!bytes) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
-  LOC_TRY(loc_validate_map(map, true));
-  LOC_TRY(loc_validate_problem(prob));
-  LOC_TRY(loc_validate_options(opt));
+  RB_TRY(loc_validate_map(map, true));
+  RB_TRY(loc_validate_problem(prob));
+  RB_TRY(loc_validate_options(opt));
   *bytes = loc_bytes(map, prob, opt, nullptr);
   return RBPF_OK;
 }
@@ -540,20 +525,20 @@ int rbpf_loc_create(const rbpf_loc_map* map, const rbpf_loc_problem* prob, const
                     rbpf_ctx** out) {
   if (!out) { set_error("ctx out pointer is NULL"); return RBPF_ERR_INVALID_ARG; }
   *out = nullptr;
-  LOC_TRY(loc_validate_map(map, true));
-  LOC_TRY(loc_validate_problem(prob));
-  LOC_TRY(loc_validate_options(opt));
+  RB_TRY(loc_validate_map(map, true));
+  RB_TRY(loc_validate_problem(prob));
+  RB_TRY(loc_validate_options(opt));
   if (!rng) { set_error("rng is NULL"); return RBPF_ERR_INVALID_ARG; }
   const int N = prob->N_P, T = prob->N_T, n = map->m_basis + 3;
   if (rng->mode == RBPF_RNG_REPLAY && T > 1 && (!rng->U || !rng->Z)) { set_error("replay rng needs U and Z"); return RBPF_ERR_INVALID_ARG; }
   if (rng->mode != RBPF_RNG_REPLAY && rng->mode != RBPF_RNG_PHILOX) { set_error("unknown rng mode"); return RBPF_ERR_INVALID_ARG; }
   std::vector<double> S;
   int s_pages = 1;
-  LOC_TRY(loc_noise_pages(prob, S, s_pages));
+  RB_TRY(loc_noise_pages(prob, S, s_pages));
   ModelDev M;
   std::vector<int> nn;
-  LOC_TRY(loc_model_dev(map, M, nn));
-  if (!loc_have_device()) { set_error("no HIP device: the localisation filter has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  RB_TRY(loc_model_dev(map, M, nn));
+  if (!have_device()) { set_error("no HIP device: the localisation filter has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
 
   rbpf_ctx* c = new rbpf_ctx();
   LocState* L = new LocState();
@@ -563,44 +548,41 @@ int rbpf_loc_create(const rbpf_loc_map* map, const rbpf_loc_problem* prob, const
   c->N = N; c->T = T; c->mdl = M; c->rng_mode = rng->mode; c->seed = rng->seed;
   L->n = n; L->sigma2 = map->sigma2; L->s_pages = s_pages; L->x0_cols = prob->x0_cols;
   const bool hist = c->opt.keep_history != 0, trace = c->opt.trace != 0;
-  auto fail = [&](int s) { ctx_free(c); return s; };
-#define LOC_C(x) do { int _s = (x); if (_s != RBPF_OK) return fail(_s); } while (0)
-#define LOC_H(x) do { hipError_t _e = (x); if (_e != hipSuccess) return fail(hip_fail(_e, #x, __FILE__, __LINE__)); } while (0)
-  LOC_H(hipGetDevice(&c->device));
-  LOC_H(hipStreamCreate(&c->stream));
-  LOC_C(loc_upload(&c->d_NN, nn.data(), nn.size()));
+  std::unique_ptr<rbpf_ctx, void (*)(rbpf_ctx*)> guard(c, [](rbpf_ctx* p) { ctx_free(p); });
+  HIPCHK(hipGetDevice(&c->device));
+  HIPCHK(hipStreamCreate(&c->stream));
+  RB_TRY(c->pool.upload(&c->d_NN, nn.data(), nn.size()));
   c->mdl.NN = c->d_NN;
-  LOC_C(loc_upload(&L->d_mean, map->mean, (size_t)n));
-  if (map->V) LOC_C(loc_upload(&L->d_V, map->V, (size_t)n * n));
-  if (map->var_table) LOC_C(loc_upload(&L->d_vartab, map->var_table, (size_t)3 * N));
-  LOC_C(loc_upload(&L->d_S, S.data(), S.size()));
-  LOC_C(loc_upload(&L->d_x0, prob->x0_nonlin, (size_t)7 * prob->x0_cols));
+  RB_TRY(L->pool.upload(&L->d_mean, map->mean, (size_t)n));
+  if (map->V) RB_TRY(L->pool.upload(&L->d_V, map->V, (size_t)n * n));
+  if (map->var_table) RB_TRY(L->pool.upload(&L->d_vartab, map->var_table, (size_t)3 * N));
+  RB_TRY(L->pool.upload(&L->d_S, S.data(), S.size()));
+  RB_TRY(L->pool.upload(&L->d_x0, prob->x0_nonlin, (size_t)7 * prob->x0_cols));
   {
     // y [N_T x 3] column-major -> [t][3]; odometry [ld x 7] -> [t][7]
     std::vector<double> yy((size_t)T * 3), oo((size_t)std::max(T - 1, 1) * 7, 0.0);
     for (int t = 0; t < T; ++t) for (int k = 0; k < 3; ++k) yy[(size_t)t * 3 + k] = prob->y[t + (size_t)T * k];
     for (int t = 0; t + 1 < T; ++t) for (int k = 0; k < 7; ++k) oo[(size_t)t * 7 + k] = prob->odometry[t + (size_t)prob->odo_ld * k];
-    LOC_C(loc_upload(&c->d_y, yy.data(), yy.size()));
-    LOC_C(loc_upload(&c->d_odo, oo.data(), oo.size()));
+    RB_TRY(c->pool.upload(&c->d_y, yy.data(), yy.size()));
+    RB_TRY(c->pool.upload(&c->d_odo, oo.data(), oo.size()));
   }
   if (rng->mode == RBPF_RNG_REPLAY && T > 1) {
-    LOC_C(loc_upload(&c->d_U, rng->U, (size_t)N * (T - 1)));
-    LOC_C(loc_upload(&c->d_Z, rng->Z, (size_t)6 * N * (T - 1)));
+    RB_TRY(c->pool.upload(&c->d_U, rng->U, (size_t)N * (T - 1)));
+    RB_TRY(c->pool.upload(&c->d_Z, rng->Z, (size_t)6 * N * (T - 1)));
   }
-  LOC_H(hipMalloc((void**)&c->X, (size_t)(hist ? T : 2) * 7 * N * sizeof(double)));
-  LOC_H(hipMalloc((void**)&c->A, (size_t)(hist ? T : 1) * N * sizeof(int)));
-  LOC_H(hipMemset(c->A, 0, (size_t)(hist ? T : 1) * N * sizeof(int)));
-  LOC_H(hipMalloc((void**)&c->logw, (size_t)(trace ? T : 1) * N * sizeof(double)));
-  LOC_H(hipMalloc((void**)&c->w, (size_t)(trace ? T : 1) * N * sizeof(double)));
-  LOC_H(hipMalloc((void**)&c->wc, (size_t)N * sizeof(double)));
-  LOC_H(hipMalloc((void**)&c->traj_max, (size_t)T * 7 * sizeof(double)));
-  LOC_H(hipMalloc((void**)&c->traj_mean, (size_t)T * 7 * sizeof(double)));
-  LOC_H(hipMalloc((void**)&L->d_lse, (size_t)T * sizeof(double)));
-  LOC_H(hipMalloc((void**)&c->d_flags, 16 * sizeof(int)));
-  LOC_H(hipMemset(c->d_flags, 0, 16 * sizeof(int)));
-  LOC_H(hipMalloc((void**)&c->d_rs, resample_scratch_doubles(N) * sizeof(double)));
-#undef LOC_C
-#undef LOC_H
+  RB_TRY(c->pool.alloc(&c->X, (size_t)(hist ? T : 2) * 7 * N));
+  RB_TRY(c->pool.alloc(&c->A, (size_t)(hist ? T : 1) * N));
+  HIPCHK(hipMemset(c->A, 0, (size_t)(hist ? T : 1) * N * sizeof(int)));
+  RB_TRY(c->pool.alloc(&c->logw, (size_t)(trace ? T : 1) * N));
+  RB_TRY(c->pool.alloc(&c->w, (size_t)(trace ? T : 1) * N));
+  RB_TRY(c->pool.alloc(&c->wc, (size_t)N));
+  RB_TRY(c->pool.alloc(&c->traj_max, (size_t)T * 7));
+  RB_TRY(c->pool.alloc(&c->traj_mean, (size_t)T * 7));
+  RB_TRY(L->pool.alloc(&L->d_lse, (size_t)T));
+  RB_TRY(c->pool.alloc(&c->d_flags, 16));
+  HIPCHK(hipMemset(c->d_flags, 0, 16 * sizeof(int)));
+  RB_TRY(c->pool.alloc(&c->d_rs, resample_scratch_doubles(N)));
+  guard.release();
   *out = c;
   return RBPF_OK;
 }
@@ -609,22 +591,22 @@ int rbpf_loc_advance(rbpf_ctx* c, int32_t n_steps) {
   if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
   for (int s = 0; s < n_steps; ++s) {
-    LOC_TRY(loc_step(c));
-    LOC_TRY(ctx_call_on_step(c, c->t - 1, false));       // particleFilterLocalization.m:129-131
+    RB_TRY(loc_step(c));
+    RB_TRY(ctx_call_on_step(c, c->t - 1, false));       // particleFilterLocalization.m:129-131
   }
   return RBPF_OK;
 }
 
 int rbpf_loc_finish(rbpf_ctx* c, rbpf_loc_out* o) {
   if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
-  LOC_TRY(loc_size_ok(o, "rbpf_loc_out"));
+  RB_TRY(loc_size_ok(o, "rbpf_loc_out"));
   HIPCHK(hipSetDevice(c->device));
   const int N = c->N, Td = c->t;
   const bool hist = c->opt.keep_history != 0, trace = c->opt.trace != 0;
   if ((o->trace_logw || o->trace_w) && !trace) { set_error("trace_logw / trace_w need rbpf_options.trace"); return RBPF_ERR_STATE; }
   if ((o->trace_ai || o->xn_traj) && !hist) { set_error("trace_ai / xn_traj need rbpf_options.keep_history"); return RBPF_ERR_STATE; }
   HIPCHK(hipStreamSynchronize(c->stream));
-  LOC_TRY(ctx_check_flags(c));
+  RB_TRY(ctx_check_flags(c));
   o->first_degenerate_step = -1;
   if (Td == 0) return RBPF_OK;
   std::vector<double> lse((size_t)Td);
@@ -639,23 +621,21 @@ int rbpf_loc_finish(rbpf_ctx* c, rbpf_loc_out* o) {
   if (o->trace_ai) HIPCHK(hipMemcpy(o->trace_ai, c->A, (size_t)Td * N * sizeof(int), hipMemcpyDeviceToHost));
   const double* X_last = c->X + (size_t)(hist ? Td - 1 : ((Td - 1) & 1)) * 7 * N;
   if (o->final_xn || o->xn_traj) {
+    DevicePool tmp;
     double* d_tmp = nullptr;
     const size_t cnt = (size_t)7 * N * (o->xn_traj ? Td : 1);
-    HIPCHK(hipMalloc((void**)&d_tmp, cnt * sizeof(double)));
-    hipError_t e = hipSuccess;
+    RB_TRY(tmp.alloc(&d_tmp, cnt));
     if (o->final_xn) {
-      e = launch_transpose_soa(N, 7, X_last, d_tmp, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e == hipSuccess) e = hipMemcpy(o->final_xn, d_tmp, (size_t)7 * N * sizeof(double), hipMemcpyDeviceToHost);
+      HIPCHK(launch_transpose_soa(N, 7, X_last, d_tmp, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(o->final_xn, d_tmp, (size_t)7 * N * sizeof(double), hipMemcpyDeviceToHost));
     }
-    if (e == hipSuccess && o->xn_traj) {
+    if (o->xn_traj) {
       // xn_traj(:,:,1:t-1) = xn_traj(:,ai,1:t-1) of every step (:101-104) = every slot's path through the ancestor table
-      e = launch_backtrace(N, 7, Td, c->X, c->A, nullptr, N, d_tmp, c->stream, 0);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e == hipSuccess) e = hipMemcpy(o->xn_traj, d_tmp, cnt * sizeof(double), hipMemcpyDeviceToHost);
+      HIPCHK(launch_backtrace(N, 7, Td, c->X, c->A, nullptr, N, d_tmp, c->stream, 0));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(o->xn_traj, d_tmp, cnt * sizeof(double), hipMemcpyDeviceToHost));
     }
-    hipFree(d_tmp);
-    HIPCHK(e);
   }
   return RBPF_OK;
 }
@@ -672,24 +652,25 @@ int rbpf_particle_filter_localization(const rbpf_loc_map* map, const rbpf_loc_pr
 }
 
 int rbpf_loc_predict(const rbpf_loc_map* map, int32_t n_pred, const double* xn, double* dEft, double* var, int32_t reps, double* ms) {
-  LOC_TRY(loc_validate_map(map, false));
+  RB_TRY(loc_validate_map(map, false));
   if (!xn || n_pred < 1 || (!dEft && !var)) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }
   if (var && !map->V) { set_error("rbpf_loc_predict: var needs map->V"); return RBPF_ERR_INVALID_ARG; }
   ModelDev M;
   std::vector<int> nn;
-  LOC_TRY(loc_model_dev(map, M, nn));
-  if (!loc_have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
+  RB_TRY(loc_model_dev(map, M, nn));
+  if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   const int n = map->m_basis + 3;
+  DevicePool tmp;
   int* d_nn = nullptr;
   double *d_xn = nullptr, *d_mean = nullptr, *d_V = nullptr, *d_E = nullptr, *d_var = nullptr;
+  RB_TRY(tmp.upload(&d_nn, nn.data(), nn.size()));
+  RB_TRY(tmp.upload(&d_xn, xn, (size_t)7 * n_pred));
+  RB_TRY(tmp.upload(&d_mean, map->mean, (size_t)n));
+  if (map->V && var) RB_TRY(tmp.upload(&d_V, map->V, (size_t)n * n));
+  RB_TRY(tmp.alloc(&d_E, (size_t)3 * n_pred));
+  RB_TRY(tmp.alloc(&d_var, (size_t)3 * n_pred));
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  auto run = [&]() -> int {
-    LOC_TRY(loc_upload(&d_nn, nn.data(), nn.size()));
-    LOC_TRY(loc_upload(&d_xn, xn, (size_t)7 * n_pred));
-    LOC_TRY(loc_upload(&d_mean, map->mean, (size_t)n));
-    if (map->V && var) LOC_TRY(loc_upload(&d_V, map->V, (size_t)n * n));
-    HIPCHK(hipMalloc((void**)&d_E, (size_t)3 * n_pred * sizeof(double)));
-    HIPCHK(hipMalloc((void**)&d_var, (size_t)3 * n_pred * sizeof(double)));
+  auto run = [&]() -> int {                       // (the events are destroyed whichever way it returns)
     LocArgs a;
     a.mdl = M; a.mdl.NN = d_nn; a.n = n; a.npart = n_pred;
     a.xn = d_xn; a.xn_cs = 1; a.xn_ps = 7;
@@ -717,7 +698,6 @@ int rbpf_loc_predict(const rbpf_loc_map* map, int32_t n_pred, const double* xn, 
   };
   const int s = run();
   for (auto& p : ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  hipFree(d_nn); hipFree(d_xn); hipFree(d_mean); hipFree(d_V); hipFree(d_E); hipFree(d_var);
   return s;
 }
 
@@ -728,24 +708,20 @@ int rbpf_loc_dyn_model(int32_t n_p, const double* xn, const double* odo, double 
   p.N_T = 2; p.q_pages = 1; p.dt_len = 1; p.Q = Q; p.dt = &dt;
   std::vector<double> S;
   int pages = 1;
-  LOC_TRY(loc_noise_pages(&p, S, pages));
-  if (!loc_have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
+  RB_TRY(loc_noise_pages(&p, S, pages));
+  if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
+  DevicePool tmp;
   double *d_x = nullptr, *d_o = nullptr, *d_S = nullptr, *d_z = nullptr, *d_out = nullptr;
-  auto run = [&]() -> int {
-    LOC_TRY(loc_upload(&d_x, xn, (size_t)7 * n_p));
-    LOC_TRY(loc_upload(&d_o, odo, (size_t)7));
-    LOC_TRY(loc_upload(&d_S, S.data(), (size_t)36));
-    LOC_TRY(loc_upload(&d_z, z, (size_t)6 * n_p));
-    HIPCHK(hipMalloc((void**)&d_out, (size_t)7 * n_p * sizeof(double)));
-    hipLaunchKernelGGL(loc_dyn_model_kernel, dim3((n_p + 63) / 64), dim3(64), 0, 0, n_p, d_x, d_o, d_S, d_z, d_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(xn_next, d_out, (size_t)7 * n_p * sizeof(double), hipMemcpyDeviceToHost));
-    return RBPF_OK;
-  };
-  const int s = run();
-  hipFree(d_x); hipFree(d_o); hipFree(d_S); hipFree(d_z); hipFree(d_out);
-  return s;
+  RB_TRY(tmp.upload(&d_x, xn, (size_t)7 * n_p));
+  RB_TRY(tmp.upload(&d_o, odo, (size_t)7));
+  RB_TRY(tmp.upload(&d_S, S.data(), (size_t)36));
+  RB_TRY(tmp.upload(&d_z, z, (size_t)6 * n_p));
+  RB_TRY(tmp.alloc(&d_out, (size_t)7 * n_p));
+  hipLaunchKernelGGL(loc_dyn_model_kernel, dim3((n_p + 63) / 64), dim3(64), 0, 0, n_p, d_x, d_o, d_S, d_z, d_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(xn_next, d_out, (size_t)7 * n_p * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
 }
 
 }  // extern "C"

@@ -21,15 +21,6 @@ namespace rbpf {
 void shard_free(rbpf_ctx* c) {
   ShardState* s = c->sh;
   if (!s) return;
-  hipFree(s->fwd_local); hipFree(s->fwd_gather); hipFree(s->logw_glob); hipFree(s->xn_glob); hipFree(s->w_glob);
-  hipFree(s->wc_glob); hipFree(s->ai_glob); hipFree(s->perm); hipFree(s->ai_bank); hipFree(s->slot_ids);
-  hipFree(s->pack_idx); hipFree(s->send_rec); hipFree(s->recv_rec); hipFree(s->d_share_lead); hipFree(s->d_share);
-  hipFree(s->pb.key); hipFree(s->pb.counts); hipFree(s->pb.offsets); hipFree(s->pb.fill); hipFree(s->pb.tmp);
-  hipFree(s->pb.order); hipFree(s->pb.mv_child); hipFree(s->pb.mv_src); hipFree(s->pb.mv_q); hipFree(s->pb.pref);
-  hipFree(s->pb.slot_ids); hipFree(s->pb.anc_bank); hipFree(s->pb.send_idx); hipFree(s->pb.scalars); hipFree(s->pb.counts_dev);
-  hipFree(s->gid_buf[0]); hipFree(s->gid_buf[1]);
-  hipFree(s->Xhist); hipFree(s->Ahist); hipFree(s->anc_gather); hipFree(s->anc_glob);      // anc_local is a row of fwd_local
-  hipFree(s->anc_w); hipFree(s->anc_wc); hipFree(s->w_local); hipFree(s->ident_bank);
   if (s->counts_pin) hipHostFree(s->counts_pin);
   delete s;
   c->sh = nullptr;
@@ -38,17 +29,6 @@ void shard_free(rbpf_ctx* c) {
 }  // namespace rbpf
 
 using namespace rbpf;
-
-#define RB_TRY(x) do { int _s = (x); if (_s != RBPF_OK) return _s; } while (0)
-
-template <typename T>
-static int dmalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-  if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-  return RBPF_OK;
-}
 
 int rbpf::shard_create_impl(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng, const rbpf_options* opt,
                             int32_t rank, int32_t world, bool smoother, int N_K, rbpf_ctx** out) {
@@ -106,49 +86,48 @@ int rbpf::shard_create_impl(const rbpf_model* model, const rbpf_problem* prob, c
     s->recv_cap = std::min(s->step_cap, Nloc) * (size_t)std::max(c->lazy_depth, 1);
   }
   s->rec_used_all.assign((size_t)world, 0);
-  int st = RBPF_OK;
-  auto A = [&](int r) { if (st == RBPF_OK) st = r; };
+  std::unique_ptr<rbpf_ctx, void (*)(rbpf_ctx*)> guard(c, [](rbpf_ctx* p) { ctx_free(p); });
+  DevicePool& pool = s->pool;
   s->fwd_rows = nN + 1 + (smoother ? 1 : 0);
-  A(dmalloc(&s->fwd_local, Nloc * (size_t)s->fwd_rows));
-  A(dmalloc(&s->fwd_gather, (size_t)s->Nglob * s->fwd_rows));
-  A(dmalloc(&s->logw_glob, (size_t)s->Nglob));
-  A(dmalloc(&s->xn_glob, (size_t)s->Nglob * nN));
-  A(dmalloc(&s->w_glob, (size_t)s->Nglob));
-  A(dmalloc(&s->wc_glob, (size_t)s->Nglob));
-  A(dmalloc(&s->ai_glob, (size_t)s->Nglob));
-  A(dmalloc(&s->perm, (size_t)s->Nglob));
-  A(dmalloc(&s->ai_bank, Nloc));
-  A(dmalloc(&s->slot_ids, Nloc));
-  A(dmalloc(&s->pack_idx, s->send_cap));
-  A(dmalloc(&s->send_rec, s->send_cap * s->recsz));
-  A(dmalloc(&s->recv_rec, s->recv_cap * s->recsz));
+  RB_TRY(pool.alloc(&s->fwd_local, Nloc * (size_t)s->fwd_rows));
+  RB_TRY(pool.alloc(&s->fwd_gather, (size_t)s->Nglob * s->fwd_rows));
+  RB_TRY(pool.alloc(&s->logw_glob, (size_t)s->Nglob));
+  RB_TRY(pool.alloc(&s->xn_glob, (size_t)s->Nglob * nN));
+  RB_TRY(pool.alloc(&s->w_glob, (size_t)s->Nglob));
+  RB_TRY(pool.alloc(&s->wc_glob, (size_t)s->Nglob));
+  RB_TRY(pool.alloc(&s->ai_glob, (size_t)s->Nglob));
+  RB_TRY(pool.alloc(&s->perm, (size_t)s->Nglob));
+  RB_TRY(pool.alloc(&s->ai_bank, Nloc));
+  RB_TRY(pool.alloc(&s->slot_ids, Nloc));
+  // (one rank: no exchange, capacity 0 -- the views still hand out non-null pointers)
+  RB_TRY(pool.alloc(&s->pack_idx, std::max<size_t>(s->send_cap, 1)));
+  RB_TRY(pool.alloc(&s->send_rec, std::max<size_t>(s->send_cap * s->recsz, 1)));
+  RB_TRY(pool.alloc(&s->recv_rec, std::max<size_t>(s->recv_cap * s->recsz, 1)));
   {
     const size_t Ng = (size_t)s->Nglob;
-    A(dmalloc(&s->pb.key, Ng)); A(dmalloc(&s->pb.counts, Ng + 1)); A(dmalloc(&s->pb.offsets, Ng + 1));
-    A(dmalloc(&s->pb.fill, Ng)); A(dmalloc(&s->pb.tmp, Ng)); A(dmalloc(&s->pb.order, Ng));
-    A(dmalloc(&s->pb.mv_child, Ng)); A(dmalloc(&s->pb.mv_src, Ng)); A(dmalloc(&s->pb.mv_q, Ng)); A(dmalloc(&s->pb.pref, Ng));
-    A(dmalloc(&s->pb.slot_ids, Nloc)); A(dmalloc(&s->pb.anc_bank, Nloc)); A(dmalloc(&s->pb.send_idx, Ng));
-    A(dmalloc(&s->pb.scalars, 1)); A(dmalloc(&s->pb.counts_dev, (size_t)4 * world + 1));
-    A(dmalloc(&s->gid_buf[0], Ng)); A(dmalloc(&s->gid_buf[1], Ng));
-    if (st == RBPF_OK && hipHostMalloc((void**)&s->counts_pin, ((size_t)4 * world + 1) * sizeof(long long)) != hipSuccess) st = RBPF_ERR_OUT_OF_MEMORY;
+    RB_TRY(pool.alloc(&s->pb.key, Ng)); RB_TRY(pool.alloc(&s->pb.counts, Ng + 1)); RB_TRY(pool.alloc(&s->pb.offsets, Ng + 1));
+    RB_TRY(pool.alloc(&s->pb.fill, Ng)); RB_TRY(pool.alloc(&s->pb.tmp, Ng)); RB_TRY(pool.alloc(&s->pb.order, Ng));
+    RB_TRY(pool.alloc(&s->pb.mv_child, Ng)); RB_TRY(pool.alloc(&s->pb.mv_src, Ng)); RB_TRY(pool.alloc(&s->pb.mv_q, Ng)); RB_TRY(pool.alloc(&s->pb.pref, Ng));
+    RB_TRY(pool.alloc(&s->pb.slot_ids, Nloc)); RB_TRY(pool.alloc(&s->pb.anc_bank, Nloc)); RB_TRY(pool.alloc(&s->pb.send_idx, Ng));
+    RB_TRY(pool.alloc(&s->pb.scalars, 1)); RB_TRY(pool.alloc(&s->pb.counts_dev, (size_t)4 * world + 1));
+    RB_TRY(pool.alloc(&s->gid_buf[0], Ng)); RB_TRY(pool.alloc(&s->gid_buf[1], Ng));
+    if (hipHostMalloc((void**)&s->counts_pin, ((size_t)4 * world + 1) * sizeof(long long)) != hipSuccess) return RBPF_ERR_OUT_OF_MEMORY;
   }
   if (smoother || (opt && opt->keep_history)) {
     // global history (replicated): states and ancestors of every step in logical order, for the trajectory draws
     const size_t Ng = (size_t)s->Nglob, T = (size_t)prob->N_T;
-    A(dmalloc(&s->Xhist, T * nN * Ng)); A(dmalloc(&s->Ahist, T * Ng));
-    if (st == RBPF_OK && hipMemset(s->Ahist, 0, T * Ng * sizeof(int)) != hipSuccess) st = RBPF_ERR_HIP;
+    RB_TRY(pool.alloc(&s->Xhist, T * nN * Ng)); RB_TRY(pool.alloc(&s->Ahist, T * Ng));
+    if (hipMemset(s->Ahist, 0, T * Ng * sizeof(int)) != hipSuccess) return RBPF_ERR_HIP;
   }
   if (smoother) {
     const size_t Ng = (size_t)s->Nglob;
-    if (st == RBPF_OK) {
-      s->anc_local = s->fwd_local + (size_t)(nN + 1) * Nloc;          // alias: the extra row of the forward bank
-      if (hipMemset(s->anc_local, 0, Nloc * sizeof(double)) != hipSuccess) st = RBPF_ERR_HIP;
-    }
-    A(dmalloc(&s->anc_gather, Ng)); A(dmalloc(&s->anc_glob, Ng));
-    A(dmalloc(&s->anc_w, Ng)); A(dmalloc(&s->anc_wc, Ng)); A(dmalloc(&s->ident_bank, Nloc));
+    s->anc_local = s->fwd_local + (size_t)(nN + 1) * Nloc;            // alias: the extra row of the forward bank
+    if (hipMemset(s->anc_local, 0, Nloc * sizeof(double)) != hipSuccess) return RBPF_ERR_HIP;
+    RB_TRY(pool.alloc(&s->anc_gather, Ng)); RB_TRY(pool.alloc(&s->anc_glob, Ng));
+    RB_TRY(pool.alloc(&s->anc_w, Ng)); RB_TRY(pool.alloc(&s->anc_wc, Ng)); RB_TRY(pool.alloc(&s->ident_bank, Nloc));
   }
-  A(dmalloc(&s->w_local, Nloc));
-  if (st != RBPF_OK) { ctx_free(c); return st; }
+  RB_TRY(pool.alloc(&s->w_local, Nloc));
+  guard.release();
   *out = c;
   return RBPF_OK;
 }
@@ -323,12 +302,12 @@ int rbpf::shard_step_impl(rbpf_ctx* c, const int32_t* anc_bank_host, const int32
     const size_t keys = (size_t)N + s->recv_cap;
     if (s->share_keys < keys) {
       HIPCHK(hipStreamSynchronize(c->stream));
-      hipFree(s->d_share_lead); s->d_share_lead = nullptr;
-      RB_TRY(dmalloc(&s->d_share_lead, keys));
+      s->pool.release(s->d_share_lead);
+      RB_TRY(s->pool.alloc(&s->d_share_lead, keys));
       s->share_keys = keys;
     }
-    if (!s->d_share) RB_TRY(dmalloc(&s->d_share, (size_t)2 * N));
-    if (!c->d_share_writers) { RB_TRY(dmalloc(&c->d_share_writers, 1)); HIPCHK(hipMemset(c->d_share_writers, 0, sizeof(unsigned long long))); c->share_flush = true; }
+    if (!s->d_share) RB_TRY(s->pool.alloc(&s->d_share, (size_t)2 * N));
+    if (!c->d_share_writers) { RB_TRY(c->pool.alloc(&c->d_share_writers, 1)); HIPCHK(hipMemset(c->d_share_writers, 0, sizeof(unsigned long long))); c->share_flush = true; }
     HIPCHK(launch_share_plan(N, (int)keys, a.ai_bank, s->d_share_lead, s->d_share, s->d_share + N, c->timing_on ? c->d_share_writers : nullptr, c->stream));
     a.dst_slot = s->d_share; a.phase_of = s->d_share + N; a.share_flush = 1;
   }
@@ -405,18 +384,18 @@ int rbpf_shard_plan(rbpf_ctx* c, int64_t* counts_host) {
       cap = std::min(cap, (size_t)s->Nloc * (size_t)(s->world - 1));
       const size_t new_send = cap, new_recv = std::max(std::min(cap, (size_t)s->Nloc) * lz, (size_t)need_hold);
       double *ns = nullptr, *nr = nullptr; int* ni = nullptr;
-      int st = dmalloc(&ns, new_send * s->recsz);
-      if (st == RBPF_OK) st = dmalloc(&nr, new_recv * s->recsz);
-      if (st == RBPF_OK) st = dmalloc(&ni, new_send);
-      if (st != RBPF_OK) {
-        hipFree(ns); hipFree(nr); hipFree(ni);
+      int st = s->pool.alloc(&ns, new_send * s->recsz);
+      if (st == RBPF_OK) st = s->pool.alloc(&nr, new_recv * s->recsz);
+      if (st == RBPF_OK) st = s->pool.alloc(&ni, new_send);
+      if (st != RBPF_OK) {                                 // the old buffers stay
+        s->pool.release(ns); s->pool.release(nr); s->pool.release(ni);
         set_error("exchange buffers could not be grown to " + std::to_string(new_send) + " / " + std::to_string(new_recv) + " records");
         return RBPF_ERR_OUT_OF_MEMORY;
       }
       // records received earlier in this lazy cycle stay alive: they move to the new buffer
       if (s->rec_used > 0) HIPCHK(hipMemcpyAsync(nr, s->recv_rec, (size_t)s->rec_used * s->recsz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
-      hipFree(s->send_rec); hipFree(s->recv_rec); hipFree(s->pack_idx);
+      s->pool.release(s->send_rec); s->pool.release(s->recv_rec); s->pool.release(s->pack_idx);
       s->send_rec = ns; s->recv_rec = nr; s->pack_idx = ni;
       s->step_cap = cap; s->send_cap = new_send; s->recv_cap = new_recv;
       ++s->regrown;
@@ -478,26 +457,22 @@ int rbpf::shard_unpack_particle(rbpf_ctx* c, int idx, double* dP) {
   ShardState* s = c->sh;
   const Layout& L = c->lay;
   const int d = c->mdl.d, N = s->Nloc;
+  DevicePool tmp;
   int* didx = nullptr;
-  RB_TRY(dmalloc(&didx, 1));
-  hipError_t e = hipMemcpyAsync(didx, &idx, sizeof(int), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && c->lazy_depth >= 2) {
+  RB_TRY(tmp.alloc(&didx, 1));
+  HIPCHK(hipMemcpyAsync(didx, &idx, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (c->lazy_depth >= 2) {
     const PendingSets ps = ctx_pending_sets(c, N);
     double* rec = nullptr;
-    int st = dmalloc(&rec, s->recsz);
-    if (st != RBPF_OK) { hipFree(didx); return st; }
-    e = launch_pack_records_flushed(L, d, didx, 1, c->Pt[c->cur], c->Pb[c->cur], ps.n, ps.fset, ps.fidx, c->base[c->tcur], N, s->recv_rec,
-                                    s->recsz, c->xl[c->xcur], rec, c->stream, c->fp32 ? 1 : 0);
+    RB_TRY(tmp.alloc(&rec, s->recsz));
+    HIPCHK(launch_pack_records_flushed(L, d, didx, 1, c->Pt[c->cur], c->Pb[c->cur], ps.n, ps.fset, ps.fidx, c->base[c->tcur], N, s->recv_rec,
+                                       s->recsz, c->xl[c->xcur], rec, c->stream, c->fp32 ? 1 : 0));
     const size_t per = c->fp32 ? 2 : 1;
-    if (e == hipSuccess) e = launch_unpack_P(L, d, rec, rec + L.szT / per, nullptr, nullptr, 1, dP, c->stream, c->fp32 ? 1 : 0);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(rec);
-  } else if (e == hipSuccess) {
-    e = launch_unpack_P(L, d, c->Pt[c->cur], c->Pb[c->cur], c->t > 0 ? c->F[c->cur] : nullptr, didx, 1, dP, c->stream, c->fp32 ? 1 : 0);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIPCHK(launch_unpack_P(L, d, rec, rec + L.szT / per, nullptr, nullptr, 1, dP, c->stream, c->fp32 ? 1 : 0));
+  } else {
+    HIPCHK(launch_unpack_P(L, d, c->Pt[c->cur], c->Pb[c->cur], c->t > 0 ? c->F[c->cur] : nullptr, didx, 1, dP, c->stream, c->fp32 ? 1 : 0));
   }
-  hipFree(didx);
-  HIPCHK(e);
+  HIPCHK(hipStreamSynchronize(c->stream));
   return RBPF_OK;
 }
 
@@ -541,38 +516,32 @@ int rbpf_shard_finish(rbpf_ctx* c, int32_t phase, double* xl_max, double* P_max,
     if (P_max) {
       std::memset(P_max, 0, (size_t)n * n * sizeof(double));
       if (owner == s->rank) {
+        DevicePool tmp;
         double* dP = nullptr;
-        RB_TRY(dmalloc(&dP, (size_t)n * n));
-        int rc = shard_unpack_particle(c, idx, dP);
-        hipError_t e = (rc == RBPF_OK) ? hipMemcpy(P_max, dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost) : hipSuccess;
-        hipFree(dP);
-        if (rc != RBPF_OK) return rc;
-        HIPCHK(e);
+        RB_TRY(tmp.alloc(&dP, (size_t)n * n));
+        RB_TRY(shard_unpack_particle(c, idx, dP));
+        HIPCHK(hipMemcpy(P_max, dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost));
       }
     }
     if (xl_mean) {                       // my share of sum_i w_i xl_i (particleFilter.m:224)
       hipLaunchKernelGGL(shard_w_local_kernel, dim3((Nloc + 255) / 256), dim3(256), 0, st, Nloc, s->rank * Nloc,
                          s->placed ? s->pb.slot_ids : nullptr, s->w_glob, s->w_local);
+      DevicePool tmp;
       double* dm = nullptr;
-      RB_TRY(dmalloc(&dm, (size_t)n));
-      hipError_t e = launch_weighted_mean_xl(Nloc, n, L.ldx, c->xl[c->xcur], s->w_local, dm, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(xl_mean, dm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      hipFree(dm);
-      HIPCHK(e);
+      RB_TRY(tmp.alloc(&dm, (size_t)n));
+      HIPCHK(launch_weighted_mean_xl(Nloc, n, L.ldx, c->xl[c->xcur], s->w_local, dm, st));
+      HIPCHK(hipMemcpyAsync(xl_mean, dm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
     }
     if (traj_sample_iwmax) {             // :233, back-trace through the replicated history
       if (!s->Xhist) { set_error("traj_sample_iwmax needs keep_history = 1"); return RBPF_ERR_STATE; }
+      DevicePool tmp;
       double* dout = nullptr; int* didx = nullptr;
-      RB_TRY(dmalloc(&dout, (size_t)nN * Td));
-      int s2 = dmalloc(&didx, 1);
-      if (s2 != RBPF_OK) { hipFree(dout); return s2; }
-      hipError_t e = hipMemcpy(didx, &iw, sizeof(int), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = launch_backtrace(N, nN, Td, s->Xhist, s->Ahist, didx, 1, dout, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e == hipSuccess) e = hipMemcpy(traj_sample_iwmax, dout, (size_t)nN * Td * sizeof(double), hipMemcpyDeviceToHost);
-      hipFree(dout); hipFree(didx);
-      HIPCHK(e);
+      RB_TRY(tmp.alloc(&dout, (size_t)nN * Td));
+      RB_TRY(tmp.upload(&didx, &iw, 1));
+      HIPCHK(launch_backtrace(N, nN, Td, s->Xhist, s->Ahist, didx, 1, dout, st));
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpy(traj_sample_iwmax, dout, (size_t)nN * Td * sizeof(double), hipMemcpyDeviceToHost));
     }
     return RBPF_OK;
   }
@@ -583,17 +552,15 @@ int rbpf_shard_finish(rbpf_ctx* c, int32_t phase, double* xl_max, double* P_max,
   int owner = 0, idx = 0;
   RB_TRY(locate(N - 1, owner, idx));
   if (owner == s->rank) {
+    DevicePool tmp;
     double* dP = nullptr;
-    RB_TRY(dmalloc(&dP, (size_t)n * n));
+    RB_TRY(tmp.alloc(&dP, (size_t)n * n));
     std::vector<double> Pl((size_t)n * n), xll(n);
     double wl = 0.0;
-    int rc = shard_unpack_particle(c, idx, dP);
-    hipError_t e = (rc == RBPF_OK) ? hipMemcpy(Pl.data(), dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost) : hipSuccess;
-    hipFree(dP);
-    if (rc != RBPF_OK) return rc;
-    if (e == hipSuccess) e = hipMemcpy(xll.data(), c->xl[c->xcur] + (size_t)idx * L.ldx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&wl, s->w_glob + (N - 1), sizeof(double), hipMemcpyDeviceToHost);
-    HIPCHK(e);
+    RB_TRY(shard_unpack_particle(c, idx, dP));
+    HIPCHK(hipMemcpy(Pl.data(), dP, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(xll.data(), c->xl[c->xcur] + (size_t)idx * L.ldx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&wl, s->w_glob + (N - 1), sizeof(double), hipMemcpyDeviceToHost));
     for (int cc = 0; cc < n; ++cc)
       for (int r = 0; r < n; ++r)
         P_mean[r + (size_t)n * cc] = wl * (Pl[r + (size_t)n * cc] + (xl_mean[r] - xll[r]) * (xl_mean[cc] - xll[cc]));
@@ -615,18 +582,16 @@ int rbpf_shard_xn_traj(rbpf_ctx* c, double* xn_traj) {
   // chunk's are nN * cnt: one strided copy per chunk)
   const size_t budget = (size_t)256 << 20;
   const int chunk = (int)std::max<size_t>(64, std::min<size_t>((size_t)N, budget / ((size_t)nN * Td * sizeof(double))));
+  DevicePool tmp;
   double* dout = nullptr;
-  RB_TRY(dmalloc(&dout, (size_t)nN * chunk * Td));
-  hipError_t e = hipSuccess;
-  for (int p0 = 0; p0 < N && e == hipSuccess; p0 += chunk) {
+  RB_TRY(tmp.alloc(&dout, (size_t)nN * chunk * Td));
+  for (int p0 = 0; p0 < N; p0 += chunk) {
     const int cnt = std::min(chunk, N - p0);
-    e = launch_backtrace(N, nN, Td, s->Xhist, s->Ahist, nullptr, cnt, dout, c->stream, p0);      // particleFilter.m:117-118
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy2D(xn_traj + (size_t)nN * p0, (size_t)nN * N * sizeof(double), dout, (size_t)nN * cnt * sizeof(double),
-                                         (size_t)nN * cnt * sizeof(double), (size_t)Td, hipMemcpyDeviceToHost);
+    HIPCHK(launch_backtrace(N, nN, Td, s->Xhist, s->Ahist, nullptr, cnt, dout, c->stream, p0));  // particleFilter.m:117-118
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy2D(xn_traj + (size_t)nN * p0, (size_t)nN * N * sizeof(double), dout, (size_t)nN * cnt * sizeof(double),
+                       (size_t)nN * cnt * sizeof(double), (size_t)Td, hipMemcpyDeviceToHost));
   }
-  hipFree(dout);
-  HIPCHK(e);
   return RBPF_OK;
 }
 

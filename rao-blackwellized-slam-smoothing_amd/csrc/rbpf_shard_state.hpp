@@ -6,6 +6,7 @@
 namespace rbpf {
 
 struct ShardState {
+  DevicePool pool;                 // owns every device buffer below, pb's included (anc_local is a row of fwd_local)
   int rank = 0, world = 1, Nloc = 0, Nglob = 0;
   size_t recsz = 0, recv_cap = 0, send_cap = 0;
   int fwd_rows = 0;                // rows of the forward bank: nN + 1 (states, log-weight); + 1 in the smoother (anc_local)

@@ -20,6 +20,7 @@
 namespace rbpf {
 
 struct SmootherState {
+  DevicePool pool;              // owns every device buffer below
   double* d_xnk = nullptr;      // [T][nN] reference trajectory of this iteration (row per step)
   double* d_dyref = nullptr;    // [T][d][n] H along the reference trajectory (:120)
   double* d_pant_log = nullptr; // [N]
@@ -83,13 +84,6 @@ struct SmootherState {
 void smoother_free(rbpf_ctx* c) {
   SmootherState* s = c->sm;
   if (!s) return;
-  hipFree(s->d_xnk); hipFree(s->d_dyref); hipFree(s->d_pant_log); hipFree(s->d_pant); hipFree(s->d_wc2);
-  hipFree(s->d_Pfull); hipFree(s->d_G); hipFree(s->d_S); hipFree(s->d_L); hipFree(s->d_e);
-  for (int b = 0; b < 2; ++b) { hipFree(s->d_Imat[b]); hipFree(s->d_Hb[b]); hipFree(s->d_ivec[b]); hipFree(s->d_hld[b]); hipFree(s->d_qf[b]); }
-  hipFree(s->d_ImatAdd); hipFree(s->d_ivecAdd); hipFree(s->d_Imat0); hipFree(s->d_ak); hipFree(s->d_ivec0); hipFree(s->d_hld0);
-  hipFree(s->d_Rinv); hipFree(s->d_Lsw[0]); hipFree(s->d_Lsw[1]); hipFree(s->d_W);
-  hipFree(s->d_base_slot); hipFree(s->d_Xp); hipFree(s->d_marks);
-  hipFree(s->d_owner_now); hipFree(s->d_base_gid); hipFree(s->d_base_loc); hipFree(s->d_rf_send); hipFree(s->d_rf_recv); hipFree(s->d_rf_idx);
   delete s;
   c->sm = nullptr;
 }
@@ -844,17 +838,6 @@ static int info_begin_iteration(rbpf_ctx* c, const double* ivec0, double hld0, d
 static int info_fill_chol_args(rbpf_ctx* c, CholArgs& ca, const double* d_Rinv, const int* anc);
 static int info_step(rbpf_ctx* c, int k, int t, const double* xref, int n_draw, const double* d_Rinv);
 
-#define RB_TRY(x) do { int _s = (x); if (_s != RBPF_OK) return _s; } while (0)
-
-template <typename T>
-static int dmalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-  if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-  return RBPF_OK;
-}
-
 // Normalise N ancestor log-probabilities (particleSmoother.m:236-238) and draw ONE index from them into ai[slot]
 // (:241).  Up to 8192 entries: the single-workgroup kernel with the strict left-to-right running sum.  Above: the
 // multi-workgroup pipeline (parallel prefix + certified search + exact fallback), same indices, ~0.15 ms instead of
@@ -882,18 +865,8 @@ static int normalise_draw_one(rbpf_ctx* c, int N, int t, int k, const double* lo
 static int invert_R(const std::vector<double>& Rh, int d, std::vector<double>& Rinv, double& halfLogDetR) {
   halfLogDetR = 0.0;
   std::vector<double> Lr((size_t)d * d, 0.0);
-  for (int j = 0; j < d; ++j) {
-    double sdiag = Rh[j + (size_t)d * j];
-    for (int k = 0; k < j; ++k) sdiag -= Lr[j + (size_t)d * k] * Lr[j + (size_t)d * k];
-    if (!(sdiag > 0)) { set_error("R must be positive definite"); return RBPF_ERR_CHOL_FAILED; }
-    Lr[j + (size_t)d * j] = std::sqrt(sdiag);
-    for (int i = j + 1; i < d; ++i) {
-      double v = Rh[i + (size_t)d * j];
-      for (int k = 0; k < j; ++k) v -= Lr[i + (size_t)d * k] * Lr[j + (size_t)d * k];
-      Lr[i + (size_t)d * j] = v / Lr[j + (size_t)d * j];
-    }
-    halfLogDetR += std::log(Lr[j + (size_t)d * j]);
-  }
+  if (!chol_lower_host(Rh.data(), d, d, Lr.data(), d)) { set_error("R must be positive definite"); return RBPF_ERR_CHOL_FAILED; }
+  for (int j = 0; j < d; ++j) halfLogDetR += std::log(Lr[j + (size_t)d * j]);
   for (int col = 0; col < d; ++col) {             // solve R x = e_col
     std::vector<double> y(d), x(d);
     for (int i = 0; i < d; ++i) { double v = (i == col); for (int k = 0; k < i; ++k) v -= Lr[i + (size_t)d * k] * y[k]; y[i] = v / Lr[i + (size_t)d * i]; }
@@ -919,16 +892,7 @@ static void info_initial_values(rbpf_ctx* c, std::vector<double>& ivec0, std::ve
 static void whitening_factor(const std::vector<double>& Rh, int d, std::vector<double>& Wm) {
   std::vector<double> Lr((size_t)d * d, 0.0);
   Wm.assign((size_t)d * d, 0.0);
-  for (int j = 0; j < d; ++j) {
-    double sd = Rh[j + (size_t)d * j];
-    for (int q = 0; q < j; ++q) sd -= Lr[j + (size_t)d * q] * Lr[j + (size_t)d * q];
-    Lr[j + (size_t)d * j] = std::sqrt(sd);
-    for (int i = j + 1; i < d; ++i) {
-      double v = Rh[i + (size_t)d * j];
-      for (int q = 0; q < j; ++q) v -= Lr[i + (size_t)d * q] * Lr[j + (size_t)d * q];
-      Lr[i + (size_t)d * j] = v / Lr[j + (size_t)d * j];
-    }
-  }
+  (void)chol_lower_host(Rh.data(), d, d, Lr.data(), d);    // R is positive definite: invert_R has passed
   for (int col = 0; col < d; ++col)
     for (int i = 0; i < d; ++i) {
       double v = (i == col);
@@ -982,37 +946,35 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
     return RBPF_ERR_INVALID_ARG;
   }
   if (generic && !drn_cb && !c->cholQfull_ok) { set_error("isempty(dynResNorm): chol(dt*Q,'lower') failed (particleSmoother.m:177)"); return RBPF_ERR_CHOL_FAILED; }
+  DevicePool tmp;                                                    // scratch of this run
   double* d_edyn = nullptr;
-  struct EdynGuard { double** p; ~EdynGuard() { hipFree(*p); } } edyn_guard{&d_edyn};
-  if (drn_cb) RB_TRY(dmalloc(&d_edyn, (size_t)N * nw));
+  if (drn_cb) RB_TRY(tmp.alloc(&d_edyn, (size_t)N * nw));
   std::vector<double> h_edyn;
   const size_t Mmax = (size_t)d * T;
   s->Mmax = Mmax;
-  RB_TRY(dmalloc(&s->d_xnk, (size_t)T * nN));
-  RB_TRY(dmalloc(&s->d_dyref, (size_t)T * d * n));
-  RB_TRY(dmalloc(&s->d_pant_log, (size_t)N));
-  RB_TRY(dmalloc(&s->d_pant, (size_t)N * (c->opt.trace ? (size_t)T * N_K : 1)));
+  RB_TRY(s->pool.alloc(&s->d_xnk, (size_t)T * nN));
+  RB_TRY(s->pool.alloc(&s->d_dyref, (size_t)T * d * n));
+  RB_TRY(s->pool.alloc(&s->d_pant_log, (size_t)N));
+  RB_TRY(s->pool.alloc(&s->d_pant, (size_t)N * (c->opt.trace ? (size_t)T * N_K : 1)));
   {
     const size_t cnt = (size_t)N * (c->opt.trace ? (size_t)T * N_K : 1);
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, cnt, (double)NAN, s->d_pant);
     HIPCHK(hipGetLastError());
   }
-  RB_TRY(dmalloc(&s->d_wc2, (size_t)N));
-  RB_TRY(dmalloc(&s->d_ak, 4));
+  RB_TRY(s->pool.alloc(&s->d_wc2, (size_t)N));
+  RB_TRY(s->pool.alloc(&s->d_ak, 4));
   std::vector<double> Rinv((size_t)d * d), Rh(c->h_R);
   double halfLogDetR = 0.0;
   RB_TRY(invert_R(Rh, d, Rinv, halfLogDetR));
   double *d_R = nullptr, *d_Rinv = nullptr;
-  RB_TRY(dmalloc(&d_R, (size_t)d * d));
-  RB_TRY(dmalloc(&d_Rinv, (size_t)d * d));
-  struct Guard { double* a; double* b; ~Guard() { hipFree(a); hipFree(b); } } guard{d_R, d_Rinv};
+  RB_TRY(tmp.alloc(&d_R, (size_t)d * d));
+  RB_TRY(tmp.alloc(&d_Rinv, (size_t)d * d));
   HIPCHK(hipMemcpy(d_R, Rh.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_Rinv, Rinv.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
 
   const bool sparse = c->mdl.kind == RBPF_MODEL_SPARSE_VISUAL_2D;
   std::vector<int> pair_t, pair_j, pair_off((size_t)T + 1, 0);
   int *d_pair_t = nullptr, *d_pair_j = nullptr;
-  struct PairGuard { int** a; int** b; ~PairGuard() { hipFree(*a); hipFree(*b); } } pair_guard{&d_pair_t, &d_pair_j};
   if (sparse) {
     if (info_form) { set_error("This code has only been implemented for dense features"); return RBPF_ERR_UNSUPPORTED; }   // InformationForm.m:77-80
     // observed (time, output) pairs, time-major: the future observations of step t are the suffix from pair_off[t]
@@ -1025,20 +987,20 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
     const size_t Ms = (T > 1) ? (size_t)(pair_off[T] - pair_off[1]) : 0;
     if (Ms > 1023) { set_error("sparse smoother: more than 1023 future observations (particleSmoother.m:197-212 stacks them all)"); return RBPF_ERR_UNSUPPORTED; }
     s->Mmax = Ms;
-    RB_TRY(dmalloc(&d_pair_t, pair_t.size()));
-    RB_TRY(dmalloc(&d_pair_j, pair_j.size()));
+    RB_TRY(tmp.alloc(&d_pair_t, std::max<size_t>(pair_t.size(), 1)));   // (kernel arguments: non-null without observations too)
+    RB_TRY(tmp.alloc(&d_pair_j, std::max<size_t>(pair_j.size(), 1)));
     if (!pair_t.empty()) {
       HIPCHK(hipMemcpy(d_pair_t, pair_t.data(), pair_t.size() * sizeof(int), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(d_pair_j, pair_j.data(), pair_j.size() * sizeof(int), hipMemcpyHostToDevice));
     }
-    RB_TRY(dmalloc(&s->d_S, (size_t)N * Ms * Ms));
-    RB_TRY(dmalloc(&s->d_e, (size_t)N * Ms));
-    RB_TRY(dmalloc(&s->d_L, (size_t)N * chol_factor_doubles((int)Ms)));
+    RB_TRY(s->pool.alloc(&s->d_S, std::max<size_t>((size_t)N * Ms * Ms, 1)));
+    RB_TRY(s->pool.alloc(&s->d_e, std::max<size_t>((size_t)N * Ms, 1)));
+    RB_TRY(s->pool.alloc(&s->d_L, (size_t)N * chol_factor_doubles((int)Ms)));
   } else if (!info_form) {
-    RB_TRY(dmalloc(&s->d_Pfull, (size_t)N * n * n));
-    RB_TRY(dmalloc(&s->d_G, (size_t)N * Mmax * n));
-    RB_TRY(dmalloc(&s->d_S, (size_t)N * Mmax * Mmax));
-    RB_TRY(dmalloc(&s->d_L, (size_t)N * chol_factor_doubles((int)Mmax)));
+    RB_TRY(s->pool.alloc(&s->d_Pfull, (size_t)N * n * n));
+    RB_TRY(s->pool.alloc(&s->d_G, (size_t)N * Mmax * n));
+    RB_TRY(s->pool.alloc(&s->d_S, (size_t)N * Mmax * Mmax));
+    RB_TRY(s->pool.alloc(&s->d_L, (size_t)N * chol_factor_doubles((int)Mmax)));
     if (Mmax > 1023) { set_error("covariance-form smoother supports ny*N_T <= 1023 (use the information form for long T)"); return RBPF_ERR_UNSUPPORTED; }
   } else {
     if (n > 1023) { set_error("information-form smoother supports nLin <= 1023"); return RBPF_ERR_UNSUPPORTED; }
@@ -1073,34 +1035,34 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
     s->seg_len = 32;
     for (int b = 0; b < 2; ++b) {
       const size_t n_mat = s->refresh_free ? (b == 0 ? (size_t)s->l_chunk : (size_t)0) : (size_t)N;
-      RB_TRY(dmalloc(&s->d_Imat[b], n_mat * s->imat_len));
+      RB_TRY(s->pool.alloc(&s->d_Imat[b], std::max<size_t>(n_mat * s->imat_len, 1)));   // (refresh-free: bank 1 is a kernel argument nobody reads)
       if (s->imat_packed && n_mat) HIPCHK(hipMemsetAsync(s->d_Imat[b], 0, n_mat * s->imat_len * 8, st));   // the never-written upper halves of the diagonal tiles
-      RB_TRY(dmalloc(&s->d_Hb[b], (size_t)N * d * L.ldx));
-      RB_TRY(dmalloc(&s->d_ivec[b], (size_t)N * L.ldx));
-      RB_TRY(dmalloc(&s->d_hld[b], (size_t)N));
-      RB_TRY(dmalloc(&s->d_qf[b], (size_t)N));
+      RB_TRY(s->pool.alloc(&s->d_Hb[b], (size_t)N * d * L.ldx));
+      RB_TRY(s->pool.alloc(&s->d_ivec[b], (size_t)N * L.ldx));
+      RB_TRY(s->pool.alloc(&s->d_hld[b], (size_t)N));
+      RB_TRY(s->pool.alloc(&s->d_qf[b], (size_t)N));
     }
     // factor workspaces of the 64-column kernel: one per particle -- or, with carried factors, per particle of a CHUNK of the
     // refresh (they are converted to the sweep layout chunk by chunk): 2.2 MB per particle at nLin = 515 that N_P = 32 768 has no room for
-    RB_TRY(dmalloc(&s->d_L, (size_t)s->l_chunk * chol_factor_doubles(n)));
-    RB_TRY(dmalloc(&s->d_ImatAdd, (size_t)n * n));
-    RB_TRY(dmalloc(&s->d_ivecAdd, (size_t)n));
-    RB_TRY(dmalloc(&s->d_Imat0, (size_t)n * n));
+    RB_TRY(s->pool.alloc(&s->d_L, (size_t)s->l_chunk * chol_factor_doubles(n)));
+    RB_TRY(s->pool.alloc(&s->d_ImatAdd, (size_t)n * n));
+    RB_TRY(s->pool.alloc(&s->d_ivecAdd, (size_t)n));
+    RB_TRY(s->pool.alloc(&s->d_Imat0, (size_t)n * n));
     if (s->refresh) {
-      for (int b = 0; b < 2; ++b) RB_TRY(dmalloc(&s->d_Lsw[b], (size_t)N * sweep_factor_doubles(n)));
-      RB_TRY(dmalloc(&s->d_W, (size_t)d * d));
+      for (int b = 0; b < 2; ++b) RB_TRY(s->pool.alloc(&s->d_Lsw[b], (size_t)N * sweep_factor_doubles(n)));
+      RB_TRY(s->pool.alloc(&s->d_W, (size_t)d * d));
       std::vector<double> Wm;
       whitening_factor(Rh, d, Wm);
       HIPCHK(hipMemcpy(s->d_W, Wm.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
       if (s->lazy_imat) {
-        RB_TRY(dmalloc(&s->d_base_slot, (size_t)N));
+        RB_TRY(s->pool.alloc(&s->d_base_slot, (size_t)N));
         if (s->refresh_free) {                                             // a chunk of particles x a segment of generations at a time
-          RB_TRY(dmalloc(&s->d_Xp, (size_t)s->l_chunk * s->seg_len * nN));
-          RB_TRY(dmalloc(&s->d_G, (size_t)s->l_chunk * s->seg_len * d * n));
-          RB_TRY(dmalloc(&s->d_marks, (size_t)((T + s->seg_len - 1) / s->seg_len) * N));
+          RB_TRY(s->pool.alloc(&s->d_Xp, (size_t)s->l_chunk * s->seg_len * nN));
+          RB_TRY(s->pool.alloc(&s->d_G, (size_t)s->l_chunk * s->seg_len * d * n));
+          RB_TRY(s->pool.alloc(&s->d_marks, (size_t)((T + s->seg_len - 1) / s->seg_len) * N));
         } else {
-          RB_TRY(dmalloc(&s->d_Xp, (size_t)N * s->refresh * nN));          // generations a refresh walks back: K
-          RB_TRY(dmalloc(&s->d_G, (size_t)N * s->refresh * d * n));
+          RB_TRY(s->pool.alloc(&s->d_Xp, (size_t)N * s->refresh * nN));          // generations a refresh walks back: K
+          RB_TRY(s->pool.alloc(&s->d_G, (size_t)N * s->refresh * d * n));
         }
       }
     }
@@ -1326,13 +1288,12 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
       (void)cur;
       if (out->XLK) HIPCHK(hipMemcpy(out->XLK + (size_t)k * n, c->xl[c->xcur] + (size_t)ak * L.ldx, (size_t)n * 8, hipMemcpyDeviceToHost));
       if (out->PK) {
+        DevicePool pk;
         double* dP = nullptr;
-        RB_TRY(dmalloc(&dP, (size_t)n * n));
-        hipError_t e = (ctx_unpack(c, s->d_ak, 1, dP) == RBPF_OK) ? hipSuccess : hipErrorUnknown;   // pending downdates applied
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipMemcpy(out->PK + (size_t)k * n * n, dP, (size_t)n * n * 8, hipMemcpyDeviceToHost);
-        hipFree(dP);
-        HIPCHK(e);
+        RB_TRY(pk.alloc(&dP, (size_t)n * n));
+        RB_TRY(ctx_unpack(c, s->d_ak, 1, dP));                // pending downdates applied
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(out->PK + (size_t)k * n * n, dP, (size_t)n * n * 8, hipMemcpyDeviceToHost));
       }
       if (out->trace_ak) out->trace_ak[k] = ak;
       if (c->opt.trace) {
@@ -1352,8 +1313,8 @@ static int info_begin_iteration(rbpf_ctx* c, const double* ivec0, double hld0, d
   SmootherState* s = c->sm;
   const Layout& L = c->lay;
   if (!s->d_ivec0) {
-    RB_TRY(dmalloc(&s->d_ivec0, (size_t)L.ldx));
-    RB_TRY(dmalloc(&s->d_hld0, 1));
+    RB_TRY(s->pool.alloc(&s->d_ivec0, (size_t)L.ldx));
+    RB_TRY(s->pool.alloc(&s->d_hld0, 1));
   }
   HIPCHK(hipMemcpyAsync(s->d_ivec0, ivec0, (size_t)L.ldx * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(s->d_hld0, &hld0, 8, hipMemcpyHostToDevice, c->stream));
@@ -1495,26 +1456,26 @@ int rbpf_shard_smoother_create(const rbpf_model* model, const rbpf_problem* prob
   // factorisation runs chunk by chunk (as in the single-device smoother, smoother_run)
   s->refresh_free = s->lazy_imat && s->refresh >= T - 1;
   s->seg_len = 32;
-  RB_TRY(dmalloc(&s->d_xnk, (size_t)T * nN));
-  RB_TRY(dmalloc(&s->d_dyref, (size_t)T * d * n));
-  RB_TRY(dmalloc(&s->d_ak, 4));
+  RB_TRY(s->pool.alloc(&s->d_xnk, (size_t)T * nN));
+  RB_TRY(s->pool.alloc(&s->d_dyref, (size_t)T * d * n));
+  RB_TRY(s->pool.alloc(&s->d_ak, 4));
   s->imat_packed = imat_storage_packed(n, d, s->refresh, true);
   s->imat_len = s->imat_packed ? imat_packed_doubles(n) : (size_t)n * n;
   s->l_chunk = s->lazy_imat ? std::min(N, 4096) : N;
   for (int b = 0; b < 2; ++b) {
     const size_t n_mat = s->refresh_free ? (b == 0 ? (size_t)s->l_chunk : (size_t)0) : (size_t)N;
-    RB_TRY(dmalloc(&s->d_Imat[b], n_mat * s->imat_len));
+    RB_TRY(s->pool.alloc(&s->d_Imat[b], std::max<size_t>(n_mat * s->imat_len, 1)));   // (refresh-free: bank 1 is a kernel argument nobody reads)
     if (s->imat_packed && n_mat) HIPCHK(hipMemset(s->d_Imat[b], 0, n_mat * s->imat_len * 8));
-    RB_TRY(dmalloc(&s->d_Hb[b], (size_t)N * d * L.ldx));
-    RB_TRY(dmalloc(&s->d_ivec[b], (size_t)N * L.ldx));
-    RB_TRY(dmalloc(&s->d_hld[b], (size_t)N));
-    RB_TRY(dmalloc(&s->d_qf[b], (size_t)N));
+    RB_TRY(s->pool.alloc(&s->d_Hb[b], (size_t)N * d * L.ldx));
+    RB_TRY(s->pool.alloc(&s->d_ivec[b], (size_t)N * L.ldx));
+    RB_TRY(s->pool.alloc(&s->d_hld[b], (size_t)N));
+    RB_TRY(s->pool.alloc(&s->d_qf[b], (size_t)N));
   }
-  RB_TRY(dmalloc(&s->d_L, (size_t)s->l_chunk * chol_factor_doubles(n)));
-  RB_TRY(dmalloc(&s->d_ImatAdd, (size_t)n * n));
-  RB_TRY(dmalloc(&s->d_ivecAdd, (size_t)n));
-  RB_TRY(dmalloc(&s->d_Imat0, (size_t)n * n));
-  RB_TRY(dmalloc(&s->d_Rinv, (size_t)d * d));
+  RB_TRY(s->pool.alloc(&s->d_L, (size_t)s->l_chunk * chol_factor_doubles(n)));
+  RB_TRY(s->pool.alloc(&s->d_ImatAdd, (size_t)n * n));
+  RB_TRY(s->pool.alloc(&s->d_ivecAdd, (size_t)n));
+  RB_TRY(s->pool.alloc(&s->d_Imat0, (size_t)n * n));
+  RB_TRY(s->pool.alloc(&s->d_Rinv, (size_t)d * d));
   std::vector<double> Rinv((size_t)d * d), Imat0((size_t)n * n, 0.0);
   double halfLogDetR = 0.0;
   RB_TRY(invert_R(c->h_R, d, Rinv, halfLogDetR));
@@ -1530,26 +1491,26 @@ int rbpf_shard_smoother_create(const rbpf_model* model, const rbpf_problem* prob
     // and the exchange buffers for base matrices that sit on another rank
     if (sweep_slots(n) > kSweepMaxSlots || chol64_lds_bytes(n, d) > kC64MaxLds || (d != 1 && d != 3)) { set_error("chol_refresh > 1 supports nLin <= 575 and n_y = 1 or 3"); return RBPF_ERR_UNSUPPORTED; }
     ShardState* sh = c->sh;
-    for (int b = 0; b < 2; ++b) RB_TRY(dmalloc(&s->d_Lsw[b], (size_t)N * sweep_factor_doubles(n)));
-    RB_TRY(dmalloc(&s->d_W, (size_t)d * d));
+    for (int b = 0; b < 2; ++b) RB_TRY(s->pool.alloc(&s->d_Lsw[b], (size_t)N * sweep_factor_doubles(n)));
+    RB_TRY(s->pool.alloc(&s->d_W, (size_t)d * d));
     std::vector<double> Wm;
     whitening_factor(c->h_R, d, Wm);
     HIPCHK(hipMemcpy(s->d_W, Wm.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
-    RB_TRY(dmalloc(&s->d_base_slot, (size_t)N));
+    RB_TRY(s->pool.alloc(&s->d_base_slot, (size_t)N));
     const size_t Kwin = s->refresh_free ? 1 : (size_t)s->refresh;        // generations a refresh walks back
-    RB_TRY(dmalloc(&s->d_Xp, (size_t)N * Kwin * nN));
-    RB_TRY(dmalloc(&s->d_G, (s->refresh_free ? (size_t)s->l_chunk : (size_t)N) * Kwin * d * n));
-    RB_TRY(dmalloc(&s->d_owner_now, (size_t)sh->Nglob));
-    RB_TRY(dmalloc(&s->d_base_gid, (size_t)sh->Nglob));
-    RB_TRY(dmalloc(&s->d_base_loc, (size_t)sh->Nglob));
+    RB_TRY(s->pool.alloc(&s->d_Xp, (size_t)N * Kwin * nN));
+    RB_TRY(s->pool.alloc(&s->d_G, (s->refresh_free ? (size_t)s->l_chunk : (size_t)N) * Kwin * d * n));
+    RB_TRY(s->pool.alloc(&s->d_owner_now, (size_t)sh->Nglob));
+    RB_TRY(s->pool.alloc(&s->d_base_gid, (size_t)sh->Nglob));
+    RB_TRY(s->pool.alloc(&s->d_base_loc, (size_t)sh->Nglob));
     // every particle needs one base matrix at most; half of the local particles importing theirs is far beyond what the
     // owner-computes placement produces between two refreshes (identical on every rank: a function of the options only)
     // (a starting value: rbpf_shard_smoother_refresh_reserve grows the buffers when a refresh needs more; exchange_capacity < 0 asks for
     //  a small start, which is how the tests reach the growth path)
     s->rf_cap = (world > 1) ? std::min<size_t>((size_t)N, std::max<size_t>(2 * sh->step_cap, c->opt.exchange_capacity < 0 ? 1 : 64)) : 1;
-    RB_TRY(dmalloc(&s->d_rf_send, s->rf_cap * s->imat_len));
-    RB_TRY(dmalloc(&s->d_rf_recv, s->rf_cap * s->imat_len));
-    RB_TRY(dmalloc(&s->d_rf_idx, s->rf_cap));
+    RB_TRY(s->pool.alloc(&s->d_rf_send, s->rf_cap * s->imat_len));
+    RB_TRY(s->pool.alloc(&s->d_rf_recv, s->rf_cap * s->imat_len));
+    RB_TRY(s->pool.alloc(&s->d_rf_idx, s->rf_cap));
   }
   guard.release();
   *out = c;
@@ -1713,11 +1674,11 @@ int rbpf_shard_smoother_refresh_reserve(rbpf_ctx* c, int64_t count) {
   const size_t nn = s->imat_len;
   HIPCHK(hipStreamSynchronize(c->stream));
   double *ns_ = nullptr, *nr_ = nullptr; int* ni_ = nullptr;
-  int rc = dmalloc(&ns_, cap * nn);
-  if (rc == RBPF_OK) rc = dmalloc(&nr_, cap * nn);
-  if (rc == RBPF_OK) rc = dmalloc(&ni_, cap);
-  if (rc != RBPF_OK) { hipFree(ns_); hipFree(nr_); hipFree(ni_); return rc; }
-  hipFree(s->d_rf_send); hipFree(s->d_rf_recv); hipFree(s->d_rf_idx);
+  int rc = s->pool.alloc(&ns_, cap * nn);
+  if (rc == RBPF_OK) rc = s->pool.alloc(&nr_, cap * nn);
+  if (rc == RBPF_OK) rc = s->pool.alloc(&ni_, cap);
+  if (rc != RBPF_OK) { s->pool.release(ns_); s->pool.release(nr_); s->pool.release(ni_); return rc; }   // the old buffers stay
+  s->pool.release(s->d_rf_send); s->pool.release(s->d_rf_recv); s->pool.release(s->d_rf_idx);
   s->d_rf_send = ns_; s->d_rf_recv = nr_; s->d_rf_idx = ni_; s->rf_cap = cap;
   return RBPF_OK;
 }
@@ -1890,13 +1851,11 @@ int rbpf_shard_smoother_end(rbpf_ctx* c, double* XNK_k, double* XLK_k, double* P
   if (PK_k) {
     std::memset(PK_k, 0, (size_t)n * n * 8);
     if (owner == sh->rank) {
+      DevicePool tmp;
       double* dP = nullptr;
-      RB_TRY(dmalloc(&dP, (size_t)n * n));
-      int rc = shard_unpack_particle(c, idx, dP);                 // pending downdates applied, lineage base in a record or the bank
-      hipError_t e = (rc == RBPF_OK) ? hipMemcpy(PK_k, dP, (size_t)n * n * 8, hipMemcpyDeviceToHost) : hipSuccess;
-      hipFree(dP);
-      if (rc != RBPF_OK) return rc;
-      HIPCHK(e);
+      RB_TRY(tmp.alloc(&dP, (size_t)n * n));
+      RB_TRY(shard_unpack_particle(c, idx, dP));                  // pending downdates applied, lineage base in a record or the bank
+      HIPCHK(hipMemcpy(PK_k, dP, (size_t)n * n * 8, hipMemcpyDeviceToHost));
     }
   }
   return RBPF_OK;
@@ -1908,8 +1867,7 @@ int rbpf_shard_smoother_end(rbpf_ctx* c, double* XNK_k, double* XLK_k, double* P
 // the launch and reports the mean kernel time in *ms (HIP events on the launch stream).
 int rbpf_chol_weights(int32_t M, int32_t batch, const double* S, const double* e, double jitter, int32_t variant,
                       int32_t reps, double* logw, int32_t* status, double* ms) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
+  if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   const bool info = variant >= 1000;                 // information-form expression and loaders (see rbpf.h)
   if (info) variant -= 1000;
   if (!S || !e || !logw || M < 1 || M > 1023 || batch < 1 || reps < 1 ||
@@ -1918,17 +1876,13 @@ int rbpf_chol_weights(int32_t M, int32_t batch, const double* S, const double* e
     set_error("bad argument"); return RBPF_ERR_INVALID_ARG;
   }
   double *dS = nullptr, *de = nullptr, *dL = nullptr, *dlw = nullptr; int* dst = nullptr;
-  double* dzero_p = nullptr;
-  auto cleanup = [&]() { hipFree(dS); hipFree(de); hipFree(dL); hipFree(dlw); hipFree(dst); hipFree(dzero_p); };
-  int rc = dmalloc(&dS, (size_t)batch * M * M);
-  if (rc == RBPF_OK) rc = dmalloc(&de, (size_t)batch * M);
-  if (rc == RBPF_OK) rc = dmalloc(&dL, (size_t)batch * chol_factor_doubles(M));
-  if (rc == RBPF_OK) rc = dmalloc(&dlw, (size_t)batch);
-  if (rc == RBPF_OK) rc = dmalloc(&dst, 4);
-  if (rc != RBPF_OK) { cleanup(); return rc; }
-  hipError_t err = hipMemcpy(dS, S, (size_t)batch * M * M * 8, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(de, e, (size_t)batch * M * 8, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemset(dst, 0, 16);
+  DevicePool tmp;
+  RB_TRY(tmp.upload(&dS, S, (size_t)batch * M * M));
+  RB_TRY(tmp.upload(&de, e, (size_t)batch * M));
+  RB_TRY(tmp.alloc(&dL, (size_t)batch * chol_factor_doubles(M)));
+  RB_TRY(tmp.alloc(&dlw, (size_t)batch));
+  RB_TRY(tmp.alloc(&dst, 4));
+  HIPCHK(hipMemset(dst, 0, 16));
   CholArgs ca;
   std::memset(&ca, 0, sizeof(ca));
   ca.Msz = M; ca.d = 1; ca.n = M; ca.ldx = M; ca.Lbuf = dL; ca.ldL = (long)chol_factor_doubles(M);
@@ -1937,14 +1891,13 @@ int rbpf_chol_weights(int32_t M, int32_t batch, const double* S, const double* e
   if (!info) {
     ca.mode = 0; ca.S = dS; ca.R = nullptr; ca.rhs = de;
   } else {
-    if (err == hipSuccess) err = hipMalloc(&dzero, ((size_t)M * M + M + batch) * 8);
-    if (err == hipSuccess) err = hipMemset(dzero, 0, ((size_t)M * M + M + batch) * 8);
+    RB_TRY(tmp.alloc(&dzero, (size_t)M * M + M + batch));
+    HIPCHK(hipMemset(dzero, 0, ((size_t)M * M + M + batch) * 8));
     ca.mode = 1; ca.Imat = dS; ca.imat_stride = (long)M * M; ca.ivec = de; ca.ImatAdd = dzero; ca.ivecAdd = dzero + (size_t)M * M;
     ca.qf = dzero + (size_t)M * M + M; ca.hld = ca.qf;
-    dzero_p = dzero;
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (err == hipSuccess) err = hipEventCreate(&e0);
+  hipError_t err = hipEventCreate(&e0);
   if (err == hipSuccess) err = hipEventCreate(&e1);
   float total = 0.f;
   for (int r = 0; r < reps && err == hipSuccess; ++r) {
@@ -1972,7 +1925,6 @@ int rbpf_chol_weights(int32_t M, int32_t batch, const double* S, const double* e
   if (err == hipSuccess) err = hipMemcpy(flags, dst, 16, hipMemcpyDeviceToHost);
   if (e0) hipEventDestroy(e0);
   if (e1) hipEventDestroy(e1);
-  cleanup();
   if (err != hipSuccess) return hip_fail(err, "rbpf_chol_weights", __FILE__, __LINE__);
   if (status) *status = flags[0];
   if (ms) *ms = (double)total / reps;
@@ -1993,8 +1945,7 @@ __global__ void sweep_probe_fill_kernel(size_t len, int batch, const double* __r
 
 int rbpf_chol_sweep_probe(int32_t n, int32_t d, int32_t batch, const double* L, const double* U, const double* V, const double* eta,
                           int32_t reps, double* L_out, double* logw, int32_t* status, double* ms) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
+  if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   if (!L || !U || !V || !eta || n < 1 || sweep_slots(n) > kSweepMaxSlots || (d != 1 && d != 3) || batch < 1 || reps < 1) {
     set_error("bad argument (n <= 575, d = 1 or 3)"); return RBPF_ERR_INVALID_ARG;
   }
@@ -2018,37 +1969,29 @@ int rbpf_chol_sweep_probe(int32_t n, int32_t d, int32_t batch, const double* L, 
   }
   double *d1 = nullptr, *dold = nullptr, *dnew = nullptr, *dH1 = nullptr, *dH = nullptr, *dHref = nullptr, *dW = nullptr, *dy = nullptr, *dz = nullptr, *dlw = nullptr;
   int* dst = nullptr;
-  auto cleanup = [&]() { hipFree(d1); hipFree(dold); hipFree(dnew); hipFree(dH1); hipFree(dH); hipFree(dHref); hipFree(dW); hipFree(dy); hipFree(dz); hipFree(dlw); hipFree(dst); };
-  int rc = dmalloc(&d1, fd);
-  if (rc == RBPF_OK) rc = dmalloc(&dold, (size_t)batch * fd);
-  if (rc == RBPF_OK) rc = dmalloc(&dnew, (size_t)batch * fd);
-  if (rc == RBPF_OK) rc = dmalloc(&dH1, (size_t)d * ldx);
-  if (rc == RBPF_OK) rc = dmalloc(&dH, (size_t)batch * d * ldx);
-  if (rc == RBPF_OK) rc = dmalloc(&dHref, (size_t)d * n);
-  if (rc == RBPF_OK) rc = dmalloc(&dW, (size_t)d * d);
-  if (rc == RBPF_OK) rc = dmalloc(&dy, (size_t)d);
-  if (rc == RBPF_OK) rc = dmalloc(&dz, (size_t)batch);
-  if (rc == RBPF_OK) rc = dmalloc(&dlw, (size_t)batch);
-  if (rc == RBPF_OK) rc = dmalloc(&dst, 4);
-  if (rc != RBPF_OK) { cleanup(); return rc; }
-  hipError_t err = hipMemcpy(d1, hsw.data(), fd * 8, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dH1, hH.data(), hH.size() * 8, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dHref, hHref.data(), hHref.size() * 8, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dW, hW.data(), hW.size() * 8, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dy, eta, (size_t)d * 8, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemset(dz, 0, (size_t)batch * 8);
-  if (err == hipSuccess) err = hipMemset(dst, 0, 16);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(sweep_probe_fill_kernel, dim3((unsigned)((fd + 255) / 256), 64), dim3(256), 0, nullptr, fd, batch, d1, dold);
-    hipLaunchKernelGGL(sweep_probe_fill_kernel, dim3((unsigned)(((size_t)d * ldx + 255) / 256), 64), dim3(256), 0, nullptr, (size_t)d * ldx, batch, dH1, dH);
-    err = hipGetLastError();
-  }
+  DevicePool tmp;
+  RB_TRY(tmp.upload(&d1, hsw.data(), fd));
+  RB_TRY(tmp.alloc(&dold, (size_t)batch * fd));
+  RB_TRY(tmp.alloc(&dnew, (size_t)batch * fd));
+  RB_TRY(tmp.upload(&dH1, hH.data(), hH.size()));
+  RB_TRY(tmp.alloc(&dH, (size_t)batch * d * ldx));
+  RB_TRY(tmp.upload(&dHref, hHref.data(), hHref.size()));
+  RB_TRY(tmp.upload(&dW, hW.data(), hW.size()));
+  RB_TRY(tmp.upload(&dy, eta, (size_t)d));
+  RB_TRY(tmp.alloc(&dz, (size_t)batch));
+  RB_TRY(tmp.alloc(&dlw, (size_t)batch));
+  RB_TRY(tmp.alloc(&dst, 4));
+  HIPCHK(hipMemset(dz, 0, (size_t)batch * 8));
+  HIPCHK(hipMemset(dst, 0, 16));
+  hipLaunchKernelGGL(sweep_probe_fill_kernel, dim3((unsigned)((fd + 255) / 256), 64), dim3(256), 0, nullptr, fd, batch, d1, dold);
+  hipLaunchKernelGGL(sweep_probe_fill_kernel, dim3((unsigned)(((size_t)d * ldx + 255) / 256), 64), dim3(256), 0, nullptr, (size_t)d * ldx, batch, dH1, dH);
+  HIPCHK(hipGetLastError());
   SweepArgs sw;
   sw.n = n; sw.d = d; sw.ldx = ldx; sw.NS = NS; sw.tailc = tailc; sw.N = batch; sw.ref_slot = -1;
   sw.Lold = dold; sw.Lnew = dnew; sw.stride = fd; sw.anc = nullptr; sw.order = nullptr;
   sw.Hb = dH; sw.Href = dHref; sw.W = dW; sw.yt = dy; sw.qf = dz; sw.hld = dz; sw.pant_log = dlw; sw.status = dst;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (err == hipSuccess) err = hipEventCreate(&e0);
+  hipError_t err = hipEventCreate(&e0);
   if (err == hipSuccess) err = hipEventCreate(&e1);
   float total = 0.f;
   for (int r = 0; r < reps && err == hipSuccess; ++r) {
@@ -2068,7 +2011,6 @@ int rbpf_chol_sweep_probe(int32_t n, int32_t d, int32_t batch, const double* L, 
   if (err == hipSuccess) err = hipMemcpy(flags, dst, 16, hipMemcpyDeviceToHost);
   if (e0) hipEventDestroy(e0);
   if (e1) hipEventDestroy(e1);
-  cleanup();
   if (err != hipSuccess) return hip_fail(err, "rbpf_chol_sweep_probe", __FILE__, __LINE__);
   if (L_out) {
     std::memset(L_out, 0, (size_t)n1 * n1 * 8);

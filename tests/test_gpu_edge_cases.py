@@ -193,14 +193,21 @@ def test_device_kalman_recursion_equals_batch_gp_posterior(rbpf, oracle, lazy_de
 @pytest.mark.parametrize("lazy_depth", [0, 3])
 def test_fix_p_mean_accumulates_over_particles(rbpf, oracle, lazy_depth):
     """rbpf_options.fix_p_mean = 1 (off by default): P_mean = sum_i w(i)*(P_i + (xl_mean - xl_i)(xl_mean - xl_i)'), the
-    evident intent of particleFilter.m:228-230, instead of the reference's overwrite (quirk Q3, reproduced by default)."""
+    evident intent of particleFilter.m:228-230, instead of the reference's overwrite (quirk Q3, reproduced by default).
+    The option changes P_mean alone: every output extracted after it equals the default run's bit for bit."""
     c = cases.mag_case(40, 9, 130, seed=21)
     ref = oracle.particleFilter(c["model"], c["odometry"], c["y"], c["x0_nonLin"], c["x0_lin"], c["P0_lin"], c["Q"], c["R"],
                                 c["N_P"], c["dt"], c["rng"], fix_p_mean=True)
     q3 = cases.oracle_filter(c)
     mdl, x0, P0, R = cases.device_model(rbpf, c)
     out = rbpf.particleFilter(mdl.dynModel, mdl.measModel, c["odometry"], c["y"], c["x0_nonLin"], x0, P0, c["Q"], R, c["N_P"],
-                              c["dt"], rng=cases.device_rng(rbpf, c), lazy_depth=lazy_depth, fix_p_mean=True)
+                              c["dt"], rng=cases.device_rng(rbpf, c), lazy_depth=lazy_depth, fix_p_mean=True, extras=True)
+    dflt = rbpf.particleFilter(mdl.dynModel, mdl.measModel, c["odometry"], c["y"], c["x0_nonLin"], x0, P0, c["Q"], R, c["N_P"],
+                               c["dt"], rng=cases.device_rng(rbpf, c), lazy_depth=lazy_depth, extras=True)
+    for k in (0, 1, 2, 3, 4, 6, 7):                                             # everything but P_mean
+        np.testing.assert_array_equal(out[k], dflt[k])
+    for k in ("logw", "w", "ai", "xn", "xl", "P", "iw_max"):
+        np.testing.assert_array_equal(out[8][k], dflt[8][k])
     scale = np.max(np.abs(ref["P_mean"]))
     assert np.max(np.abs(out[5] - ref["P_mean"])) <= 1e-9 * scale
     assert np.max(np.abs(ref["P_mean"] - q3["P_mean"])) > 1e-3 * scale          # and it is not the quirk's value
