@@ -657,6 +657,49 @@ int rbpf_loc_predict(const rbpf_loc_map* map, int32_t n_pred, const double* xn, 
 int rbpf_loc_dyn_model(int32_t n_p, const double* xn, const double* odo, double dt, const double* Q, const double* z,
                        double* xn_next);
 
+/* ---- the EKF comparison baseline of examples/slam-dense-mag, batched over data sets ---------------
+ * ekf_dense.m:41-102 with the closures measModel_ekf / dynModel_ekf of run_dense3D_magfield.m:281-299,310-316, on the device:
+ * one Gaussian state [position(3); orientation deviation(3); map(nLin = m_basis + 3)], n = 6 + nLin, per run.  The n_runs runs
+ * of a call are independent (the Monte-Carlo protocol of main.m:37-57 has 80) and a run's results are bit-identical alone and
+ * at any position of a batch.  Arrays carry the run as their slowest axis; within a run the conventions of rbpf_problem hold.
+ * These structs are additions to ABI 9: each starts with its own struct_size (0 is accepted as in rbpf_options).            */
+typedef struct {
+  int32_t struct_size;       /* sizeof(rbpf_ekf_problem) = rbpf_abi_sizeof(12)                           */
+  int32_t n_runs;            /* B >= 1                                                                   */
+  int32_t N_T;               /* time steps = size(y,1), the same for every run                           */
+  int32_t q_pages;           /* 1 or >= N_T-1  (ekf_dense.m:47-49)                                       */
+  int32_t dt_len;            /* 1 or >= N_T-1  (:52-54)                                                  */
+  int32_t odo_ld;            /* leading dimension of each run's odometry                                 */
+  int32_t keep_P;            /* 0: rbpf_ekf_out.Pf is the final covariance; 1: the covariance of every step */
+  const rbpf_model* const* models; /* [n_runs] dense-mag models with one m_basis; pointers may repeat    */
+  const double* odometry;    /* [odo_ld x 7 x n_runs], odo_ld >= N_T-1                                   */
+  const double* y;           /* [N_T x 3 x n_runs]                                                       */
+  const double* x0;          /* [n x n_runs]                                                             */
+  const double* q0;          /* [4 x n_runs]                                                             */
+  const double* P0;          /* [n x n x n_runs], symmetric                                              */
+  const double* R;           /* [3 x 3 x n_runs]                                                         */
+  const double* LL;          /* [2 x 3 x n_runs] domain bounds (lower; upper) handed to JacobianPhi3D (:292) */
+  const double* Q;           /* [6 x 6 x q_pages], shared by the runs                                    */
+  const double* dt;          /* [dt_len], shared by the runs                                             */
+} rbpf_ekf_problem;
+
+/* NULL pointers are skipped. */
+typedef struct {
+  int32_t struct_size;       /* sizeof(rbpf_ekf_out) = rbpf_abi_sizeof(13)                               */
+  int32_t reserved;
+  double* xf_traj;           /* [n x N_T x n_runs]                                                       */
+  double* qnb_traj;          /* [4 x N_T x n_runs]                                                       */
+  double* Pf;                /* keep_P = 0: [n x n x n_runs]; keep_P = 1: Pf_traj [n x n x N_T x n_runs]  */
+} rbpf_ekf_out;
+
+/* One shot.  Of `opt` (may be NULL) only struct_size is read.  A model of another family: RBPF_ERR_UNSUPPORTED; models of
+ * different m_basis, nLin outside 4 .. 1151 or an unsymmetric P0: RBPF_ERR_INVALID_ARG; a workspace that does not fit the
+ * device: RBPF_ERR_OUT_OF_MEMORY before anything is launched; an innovation covariance that fails its factorisation with and
+ * without the jitter of ekf_dense.m:83-86 in any run: RBPF_ERR_CHOL_FAILED (no output is written).                          */
+int rbpf_ekf_dense(const rbpf_ekf_problem* prob, const rbpf_options* opt, rbpf_ekf_out* out);
+/* Bytes of device memory such a call needs, the keep_P = 1 history included (no device access).                             */
+int rbpf_ekf_workspace_bytes(const rbpf_ekf_problem* prob, const rbpf_options* opt, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,9 +125,21 @@ class rbpf_loc_out(_SizedStructure):
                 ("final_xn", c_double_p), ("xn_traj", c_double_p), ("log_sum_w", c_double_p)]
 
 
+class rbpf_ekf_problem(_SizedStructure):
+    _fields_ = [("struct_size", C.c_int32), ("n_runs", C.c_int32), ("N_T", C.c_int32), ("q_pages", C.c_int32),
+                ("dt_len", C.c_int32), ("odo_ld", C.c_int32), ("keep_P", C.c_int32), ("models", C.POINTER(C.POINTER(rbpf_model))),
+                ("odometry", c_double_p), ("y", c_double_p), ("x0", c_double_p), ("q0", c_double_p), ("P0", c_double_p),
+                ("R", c_double_p), ("LL", c_double_p), ("Q", c_double_p), ("dt", c_double_p)]
+
+
+class rbpf_ekf_out(_SizedStructure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("xf_traj", c_double_p), ("qnb_traj", c_double_p),
+                ("Pf", c_double_p)]
+
+
 # rbpf_abi_sizeof(which): the mirrors in the order of its `which` argument
 ABI_STRUCTS = [rbpf_model, rbpf_problem, rbpf_rng, rbpf_options, rbpf_filter_out, rbpf_smoother_out, rbpf_timing, rbpf_callbacks, rbpf_view,
-               rbpf_loc_map, rbpf_loc_problem, rbpf_loc_out]
+               rbpf_loc_map, rbpf_loc_problem, rbpf_loc_out, rbpf_ekf_problem, rbpf_ekf_out]
 
 # every symbol include/rbpf.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTS = [
@@ -146,6 +158,7 @@ EXPORTS = [
     "rbpf_shard_smoother_step", "rbpf_shard_smoother_end",
     "rbpf_particle_filter_localization", "rbpf_loc_create", "rbpf_loc_advance", "rbpf_loc_finish", "rbpf_loc_workspace_bytes",
     "rbpf_loc_predict", "rbpf_loc_dyn_model",
+    "rbpf_ekf_dense", "rbpf_ekf_workspace_bytes",
 ]
 
 ABI_VERSION = 9            # RBPF_ABI_VERSION of include/rbpf.h this mirror was written against
@@ -251,6 +264,8 @@ def load_library(build_if_missing: bool = True):
                                              C.POINTER(C.c_size_t)]
     lib.rbpf_loc_predict.argtypes = [C.POINTER(rbpf_loc_map), C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
     lib.rbpf_loc_dyn_model.argtypes = [C.c_int32, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p]
+    lib.rbpf_ekf_dense.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(rbpf_ekf_out)]
+    lib.rbpf_ekf_workspace_bytes.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(C.c_size_t)]
     _lib = lib
     return lib
 

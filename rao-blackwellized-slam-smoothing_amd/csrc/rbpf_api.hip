@@ -921,6 +921,8 @@ int rbpf_abi_sizeof(int32_t which) {
     case 9: return (int)sizeof(rbpf_loc_map);
     case 10: return (int)sizeof(rbpf_loc_problem);
     case 11: return (int)sizeof(rbpf_loc_out);
+    case 12: return (int)sizeof(rbpf_ekf_problem);
+    case 13: return (int)sizeof(rbpf_ekf_out);
     default: return -1;
   }
 }

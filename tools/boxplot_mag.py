@@ -12,7 +12,10 @@ boxes per disturbance of boxplot-mag.png (main.m:70-73: columns [1,3] of rmses_e
 Read off the PNG (y axis [0, 0.3] m, main.m:80): o = 0 medians ~ EKF 0.125 / PF 0.14 / PS 0.115 m; o = 10 ~ EKF 0.26 / PF 0.145 /
 PS 0.13 m; PS below PF in all four panels; the EKF degrades with the disturbance, the particle methods hardly do.
 
-    python tools/boxplot_mag.py [n_sim=20] [N_K=10] [N_P=100] [m=512] [out=profiles/r03_boxplot_mag.json]
+    python tools/boxplot_mag.py [n_sim=20] [N_K=10] [N_P=100] [m=512] [ekf=host|device] [out=profiles/r03_boxplot_mag.json]
+
+ekf=device runs the EKF on the device (ekf.ekf_dense_batch): the four disturbance levels of a simulation are one call.  The
+default, ekf=host, is the numpy recursion over the device helper kernels.
 
 MATLAB's random stream cannot be replayed here, so the simulations use numpy data seeds 1..n_sim (one data set per simulation,
 shared by the four disturbance levels -- the reference draws fresh data for every run) and device Philox streams."""
@@ -29,7 +32,10 @@ sys.path.insert(0, ROOT)
 MAG_DIST = (0.0, 1.0, 5.0, 10.0)                                            # main.m:41, second column
 
 
-def run_protocol(n_sim=20, N_K=10, N_P=100, m=512, N_T=192, levels=MAG_DIST, verbose=False):
+def run_protocol(n_sim=20, N_K=10, N_P=100, m=512, N_T=192, levels=MAG_DIST, verbose=False, ekf="host"):
+    if ekf not in ("host", "device"):
+        raise ValueError('ekf must be "host" or "device"')
+    ekf_on_device = ekf == "device"
     rbpf = importlib.import_module("rao-blackwellized-slam-smoothing_amd")
     dg = importlib.import_module("rao-blackwellized-slam-smoothing_amd.datagen")
     mt = importlib.import_module("rao-blackwellized-slam-smoothing_amd.metrics")
@@ -43,13 +49,26 @@ def run_protocol(n_sim=20, N_K=10, N_P=100, m=512, N_T=192, levels=MAG_DIST, ver
         d = dg.bean_6D(N_T, Q, theta, dt, seed=sim)
         mdl, x0_lin, P0_lin, R = rbpf.dense_mag_prior(m, d["LL"], theta)
         n = mdl.nLin
-        for o in levels:
-            y = d["y"] + np.array([0.0, o, 0.0])                             # run_dense3D_magfield.m:81
+        if ekf_on_device:                                                    # the levels of this simulation in one call
             t0 = time.perf_counter()
-            x0 = np.concatenate((d["initState"][0:3], np.zeros(3), np.asarray(x0_lin).ravel()))   # :248-250
+            x0 = np.concatenate((d["initState"][0:3], np.zeros(3), np.asarray(x0_lin).ravel()))
             P0 = np.zeros((6 + n, 6 + n))
             P0[6:, 6:] = P0_lin
-            xf, qnb, _ = ekf.ekf_dense(mdl, d["LL"], d["dx"], y, x0, d["initState"][3:7], P0, Q, R, dt)
+            nl = len(levels)
+            rep = lambda a: np.stack([np.asarray(a, dtype=np.float64)] * nl)                       # noqa: E731
+            xf_b, qnb_b, _ = ekf.ekf_dense_batch([mdl] * nl, rep(d["LL"]), rep(d["dx"]), np.stack([d["y"] + np.array([0.0, o, 0.0]) for o in levels]),
+                                                 rep(x0), rep(d["initState"][3:7]), rep(P0), Q, R, dt, keep_P=False)
+            secs["ekf"] += time.perf_counter() - t0
+        for io, o in enumerate(levels):
+            y = d["y"] + np.array([0.0, o, 0.0])                             # run_dense3D_magfield.m:81
+            t0 = time.perf_counter()
+            if ekf_on_device:
+                xf, qnb = xf_b[io], qnb_b[io]
+            else:
+                x0 = np.concatenate((d["initState"][0:3], np.zeros(3), np.asarray(x0_lin).ravel()))   # :248-250
+                P0 = np.zeros((6 + n, 6 + n))
+                P0[6:, 6:] = P0_lin
+                xf, qnb, _ = ekf.ekf_dense(mdl, d["LL"], d["dx"], y, x0, d["initState"][3:7], P0, Q, R, dt)
             rows[o]["ekf"].append(total(mt.rmse_dense_mag(d["pos"], d["quat"], np.vstack((xf[0:3], qnb)))[0]))
             t1 = time.perf_counter()
             out = rbpf.particleFilter(mdl.dynModel, mdl.measModel, d["dx"], y, d["initState"], x0_lin, P0_lin, Q, R, N_P, dt,
@@ -75,7 +94,7 @@ def run_protocol(n_sim=20, N_K=10, N_P=100, m=512, N_T=192, levels=MAG_DIST, ver
                           ekf_q25_median_q75=q(r["ekf"]), pf_q25_median_q75=q(r["pf"]), ps_q25_median_q75=q(r["ps"]),
                           ps_median_by_iteration=[round(float(x), 4) for x in np.median(np.asarray(r["ps_iter"]), axis=0)],
                           ekf=[round(x, 4) for x in r["ekf"]], pf=[round(x, 4) for x in r["pf"]], ps=[round(x, 4) for x in r["ps"]]))
-    return dict(protocol="examples/slam-dense-mag/main.m:37-57 (boxplot-mag.png)", N_P=N_P, N_K=N_K, N_T=N_T, m=m, n_sim=n_sim,
+    return dict(protocol="examples/slam-dense-mag/main.m:37-57 (boxplot-mag.png)", ekf=("device" if ekf_on_device else "host"), N_P=N_P, N_K=N_K, N_T=N_T, m=m, n_sim=n_sim,
                 smoother="particleSmoother (covariance form), last iteration", filter="particleFilter, weighted mean",
                 seconds=dict((k, round(v, 2)) for k, v in secs.items()), table=table,
                 reference_png_medians_read_by_eye={"0": dict(ekf=0.125, pf=0.14, ps=0.115), "10": dict(ekf=0.26, pf=0.145, ps=0.13)})
@@ -104,7 +123,7 @@ def check_ordering(res, slack=1.0):
 if __name__ == "__main__":
     kw = dict(a.split("=") for a in sys.argv[1:])
     out_path = kw.pop("out", os.path.join(ROOT, "profiles", "r03_boxplot_mag.json"))
-    res = run_protocol(verbose=True, **{k: int(v) for k, v in kw.items()})
+    res = run_protocol(verbose=True, ekf=kw.pop("ekf", "host"), **{k: int(v) for k, v in kw.items()})
     res["ordering_problems"] = check_ordering(res)
     with open(out_path, "w") as f:
         json.dump(res, f, indent=1)

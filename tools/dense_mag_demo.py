@@ -4,7 +4,7 @@ generator), the reduced-rank GP prior, then dead reckoning, the EKF baseline (ek
 particleSmootherInformationForm (N_K iterations), each scored as the runner scores them (run_dense3D_magfield.m:155-183,216-237):
 per-axis RMS position error after a Procrustes alignment and RMS orientation error in degrees.
 
-    python tools/dense_mag_demo.py [N_T=500] [m=512] [N_P=100] [N_K=10] [seed=1] [lazy_depth=0] [chol_refresh=0]
+    python tools/dense_mag_demo.py [N_T=500] [m=512] [N_P=100] [N_K=10] [seed=1] [lazy_depth=0] [chol_refresh=0] [ekf=host|device]
 
 Prints one JSON line per estimator.  (One run says little about which estimator wins: the reference's own comparison, main.m:
 37-57, averages 20 simulations per disturbance level.)"""
@@ -38,7 +38,9 @@ def dead_reckoning(d):
     return x
 
 
-def run(N_T=500, m=512, N_P=100, N_K=10, seed=1, lazy_depth=0, chol_refresh=0, with_ekf=True):
+def run(N_T=500, m=512, N_P=100, N_K=10, seed=1, lazy_depth=0, chol_refresh=0, with_ekf=True, ekf_path="host"):
+    if ekf_path not in ("host", "device"):
+        raise ValueError('ekf_path must be "host" or "device"')
     Q, theta, dt = bench.q_mag(), bench.THETA_MAG, 0.01
     d = dg.bean_6D(N_T, Q, theta, dt, seed=seed)
     mdl, x0_lin, P0_lin, R = rbpf.dense_mag_prior(m, d["LL"], theta)
@@ -56,8 +58,11 @@ def run(N_T=500, m=512, N_P=100, N_K=10, seed=1, lazy_depth=0, chol_refresh=0, w
         P0 = np.zeros((6 + n, 6 + n))
         P0[6:, 6:] = P0_lin
         t0 = time.perf_counter()
-        xf, qnb, _ = ekf.ekf_dense(mdl, d["LL"], d["dx"], d["y"], x0, d["initState"][3:7], P0, Q, R, dt)
-        score("EKF", np.vstack((xf[0:3], qnb)), time.perf_counter() - t0)
+        if ekf_path == "device":                                              # the device recursion, final covariance only
+            xf, qnb, _ = ekf.ekf_dense_device(mdl, d["LL"], d["dx"], d["y"], x0, d["initState"][3:7], P0, Q, R, dt, keep_P=False)
+        else:
+            xf, qnb, _ = ekf.ekf_dense(mdl, d["LL"], d["dx"], d["y"], x0, d["initState"][3:7], P0, Q, R, dt)
+        score("EKF", np.vstack((xf[0:3], qnb)), time.perf_counter() - t0, path=ekf_path)
     t0 = time.perf_counter()
     out = rbpf.particleFilter(mdl.dynModel, mdl.measModel, d["dx"], d["y"], d["initState"], x0_lin, P0_lin, Q, R, N_P, dt,
                               rng=rbpf.PhiloxRNG(seed), lazy_depth=lazy_depth)
@@ -79,6 +84,6 @@ def run(N_T=500, m=512, N_P=100, N_K=10, seed=1, lazy_depth=0, chol_refresh=0, w
 
 if __name__ == "__main__":
     kw = dict(a.split("=") for a in sys.argv[1:])
-    r = run(**{k: int(v) for k, v in kw.items()})
+    r = run(ekf_path=kw.pop("ekf", "host"), **{k: int(v) for k, v in kw.items()})
     for row in r["results"]:
         print(json.dumps(row), flush=True)
