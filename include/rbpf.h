@@ -347,6 +347,10 @@ int rbpf_filter_tell(const rbpf_ctx* ctx, int32_t* t);
  * rewritten in place at every flush) or 2 (ping-pong banks); shared_flush = 1 when a flush step writes one matrix
  * per parent for all its children (two banks, block-lower storage).  What particleFilter.m:112-113's gather became. */
 int rbpf_filter_schedule(const rbpf_ctx* ctx, int32_t* banks, int32_t* shared_flush);
+/* Shared flush steps since the context was created that ran as ONE launch (writers and read-only siblings in one grid:
+ * two banks, fp64 tiles at eight tile rows, 2-4 pending sets); the other shared flushes took two launches.  Filter and
+ * sharded-filter contexts.                                                                          */
+int rbpf_filter_one_launch_flushes(const rbpf_ctx* ctx, int64_t* n);
 /* Generic model family (RBPF_MODEL_GENERIC_DENSE), one time step at a time:
  *   t = 0:  rbpf_filter_step_external(ctx, xn0, measModel(xn0))
  *   t > 0:  rbpf_filter_ancestors(ctx, ai, xn_prev); xn(:,i) = dynModel(xn_prev(:,ai(i)+1), ...); 

@@ -629,10 +629,13 @@ int ctx_launch_step(rbpf_ctx* c, StepArgs& a, const StepBanks& bk, FlushMode mod
       HIPCHK(launch_step(a, c->stream));
       break;
     case FlushMode::Shared:
-      // Writers (the flush variant, one per parent with children) first, then their read-only siblings (they point at their writer's
-      // new entry), one after the other.  (Measured r05 with diagnostic builds of commit 31144f4: both side by side on
-      // two streams 11.39 against 11.24 ms per step; one step of a STAGGERED flush -- a quarter of the families flushing beside three
-      // quarters of read-only particles -- 12.2 ms whether serial or concurrent, against the lock-step schedule's 11.66: DESIGN.md 9.)
+      // Writers (the flush variant, one per parent with children) and their read-only siblings (they point at their writer's new
+      // entry) in ONE launch over the processing order where the mixed kernel exists (fp64 tiles, eight tile rows, 2-4 pending sets:
+      // step_sym_kernel_shared), so that both kinds of workgroup are resident together.  Measured at N = 65 536, m = 512,
+      // lazy_depth 4: the flush step 18.95 ms against 15.98 + 4.12 ms for the two launches, the headline 11.04-11.20 against
+      // 11.34-11.47 ms per step (five runs each, alternating); HBM bytes per step by the counters 52.0 against 51.0 GB -- the gain is
+      // overlap, the siblings do not ride their writer's lines.  Everything else: writers first, then the siblings.
+      if (step_sym_shared_one_launch(a)) { HIPCHK(launch_step_sym_shared(a, c->stream)); ++c->one_launch_flushes; break; }
       a.phase = 1; HIPCHK(launch_step(a, c->stream));
       HIPCHK(launch_step(rd, c->stream));
       break;
@@ -1052,6 +1055,12 @@ int rbpf_filter_schedule(const rbpf_ctx* c, int32_t* banks, int32_t* shared_flus
   if (!c || !banks || !shared_flush) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   *banks = c->inplace ? 1 : 2;
   *shared_flush = (c->share_flush || c->share_inplace) ? 1 : 0;
+  return RBPF_OK;
+}
+
+int rbpf_filter_one_launch_flushes(const rbpf_ctx* c, int64_t* n) {
+  if (!c || !n) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  *n = c->one_launch_flushes;
   return RBPF_OK;
 }
 

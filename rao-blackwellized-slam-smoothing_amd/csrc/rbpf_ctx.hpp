@@ -104,6 +104,7 @@ struct rbpf_ctx {
   double* d_strip_ws = nullptr; size_t strip_ws_stride = 0;   // symmetric storage at sixteen tile rows: the step kernel's column strips ([N][stride])
   unsigned long long* d_share_writers = nullptr;   // writers of the timed shared flushes (device counter)
   long long share_flush_particles = 0;          // particles of the timed shared flushes (N per flush step)
+  long long one_launch_flushes = 0;             // shared flush steps issued as one launch (rbpf_filter_one_launch_flushes)
   // timed launches: reads of stored matrices counted per particle (nominal) and per DISTINCT matrix (device counter)
   int* d_distinct_mark = nullptr; size_t distinct_keys = 0; unsigned long long* d_distinct_counter = nullptr;
   long long distinct_nominal = 0; int distinct_epoch = 0;

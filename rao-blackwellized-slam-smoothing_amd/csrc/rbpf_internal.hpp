@@ -214,6 +214,9 @@ bool sym_supported(int n, int d);
 size_t sym_strip_doubles(const Layout& lay, int d);   // per workgroup, 0 unless sixteen tile rows
 size_t step_sym_lds_bytes(const ModelDev& m, const Layout& lay, int n_sets, int write_base, int extra = 0);   // extra = 1: information form
 hipError_t launch_step_sym(const StepArgs& a, hipStream_t s);
+// shared flush with two banks: writers and read-only siblings in one launch (phase < 0), where the mixed kernel is instantiated
+bool step_sym_shared_one_launch(const StepArgs& a);
+hipError_t launch_step_sym_shared(const StepArgs& a, hipStream_t s);
 // wave-level reduction primitives of the symmetric step kernel on their own (tests): in [4][64] -> out [4] lane sums
 hipError_t launch_probe_wave_reduce(const double* in, double* out, hipStream_t s);
 

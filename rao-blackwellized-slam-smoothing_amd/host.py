@@ -896,6 +896,12 @@ class FilterSession:
     def banks(self):
         return self.schedule()[0]
 
+    def one_launch_flushes(self):
+        """Shared flush steps so far that ran as one launch (rbpf_filter_one_launch_flushes)."""
+        n = C.c_int64(0)
+        check(self.lib.rbpf_filter_one_launch_flushes(self.ctx, C.byref(n)))
+        return n.value
+
     def timing(self, enable=None, reset=False):
         if enable is not None:
             check(self.lib.rbpf_timing_enable(self.ctx, 1 if enable else 0))

@@ -384,6 +384,12 @@ class ShardedFilterSession:
         self.stream.synchronize()
         self.torch.cuda.synchronize()
 
+    def one_launch_flushes(self):
+        """Shared flush steps so far that ran as one launch (rbpf_filter_one_launch_flushes)."""
+        n = C.c_int64(0)
+        check(self.lib.rbpf_filter_one_launch_flushes(self.ctx, C.byref(n)))
+        return n.value
+
     def reset(self):
         raise NotImplementedError("create a new ShardedFilterSession")
 
