@@ -673,7 +673,9 @@ static int ctx_step_diagnostics(rbpf_ctx* c, StepArgs& a, const int* A_t) {
     unsigned long long ks[8];
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(ks, c->d_counts + 2 * N + 32, sizeof(ks), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[rbpf kstamps] step %d (prev launch): A %.1f B %.1f C %.1f D(stream) %.1f comb %.1f E %.1f F %.1f us\n", t - 1, (ks[1]-ks[0])*0.01, (ks[2]-ks[1])*0.01, (ks[3]-ks[2])*0.01, (ks[4]-ks[3])*0.01, 0.0, (ks[5]-ks[4])*0.01, (ks[6]-ks[5])*0.01);
+    // ks[7]: the end of the tile stream (block-lower kernels only; step_kernel leaves it alone and D covers everything up to E)
+    const unsigned long long kd = (ks[7] >= ks[3] && ks[7] <= ks[4]) ? ks[7] : ks[4];
+    fprintf(stderr, "[rbpf kstamps] step %d (prev launch): A %.1f B %.1f C %.1f D(stream) %.1f comb %.1f E %.1f F %.1f us\n", t - 1, (ks[1]-ks[0])*0.01, (ks[2]-ks[1])*0.01, (ks[3]-ks[2])*0.01, (kd-ks[3])*0.01, (ks[4]-kd)*0.01, (ks[5]-ks[4])*0.01, (ks[6]-ks[5])*0.01);
   }
   if (t == 100) {
     unsigned long long st[8];

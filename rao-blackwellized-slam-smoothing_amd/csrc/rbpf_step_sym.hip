@@ -165,6 +165,27 @@ __device__ __forceinline__ double fold32(double a, double b) {
   const auto r1 = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
   return __hiloint2double((int)r1[0], (int)r0[0]) + __hiloint2double((int)r1[1], (int)r0[1]);
 }
+// quad mapping: the core coordinate of the row whose sums the folds of the combine leave in this lane, row
+// 16 * {0, 2, 1, 3}[lane >> 4] + (lane & 15) of tile row `row` (wave_sum4's order)
+__device__ __forceinline__ int sym_quad_row(int row, int lane) {
+  const int rho = lane >> 4;
+  return row * kSymChunk + 16 * ((rho & 1) * 2 + (rho >> 1)) + (lane & 15);
+}
+// wave_sum (rbpf_device.hpp) with the caller's lane index: the same butterfly, lane ^ 32, 16, .., 1, through ds_bpermute
+__device__ __forceinline__ double sym_wave_sum_lane(double v, int lane) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const int at = (lane ^ off) << 2;
+    const int lo = __builtin_amdgcn_ds_bpermute(at, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(at, __double2hiint(v));
+    v += __hiloint2double(hi, lo);
+  }
+  return v;
+}
+// the value lane l holds (v_readlane on both halves: workgroup code that hands one lane's number to the wave)
+__device__ __forceinline__ double sym_lane_read(double v, int l) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+  return __hiloint2double(hi, lo);
+}
 // rows of 16 lanes: [a.r0 + a.r1, b.r0 + b.r1, a.r2 + a.r3, b.r2 + b.r3]   (v_permlane16_swap: odd rows of the first operand <->
 // even rows of the second)
 __device__ __forceinline__ double fold16(double a, double b) {

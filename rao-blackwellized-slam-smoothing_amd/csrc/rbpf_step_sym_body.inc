@@ -52,7 +52,42 @@
 
   RBPF_SYM_KSTAMP(0);
   // ---- A: propagated state (propagate_kernel ran first), prior mean ----
-  if (tid < kPreDoubles) misc[tid] = a.pre_d[(size_t)pos * kPreDoubles + tid];
+  // The prologue pays one dependent global latency, that of pre_i above: whatever hangs on `pos` or on the thread alone is asked for
+  // here, next to it.  Phase B reads the propagated position itself (a workgroup-uniform address), not through `misc` and a barrier
+  // of its own; Rnb reaches phase C through `misc` as before, behind the barrier that the tables need anyway.  (All seventeen doubles
+  // as scalars cost the read-only kernels eight spilled SGPRs, the VGPR that holds them, and with it 28 bytes of scratch in the stream.)
+  const double* pre_d = a.pre_d + (size_t)pos * kPreDoubles;
+  const double px0 = pre_d[0], px1 = pre_d[1], px2 = pre_d[2];
+  // Jacobian columns: loop index ci = tid, tid + NT, ... forms column (ci + crot) mod n.  dense-mag rotates by three: the basis columns
+  // (nine divisions each) fill whole rounds of the workgroup, and the identity columns c < 3, which cost nothing, are the remainder
+  // (n = 515: two full rounds, then three lanes of copies -- not three lanes of divisions while every other wave waits).  These
+  // columns feed no reduction here, so the mapping is free.  The basis indices of a thread's first kNNPre columns are asked for now.
+  constexpr int kNNPre = 2;
+  const int crot = (M.kind == 1) ? 3 : 0;
+  auto jcol = [&](int ci) { const int c = ci + crot; return c >= n ? c - n : c; };
+  int nnp[kNNPre][3] = {};
+  if (a.H_ext == nullptr) {
+#pragma unroll
+    for (int it = 0; it < kNNPre; ++it)
+      if (tid + it * NT < n) H_column_indices(M, jcol(tid + it * NT), nnp[it]);
+  }
+  // read-only step with pending sets: K_s' H' needs H and the K rows alone, so it is formed in front of the stream.  The K rows of
+  // this thread's columns (c = tid, tid + NT, ...: the order of the sums) are asked for here, kFPre rounds of them; no supported
+  // shape has more than three (n < 3 NT), the loops behind the rounds take what is left.
+  constexpr bool kCorr = !WR && NS > 0;
+  constexpr int kFPre = NS > 6 ? 2 : 3, kSPre = kFPre;       // (seven sets: three rounds of 21 registers spilled, 60 bytes of scratch)
+  double kvp[kCorr ? kFPre : 1][NDA], ksp[kCorr ? kSPre : 1][NDA];
+  if constexpr (kCorr) {
+#pragma unroll
+    for (int it = 0; it < kFPre; ++it)
+      if (tid + it * NT < n) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+          for (int k = 0; k < D; ++k) kvp[it][s * D + k] = Fs[s][(size_t)(D + k) * ldx + tid + it * NT];
+      }
+  }
+  if (tid < kPreDoubles) misc[tid] = pre_d[tid];
   constexpr bool kXlLds = !(RBPF_SYM_LIGHT_WGS > 2 && !WR && E == 0) && !kGStrip;   // three workgroups per CU: no room for the prior mean in LDS
   if (kXlLds) for (int c = tid; c < n; c += NT) xls[c] = srcX[c];
   double Riy[D];                                               // R^-1 y (:292)
@@ -67,33 +102,82 @@
       Riy[aa] = sacc;
     }
   }
-  __syncthreads();
   RBPF_SYM_KSTAMP(1);
-  // ---- B: per-axis sin / cos tables ----
-  for (int q = tid; q < M.ktot; q += NT) basis_table_entry(M, q, misc, tabS, tabC);
+  // ---- B: per-axis sin / cos tables (no barrier in front: nothing here reads what phase A stored) ----
+  for (int q = tid; q < M.ktot; q += NT) basis_table_entry(M, q, px0, px1, px2, tabS, tabC);
   __syncthreads();
   RBPF_SYM_KSTAMP(2);
   // ---- C: measurement Jacobian, one column per thread ----
-  for (int c = tid; c < n; c += NT) {
-    double h[D];
-    if (a.H_ext != nullptr) {
+  {
+    auto column = [&](int c, const int* nn) {
+      double h[D];
+      if (a.H_ext != nullptr) {
 #pragma unroll
-      for (int k = 0; k < D; ++k) h[k] = a.H_ext[((size_t)i * D + k) * ldx + c];
-    } else {
-      H_column<D>(M, c, tabS, tabC, &misc[8], h);
-    }
+        for (int k = 0; k < D; ++k) h[k] = a.H_ext[((size_t)i * D + k) * ldx + c];
+      } else {
+        H_column<D>(M, c, nn, tabS, tabC, &misc[8], h);
+      }
 #pragma unroll
-    for (int k = 0; k < D; ++k) Hs[c * DE + k] = h[k];
-    if (E > 0) {
-      double sp = Hs[c * DE + D];                               // ivecPlus = ivec + dyi'/R*yt' (:292), the new information vector (:333)
+      for (int k = 0; k < D; ++k) Hs[c * DE + k] = h[k];
+      if (E > 0) {
+        double sp = Hs[c * DE + D];                               // ivecPlus = ivec + dyi'/R*yt' (:292), the new information vector (:333)
 #pragma unroll
-      for (int k = 0; k < D; ++k) sp = fma(h[k], Riy[k], sp);
+        for (int k = 0; k < D; ++k) sp = fma(h[k], Riy[k], sp);
 #pragma unroll
-      for (int k = 0; k < D; ++k) a.Hb_new[((size_t)i * D + k) * ldx + c] = h[k];
-      a.ivec_new[(size_t)i * ldx + c] = sp;
+        for (int k = 0; k < D; ++k) a.Hb_new[((size_t)i * D + k) * ldx + c] = h[k];
+        a.ivec_new[(size_t)i * ldx + c] = sp;
+      }
+    };
+#pragma unroll
+    for (int it = 0; it < kNNPre; ++it)
+      if (tid + it * NT < n) column(jcol(tid + it * NT), nnp[it]);
+    for (int ci = tid + kNNPre * NT; ci < n; ci += NT) {
+      int nn[3] = {0, 0, 0};
+      if (a.H_ext == nullptr) H_column_indices(M, jcol(ci), nn);
+      column(jcol(ci), nn);
     }
   }
   __syncthreads();
+  if constexpr (kCorr) {
+    // g = K_s' H', this wave's part: per thread over its columns in ascending order, a wave sum per value, parked in `red` (which
+    // nothing touches before the cross-wave sum behind the stream; g itself does not live across the stream)
+    constexpr int NG = NS * D * DE;
+    double g[NG];
+#pragma unroll
+    for (int q = 0; q < NG; ++q) g[q] = 0.0;
+    auto gcol = [&](int c, const double* kv) {
+      double h[DE];
+#pragma unroll
+      for (int k = 0; k < DE; ++k) h[k] = Hs[c * DE + k];
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+#pragma unroll
+          for (int j = 0; j < DE; ++j) g[(s * D + k) * DE + j] = fma(kv[s * D + k], h[j], g[(s * D + k) * DE + j]);
+    };
+#pragma unroll
+    for (int it = 0; it < kFPre; ++it)
+      if (tid + it * NT < n) gcol(tid + it * NT, kvp[it]);
+    for (int c = tid + kFPre * NT; c < n; c += NT) {
+      double kv[NDA];
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int k = 0; k < D; ++k) kv[s * D + k] = Fs[s][(size_t)(D + k) * ldx + c];
+      gcol(c, kv);
+    }
+    // (the lane index through an empty asm: the six partner addresses of the butterfly are then formed here and die here; taken from
+    // the lane id they are shared with the wave sums behind the stream and held across it, six registers that the read-only kernels at
+    // eight tile rows do not have)
+    int lq = lane;
+    asm volatile("" : "+v"(lq));
+#pragma unroll
+    for (int q = 0; q < NG; ++q) {
+      const double s = sym_wave_sum_lane(g[q], lq);
+      if (lane == 0) red[wave * kSymRed + q] = s;
+    }
+  }
 
   RBPF_SYM_KSTAMP(3);
   {
@@ -230,6 +314,32 @@
       }
     }
   }
+  // Behind the stream the accumulators' partners are dead: the KS rows of the correction loop and the first border columns of the quad
+  // combine are asked for now, in front of the border rows, and used two barriers later.
+  if constexpr (kCorr) {
+    // (the thread index through an empty asm: otherwise the compiler shares these addresses with those of the K rows in the prologue
+    // and keeps them across the stream -- the one-set read-only kernel at eight tile rows then spills two registers)
+    int tq = tid;
+    asm volatile("" : "+v"(tq));
+#pragma unroll
+    for (int it = 0; it < kSPre; ++it)
+      if (tq + it * NT < n) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+          for (int k = 0; k < D; ++k) ksp[it][s * D + k] = Fs[s][(size_t)k * ldx + tq + it * NT];
+      }
+  }
+  constexpr int kBPre = 4;
+  double pvp[kQuad ? kSymRows : 1][kBPre];
+  if constexpr (kQuad) {
+#pragma unroll
+    for (int q = 0; q < kSymRows; ++q)
+#pragma unroll
+      for (int b = 0; b < kBPre; ++b)
+        if (b < nb) pvp[q][b] = (double)srcB[(size_t)b * ldb + nb + sym_quad_row(rows[q], lane)];
+  }
+  RBPF_SYM_KSTAMP(7);                                         // (wave 0 leaves the stream: the border rows, the combine and the correction follow)
   // border rows (row-major block B, all n columns): lanes walk columns, wave-reduce per row (as in step_kernel)
   for (int b = wave; b < nb; b += NW) {
     const TS* src = srcB + (size_t)b * ldb;
@@ -283,8 +393,7 @@
       // quad mapping: the four lane groups hold the row sums of rows r16 + 16 rq over their quarter of the columns; two folds add the
       // groups and leave row 16 * {0, 2, 1, 3}[lane >> 4] + r16 in this lane (wave_sum4's order), plus the border columns' part,
       // which the plain mapping accumulated for row `lane`
-      const int rho = lane >> 4;
-      const int rc = rows[q] * kSymChunk + (kQuad ? 16 * ((rho & 1) * 2 + (rho >> 1)) + (lane & 15) : lane);   // core coordinate
+      const int rc = kQuad ? sym_quad_row(rows[q], lane) : rows[q] * kSymChunk + lane;   // core coordinate
       double s[DE];
 #pragma unroll
       for (int k = 0; k < DE; ++k) s[k] = accr[q][k];
@@ -292,7 +401,13 @@
         // the border columns of this lane's row, P(r, b) = B(b, r) (not live across the stream: twelve registers for its loads)
 #pragma unroll
         for (int k = 0; k < DE; ++k) s[k] = 0.0;
-        for (int b = 0; b < nb; ++b) {
+#pragma unroll
+        for (int b = 0; b < kBPre; ++b)
+          if (b < nb) {
+#pragma unroll
+            for (int k = 0; k < DE; ++k) s[k] = fma(pvp[q][b], Hs[b * DE + k], s[k]);
+          }
+        for (int b = kBPre; b < nb; ++b) {
           const double pv = (double)srcB[(size_t)b * ldb + nb + rc];
 #pragma unroll
           for (int k = 0; k < DE; ++k) s[k] = fma(pv, Hs[b * DE + k], s[k]);
@@ -327,49 +442,40 @@
   }
   if (!WR && NS > 0) {
     // read-only step: PHt holds P_base * H'; subtract sum_s KS_s * (K_s' * H')
+    // (the waves' parts of g = K_s' H' have lain in `red` since the prologue; they are added here in wave order)
     constexpr int NG = NS * D * DE > 0 ? NS * D * DE : 1;
     double g[NG];
-#pragma unroll
-    for (int q = 0; q < NG; ++q) g[q] = 0.0;
-    for (int c = tid; c < n; c += NT) {
-      double h[DE];
-#pragma unroll
-      for (int k = 0; k < DE; ++k) h[k] = Hs[c * DE + k];
-#pragma unroll
-      for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          const double kv = Fs[s][(size_t)(D + k) * ldx + c];
-#pragma unroll
-          for (int j = 0; j < DE; ++j) g[(s * D + k) * DE + j] = fma(kv, h[j], g[(s * D + k) * DE + j]);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NG; ++q) {
-      const double s = wave_sum(g[q]);
-      if (lane == 0) red[wave * kSymRed + q] = s;
-    }
-    __syncthreads();
 #pragma unroll
     for (int q = 0; q < NG; ++q) {
       double s = red[q];
       for (int w = 1; w < NW; ++w) s += red[w * kSymRed + q];
       g[q] = s;
     }
-    for (int r = tid; r < n; r += NT) {
+    auto corr = [&](int r, const double* ksr) {
       double ph[DE];
 #pragma unroll
       for (int j = 0; j < DE; ++j) ph[j] = PHt[(size_t)j * ldx + r];
 #pragma unroll
       for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int k = 0; k < D; ++k) {
-          const double ksv = Fs[s][(size_t)k * ldx + r];
+        for (int k = 0; k < D; ++k)
 #pragma unroll
-          for (int j = 0; j < DE; ++j) ph[j] = fma(-ksv, g[(s * D + k) * DE + j], ph[j]);
-        }
+          for (int j = 0; j < DE; ++j) ph[j] = fma(-ksr[s * D + k], g[(s * D + k) * DE + j], ph[j]);
 #pragma unroll
       for (int j = 0; j < DE; ++j) PHt[(size_t)j * ldx + r] = ph[j];
+    };
+#pragma unroll
+    for (int it = 0; it < kSPre; ++it)
+      if (tid + it * NT < n) corr(tid + it * NT, ksp[kCorr ? it : 0]);
+    int tq = tid;
+    asm volatile("" : "+v"(tq));                               // (as above)
+    for (int r = tq + kSPre * NT; r < n; r += NT) {
+      double ksr[NDA];
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int k = 0; k < D; ++k) ksr[s * D + k] = Fs[s][(size_t)k * ldx + r];
+      corr(r, ksr);
     }
     __syncthreads();
   }
@@ -409,18 +515,20 @@
     }
   }
   __syncthreads();
-  if (tid == 0) {
-    double SS[D * D], e[D], cS[D * D], v[D];
-    for (int q = 0; q < D * D; ++q) {
-      double s = red[q];
-      for (int w = 1; w < NW; ++w) s += red[w * kSymRed + q];
-      SS[q] = s + M.R[q];                                                   // particleFilter.m:141
+  if (wave == 0) {
+    // Lane q < NRED adds value q over the waves, in wave order; lane reads then hand every sum to every lane, and the lanes of the
+    // wave run the factorisation side by side on the same numbers (one lane stores).  The D logarithms are one call: lane q takes
+    // cS(q, q).  Each expression is the one a single lane evaluated before.
+    double sq = 0.0;
+    if (lane < NRED) {
+      sq = red[lane];
+      for (int w = 1; w < NW; ++w) sq += red[w * kSymRed + lane];
     }
-    for (int q = 0; q < D; ++q) {
-      double s = red[D * D + q];
-      for (int w = 1; w < NW; ++w) s += red[w * kSymRed + D * D + q];
-      e[q] = a.y[q] - s;                                                    // :140
-    }
+    double SS[D * D], e[D], cS[D * D] = {}, v[D];                           // (cS: a failed factorisation leaves part of it unwritten)
+#pragma unroll
+    for (int q = 0; q < D * D; ++q) SS[q] = sym_lane_read(sq, q) + M.R[q];    // particleFilter.m:141
+#pragma unroll
+    for (int q = 0; q < D; ++q) e[q] = a.y[q] - sym_lane_read(sq, D * D + q); // :140
     bool ok = chol_lower_small<D>(SS, cS);                                  // :145
     if (!ok) {
       double SJ[D * D];
@@ -428,27 +536,33 @@
       for (int q = 0; q < D; ++q) SJ[q + D * q] += M.jitter;                // :147
       ok = chol_lower_small<D>(SJ, cS);
     }
-    double lw = 0.0;
+    double dg = cS[0];
+#pragma unroll
+    for (int q = 1; q < D; ++q) dg = (lane == q) ? cS[q + D * q] : dg;
+    const double lg = log(dg);                                              // (of whatever a failed factorisation left: not used then)
+    double lgq[D];
+#pragma unroll
+    for (int q = 0; q < D; ++q) lgq[q] = sym_lane_read(lg, q);
+    double lw = 0.0, sl = 0.0;
     if (ok) {
       fwd_subst<D>(cS, e, v);                                               // :149
-      double vv = 0.0, sl = 0.0;
-      for (int q = 0; q < D; ++q) { sl += log(cS[q + D * q]); vv += v[q] * v[q]; }
+      double vv = 0.0;
+      for (int q = 0; q < D; ++q) { sl += lgq[q]; vv += v[q] * v[q]; }
       lw = -sl - 0.5 * vv + M.logconst;                                     // :150
     } else {
-      atomicOr(a.status, 1);
       lw = nan("");
       for (int q = 0; q < D * D; ++q) cS[q] = 0.0;
       for (int q = 0; q < D; ++q) cS[q + D * q] = 1.0;
     }
-    if (E == 0) a.logw[i] = lw;
-    for (int q = 0; q < D * D; ++q) { misc[20 + q] = cS[q]; misc[30 + q] = SS[q]; }
-    for (int q = 0; q < D; ++q) misc[40 + q] = e[q];
+    if (lane == 0) {
+      if (!ok) atomicOr(a.status, 1);
+      if (E == 0) a.logw[i] = lw;
+      for (int q = 0; q < D * D; ++q) { misc[20 + q] = cS[q]; misc[30 + q] = SS[q]; }
+      for (int q = 0; q < D; ++q) misc[40 + q] = e[q];
+    }
     if (E > 0) {
-      double qa = red[D * D + D], qb = red[D * D + D + 1];
-      for (int w = 1; w < NW; ++w) { qa += red[w * kSymRed + D * D + D]; qb += red[w * kSymRed + D * D + D + 1]; }
-      double sl2 = 0.0;
-      for (int q = 0; q < D; ++q) sl2 += log(cS[q + D * q]);
-      misc[44] = qa; misc[45] = qb; misc[46] = ok ? sl2 : nan("");
+      const double qa = sym_lane_read(sq, D * D + D), qb = sym_lane_read(sq, D * D + D + 1);
+      if (lane == 0) { misc[44] = qa; misc[45] = qb; misc[46] = ok ? sl : nan(""); }   // sl: the sum of the logarithms, in order
     }
   }
   __syncthreads();
