@@ -360,6 +360,31 @@ int rbpf_filter_one_launch_flushes(const rbpf_ctx* ctx, int64_t* n);
  * ([N_P x n_lin] memory for n_y = 1).                                                                       */
 int rbpf_filter_ancestors(rbpf_ctx* ctx, int32_t* ai, double* xn_prev);
 int rbpf_filter_step_external(rbpf_ctx* ctx, const double* xn_new, const double* dy);
+/* The generic family with handles that live on the device: the same step, but states and Jacobians are read from and
+ * handed out in DEVICE memory, in stream order on rbpf_stream_get(ctx); between two steps nothing crosses to the host
+ * and the library does not synchronise with it.  All four entry points take a filter context of the generic family
+ * created with rbpf_model.callbacks == NULL (any other context: RBPF_ERR_STATE; NULL arguments and an unknown dy_layout:
+ * RBPF_ERR_INVALID_ARG, before anything touches a device).
+ *   dy_layout 0  MATLAB order as measModel returns it, dy(i,k,c) at i + N_P*(k + n_y*c)
+ *             2  C-contiguous [N_P][n_y][n_lin], unpadded
+ *             1  the native layout of the step kernels, H[(i*n_y + k)*ldx + c] with the row stride ldx >= n_lin of
+ *                rbpf_filter_external_layout, consumed in place: the caller leaves columns n_lin..ldx-1 zero
+ * Layouts 0 and 2 are packed into the native one by a kernel (one read and one write of the Jacobians).
+ *   rbpf_filter_ancestors_device  as rbpf_filter_ancestors (RBPF_ERR_STATE before the first step and after the last):
+ *        *ai_dev [N_P] the 0-based ancestors of the step about to run, *xn_anc_dev [n_nonlin x N_P] column-major their
+ *        states, xn_anc(q,i) = xn_{t-1}(q, ai(i)).  Both are owned by the context and valid in stream order until the next
+ *        step call.
+ *   rbpf_filter_step_device       as rbpf_filter_step_external at every t; xn_new_dev [n_nonlin x N_P] column-major.
+ *        Returns without waiting unless an on_step hook is set (then: synchronise, call the hook).
+ *   rbpf_filter_set_device_callbacks  from now on rbpf_filter_advance drives the context with these callbacks and hands
+ *        them device pointers: dyn_model(user, t, N_P, xn_anc_dev, xn_new_dev), meas_model(user, N_P, xn_dev, dy_dev) with
+ *        dy_dev in dy_layout -- layout 1: the context's own Jacobian buffer (its pad zeroed here, once), 0 / 2: a staging
+ *        buffer of the context.  The callbacks enqueue on rbpf_stream_get(ctx) or synchronise themselves; a non-zero
+ *        return is RBPF_ERR_CALLBACK; dyn_res_norm is ignored.                                                        */
+int rbpf_filter_external_layout(const rbpf_ctx* ctx, int32_t* ldx);
+int rbpf_filter_ancestors_device(rbpf_ctx* ctx, const int32_t** ai_dev, const double** xn_anc_dev);
+int rbpf_filter_step_device(rbpf_ctx* ctx, const double* xn_new_dev, const double* dy_dev, int32_t dy_layout);
+int rbpf_filter_set_device_callbacks(rbpf_ctx* ctx, const rbpf_callbacks* callbacks, int32_t dy_layout);
 /* Enable (1) / disable (0) per-launch HIP-event timing of the stream kernel; read / reset it.     */
 int rbpf_timing_enable(rbpf_ctx* ctx, int32_t on);
 int rbpf_timing_read(rbpf_ctx* ctx, rbpf_timing* out, int32_t reset);

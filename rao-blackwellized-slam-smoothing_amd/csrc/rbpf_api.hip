@@ -517,6 +517,64 @@ int generic_finish_inputs(rbpf_ctx* c, const double* xref_host) {
   return RBPF_OK;
 }
 
+// ---- generic family with handles on the device --------------------------------------------------------------------
+// The same contracts with device pointers: the ancestors' states are gathered by a kernel, the handles' results are brought
+// into the step kernels' layouts by kernels (rbpf_external.hip), everything in stream order.  No copy to or from the host,
+// no host synchronisation.
+static int ext_device_ctx_ok(const rbpf_ctx* c) {
+  if (c->mdl.kind != RBPF_MODEL_GENERIC_DENSE || c->has_cb || c->smoother || c->sh || !c->d_xn_ext || !c->d_H_ext) {
+    set_error("the device entry points of the generic family need a filter context created with rbpf_model.callbacks == NULL");
+    return RBPF_ERR_STATE;
+  }
+  return RBPF_OK;
+}
+
+static int ext_device_buffers(rbpf_ctx* c, bool callbacks, bool stage) {
+  const size_t ns = (size_t)c->mdl.nN * c->N;
+  if (!c->d_xn_anc) RB_TRY(c->pool.alloc(&c->d_xn_anc, ns));
+  if (callbacks && !c->d_xn_cm) RB_TRY(c->pool.alloc(&c->d_xn_cm, ns));
+  if (stage && !c->d_dy_stage) RB_TRY(c->pool.alloc(&c->d_dy_stage, (size_t)c->N * c->mdl.d * c->mdl.n));
+  return RBPF_OK;
+}
+
+// ancestors of the step about to run (t >= 1) and their states, column-major, into d_xn_anc
+static int ext_gather_ancestors(rbpf_ctx* c, const int** ai_dev) {
+  const int t = c->t, N = c->N, nN = c->mdl.nN;
+  const bool hist = c->opt.keep_history != 0;
+  const int* A_t = c->A + (hist ? (size_t)t * N : 0);
+  const double* X_old = c->X + (size_t)(hist ? t - 1 : ((t - 1) & 1)) * nN * N;
+  HIPCHK(launch_ext_gather_states(N, nN, X_old, A_t, c->d_xn_anc, c->stream));
+  *ai_dev = A_t;
+  return RBPF_OK;
+}
+
+// new states (column-major, device) and Jacobians (device, dy_layout) -> what ctx_step consumes
+static int ext_set_inputs(rbpf_ctx* c, const double* xn_new_dev, const double* dy_dev, int dy_layout) {
+  const int N = c->N, nN = c->mdl.nN, d = c->mdl.d, n = c->mdl.n, ldx = c->lay.ldx;
+  HIPCHK(launch_ext_states_to_soa(N, nN, xn_new_dev, c->d_xn_ext, c->stream));
+  if (dy_layout != 1) HIPCHK(launch_ext_pack_dy(dy_layout, N, d, n, ldx, dy_dev, c->d_H_ext, c->stream));
+  c->ext_xn = c->d_xn_ext;
+  c->ext_H = (dy_layout == 1) ? dy_dev : c->d_H_ext;
+  return RBPF_OK;
+}
+
+// rbpf_filter_advance with device callbacks: the handles of step c->t
+static int generic_device_inputs(rbpf_ctx* c) {
+  const int t = c->t, N = c->N, nN = c->mdl.nN;
+  if (t >= c->T) { set_error("advance past N_T"); return RBPF_ERR_STATE; }
+  if (t == 0) {                                      // particleFilter.m:59: the slab ctx_reset filled with x0_nonLin
+    HIPCHK(launch_ext_gather_states(N, nN, c->X, nullptr, c->d_xn_cm, c->stream));
+  } else {
+    if (c->ready_step != t && c->drawn_step != t) { RB_TRY(ctx_draw_ancestors(c, 0, N)); c->drawn_step = t; }
+    const int* ai = nullptr;
+    RB_TRY(ext_gather_ancestors(c, &ai));
+    if (c->dev_cb.dyn_model(c->dev_cb.user, t - 1, N, c->d_xn_anc, c->d_xn_cm) != 0) { set_error("the dynModel callback failed"); return RBPF_ERR_CALLBACK; }
+  }
+  double* dy = (c->dev_dy_layout == 1) ? c->d_H_ext : c->d_dy_stage;
+  if (c->dev_cb.meas_model(c->dev_cb.user, N, c->d_xn_cm, dy) != 0) { set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK; }
+  return ext_set_inputs(c, c->d_xn_cm, dy, c->dev_dy_layout);
+}
+
 // Bytes a timed launch of the step kernel has to move (rbpf_timing.scheduled_bytes_per_launch): the stored covariance in
 // (and out when it is rewritten), the pending factor sets it applies and the one it produces, the means and the states in
 // and out (+ ivec in / out and H out for the information form).
@@ -988,9 +1046,11 @@ int rbpf_filter_advance(rbpf_ctx* c, int32_t n_steps) {
     if (c->has_cb) {                                   // generic family: evaluate the handles of this step on the host
       RB_TRY(generic_draw_propagate(c, 0, c->N));
       RB_TRY(generic_finish_inputs(c, nullptr));
+    } else if (c->has_dev_cb) {                        // ... or on the device, in stream order
+      RB_TRY(generic_device_inputs(c));
     }
     const int st = ctx_step(c, 0, nullptr, c->N, nullptr);
-    if (c->has_cb) { c->ext_xn = nullptr; c->ext_H = nullptr; }
+    if (c->has_cb || c->has_dev_cb) { c->ext_xn = nullptr; c->ext_H = nullptr; }
     RB_TRY(st);
     RB_TRY(ctx_call_on_step(c, c->t - 1, false));      // particleFilter.m:215-217
   }
@@ -1033,6 +1093,56 @@ int rbpf_filter_step_external(rbpf_ctx* c, const double* xn_new, const double* d
   if (st != RBPF_OK) return st;
   HIPCHK(hipStreamSynchronize(c->stream));          // the host vectors above go out of scope
   return ctx_call_on_step(c, c->t - 1, false);
+}
+
+int rbpf_filter_external_layout(const rbpf_ctx* c, int32_t* ldx) {
+  if (!c || !ldx) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(ext_device_ctx_ok(c));
+  *ldx = c->lay.ldx;
+  return RBPF_OK;
+}
+
+int rbpf_filter_ancestors_device(rbpf_ctx* c, const int32_t** ai_dev, const double** xn_anc_dev) {
+  if (!c || !ai_dev || !xn_anc_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(ext_device_ctx_ok(c));
+  if (c->t < 1 || c->t >= c->T || c->ready_step != c->t) { set_error("no ancestors drawn for the next step (run a step first)"); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  RB_TRY(ext_device_buffers(c, false, false));
+  const int* ai = nullptr;
+  RB_TRY(ext_gather_ancestors(c, &ai));
+  *ai_dev = ai;
+  *xn_anc_dev = c->d_xn_anc;
+  return RBPF_OK;
+}
+
+int rbpf_filter_step_device(rbpf_ctx* c, const double* xn_new_dev, const double* dy_dev, int32_t dy_layout) {
+  if (!c || !xn_new_dev || !dy_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (dy_layout < 0 || dy_layout > 2) { set_error("dy_layout must be 0 (MATLAB order), 1 (native) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(ext_device_ctx_ok(c));
+  if (c->t >= c->T) { set_error("advance past N_T"); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  RB_TRY(ext_set_inputs(c, xn_new_dev, dy_dev, dy_layout));
+  c->fuse_resample = true;
+  const int st = ctx_step(c, 0, nullptr, c->N, nullptr);
+  c->ext_xn = nullptr; c->ext_H = nullptr;
+  if (st != RBPF_OK) return st;
+  if (!c->opt.on_step) return RBPF_OK;
+  HIPCHK(hipStreamSynchronize(c->stream));          // as rbpf_filter_step_external: the hook sees a finished step
+  return ctx_call_on_step(c, c->t - 1, false);
+}
+
+int rbpf_filter_set_device_callbacks(rbpf_ctx* c, const rbpf_callbacks* cb, int32_t dy_layout) {
+  if (!c || !cb || !cb->dyn_model || !cb->meas_model) { set_error("NULL argument (the callbacks need dyn_model and meas_model)"); return RBPF_ERR_INVALID_ARG; }
+  if (dy_layout < 0 || dy_layout > 2) { set_error("dy_layout must be 0 (MATLAB order), 1 (native) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(ext_device_ctx_ok(c));
+  HIPCHK(hipSetDevice(c->device));
+  RB_TRY(ext_device_buffers(c, true, dy_layout != 1));
+  // layout 1: the handle fills columns 0..nLin-1 of the context's own buffer; the pad is zeroed here, once
+  if (dy_layout == 1) HIPCHK(hipMemsetAsync(c->d_H_ext, 0, (size_t)c->N * c->mdl.d * c->lay.ldx * sizeof(double), c->stream));
+  c->dev_cb = *cb; c->dev_cb.dyn_res_norm = nullptr;
+  c->dev_dy_layout = dy_layout;
+  c->has_dev_cb = true;
+  return RBPF_OK;
 }
 
 int rbpf_filter_reset(rbpf_ctx* c) {

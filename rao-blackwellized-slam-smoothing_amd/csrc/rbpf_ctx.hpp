@@ -87,6 +87,13 @@ struct rbpf_ctx {
   const double *ext_xn = nullptr, *ext_H = nullptr;
   rbpf_callbacks cb = {nullptr, nullptr, nullptr, nullptr};   // the model's handles (copied at create; all null: caller-driven)
   bool has_cb = false;
+  // generic family on the device: callbacks that take device pointers (rbpf_filter_set_device_callbacks), their dy layout,
+  // and the buffers handed to them or to the caller -- ancestors' states and new states [nN x N] column-major, the staging
+  // buffer of dy layouts 0 / 2 [N][d][n].  Allocated on first use.
+  rbpf_callbacks dev_cb = {nullptr, nullptr, nullptr, nullptr};
+  bool has_dev_cb = false;
+  int dev_dy_layout = 0;
+  double *d_xn_anc = nullptr, *d_xn_cm = nullptr, *d_dy_stage = nullptr;
   std::vector<double> h_xn;      // generic family: states of the last step [nN x N] column-major (host evaluates dynModel)
   std::vector<double> h_xn_new, h_dy;   // scratch of the callbacks
   std::vector<int> h_ai;

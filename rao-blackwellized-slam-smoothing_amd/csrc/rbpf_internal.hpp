@@ -275,6 +275,11 @@ hipError_t launch_jacobian_phi3d(const ModelDev& m, int np, const double* x, con
                                  double* J, hipStream_t s);
 hipError_t launch_quat_helpers(int op, int n, const double* in, double* out, hipStream_t s);
 hipError_t launch_transpose_soa(int N, int nN, const double* soa, double* aos, hipStream_t s);
+// generic family on the device (rbpf_external.hip): cm [nN x N] column-major = soa [nN][N] gathered through ai (null: identity)
+// and back; dy in layout 0 (MATLAB order) or 2 (C-contiguous [N][d][n]) -> H [N][d][ldx], columns n..ldx-1 zero
+hipError_t launch_ext_gather_states(int N, int nN, const double* soa, const int* ai, double* cm, hipStream_t s);
+hipError_t launch_ext_states_to_soa(int N, int nN, const double* cm, double* soa, hipStream_t s);
+hipError_t launch_ext_pack_dy(int layout, int N, int d, int n, int ldx, const double* dy, double* H, hipStream_t s);
 hipError_t launch_pack_records(const Layout& lay, int d, const int* idx, int count, const double* Pt, const double* Pb,
                                const double* F, const double* xl, double* rec, hipStream_t s, size_t rec_stride = 0,
                                int fp32 = 0);

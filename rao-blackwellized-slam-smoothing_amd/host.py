@@ -302,6 +302,179 @@ class GenericDenseModel:
         return d
 
 
+class DeviceHandles:
+    """An arbitrary (unrecognised) dense model whose handles are device code: batched callables on torch float64 tensors of
+    the library's device,
+
+        xn_new (n_nonlin, N_P) = dynModel(xn_anc (n_nonlin, N_P), dx (n_odo,), dt, Q (n_w, n_w))   -- draws its own random numbers
+        dy (N_P, n_y, nLin)    = measModel(xn (n_nonlin, N_P))            ((N_P, nLin) is accepted for n_y = 1)
+
+    handed to particleFilter / FilterSession in place of the handle pair.  They run inside torch.cuda.stream(the library's
+    stream); xn_anc and xn are views of library memory.  Between two steps nothing is copied to the host and nothing waits
+    for it (rbpf_filter_ancestors_device / rbpf_filter_step_device).
+
+    dy_layout=None (default): the binding drives the filter step by step and looks at the strides of every returned dy --
+    MATLAB-order strides (1, N_P, N_P n_y) are packed by the transpose kernel (layout 0), a C-contiguous tensor by the row
+    copy (layout 2), the native view filled in place is consumed where it is (layout 1, see native_out); anything else costs
+    one contiguous() and goes the way of layout 2.
+    dy_layout=0 / 1 / 2: the handles are registered as device callbacks (rbpf_filter_set_device_callbacks) and
+    rbpf_filter_advance runs the steps; measModel's result is copied into the library's buffer of that layout unless it is
+    that buffer.
+    native_out=True: measModel is called as measModel(xn, out) with `out` (N_P, n_y, nLin) a view of the buffer the step
+    kernels will read (strides (n_y ldx, ldx, 1) by default); filling it and returning it saves the pack kernel."""
+
+    def __init__(self, dynModel, measModel, dy_layout=None, native_out=False):
+        if not (callable(dynModel) and callable(measModel)):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "dynModel / measModel must be callable")
+        if dy_layout not in (None, 0, 1, 2):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "dy_layout must be None, 0 (MATLAB order), 1 (native) or 2 (C-contiguous)")
+        self.dynModel, self.measModel = dynModel, measModel
+        self.dy_layout, self.native_out = dy_layout, bool(native_out)
+
+
+def _refuse_device_handles(what, *handles):
+    if any(isinstance(h, DeviceHandles) for h in handles):
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceHandles are not supported by %s: the filter on one GPU only "
+                                                   "(particleFilter, FilterSession)" % what)
+
+
+class _DeviceDriver:
+    """Runs the steps of a generic-family filter context with DeviceHandles (see there)."""
+
+    def __init__(self, lib, ctx, handles, model, prob):
+        import torch
+        from .multigpu import _view
+        self.torch, self._view = torch, _view
+        self.lib, self.ctx, self.h = lib, ctx, handles
+        self.nN, self.n, self.d, self.N, self.T = model.nNonLin, model.nLin, model.ny, prob.N_P, prob.N_T
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        sp = C.c_void_p()
+        check(lib.rbpf_stream_get(ctx, C.byref(sp)))
+        self.stream = torch.cuda.ExternalStream(sp.value, device=self.device)
+        ldx = C.c_int32(0)
+        check(lib.rbpf_filter_external_layout(ctx, C.byref(ldx)))
+        self.ldx = ldx.value
+        self.odo = torch.as_tensor(np.ascontiguousarray(model._odo), device=self.device)
+        self.Q = torch.as_tensor(np.ascontiguousarray(np.moveaxis(model._Q, 2, 0)), device=self.device)     # [pages][nw][nw]
+        self.dt = model._dt
+        self.x0 = torch.as_tensor(prob.x0n, device=self.device).repeat(self.N, 1)                            # particleFilter.m:59
+        self.error = None
+        self._keep = None
+        self._native = None
+        self._cb = None
+        torch.cuda.current_stream(self.device).synchronize()           # the constants above, before the library's stream reads them
+        if handles.dy_layout is not None:
+            self._register(int(handles.dy_layout))
+
+    # -- the handles ------------------------------------------------------------------------------------
+    def _dyn(self, t, xn_anc):
+        Q = self.Q[t if self.Q.shape[0] > 1 else 0]
+        xn = self.h.dynModel(xn_anc, self.odo[t], float(self.dt[t if self.dt.size > 1 else 0]), Q)
+        if tuple(xn.shape) != (self.nN, self.N) or xn.dtype != self.torch.float64 or not xn.is_cuda:
+            raise ValueError(f"dynModel returned {tuple(xn.shape)} {xn.dtype} on {xn.device}, expected a float64 device tensor of "
+                             f"shape {(self.nN, self.N)}")
+        return xn
+
+    def _meas(self, xn, out):
+        dy = self.h.measModel(xn, out) if self.h.native_out else self.h.measModel(xn)
+        if dy.dim() == 2 and self.d == 1:
+            dy = dy.unsqueeze(1)
+        if tuple(dy.shape) != (self.N, self.d, self.n) or dy.dtype != self.torch.float64 or not dy.is_cuda:
+            raise ValueError(f"measModel returned {tuple(dy.shape)} {dy.dtype} on {dy.device}, expected a float64 device tensor of "
+                             f"shape {(self.N, self.d, self.n)}")
+        return dy
+
+    @staticmethod
+    def _same(a, b):
+        return b is not None and a.data_ptr() == b.data_ptr() and a.stride() == b.stride()
+
+    def _dy_view(self, ptr, layout):
+        """(N, n_y, nLin) view of a dy buffer of the C ABI's layout 0 / 1 / 2."""
+        N, d, n = self.N, self.d, self.n
+        if layout == 0:
+            return self._view(self.torch, ptr, (n, d, N), self.device).permute(2, 1, 0)
+        if layout == 1:
+            return self._view(self.torch, ptr, (N, d, self.ldx), self.device)[:, :, :n]
+        return self._view(self.torch, ptr, (N, d, n), self.device)
+
+    # -- caller-driven: one step at a time, the layout of every dy read off its strides --------------------
+    def _step(self, t):
+        torch, lib = self.torch, self.lib
+        with torch.cuda.stream(self.stream):
+            if t == 0:
+                xn_cm = self.x0
+            else:
+                ai, anc = C.c_void_p(), C.c_void_p()
+                check(lib.rbpf_filter_ancestors_device(self.ctx, C.byref(ai), C.byref(anc)))
+                xn = self._dyn(t - 1, self._view(torch, anc, (self.N, self.nN), self.device).t())
+                xn_cm = xn.t().contiguous()                               # [n_nonlin x N_P] column-major (no copy if it is)
+            out = None
+            if self.h.native_out:
+                if self._native is None:
+                    self._native = torch.zeros((self.N, self.d, self.ldx), dtype=torch.float64, device=self.device)
+                out = self._native[:, :, :self.n]
+            dy = self._meas(xn_cm.t(), out)
+            if self._same(dy, out):
+                layout = 1
+            elif dy.is_contiguous():
+                layout = 2
+            elif dy.permute(2, 1, 0).is_contiguous():
+                layout = 0
+            else:
+                dy, layout = dy.contiguous(), 2
+            self._keep = (xn_cm, dy)                                      # read in stream order by the step just enqueued
+            check(lib.rbpf_filter_step_device(self.ctx, C.c_void_p(xn_cm.data_ptr()), C.c_void_p(dy.data_ptr()), layout))
+
+    # -- device callbacks: rbpf_filter_advance runs the steps ---------------------------------------------
+    def _register(self, layout):
+        torch = self.torch
+
+        def dyn(_user, t, n_cols, xn_anc, xn_new):
+            try:
+                with torch.cuda.stream(self.stream):
+                    anc = self._view(torch, xn_anc, (n_cols, self.nN), self.device).t()
+                    self._view(torch, xn_new, (n_cols, self.nN), self.device).t().copy_(self._dyn(t, anc))
+                return 0
+            except Exception as exc:                                                      # noqa: BLE001
+                self.error = self.error or exc
+                return 1
+
+        def meas(_user, n_cols, xn, dy_p):
+            try:
+                with torch.cuda.stream(self.stream):
+                    target = self._dy_view(dy_p, layout)
+                    dy = self._meas(self._view(torch, xn, (n_cols, self.nN), self.device).t(), target)
+                    if not self._same(dy, target):
+                        target.copy_(dy)
+                return 0
+            except Exception as exc:                                                      # noqa: BLE001
+                self.error = self.error or exc
+                return 1
+
+        cb = _ffi.rbpf_callbacks()
+        self._fns = (_ffi.DYN_MODEL_FN(dyn), _ffi.MEAS_MODEL_FN(meas))
+        cb.dyn_model, cb.meas_model = self._fns
+        cb.user = None
+        self._cb = cb
+        check(self.lib.rbpf_filter_set_device_callbacks(self.ctx, C.byref(cb), layout))
+
+    def advance(self, n_steps):
+        try:
+            if self._cb is not None:
+                check(self.lib.rbpf_filter_advance(self.ctx, int(n_steps)))
+                return
+            t0 = C.c_int32(0)
+            check(self.lib.rbpf_filter_tell(self.ctx, C.byref(t0)))
+            if t0.value + int(n_steps) > self.T:
+                raise RBPFError(_ffi.RBPF_ERR_STATE, "advance past N_T")
+            for t in range(t0.value, t0.value + int(n_steps)):
+                self._step(t)
+        except RBPFError as exc:
+            if exc.status == _ffi.RBPF_ERR_CALLBACK and self.error is not None:
+                raise self.error from exc
+            raise
+
+
 def dense_mag_prior(m, LL, theta):
     """GP prior of run_dense3D_magfield.m:83-107,122-131 -> (model, x0_lin, P0_lin, R)."""
     L, NN = domain_cartesian_dx(m, 3, LL)
@@ -484,6 +657,16 @@ def _recognise(dynModel, measModel, dynResNorm=None):
     return mdl, use_drn
 
 
+def _device_handles(dynModel, measModel):
+    """The DeviceHandles object given in place of the handle pair (as dynModel, measModel None or the same object), or None."""
+    if not isinstance(dynModel, DeviceHandles) and not isinstance(measModel, DeviceHandles):
+        return None
+    if not isinstance(dynModel, DeviceHandles) or (measModel is not None and measModel is not dynModel):
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "DeviceHandles replace the handle pair: pass the object as dynModel and None "
+                                                   "(or the same object) as measModel")
+    return dynModel
+
+
 def _generic_model(dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, Q, dt):
     """GenericDenseModel for arbitrary callables, sized from the problem arrays."""
     y2 = np.asarray(y, dtype=np.float64)
@@ -523,13 +706,22 @@ def particleFilter(dynModel, measModel, odometry, y, x0_nonLin, x0_lin, P0_lin, 
         dy [N x ny x nLin] (or [N x nLin] for ny = 1) = measModel(xn [nN x N])
     evaluated on the host through `rbpf_callbacks`; resampling uniforms still come from `rng` (the normals of a ReplayRNG
     are not used: dynModel owns its randomness, as in the reference).
+    A DeviceHandles object as dynModel (measModel None) keeps such a model on the device: batched handles on torch tensors, no
+    host round trip (see DeviceHandles; one GPU, no n_devices).
     makePlots is called after every step with the reference's nine arguments (particleFilter.m:215-217) through the
     library's on_step hook.
     n_devices = W > 1 (rbpf_options.n_devices): the library shards the N_P particles over W GPUs itself -- one host thread per
     device, RCCL collectives -- and returns the reference's eight outputs (xn_traj from the replicated state history; None with
     want_xn_traj=False); device_ids names the HIP devices
     (a device named twice makes its ranks share it over a host-staged transport: tests on one GPU)."""
-    model, _ = _recognise(dynModel, measModel, model_dyn_res_norm(dynModel))
+    handles = _device_handles(dynModel, measModel)
+    if handles is not None:                                   # device code: no host callbacks, the binding drives the context
+        if int(n_devices) > 1 or (int(n_devices) == 1 and device_ids is not None):
+            _refuse_device_handles("sharded sessions (n_devices)", handles)
+        dynModel = measModel = None
+        model = None
+    else:
+        model, _ = _recognise(dynModel, measModel, model_dyn_res_norm(dynModel))
     generic = model is None
     if generic:
         if sparseFeatures:
@@ -615,7 +807,11 @@ def particleFilter(dynModel, measModel, odometry, y, x0_nonLin, x0_lin, P0_lin, 
     check(lib.rbpf_filter_create(C.byref(mdesc), C.byref(prob.c), C.byref(blk), C.byref(opt), C.byref(ctx)))
     try:
         try:
-            check(lib.rbpf_filter_advance(ctx, T))
+            if handles is not None:
+                driver = _DeviceDriver(lib, ctx, handles, model, prob)    # (alive until the context is gone: it owns what the last step reads)
+                driver.advance(T)
+            else:
+                check(lib.rbpf_filter_advance(ctx, T))
         except RBPFError as exc:
             if exc.status == _ffi.RBPF_ERR_CALLBACK and hook_error:
                 raise hook_error[0] from exc
@@ -683,6 +879,7 @@ def model_dyn_res_norm(dynModel):
 def _smoother(info_form, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, N_K, dt,
               sparseFeatures, makePlots, rng, extras, chol_variant=0, lazy_depth=0, chol_refresh=0, n_devices=0, device_ids=None,
               storage="fp64", exchange_capacity=0, inplace=0, info_rebuild=0):
+    _refuse_device_handles("the smoothers", dynModel, measModel, dynResNorm)
     if sparseFeatures:
         if info_form:
             # particleSmootherInformationForm.m:77-80 prints and returns with outputs unassigned
@@ -861,7 +1058,13 @@ class FilterSession:
     def __init__(self, model, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, dt, rng=None, keep_history=False,
                  trace=False, lazy_depth=0, inplace=0, storage="fp64"):
         self.lib = load_library()
+        handles = model if isinstance(model, DeviceHandles) else None
+        if handles is not None:                                # device code in place of a model: the generic family, caller-driven
+            model = _generic_model(None, None, None, odometry, y, x0_nonLin, x0_lin, Q, dt)
+            if isinstance(rng, ReplayRNG) and (rng.Z is None or rng.Z.size == 0):
+                rng = ReplayRNG(rng.U, np.zeros(rng.U.shape + (model.nw,)), rng.Ufin)
         self.model = model
+        self._driver = None
         self.prob = _Problem(model, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, dt)
         self.blk, self._rng = _rng_block(rng, self.prob.N_P, self.prob.N_T, model.nw, 1)
         self.opt = _ffi.rbpf_options(keep_history=1 if keep_history else 0, trace=1 if trace else 0, fix_p_mean=0,
@@ -871,8 +1074,16 @@ class FilterSession:
         self.ctx = C.c_void_p()
         check(self.lib.rbpf_filter_create(C.byref(self.mdesc), C.byref(self.prob.c), C.byref(self.blk),
                                           C.byref(self.opt), C.byref(self.ctx)))
+        if handles is not None:
+            try:
+                self._driver = _DeviceDriver(self.lib, self.ctx, handles, model, self.prob)
+            except Exception:
+                self.close()
+                raise
 
     def advance(self, n_steps):
+        if self._driver is not None:
+            return self._driver.advance(n_steps)
         check(self.lib.rbpf_filter_advance(self.ctx, int(n_steps)))
 
     def reset(self):
@@ -934,6 +1145,7 @@ class FilterSession:
         if self.ctx:
             self.lib.rbpf_destroy(self.ctx)
             self.ctx = C.c_void_p()
+        self._driver = None
 
     def __enter__(self):
         return self

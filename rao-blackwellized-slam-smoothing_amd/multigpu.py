@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import check, load_library
-from .host import PhiloxRNG, _Problem, _dp, _ip, _rng_block, _storage_code
+from .host import PhiloxRNG, _Problem, _dp, _ip, _refuse_device_handles, _rng_block, _storage_code
 
 
 # ------------------------------------------------------------------------------------------------
@@ -169,6 +169,7 @@ class ShardedFilterSession:
     def __init__(self, model, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_local, dt, rng=None, rank=0, world=1,
                  transport="device", planner="device", lazy_depth=0, storage="fp64", keep_history=False, exchange_capacity=0,
                  sync_phases=False, force_collectives=False):
+        _refuse_device_handles("sharded sessions", model)
         import torch
         import torch.distributed as dist
         self.torch, self.dist = torch, dist
@@ -544,6 +545,7 @@ class ShardedSmootherSession(ShardedFilterSession):
     def __init__(self, model, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_local, N_K, dt, rng=None, rank=0, world=1,
                  transport="device", exchange_capacity=0, sync_phases=False, lazy_depth=0, chol_refresh=0, force_collectives=False,
                  storage="fp64"):
+        _refuse_device_handles("sharded sessions", model)
         self.N_K = int(N_K)
         self.chol_refresh_requested = int(chol_refresh)
         lib = load_library()
