@@ -686,6 +686,35 @@ int rbpf_loc_predict(const rbpf_loc_map* map, int32_t n_pred, const double* xn, 
 int rbpf_loc_dyn_model(int32_t n_p, const double* xn, const double* odo, double dt, const double* Q, const double* z,
                        double* xn_next);
 
+/* ---- backward-simulation smoother for localisation in a fixed map --------------------------------
+ * Forward filter, backward simulation (Godsill, Doucet & West 2004).  In a fixed map the state (pos3 + quat4) is Markov, so
+ * n_traj trajectories are drawn backwards through the forward particles X [7 x N_P x N_T] (as propagated) and normalised weights
+ * w of a localisation context created with keep_history = 1 and trace = 1, all N_T steps done:
+ *     b(j, N_T) = sample(w(:, N_T));   t = N_T-1 .. 1:  l(i) = log(w(i, t)) + logp(xs(:, j, t+1) | X(:, i, t)),  b(j, t) = sample(p)
+ * with p the log-sum-exp normalisation of l (particleSmoother.m:232, :236-238, :241).  logp is the density of dynModel
+ * (run_localization.m:274-281) as it draws, constants omitted (particleSmoother.m:181-182), with odometry row t, dt(t), Q(:,:,t):
+ *     a = qRight(q_i) dq,  e = qLeft(qInv(a)) q~,  phi = logq(e),  r = [p~ - p_i - dx(1:3); phi],
+ *     z = blkdiag(S_pos, S_rot) \ r  (S = sqrt(dt Q) element-wise on the diagonal blocks),  logp = -z'z / 2.
+ * A singular S block is RBPF_ERR_INVALID_ARG.  w(i) = 0 is never selected.  A draw past the last cdf edge is clamped to the
+ * last particle with a non-zero term and counted with the filter's clamped draws.
+ * u [N_T x n_traj], row t = step t (u[t * n_traj + j]), uniforms in (0, 1); NULL: Philox4x32-10 keyed by `seed` on the counters
+ * (slot = j, step = t, lane = 0x42530000, iter = 0), first uniform -- disjoint from the filter's lanes 0 .. 3.
+ * Outputs (NULL pointers are skipped): xs_traj [7 x n_traj x N_T], index [n_traj x N_T] 0-based, traj_smooth_mean [7 x N_T] (plain
+ * means over the trajectories of all 7 rows, as particleFilterLocalization.m:123).  The workspace comes from the context's pool
+ * and is returned before the call returns.  RBPF_ERR_STATE: steps missing, no keep_history / trace, or a degenerate forward step;
+ * RBPF_ERR_INVALID_ARG: not a localisation context, n_traj < 1.  The context stays usable after a refusal.                     */
+int rbpf_loc_backward_simulate(rbpf_ctx* ctx, int32_t n_traj, const double* u, uint64_t seed, double* xs_traj, int32_t* index,
+                               double* traj_smooth_mean);
+/* The forward particles as propagated, NOT traced back: xn_fwd [7 x N_P x T_done] (needs keep_history).                       */
+int rbpf_loc_history(rbpf_ctx* ctx, double* xn_fwd);
+/* Bytes of device memory rbpf_loc_backward_simulate takes from the pool while it runs (no device access).                     */
+int rbpf_loc_backward_workspace_bytes(int32_t N_P, int32_t N_T, int32_t n_traj, size_t* bytes);
+/* One backward step on the caller's arrays, the kernel-level probe: xn [7 x N], w [N], xs_next [7 x M], odo [7], Q [6 x 6],
+ * u [M] -> index [M]; logp [N x M] column-major (may be NULL) = the transition log densities without log(w).  reps >= 1 repeats
+ * the step's launches; *ms (may be NULL) = median time of one step.                                                            */
+int rbpf_loc_backward_step(int32_t N, int32_t M, const double* xn, const double* w, const double* xs_next, const double* odo,
+                           double dt, const double* Q, const double* u, int32_t* index, double* logp, int32_t reps, double* ms);
+
 /* ---- the EKF comparison baseline of examples/slam-dense-mag, batched over data sets ---------------
  * ekf_dense.m:41-102 with the closures measModel_ekf / dynModel_ekf of run_dense3D_magfield.m:281-299,310-316, on the device:
  * one Gaussian state [position(3); orientation deviation(3); map(nLin = m_basis + 3)], n = 6 + nLin, per run.  The n_runs runs

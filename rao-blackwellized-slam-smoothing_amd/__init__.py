@@ -14,7 +14,8 @@ from .host import (particleFilter, particleSmoother, particleSmootherInformation
                    DenseMagModel, DenseRadioModel, SparseVisualModel, dense_mag_prior, dense_radio_prior,
                    domain_cartesian_dx, eigenval, PhiloxRNG, ReplayRNG, FilterSession, sample, chol_weights, chol_sweep_probe, quat_helper,
                    GenericDenseModel, DeviceHandles, particle_filter_external, chol_refresh_in_use,
-                   DenseMagMap, particleFilterLocalization, LocalizationSession, loc_workspace_bytes)
+                   DenseMagMap, particleFilterLocalization, LocalizationSession, loc_workspace_bytes,
+                   particleSmootherLocalization, loc_backward_step, loc_backward_workspace_bytes)
 
 
 def device_count() -> int:

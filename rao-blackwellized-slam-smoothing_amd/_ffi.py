@@ -159,6 +159,7 @@ EXPORTS = [
     "rbpf_shard_smoother_step", "rbpf_shard_smoother_end",
     "rbpf_particle_filter_localization", "rbpf_loc_create", "rbpf_loc_advance", "rbpf_loc_finish", "rbpf_loc_workspace_bytes",
     "rbpf_loc_predict", "rbpf_loc_dyn_model",
+    "rbpf_loc_backward_simulate", "rbpf_loc_history", "rbpf_loc_backward_workspace_bytes", "rbpf_loc_backward_step",
     "rbpf_ekf_dense", "rbpf_ekf_workspace_bytes",
 ]
 
@@ -271,6 +272,11 @@ def load_library(build_if_missing: bool = True):
                                              C.POINTER(C.c_size_t)]
     lib.rbpf_loc_predict.argtypes = [C.POINTER(rbpf_loc_map), C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
     lib.rbpf_loc_dyn_model.argtypes = [C.c_int32, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p]
+    lib.rbpf_loc_backward_simulate.argtypes = [C.c_void_p, C.c_int32, c_double_p, C.c_uint64, c_double_p, c_int32_p, c_double_p]
+    lib.rbpf_loc_history.argtypes = [C.c_void_p, c_double_p]
+    lib.rbpf_loc_backward_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_backward_step.argtypes = [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p,
+                                           c_double_p, c_int32_p, c_double_p, C.c_int32, c_double_p]
     lib.rbpf_ekf_dense.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(rbpf_ekf_out)]
     lib.rbpf_ekf_workspace_bytes.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(C.c_size_t)]
     _lib = lib

@@ -15,6 +15,7 @@
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
 #include "rbpf_ctx.hpp"
+#include "rbpf_loc_state.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -349,14 +350,6 @@ __global__ void loc_fill_x0_kernel(int N, int cols, const double* __restrict__ x
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-struct LocState {
-  DevicePool pool;                 // owns the device buffers below; the context-level arrays of a localisation session are in rbpf_ctx::pool
-  int n = 0;
-  double sigma2 = 0.0;
-  double *d_mean = nullptr, *d_V = nullptr, *d_vartab = nullptr, *d_S = nullptr, *d_lse = nullptr, *d_x0 = nullptr;
-  int s_pages = 1, x0_cols = 1;
-};
-
 void loc_free(rbpf_ctx* c) {
   if (!c || !c->loc) return;
   LocState* L = c->loc;

@@ -1,0 +1,481 @@
+// Backward-simulation smoother for localisation in a fixed map (forward filter, backward simulation: Godsill, Doucet & West 2004).
+// In a fixed map the state (pos3 + quat4) is Markov, so M trajectories are drawn backwards through the stored forward particles
+// X [T][7][N] and weights w [T][N] of a localisation context (keep_history = 1, trace = 1):
+//     b[T-1][j] = sample(w[T-1], u[T-1][j]);   t = T-2 .. 0:  l_i = log w[t][i] + logp(xs[t+1][j] | X[t][:, i]),  b[t][j] = sample(p, u[t][j])
+// with p the log-sum-exp normalisation of l (particleSmoother.m:232, :236-238, :241) and sample = #{i : cumsum(p)_i < u}
+// (tools/sample.m:30-32).  logp is the density of dynModel as it draws (run_localization.m:274-281), constants omitted:
+//     a_i = qRight(q_i) dq,  e = qLeft(qInv(a_i)) q~,  phi = logq(e),  r = [p~ - (p_i + dx(1:3)); phi],  z = blkdiag(S_pos, S_rot) \ r,  logp = -z'z / 2
+// logq(e) = acos(e0) e_v / sin(acos(e0)) after the sign flip of tools/logq.m:26-28 is evaluated as atan2(|e_v|, e0) e_v / |e_v|: the
+// same value for a unit e, without the cancellation of acos near 1.
+//
+// Kernels of one step t (all in stream order):
+//   bs_prologue_kernel   Xhat[t][:, i] = (p_i + dx(1:3), a_i, log w_i): 8 doubles per particle, SoA, shared by all M trajectories.
+//   bs_pass_kernel       all pairs.  Grid = (trajectory blocks of 256) x (particle chunks of C); a lane owns one trajectory, keeps
+//                        xs[t+1][j] in registers and a running (max, sum) pair; the particles come in tiles of 256 through LDS and
+//                        are read as broadcasts (all lanes one address).  No cross-lane operation.  Writes one (max, sum) per
+//                        (chunk, j).  A pair whose log w + position term alone lies more than 746 below the running max skips
+//                        its orientation term: its exp is exactly 0.
+//   bs_locate_kernel     per j: merge the chunk partials, find the chunk that holds u * total, walk it, gather xs[t][j].
+//   bs_mean_kernel       traj_smooth_mean[:, t] = mean over j (plain means of all 7 rows, particleFilterLocalization.m:123).
+//
+// SUMMATION ORDER (fixed; the indices depend on nothing else):
+//   * inside a chunk, particles in ascending i: (m, s) <- l_i: if l_i > m: s = s exp(m - l_i) + 1, m = l_i; else s += exp(l_i - m);
+//   * M_j = max over the chunks' m_c;  P_c = P_{c-1} + s_c exp(m_c - M_j) in ascending c, P_{-1} = 0; total = P_last;
+//   * c0 = first c with P_c >= u total;  walk: acc = P_{c0-1}; ascending i in chunk c0: acc += exp(l_i - M_j); the first i
+//     with a non-zero term and acc >= u total is b.  A walk that reaches the end of its chunk without crossing (the walk's sum and
+//     the chunk's rescaled partial differ by rounding) goes on, acc carried over, through the following chunks with s_c > 0; if
+//     none crosses, b = the last particle with a non-zero term (the clamp of a draw past the last cdf edge), counted in the
+//     context's clamped-draw flag like the filter's.  w_i = 0 gives l_i = -inf and a zero term: never selected.
+//   * C = chunk_size(N, M) below: a function of the two sizes only.
+//
+// PHILOX COUNTERS: u[t][j] = first uniform of philox_uniform2(seed, slot = j, step = t, lane = 0x42530000, iter = 0).  The filter's
+// draws use lanes 0 .. 3 (rbpf_device.hpp), so the two ranges are disjoint for the same seed.
+#include "../../include/rbpf.h"
+#include "rbpf_internal.hpp"
+#include "rbpf_device.hpp"
+#include "rbpf_ctx.hpp"
+#include "rbpf_loc_state.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace rbpf {
+
+constexpr int kBsTile = 256;               // particles per LDS tile = threads per workgroup
+constexpr int kBsMaxChunk = 2048;          // largest chunk (particles): the walk of the locate kernel is at most this long per chunk
+constexpr uint32_t kBsPhiloxLane = 0x42530000u;
+constexpr double kBsSkip = 746.0;          // exp(x) == 0 for x < -745.14
+
+// chunk of the all-pairs pass: enough (trajectory block) x (chunk) workgroups to give every CU four, in whole tiles
+static int bs_chunk_size(int N, int M) {
+  const int bx = (M + kBsTile - 1) / kBsTile;
+  const int want = std::max(1, (1024 + bx - 1) / bx);
+  int C = ((N + want - 1) / want + kBsTile - 1) / kBsTile * kBsTile;
+  return std::min(std::max(C, kBsTile), kBsMaxChunk);
+}
+
+struct BsNoise { double ip[9], ir[9]; };   // inv(S_pos), inv(S_rot), row-major
+
+struct BsArgs {
+  int N, M, C, nchunks;
+  int first;                       // 1: the draw of step T-1, l_i = log w_i
+  const double* Xhat;              // [8][N]
+  const double* X;                 // [7][N] particles of this step (gather)
+  const double* xs_next;           // [M][7]
+  const double* u;                 // [M]
+  double* part_m; double* part_s;  // [nchunks][M]
+  int* index;                      // [M]
+  double* xs;                      // [M][7] or null
+  int* clamped;                    // device counter
+  BsNoise nz;
+};
+
+__global__ void bs_prologue_kernel(int N, const double* __restrict__ xn, size_t cs, size_t ps, const double* __restrict__ w,
+                                   const double* __restrict__ odo, double* __restrict__ Xhat) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  double q[4];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) Xhat[(size_t)c * N + i] = xn[(size_t)c * cs + (size_t)i * ps] + odo[c];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) q[c] = xn[(size_t)(3 + c) * cs + (size_t)i * ps];
+  const double p[4] = {odo[3], odo[4], odo[5], odo[6]};
+  // qRight(q) dq (tools/qRight.m:29-34), as loc_dyn_model_dev
+  Xhat[(size_t)3 * N + i] = q[0] * p[0] + (-q[1]) * p[1] + (-q[2]) * p[2] + (-q[3]) * p[3];
+  Xhat[(size_t)4 * N + i] = q[1] * p[0] + q[0] * p[1] + q[3] * p[2] + (-q[2]) * p[3];
+  Xhat[(size_t)5 * N + i] = q[2] * p[0] + (-q[3]) * p[1] + q[0] * p[2] + q[1] * p[3];
+  Xhat[(size_t)6 * N + i] = q[3] * p[0] + q[2] * p[1] + (-q[1]) * p[2] + q[0] * p[3];
+  const double wi = w[i];
+  Xhat[(size_t)7 * N + i] = wi > 0.0 ? log(wi) : -INFINITY;
+}
+
+// -z_pos'z_pos / 2 of one pair; h: the particle's 8 doubles (predicted position, a, log w), x: the trajectory's state
+__device__ __forceinline__ double bs_pos_term(const BsNoise& nz, const double* h, const double x[7]) {
+  const double r0 = x[0] - h[0], r1 = x[1] - h[1], r2 = x[2] - h[2];
+  const double z0 = nz.ip[0] * r0 + nz.ip[1] * r1 + nz.ip[2] * r2;
+  const double z1 = nz.ip[3] * r0 + nz.ip[4] * r1 + nz.ip[5] * r2;
+  const double z2 = nz.ip[6] * r0 + nz.ip[7] * r1 + nz.ip[8] * r2;
+  return -0.5 * (z0 * z0 + z1 * z1 + z2 * z2);
+}
+
+__device__ __forceinline__ double bs_rot_term(const BsNoise& nz, const double* h, const double x[7]) {
+  // e = qLeft(qInv(a)) q~ (tools/qLeft.m:30-35, qInv.m:27-31)
+  const double a0 = h[3], a1 = -h[4], a2 = -h[5], a3 = -h[6];
+  double e0 = a0 * x[3] + (-a1) * x[4] + (-a2) * x[5] + (-a3) * x[6];
+  double e1 = a1 * x[3] + a0 * x[4] + (-a3) * x[5] + a2 * x[6];
+  double e2 = a2 * x[3] + a3 * x[4] + a0 * x[5] + (-a1) * x[6];
+  double e3 = a3 * x[3] + (-a2) * x[4] + a1 * x[5] + a0 * x[6];
+  if (e0 < 0.0) { e0 = -e0; e1 = -e1; e2 = -e2; e3 = -e3; }                       // tools/logq.m:26-28
+  const double nv = sqrt(e1 * e1 + e2 * e2 + e3 * e3);
+  const double f = (nv == 0.0) ? 1.0 : atan2(nv, e0) / nv;
+  const double p0 = f * e1, p1 = f * e2, p2 = f * e3;
+  const double z0 = nz.ir[0] * p0 + nz.ir[1] * p1 + nz.ir[2] * p2;
+  const double z1 = nz.ir[3] * p0 + nz.ir[4] * p1 + nz.ir[5] * p2;
+  const double z2 = nz.ir[6] * p0 + nz.ir[7] * p1 + nz.ir[8] * p2;
+  return -0.5 * (z0 * z0 + z1 * z1 + z2 * z2);
+}
+
+__global__ __launch_bounds__(kBsTile) void bs_pass_kernel(const BsArgs a) {
+  __shared__ double tile[kBsTile * 8];     // [particle][8]
+  const int tid = threadIdx.x;
+  const int j = blockIdx.x * kBsTile + tid;
+  const int jl = min(j, a.M - 1);          // lanes past the end recompute the last trajectory; nothing of theirs is stored
+  const int c = blockIdx.y;
+  const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
+  double x[7];
+#pragma unroll
+  for (int r = 0; r < 7; ++r) x[r] = a.first ? 0.0 : a.xs_next[(size_t)jl * 7 + r];
+  double m = -INFINITY, s = 0.0;
+  for (int base = i0; base < i1; base += kBsTile) {
+    const int cnt = min(kBsTile, i1 - base);
+    __syncthreads();
+    if (tid < cnt) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) tile[tid * 8 + r] = a.Xhat[(size_t)r * a.N + base + tid];
+    }
+    __syncthreads();
+    for (int k = 0; k < cnt; ++k) {
+      const double* h = tile + k * 8;
+      double l = h[7];
+      if (!a.first) {
+        l += bs_pos_term(a.nz, h, x);
+        if (l < m - kBsSkip) continue;
+        l += bs_rot_term(a.nz, h, x);
+      }
+      if (l == -INFINITY) continue;
+      const double d = l - m;
+      const double ex = exp(-fabs(d));
+      if (d > 0.0) { s = s * ex + 1.0; m = l; }
+      else s += ex;
+    }
+  }
+  if (j < a.M) {
+    a.part_m[(size_t)c * a.M + j] = m;
+    a.part_s[(size_t)c * a.M + j] = s;
+  }
+}
+
+__global__ void bs_locate_kernel(const BsArgs a) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.M) return;
+  double x[7];
+#pragma unroll
+  for (int r = 0; r < 7; ++r) x[r] = a.first ? 0.0 : a.xs_next[(size_t)j * 7 + r];
+  double Mx = -INFINITY;
+  for (int c = 0; c < a.nchunks; ++c) Mx = fmax(Mx, a.part_m[(size_t)c * a.M + j]);
+  int idx = -1;
+  if (Mx > -INFINITY) {
+    double total = 0.0;
+    for (int c = 0; c < a.nchunks; ++c) {
+      const double sc = a.part_s[(size_t)c * a.M + j];
+      if (sc > 0.0) total += sc * exp(a.part_m[(size_t)c * a.M + j] - Mx);
+    }
+    const double target = a.u[j] * total;
+    double acc = 0.0;
+    int c0 = 0;
+    for (; c0 < a.nchunks; ++c0) {
+      const double sc = a.part_s[(size_t)c0 * a.M + j];
+      if (!(sc > 0.0)) continue;
+      const double nxt = acc + sc * exp(a.part_m[(size_t)c0 * a.M + j] - Mx);
+      if (nxt >= target) break;
+      acc = nxt;
+    }
+    int last_nz = -1;
+    for (int c = c0; c < a.nchunks && idx < 0; ++c) {
+      if (!(a.part_s[(size_t)c * a.M + j] > 0.0)) continue;
+      const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
+      for (int i = i0; i < i1; ++i) {
+        double h[8];
+        h[7] = a.Xhat[(size_t)7 * a.N + i];
+        if (h[7] == -INFINITY) continue;
+        double l = h[7];
+        if (!a.first) {
+#pragma unroll
+          for (int r = 0; r < 7; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
+          l += bs_pos_term(a.nz, h, x);
+          if (l < Mx - kBsSkip) continue;
+          l += bs_rot_term(a.nz, h, x);
+        }
+        const double term = exp(l - Mx);
+        if (!(term > 0.0)) continue;
+        last_nz = i;
+        acc += term;
+        if (acc >= target) { idx = i; break; }
+      }
+    }
+    if (idx < 0) idx = last_nz;
+    if (idx < 0 || !(acc >= target)) atomicAdd(a.clamped, 1);
+  } else {
+    atomicAdd(a.clamped, 1);
+  }
+  if (idx < 0) {                                   // no non-zero term at all: the last particle with a non-zero weight
+    for (int i = a.N - 1; i >= 0 && idx < 0; --i)
+      if (a.Xhat[(size_t)7 * a.N + i] > -INFINITY) idx = i;
+    if (idx < 0) idx = a.N - 1;
+  }
+  a.index[j] = idx;
+  if (a.xs) {
+#pragma unroll
+    for (int r = 0; r < 7; ++r) a.xs[(size_t)j * 7 + r] = a.X[(size_t)r * a.N + idx];
+  }
+}
+
+// mean over the M trajectories of xs [M][7] -> out [7]: one workgroup, strided partial sums, then a fixed tree
+__global__ __launch_bounds__(256) void bs_mean_kernel(int M, const double* __restrict__ xs, double* __restrict__ out) {
+  __shared__ double red[7][256];
+  const int tid = threadIdx.x;
+  double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = tid; j < M; j += 256)
+#pragma unroll
+    for (int r = 0; r < 7; ++r) acc[r] += xs[(size_t)j * 7 + r];
+#pragma unroll
+  for (int r = 0; r < 7; ++r) red[r][tid] = acc[r];
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off)
+#pragma unroll
+      for (int r = 0; r < 7; ++r) red[r][tid] += red[r][tid + off];
+    __syncthreads();
+  }
+  if (tid < 7) out[tid] = red[tid][0] / (double)M;
+}
+
+// logp of every pair, without log w: out [N x M] column-major (the probe's second output)
+__global__ void bs_logp_kernel(int N, int M, const double* __restrict__ Xhat, const double* __restrict__ xs_next, BsNoise nz,
+                               double* __restrict__ out) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (size_t)N * M) return;
+  const int i = (int)(q % N), j = (int)(q / N);
+  double h[8], x[7];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) h[r] = Xhat[(size_t)r * N + i];
+#pragma unroll
+  for (int r = 0; r < 7; ++r) x[r] = xs_next[(size_t)j * 7 + r];
+  out[q] = bs_pos_term(nz, h, x) + bs_rot_term(nz, h, x);
+}
+
+__global__ void bs_philox_kernel(unsigned long long seed, int T, int M, double* __restrict__ u) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (size_t)T * M) return;
+  double u0, u1;
+  philox_uniform2(seed, (uint32_t)(q % M), (uint32_t)(q / M), kBsPhiloxLane, 0u, u0, u1);
+  u[q] = u0;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+static bool bs_inv3(const double* S, int ld, double* inv) {   // S column-major with leading dimension ld -> inv row-major
+  const double a = S[0], b = S[ld], c = S[2 * ld], d = S[1], e = S[1 + ld], f = S[1 + 2 * ld], g = S[2], h = S[2 + ld], i = S[2 + 2 * ld];
+  const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
+  double scale = 0.0;
+  for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) scale = std::max(scale, std::fabs(S[r + ld * k]));
+  if (!(std::fabs(det) > 1e-12 * scale * scale * scale) || !std::isfinite(det)) return false;
+  const double adj[9] = {e * i - f * h, c * h - b * i, b * f - c * e, f * g - d * i, a * i - c * g, c * d - a * f,
+                         d * h - e * g, b * g - a * h, a * e - b * d};
+  for (int k = 0; k < 9; ++k) inv[k] = adj[k] / det;
+  return true;
+}
+
+// S: 6 x 6 column-major element-wise sqrt(dt Q) of the diagonal blocks (loc_noise_pages)
+static int bs_noise(const double* S, BsNoise& nz) {
+  if (!bs_inv3(S, 6, nz.ip) || !bs_inv3(S + 3 + 6 * 3, 6, nz.ir)) {
+    set_error("a diagonal block of the element-wise sqrt(dt Q) is singular: the transition density of dynModel does not exist");
+    return RBPF_ERR_INVALID_ARG;
+  }
+  return RBPF_OK;
+}
+
+static size_t bs_bytes(size_t N, size_t T, size_t M, bool full_xs) {
+  const size_t nch = (N + bs_chunk_size((int)N, (int)M) - 1) / bs_chunk_size((int)N, (int)M);
+  return (8 * N + 2 * nch * M + T * M + (full_xs ? T : 2) * 7 * M + 7 * T) * sizeof(double) + T * M * sizeof(int);
+}
+
+// prologue + all-pairs pass + locate of one step, in stream order
+static hipError_t bs_launch_step(const BsArgs& a, const double* xn, size_t cs, size_t ps, const double* w, const double* odo,
+                                 double* Xhat, hipStream_t s) {
+  hipLaunchKernelGGL(bs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, xn, cs, ps, w, odo, Xhat);
+  hipLaunchKernelGGL(bs_pass_kernel, dim3((a.M + kBsTile - 1) / kBsTile, a.nchunks), dim3(kBsTile), 0, s, a);
+  hipLaunchKernelGGL(bs_locate_kernel, dim3((a.M + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace rbpf
+
+using namespace rbpf;
+
+extern "C" {
+
+int rbpf_loc_backward_workspace_bytes(int32_t N_P, int32_t N_T, int32_t n_traj, size_t* bytes) {
+  if (!bytes) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P < 1 || N_T < 1 || n_traj < 1) { set_error("N_P, N_T and n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P > kMaxParticles) { set_error("N_P above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  *bytes = bs_bytes((size_t)N_P, (size_t)N_T, (size_t)n_traj, true);
+  return RBPF_OK;
+}
+
+int rbpf_loc_history(rbpf_ctx* c, double* xn_fwd) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (!xn_fwd) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (!c->opt.keep_history) { set_error("rbpf_loc_history needs rbpf_options.keep_history"); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  const int N = c->N, Td = c->t;
+  if (Td == 0) return RBPF_OK;
+  DevicePool tmp;
+  double* d_tmp = nullptr;
+  RB_TRY(tmp.alloc(&d_tmp, (size_t)7 * N * Td));
+  for (int t = 0; t < Td; ++t) HIPCHK(launch_transpose_soa(N, 7, c->X + (size_t)t * 7 * N, d_tmp + (size_t)t * 7 * N, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(xn_fwd, d_tmp, (size_t)7 * N * Td * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+int rbpf_loc_backward_simulate(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, double* xs_traj, int32_t* index,
+                               double* traj_smooth_mean) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (n_traj < 1) { set_error("n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (!c->opt.keep_history || !c->opt.trace) {
+    set_error("rbpf_loc_backward_simulate reads the stored particles and weights: create the context with keep_history = 1 and trace = 1");
+    return RBPF_ERR_STATE;
+  }
+  if (c->t < c->T) { set_error("rbpf_loc_backward_simulate: " + std::to_string(c->t) + " of " + std::to_string(c->T) + " steps are done"); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  LocState* L = c->loc;
+  const int N = c->N, T = c->T, M = n_traj;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  {
+    std::vector<double> lse((size_t)T);
+    HIPCHK(hipMemcpy(lse.data(), L->d_lse, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
+    for (int t = 0; t < T; ++t)
+      if (!(lse[t] > std::log(1e-12))) {
+        set_error("the forward run recorded a degenerate step (t = " + std::to_string(t) + "): its weights are no filtering distribution");
+        return RBPF_ERR_STATE;
+      }
+  }
+  std::vector<BsNoise> nz((size_t)L->s_pages);
+  {
+    std::vector<double> S((size_t)L->s_pages * 36);
+    HIPCHK(hipMemcpy(S.data(), L->d_S, S.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < (T > 1 ? L->s_pages : 0); ++p) RB_TRY(bs_noise(S.data() + (size_t)p * 36, nz[p]));
+  }
+  const int C = bs_chunk_size(N, M), nch = (N + C - 1) / C;
+  const bool full_xs = xs_traj != nullptr;
+  // workspace from the context's pool, handed back on every way out
+  struct Lease {
+    DevicePool& pool; std::vector<void*> ptrs;
+    ~Lease() { for (void* p : ptrs) pool.release(p); }
+  } lease{c->pool, {}};
+  double *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_u = nullptr, *d_xs = nullptr, *d_mean = nullptr;
+  int* d_idx = nullptr;
+  auto take = [&](auto** p, size_t count) -> int { const int s = c->pool.alloc(p, count); if (s == RBPF_OK) lease.ptrs.push_back(*p); return s; };
+  RB_TRY(take(&d_Xhat, (size_t)8 * N));
+  RB_TRY(take(&d_pm, (size_t)nch * M));
+  RB_TRY(take(&d_ps, (size_t)nch * M));
+  RB_TRY(take(&d_u, (size_t)T * M));
+  RB_TRY(take(&d_xs, (size_t)(full_xs ? T : 2) * 7 * M));
+  RB_TRY(take(&d_mean, (size_t)7 * T));
+  RB_TRY(take(&d_idx, (size_t)T * M));
+  if (u) {
+    HIPCHK(hipMemcpyAsync(d_u, u, (size_t)T * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  } else {
+    const size_t cnt = (size_t)T * M;
+    hipLaunchKernelGGL(bs_philox_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, (unsigned long long)seed, T, M, d_u);
+    HIPCHK(hipGetLastError());
+  }
+  auto slab = [&](int t) { return d_xs + (size_t)(full_xs ? t : (t & 1)) * 7 * M; };
+  for (int t = T - 1; t >= 0; --t) {
+    BsArgs a;
+    a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.first = (t == T - 1);
+    a.Xhat = d_Xhat; a.X = c->X + (size_t)t * 7 * N;
+    a.xs_next = a.first ? nullptr : slab(t + 1);
+    a.u = d_u + (size_t)t * M; a.part_m = d_pm; a.part_s = d_ps;
+    a.index = d_idx + (size_t)t * M; a.xs = slab(t); a.clamped = c->d_flags + 1;
+    if (!a.first) a.nz = nz[L->s_pages > 1 ? t : 0];
+    else std::memset(&a.nz, 0, sizeof(a.nz));
+    const double* odo = c->d_odo + (size_t)(a.first ? 0 : t) * 7;          // the draw of step T-1 reads log w only
+    HIPCHK(bs_launch_step(a, a.X, (size_t)N, 1, c->w + (size_t)t * N, odo, d_Xhat, c->stream));
+    if (traj_smooth_mean) {
+      hipLaunchKernelGGL(bs_mean_kernel, dim3(1), dim3(256), 0, c->stream, M, slab(t), d_mean + (size_t)t * 7);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  RB_TRY(ctx_check_flags(c));
+  if (xs_traj) HIPCHK(hipMemcpy(xs_traj, d_xs, (size_t)7 * M * T * sizeof(double), hipMemcpyDeviceToHost));
+  if (index) HIPCHK(hipMemcpy(index, d_idx, (size_t)M * T * sizeof(int), hipMemcpyDeviceToHost));
+  if (traj_smooth_mean) HIPCHK(hipMemcpy(traj_smooth_mean, d_mean, (size_t)7 * T * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+int rbpf_loc_backward_step(int32_t N, int32_t M, const double* xn, const double* w, const double* xs_next, const double* odo, double dt,
+                           const double* Q, const double* u, int32_t* index, double* logp, int32_t reps, double* ms) {
+  if (!xn || !w || !xs_next || !odo || !Q || !u || !index) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles) { set_error("N above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  double S[36];
+  for (int q = 0; q < 36; ++q) S[q] = 0.0;
+  for (int b = 0; b < 2; ++b)
+    for (int cc = 0; cc < 3; ++cc)
+      for (int r = 0; r < 3; ++r) {
+        const int q = (3 * b + r) + 6 * (3 * b + cc);
+        const double v = dt * Q[q];
+        if (!(v >= 0.0)) { set_error("dt * Q has a negative entry in a diagonal block: the element-wise sqrt of dynModel would be complex"); return RBPF_ERR_INVALID_ARG; }
+        S[q] = std::sqrt(v);
+      }
+  BsArgs a;
+  RB_TRY(bs_noise(S, a.nz));
+  if (!have_device()) { set_error("no HIP device: the backward pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  const int C = bs_chunk_size(N, M), nch = (N + C - 1) / C;
+  DevicePool tmp;
+  double *d_xn = nullptr, *d_w = nullptr, *d_xs = nullptr, *d_odo = nullptr, *d_u = nullptr, *d_Xhat = nullptr, *d_pm = nullptr,
+         *d_ps = nullptr, *d_lp = nullptr;
+  int *d_idx = nullptr, *d_clamped = nullptr;
+  RB_TRY(tmp.upload(&d_xn, xn, (size_t)7 * N));
+  RB_TRY(tmp.upload(&d_w, w, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xs_next, (size_t)7 * M));
+  RB_TRY(tmp.upload(&d_odo, odo, (size_t)7));
+  RB_TRY(tmp.upload(&d_u, u, (size_t)M));
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)8 * N));
+  RB_TRY(tmp.alloc(&d_pm, (size_t)nch * M));
+  RB_TRY(tmp.alloc(&d_ps, (size_t)nch * M));
+  RB_TRY(tmp.alloc(&d_idx, (size_t)M));
+  RB_TRY(tmp.alloc(&d_clamped, (size_t)1));
+  HIPCHK(hipMemset(d_clamped, 0, sizeof(int)));
+  if (logp) RB_TRY(tmp.alloc(&d_lp, (size_t)N * M));
+  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.first = 0;
+  a.Xhat = d_Xhat; a.X = nullptr; a.xs_next = d_xs; a.u = d_u; a.part_m = d_pm; a.part_s = d_ps; a.index = d_idx; a.xs = nullptr;
+  a.clamped = d_clamped;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+  auto run = [&]() -> int {                       // (the events are destroyed whichever way it returns)
+    const int R = std::max(reps, 1);
+    for (int r = 0; r < R; ++r) {
+      hipEvent_t e0, e1;
+      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+      ev.emplace_back(e0, e1);
+      HIPCHK(hipEventRecord(e0, 0));
+      HIPCHK(bs_launch_step(a, d_xn, 1, 7, d_w, d_odo, d_Xhat, 0));
+      HIPCHK(hipEventRecord(e1, 0));
+    }
+    if (logp) {
+      const size_t cnt = (size_t)N * M;
+      hipLaunchKernelGGL(bs_logp_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, 0, N, M, d_Xhat, d_xs, a.nz, d_lp);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipDeviceSynchronize());
+    if (ms) {
+      std::vector<float> tt;
+      for (auto& p : ev) { float v = 0.f; HIPCHK(hipEventElapsedTime(&v, p.first, p.second)); tt.push_back(v); }
+      std::sort(tt.begin(), tt.end());
+      *ms = tt[tt.size() / 2];
+    }
+    HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+    if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
+    return RBPF_OK;
+  };
+  const int s = run();
+  for (auto& p : ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
+  return s;
+}
+
+}  // extern "C"

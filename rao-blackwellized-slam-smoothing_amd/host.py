@@ -514,12 +514,28 @@ class PhiloxRNG:
             Ufin[k] = uf.value
         return ReplayRNG(U, Z, Ufin)
 
+    def backward_uniforms(self, n_traj, N_T):
+        """The uniforms u [N_T x n_traj] rbpf_loc_backward_simulate draws from this seed: Philox4x32-10 on the counters
+        (slot = j, step = t, lane = 0x42530000, iter = 0), first uniform (53 bits).  Computed on the host, bit for bit."""
+        M32 = np.uint64(0xFFFFFFFF)
+        t, j = np.meshgrid(np.arange(int(N_T), dtype=np.uint64), np.arange(int(n_traj), dtype=np.uint64), indexing="ij")
+        c = [j, t, np.full_like(j, 0x42530000), np.zeros_like(j)]
+        k0, k1 = np.uint64(int(self.seed) & 0xFFFFFFFF), np.uint64((int(self.seed) >> 32) & 0xFFFFFFFF)
+        for _ in range(10):
+            p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+            c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & M32]
+            k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
+        a = ((c[0] << np.uint64(32)) | c[1]) >> np.uint64(11)
+        return (a.astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+
 
 class ReplayRNG:
     """Pre-drawn random numbers in the reference's call order.
-    U [n_iter, N_T-1, N_P], Z [n_iter, N_T-1, N_P, nw], Ufin [n_iter] (see include/rbpf.h)."""
+    U [n_iter, N_T-1, N_P], Z [n_iter, N_T-1, N_P, nw], Ufin [n_iter] (see include/rbpf.h); Uback [N_T, N_S]: the backward
+    uniforms of particleSmootherLocalization (row t = step t)."""
 
-    def __init__(self, U, Z, Ufin=None):
+    def __init__(self, U, Z, Ufin=None, Uback=None):
+        self.Uback = None if Uback is None else np.ascontiguousarray(np.asarray(Uback, dtype=np.float64))   # particleSmootherLocalization: u [N_T x N_S]
         self.U = np.ascontiguousarray(np.asarray(U, dtype=np.float64))
         self.Z = np.ascontiguousarray(np.asarray(Z, dtype=np.float64))
         if self.U.ndim == 2:
@@ -1437,6 +1453,44 @@ class LocalizationSession:
         b["first_degenerate_step"] = int(o.first_degenerate_step)
         return b
 
+    def history(self):
+        """rbpf_loc_history: the forward particles as propagated, NOT traced back, [7 x N_P x T_done] (needs keep_history)."""
+        X = np.empty((7, self.prob.N_P, self.tell()), order="F")
+        check(self.lib.rbpf_loc_history(self.ctx, _dp(X)))
+        return X
+
+    def backward_simulate(self, n_traj, rng=None, want=("xs_traj", "index", "traj_smooth_mean")):
+        """rbpf_loc_backward_simulate: n_traj trajectories drawn backwards through the stored particles (keep_history and trace,
+        every step done).  rng: None / PhiloxRNG(seed): the device generator (PhiloxRNG.backward_uniforms(n_traj, N_T) are its
+        draws); an array u [N_T x n_traj] of uniforms in (0, 1): replay.  Returns a dict of the arrays named in `want`:
+        xs_traj [7 x n_traj x N_T], index [n_traj x N_T] (0-based), traj_smooth_mean [7 x N_T]."""
+        M, T = int(n_traj), self.prob.N_T
+        seed, u = 0, None
+        if rng is None:
+            rng = PhiloxRNG(1)
+        if isinstance(rng, PhiloxRNG):
+            seed = int(rng.seed)
+        else:
+            u = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
+            if M >= 1 and u.shape != (T, M):
+                raise ValueError(f"u must be [{T} x {M}] (row t = step t)")
+        unknown = set(want) - {"xs_traj", "index", "traj_smooth_mean"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        Mb = max(M, 0)
+        b = {}
+        if "xs_traj" in want:
+            b["xs_traj"] = np.empty((7, Mb, T), order="F")
+        if "index" in want:
+            b["index"] = np.zeros((Mb, T), dtype=np.int32, order="F")
+        if "traj_smooth_mean" in want:
+            b["traj_smooth_mean"] = np.empty((7, T), order="F")
+        check(self.lib.rbpf_loc_backward_simulate(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed),
+                                                  _dp(b["xs_traj"]) if "xs_traj" in b else None,
+                                                  _ip(b["index"]) if "index" in b else None,
+                                                  _dp(b["traj_smooth_mean"]) if "traj_smooth_mean" in b else None))
+        return b
+
     def close(self):
         if self.ctx:
             self.lib.rbpf_destroy(self.ctx)
@@ -1447,3 +1501,58 @@ class LocalizationSession:
 
     def __exit__(self, *a):
         self.close()
+
+
+def loc_backward_workspace_bytes(N_P, N_T, n_traj):
+    """rbpf_loc_backward_workspace_bytes (no device access)."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_backward_workspace_bytes(int(N_P), int(N_T), int(n_traj), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def loc_backward_step(xn, w, xs_next, odo, dt, Q, u, want_logp=False, reps=1):
+    """rbpf_loc_backward_step, the kernel-level probe: one backward step on the caller's arrays.  xn [7 x N], w [N],
+    xs_next [7 x M], odo [7], Q [6 x 6], u [M] -> (index [M], logp [N x M] or None, median ms of one step)."""
+    lib = load_library()
+    xn = np.asfortranarray(np.asarray(xn, dtype=np.float64).reshape(7, -1))
+    xs_next = np.asfortranarray(np.asarray(xs_next, dtype=np.float64).reshape(7, -1))
+    N, M = xn.shape[1], xs_next.shape[1]
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).ravel())
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).ravel())
+    odo = np.ascontiguousarray(np.asarray(odo, dtype=np.float64).ravel())
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(6, 6))
+    if w.size != N or u.size != M or odo.size != 7:
+        raise ValueError("w must be [N], u [M] and odo [7]")
+    index = np.zeros(M, dtype=np.int32)
+    logp = np.empty((N, M), order="F") if want_logp else None
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_backward_step(N, M, _dp(xn), _dp(w), _dp(xs_next), _dp(odo), float(dt), _dp(Q), _dp(u), _ip(index),
+                                     _dp(logp) if want_logp else None, int(reps), C.byref(ms)))
+    return index, logp, ms.value
+
+
+def particleSmootherLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, N_S, dt, *, rng=None, extras=False):
+    """Forward filter, backward simulation for localisation in a fixed map: particleFilterLocalization, then N_S trajectories drawn
+    backwards through its particles -> (xs_traj [7 x N_S x N_T], traj_smooth_mean [7 x N_T][, extras]).  dynModel / measModel are
+    the handles of a DenseMagMap, R is accepted and not used, as there.  rng: PhiloxRNG (one seed keys the filter's and the
+    backward draws, on disjoint counters) or ReplayRNG(U, Z, Uback=u) with the backward uniforms u [N_T x N_S].
+    extras: the filter's outputs (traj_max, traj_mean, first_degenerate_step, ...) and the drawn `index` [N_S x N_T]."""
+    import warnings
+    mp = _recognise_map(dynModel, measModel)
+    if isinstance(rng, ReplayRNG):
+        if rng.Uback is None:
+            raise ValueError("a ReplayRNG needs Uback [N_T x N_S] to replay the backward draws")
+        back = rng.Uback
+    else:
+        back = rng
+    with LocalizationSession(mp, odometry, y, x0_nonLin, Q, N_P, dt, rng=rng, keep_history=True, trace=True) as s:
+        s.advance(s.prob.N_T)
+        fwd = s.finish(extras=extras)
+        if fwd["first_degenerate_step"] >= 0:
+            warnings.warn(f"Weights filter close to zero at t={fwd['first_degenerate_step'] + 1} !!!", RuntimeWarning, stacklevel=2)
+        out = s.backward_simulate(N_S, rng=back)
+    if extras:
+        fwd["index"] = out["index"]
+        return out["xs_traj"], out["traj_smooth_mean"], fwd
+    return out["xs_traj"], out["traj_smooth_mean"]
