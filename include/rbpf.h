@@ -351,6 +351,10 @@ int rbpf_filter_schedule(const rbpf_ctx* ctx, int32_t* banks, int32_t* shared_fl
  * two banks, fp64 tiles at eight tile rows, 2-4 pending sets); the other shared flushes took two launches.  Filter and
  * sharded-filter contexts.                                                                          */
 int rbpf_filter_one_launch_flushes(const rbpf_ctx* ctx, int64_t* n);
+/* Resampling steps since the context was created whose ancestors were recomputed with the strict left-to-right cumsum
+ * (tools/sample.m:30): the search runs on a parallel prefix sum and certifies every draw by a rounding bound; one draw inside
+ * the bound of a bin edge sends the whole step through the strict sum.  Waits for the context's stream, changes nothing.   */
+int rbpf_filter_resample_fallbacks(rbpf_ctx* ctx, int64_t* n);
 /* Generic model family (RBPF_MODEL_GENERIC_DENSE), one time step at a time:
  *   t = 0:  rbpf_filter_step_external(ctx, xn0, measModel(xn0))
  *   t > 0:  rbpf_filter_ancestors(ctx, ai, xn_prev); xn(:,i) = dynModel(xn_prev(:,ai(i)+1), ...); 
@@ -697,8 +701,9 @@ int rbpf_loc_dyn_model(int32_t n_p, const double* xn, const double* odo, double 
  *     z = blkdiag(S_pos, S_rot) \ r  (S = sqrt(dt Q) element-wise on the diagonal blocks),  logp = -z'z / 2.
  * A singular S block is RBPF_ERR_INVALID_ARG.  w(i) = 0 is never selected.  A draw past the last cdf edge is clamped to the
  * last particle with a non-zero term and counted with the filter's clamped draws.
- * u [N_T x n_traj], row t = step t (u[t * n_traj + j]), uniforms in (0, 1); NULL: Philox4x32-10 keyed by `seed` on the counters
- * (slot = j, step = t, lane = 0x42530000, iter = 0), first uniform -- disjoint from the filter's lanes 0 .. 3.
+ * u [N_T x n_traj], row t = step t (u[t * n_traj + j]), uniforms in (0, 1]; NULL: Philox4x32-10 keyed by `seed` on the counters
+ * (slot = j, step = t, lane = 0x42530000, iter = 0), first uniform -- disjoint from the filter's lanes 0 .. 4.  The generator's
+ * uniforms are (a + 0.5) 2^-53 of a 53-bit a, rounded as doubles: they lie in (0, 1] (1.0 when all 53 bits are set).
  * Outputs (NULL pointers are skipped): xs_traj [7 x n_traj x N_T], index [n_traj x N_T] 0-based, traj_smooth_mean [7 x N_T] (plain
  * means over the trajectories of all 7 rows, as particleFilterLocalization.m:123).  The workspace comes from the context's pool
  * and is returned before the call returns.  RBPF_ERR_STATE: steps missing, no keep_history / trace, or a degenerate forward step;

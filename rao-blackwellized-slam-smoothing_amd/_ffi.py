@@ -146,7 +146,7 @@ EXPORTS = [
     "rbpf_abi_version", "rbpf_abi_sizeof", "rbpf_status_string", "rbpf_last_error", "rbpf_device_count", "rbpf_device_bytes_live",
     "rbpf_particle_filter", "rbpf_particle_smoother",
     "rbpf_filter_create", "rbpf_filter_workspace_bytes", "rbpf_filter_advance", "rbpf_filter_reset", "rbpf_sync",
-    "rbpf_filter_finish", "rbpf_filter_tell", "rbpf_filter_schedule", "rbpf_filter_one_launch_flushes", "rbpf_plan_refresh", "rbpf_chol_refresh_resolve", "rbpf_shard_smoother_refresh_reserve", "rbpf_shard_xn_traj", "rbpf_filter_ancestors", "rbpf_filter_step_external", "rbpf_filter_external_layout", "rbpf_filter_ancestors_device",
+    "rbpf_filter_finish", "rbpf_filter_tell", "rbpf_filter_schedule", "rbpf_filter_one_launch_flushes", "rbpf_filter_resample_fallbacks", "rbpf_plan_refresh", "rbpf_chol_refresh_resolve", "rbpf_shard_smoother_refresh_reserve", "rbpf_shard_xn_traj", "rbpf_filter_ancestors", "rbpf_filter_step_external", "rbpf_filter_external_layout", "rbpf_filter_ancestors_device",
     "rbpf_filter_step_device", "rbpf_filter_set_device_callbacks", "rbpf_timing_enable", "rbpf_timing_read", "rbpf_destroy",
     "rbpf_philox_fill", "rbpf_meas_model", "rbpf_dyn_model", "rbpf_dyn_res_norm", "rbpf_sample",
     "rbpf_jacobian_phi3d", "rbpf_chol_weights", "rbpf_chol_sweep_probe", "rbpf_quat_helpers", "rbpf_probe_wave_reduce",
@@ -235,6 +235,7 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_filter_tell.argtypes = [C.c_void_p, c_int32_p]
     lib.rbpf_filter_schedule.argtypes = [C.c_void_p, c_int32_p, c_int32_p]
     lib.rbpf_filter_one_launch_flushes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.rbpf_filter_resample_fallbacks.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.rbpf_filter_ancestors.argtypes = [C.c_void_p, c_int32_p, c_double_p]
     lib.rbpf_filter_step_external.argtypes = [C.c_void_p, c_double_p, c_double_p]
     lib.rbpf_filter_external_layout.argtypes = [C.c_void_p, c_int32_p]

@@ -1176,6 +1176,17 @@ int rbpf_filter_one_launch_flushes(const rbpf_ctx* c, int64_t* n) {
   return RBPF_OK;
 }
 
+int rbpf_filter_resample_fallbacks(rbpf_ctx* c, int64_t* n) {
+  if (!c || !n) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (!c->d_flags) { set_error("context without a resampling search"); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  int v = 0;
+  HIPCHK(hipMemcpyAsync(&v, c->d_flags + 5, sizeof(int), hipMemcpyDeviceToHost, c->stream));   // [4] flagged draws, [5] strict recomputations
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *n = v;
+  return RBPF_OK;
+}
+
 int rbpf_timing_enable(rbpf_ctx* c, int32_t on) {
   if (!c) { set_error("ctx is NULL"); return RBPF_ERR_INVALID_ARG; }
   c->timing_on = on != 0;

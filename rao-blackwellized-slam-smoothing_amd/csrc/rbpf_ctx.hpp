@@ -122,7 +122,7 @@ struct rbpf_ctx {
   double *logw = nullptr, *w = nullptr, *wc = nullptr;
   double *traj_max = nullptr, *traj_mean = nullptr;
   double* d_scal = nullptr;
-  int* d_flags = nullptr;   // [0] status bits, [1] clamped draws, [2] iw_max, [3..] scratch
+  int* d_flags = nullptr;   // [0] status bits, [1] clamped draws, [2] iw_max, [3] scratch, [4] flagged draws of the search, [5] strict recomputations (rbpf_filter_resample_fallbacks)
   int t = 0;
   int overflow_draws = 0;
   bool timing_on = false;

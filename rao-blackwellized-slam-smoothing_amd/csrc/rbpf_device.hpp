@@ -27,7 +27,8 @@ __host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
   }
 }
 
-// two uniforms in (0,1) with 53 random bits each
+// two uniforms in (0,1] with 53 random bits each: (a + 0.5) 2^-53 is exact below a = 2^52; from there on a + 0.5 rounds to an
+// integer (ties to even), so a = 2^53 - 1 gives exactly 1.0 and 0 is never reached
 __host__ __device__ inline void philox_uniform2(unsigned long long seed, uint32_t slot, uint32_t step,
                                                 uint32_t lane, uint32_t iter, double& u0, double& u1) {
   uint32_t c[4] = {slot, step, lane, iter};

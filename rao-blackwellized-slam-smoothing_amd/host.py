@@ -834,6 +834,9 @@ def particleFilter(dynModel, measModel, odometry, y, x0_nonLin, x0_lin, P0_lin, 
             _raise_callback_error(model, exc)
         o, b = alloc_out(T, full=True)
         check(lib.rbpf_filter_finish(ctx, C.byref(o)))
+        n_fallbacks = C.c_int64(0)
+        if extras:
+            check(lib.rbpf_filter_resample_fallbacks(ctx, C.byref(n_fallbacks)))
     finally:
         lib.rbpf_destroy(ctx)
     xn_traj = b.get("xn_traj")
@@ -841,7 +844,8 @@ def particleFilter(dynModel, measModel, odometry, y, x0_nonLin, x0_lin, P0_lin, 
            b["traj_sample_iwmax"], xn_traj)
     if extras:
         ex = dict(logw=b["trace_logw"].T.copy(), w=b["trace_w"].T.copy(), ai=b["trace_ai"].T.copy(),
-                  xn=b["final_xn"], xl=b["final_xl"], P=b["final_P"], iw_max=int(b["iw_max"][0]))
+                  xn=b["final_xn"], xl=b["final_xl"], P=b["final_P"], iw_max=int(b["iw_max"][0]),
+                  resample_fallbacks=int(n_fallbacks.value))
         return res + (ex,)
     return res
 
@@ -1127,6 +1131,12 @@ class FilterSession:
         """Shared flush steps so far that ran as one launch (rbpf_filter_one_launch_flushes)."""
         n = C.c_int64(0)
         check(self.lib.rbpf_filter_one_launch_flushes(self.ctx, C.byref(n)))
+        return n.value
+
+    def resample_fallbacks(self):
+        """Resampling steps so far that were recomputed with the strict cumsum (rbpf_filter_resample_fallbacks)."""
+        n = C.c_int64(0)
+        check(self.lib.rbpf_filter_resample_fallbacks(self.ctx, C.byref(n)))
         return n.value
 
     def timing(self, enable=None, reset=False):
@@ -1462,7 +1472,7 @@ class LocalizationSession:
     def backward_simulate(self, n_traj, rng=None, want=("xs_traj", "index", "traj_smooth_mean")):
         """rbpf_loc_backward_simulate: n_traj trajectories drawn backwards through the stored particles (keep_history and trace,
         every step done).  rng: None / PhiloxRNG(seed): the device generator (PhiloxRNG.backward_uniforms(n_traj, N_T) are its
-        draws); an array u [N_T x n_traj] of uniforms in (0, 1): replay.  Returns a dict of the arrays named in `want`:
+        draws); an array u [N_T x n_traj] of uniforms in (0, 1]: replay.  Returns a dict of the arrays named in `want`:
         xs_traj [7 x n_traj x N_T], index [n_traj x N_T] (0-based), traj_smooth_mean [7 x N_T]."""
         M, T = int(n_traj), self.prob.N_T
         seed, u = 0, None
