@@ -19,6 +19,15 @@
 
 namespace rbpf {
 
+enum class SmootherForm { Sparse, Cov, Info };   // covariance form with sparse features / with dense features, information form
+
+// sparse-visual family: the observed (time, output) pairs, time-major -- the future observations of step t are the suffix from off[t]
+struct SparsePairs {
+  std::vector<int> off;                    // [T + 1]
+  int *d_t = nullptr, *d_j = nullptr;      // the pairs' times and outputs
+  int future(int t) const { return off.back() - off[t]; }
+};
+
 struct SmootherState {
   DevicePool pool;              // owns every device buffer below
   double* d_xnk = nullptr;      // [T][nN] reference trajectory of this iteration (row per step)
@@ -63,10 +72,15 @@ struct SmootherState {
                                 // from Imat0 along the whole ancestral path, chunk by chunk -- the Imat "bank" is one chunk of l_chunk matrices
   int seg_len = 0;              // ... in segments of this many generations (d_G / d_Xp hold l_chunk x seg_len rows)
   int* d_marks = nullptr;       // [ceil(T / seg_len)][N] slot of every particle's ancestor at the top generation of each segment
-  // sharded information-form smoother
   double* d_Rinv = nullptr;     // [d*d]
-  std::vector<double> h_ivec0;  // [ldx]
+  std::vector<double> h_ivec0;  // [ldx] the initial values on the host
   double hld0 = 0.0;
+  // single-device smoother (smoother_run)
+  SmootherForm form = SmootherForm::Info;
+  double* d_R = nullptr;        // [d*d] (the covariance form reads it)
+  double* d_edyn = nullptr;     // [N][nw] generic family with a dynResNorm handle: its values
+  std::vector<double> h_xnk, h_edyn;   // host copies of d_xnk (the callbacks read it) and d_edyn
+  SparsePairs pairs;
   // sharded smoother with carried factors: where every logical slot's particle lives now / lived when the Imat bank was
   // materialised, and the base matrices fetched from (packed for) other ranks at a refresh
   int* d_owner_now = nullptr;   // [Nglob] rank * Nloc + physical slot
@@ -833,11 +847,6 @@ static std::vector<double> imat_host_storage(const std::vector<double>& full, in
   return pk;
 }
 
-// information-form hooks (defined below)
-static int info_begin_iteration(rbpf_ctx* c, const double* ivec0, double hld0, double qf0, double halfLogDetR, const double* d_Rinv);
-static int info_fill_chol_args(rbpf_ctx* c, CholArgs& ca, const double* d_Rinv, const int* anc);
-static int info_step(rbpf_ctx* c, int k, int t, const double* xref, int n_draw, const double* d_Rinv);
-
 // Normalise N ancestor log-probabilities (particleSmoother.m:236-238) and draw ONE index from them into ai[slot]
 // (:241).  Up to 8192 entries: the single-workgroup kernel with the strict left-to-right running sum.  Above: the
 // multi-workgroup pipeline (parallel prefix + certified search + exact fallback), same indices, ~0.15 ms instead of
@@ -861,12 +870,10 @@ static int normalise_draw_one(rbpf_ctx* c, int N, int t, int k, const double* lo
   return RBPF_OK;
 }
 
-// R^-1 and 0.5*log(det(R)) via Cholesky (d <= 8)
-static int invert_R(const std::vector<double>& Rh, int d, std::vector<double>& Rinv, double& halfLogDetR) {
-  halfLogDetR = 0.0;
+// R^-1 via Cholesky (d <= 8)
+static int invert_R(const std::vector<double>& Rh, int d, std::vector<double>& Rinv) {
   std::vector<double> Lr((size_t)d * d, 0.0);
   if (!chol_lower_host(Rh.data(), d, d, Lr.data(), d)) { set_error("R must be positive definite"); return RBPF_ERR_CHOL_FAILED; }
-  for (int j = 0; j < d; ++j) halfLogDetR += std::log(Lr[j + (size_t)d * j]);
   for (int col = 0; col < d; ++col) {             // solve R x = e_col
     std::vector<double> y(d), x(d);
     for (int i = 0; i < d; ++i) { double v = (i == col); for (int k = 0; k < i; ++k) v -= Lr[i + (size_t)d * k] * y[k]; y[i] = v / Lr[i + (size_t)d * i]; }
@@ -901,38 +908,375 @@ static void whitening_factor(const std::vector<double>& Rh, int d, std::vector<d
     }
 }
 
+// =============================================================================================================
+// Pieces of an information-form step.  The single-device driver (smoother_run) and the sharded entry points (rbpf_shard_smoother_*)
+// are both made of these; what differs between them -- where the ancestors, the history and the ancestor log-weights live, and the
+// exchange of base matrices between ranks -- stays with the callers.
+// =============================================================================================================
+// what every ancestor-weight factorisation of a context has in common
+static CholArgs chol_args(rbpf_ctx* c, double* pant_log) {
+  CholArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.d = c->mdl.d; ca.n = c->mdl.n; ca.ldx = c->lay.ldx; ca.pant_log = pant_log; ca.status = c->d_flags;
+  ca.variant = c->opt.chol_variant;
+  return ca;
+}
+
+// the `cnt` factors the 64-column kernel has just left in d_L, those of the particles p0 .. -> sweep layout, in the OTHER factor bank
+static int sweep_bank_from_chol64(rbpf_ctx* c, int cnt, int p0) {
+  SmootherState* s = c->sm;
+  const int n = c->mdl.n;
+  const size_t sd = sweep_factor_doubles(n);
+  HIPCHK(launch_sweep_from_chol64(n, cnt, s->d_L, chol_factor_doubles(n), s->d_Lsw[s->sw_cur ^ 1] + (size_t)p0 * sd, sd, c->stream));
+  return RBPF_OK;
+}
+
 // Refresh of the carried factors, second half: factorise Imat + ImatAddt of the N particles whose information matrices the G'G product
 // has just materialised (bank s->imat_cur) with the 64-column kernel, add logwMeas to pant_log, and store the factors in the sweep
 // layout in the OTHER factor bank (the caller flips sw_cur).  Runs in chunks of s->l_chunk particles over one set of factor
 // workspaces: same launches per particle, 2.2 MB per particle less memory at nLin = 515.
 // chunk_imat != null (refresh-free smoother): the particles first .. first + N - 1 (N <= l_chunk) whose matrices sit in that chunk buffer.
-static int refresh_factorise(rbpf_ctx* c, const double* d_Rinv, double* pant_log, int N, hipStream_t st, int first = 0,
-                             const double* chunk_imat = nullptr) {
+static int refresh_factorise(rbpf_ctx* c, double* pant_log, int N, int first = 0, const double* chunk_imat = nullptr) {
   SmootherState* s = c->sm;
   const int n = c->mdl.n, d = c->mdl.d;
-  const size_t fd = chol_factor_doubles(n), sd = sweep_factor_doubles(n);
   for (int q0 = 0; q0 < N; q0 += s->l_chunk) {
     const int cnt = std::min(s->l_chunk, N - q0), p0 = first + q0;
-    CholArgs ca;
-    std::memset(&ca, 0, sizeof(ca));
-    ca.d = d; ca.n = n; ca.ldx = c->lay.ldx; ca.status = c->d_flags; ca.pant_log = pant_log + p0;
-    ca.mode = 1; ca.Msz = n; ca.Lbuf = s->d_L; ca.ldL = (long)fd;
+    CholArgs ca = chol_args(c, pant_log + p0);
+    ca.mode = 1; ca.Msz = n; ca.Lbuf = s->d_L; ca.ldL = (long)chol_factor_doubles(n);
     ca.Imat = chunk_imat ? chunk_imat + (size_t)q0 * s->imat_len : s->d_Imat[s->imat_cur] + (size_t)p0 * s->imat_len;
     ca.imat_stride = (long)s->imat_len; ca.imat_packed = s->imat_packed ? 1 : 0;
-    ca.imat_anc = nullptr; ca.ImatOut = nullptr; ca.Hb = nullptr; ca.Rinv = d_Rinv; ca.ImatAdd = s->d_ImatAdd;
+    ca.Rinv = s->d_Rinv; ca.ImatAdd = s->d_ImatAdd;
     ca.ivec = s->d_ivec[s->icur] + (size_t)p0 * c->lay.ldx; ca.ivecAdd = s->d_ivecAdd;
     ca.qf = s->d_qf[s->icur] + p0; ca.hld = s->d_hld[s->icur] + p0;
     ca.variant = 64;                                                   // the conversion below reads the 64-column kernel's layout
-    HIPCHK(launch_chol(ca, cnt, d, st));
-    HIPCHK(launch_sweep_from_chol64(n, cnt, s->d_L, fd, s->d_Lsw[s->sw_cur ^ 1] + (size_t)p0 * sd, sd, st));
+    HIPCHK(launch_chol(ca, cnt, d, c->stream));
+    RB_TRY(sweep_bank_from_chol64(c, cnt, p0));
   }
   return RBPF_OK;
 }
 
-static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* out) {
-  const int N = c->N, T = c->T, nN = c->mdl.nN, n = c->mdl.n, d = c->mdl.d, nw = c->mdl.nw;
+// rbpf_options -> the period K of the carried factors and what follows from it.  No allocation and no refusal: the entry points
+// refuse what they do not support, info_state_create what no information-form smoother does.
+static void info_resolve_options(rbpf_ctx* c) {
+  SmootherState* s = c->sm;
+  const int N = c->N, T = c->T, n = c->mdl.n, d = c->mdl.d;
+  const int K = resolve_chol_refresh(c->mdl.kind, n, d, effective_chol_refresh(c->opt));
+  s->refresh = K > 1 ? K : 0;
+  s->lazy_imat = s->refresh && c->mdl.kind != RBPF_MODEL_GENERIC_DENSE;     // needs measModel on the device
+  s->imat_packed = imat_storage_packed(n, d, s->refresh, s->lazy_imat);
+  s->imat_len = s->imat_packed ? imat_packed_doubles(n) : (size_t)n * n;
+  s->l_chunk = s->lazy_imat ? std::min(N, 4096) : N;
+  // Refresh-free (r05): with K >= N_T - 1 the factors are never refactorised after t = 1 -- against the extended-precision arbiter
+  // their ancestor probabilities are as close with K = 999 as with K = 32 or from scratch (6.8e-10 / 7.0e-10 / 6.7e-10 over T = 1000,
+  // DESIGN.md 9) -- so no information matrix is ever read again: none is stored, the first factorisation runs chunk by chunk over
+  // one buffer of l_chunk matrices.  3.6 MB of state per particle with one covariance bank (rbpf_options.inplace): the metric's full
+  // N_P = 65 536 fits one 288 GB MI355X.
+  // (a window of more than 256 generations would need N_P x K x n_y x n doubles of Jacobians per refresh: such periods take the
+  //  rebuild from the origin as well, whose scratch is one chunk x one segment)
+  s->refresh_free = s->lazy_imat && (s->refresh >= T - 1 || c->opt.info_rebuild > 0 || s->refresh > 256);
+  s->seg_len = 32;
+}
+
+// The information-form state of this context's particles, after info_resolve_options: the banks, the factor workspaces, the suffix
+// sums, the constants (R^-1, Imat0 in bank storage, the initial values, W) and, with carried factors, the factor banks.  The buffers
+// of the refreshes (d_Xp / d_G and, sharded, the exchange tables) are the caller's: their sizes follow from how it walks the history.
+// sharded: the entry has refused info_rebuild on its own terms (which let N_T = 1 through where the single-device smoother refuses).
+static int info_state_create(rbpf_ctx* c, const std::vector<double>& Rinv, bool sharded) {
+  SmootherState* s = c->sm;
+  const int N = c->N, n = c->mdl.n, d = c->mdl.d;
   const Layout& L = c->lay;
+  if (s->refresh && (sweep_slots(n) > kSweepMaxSlots || chol64_lds_bytes(n, d) > kC64MaxLds || (d != 1 && d != 3))) {
+    set_error("chol_refresh > 1 supports nLin <= 575 and n_y = 1 or 3"); return RBPF_ERR_UNSUPPORTED;
+  }
+  if (!sharded && c->opt.info_rebuild > 0 && !s->lazy_imat) {
+    set_error("info_rebuild = 1 needs carried factors (chol_refresh != 1) and a recognised model family: the information matrices are rebuilt from measModel along the state history");
+    return RBPF_ERR_UNSUPPORTED;
+  }
+  for (int b = 0; b < 2; ++b) {
+    const size_t n_mat = s->refresh_free ? (b == 0 ? (size_t)s->l_chunk : (size_t)0) : (size_t)N;
+    RB_TRY(s->pool.alloc(&s->d_Imat[b], std::max<size_t>(n_mat * s->imat_len, 1)));   // (refresh-free: bank 1 is a kernel argument nobody reads)
+    if (s->imat_packed && n_mat) HIPCHK(hipMemsetAsync(s->d_Imat[b], 0, n_mat * s->imat_len * 8, c->stream));   // the never-written upper halves of the diagonal tiles
+    RB_TRY(s->pool.alloc(&s->d_Hb[b], (size_t)N * d * L.ldx));
+    RB_TRY(s->pool.alloc(&s->d_ivec[b], (size_t)N * L.ldx));
+    RB_TRY(s->pool.alloc(&s->d_hld[b], (size_t)N));
+    RB_TRY(s->pool.alloc(&s->d_qf[b], (size_t)N));
+  }
+  // factor workspaces of the 64-column kernel: one per particle -- or, with carried factors, per particle of a CHUNK of the
+  // refresh (they are converted to the sweep layout chunk by chunk): 2.2 MB per particle at nLin = 515 that N_P = 32 768 has no room for
+  RB_TRY(s->pool.alloc(&s->d_L, (size_t)s->l_chunk * chol_factor_doubles(n)));
+  RB_TRY(s->pool.alloc(&s->d_ImatAdd, (size_t)n * n));
+  RB_TRY(s->pool.alloc(&s->d_ivecAdd, (size_t)n));
+  RB_TRY(s->pool.alloc(&s->d_Imat0, (size_t)n * n));
+  RB_TRY(s->pool.alloc(&s->d_Rinv, (size_t)d * d));
+  RB_TRY(s->pool.alloc(&s->d_ivec0, (size_t)L.ldx));
+  RB_TRY(s->pool.alloc(&s->d_hld0, 1));
+  HIPCHK(hipMemcpy(s->d_Rinv, Rinv.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
+  std::vector<double> Imat0((size_t)n * n, 0.0);
+  s->h_ivec0.assign(L.ldx, 0.0);
+  info_initial_values(c, s->h_ivec0, Imat0, s->hld0);
+  const std::vector<double> Imat0s = imat_host_storage(Imat0, n, s->imat_packed);
+  HIPCHK(hipMemcpy(s->d_Imat0, Imat0s.data(), Imat0s.size() * 8, hipMemcpyHostToDevice));
+  if (s->refresh) {                                     // carried ancestor-weight factors (rbpf_chol_sweep.hpp)
+    for (int b = 0; b < 2; ++b) RB_TRY(s->pool.alloc(&s->d_Lsw[b], (size_t)N * sweep_factor_doubles(n)));
+    RB_TRY(s->pool.alloc(&s->d_W, (size_t)d * d));
+    std::vector<double> Wm;
+    whitening_factor(c->h_R, d, Wm);
+    HIPCHK(hipMemcpy(s->d_W, Wm.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
+    if (s->lazy_imat) RB_TRY(s->pool.alloc(&s->d_base_slot, (size_t)N));
+  }
+  return RBPF_OK;
+}
+
+// start of an iteration: the initial values of the step t = 0 (:110-115), nothing materialised
+static int info_begin_iteration(rbpf_ctx* c) {
+  SmootherState* s = c->sm;
+  HIPCHK(hipMemcpyAsync(s->d_ivec0, s->h_ivec0.data(), (size_t)c->lay.ldx * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s->d_hld0, &s->hld0, 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  s->icur = 0;
+  s->imat_cur = 0;
+  s->imat_valid = false;
+  s->base_gen = -1;
+  return RBPF_OK;
+}
+
+// ImatAddt / ivecAddt += sign * the terms of the steps [t0, t1) along the reference trajectory
+static int info_addt(rbpf_ctx* c, int t0, int t1, double sign) {
+  SmootherState* s = c->sm;
+  const int n = c->mdl.n, d = c->mdl.d;
+  hipLaunchKernelGGL(info_addt_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, c->stream, n, d, t0, t1, sign,
+                     s->d_dyref, s->d_Rinv, c->d_y, s->d_ImatAdd, s->d_ivecAdd, s->imat_packed ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  return RBPF_OK;
+}
+
+// the suffix sums over the whole reference trajectory (:132-146), from its Jacobians in d_dyref
+static int info_reference_sums(rbpf_ctx* c) {
+  SmootherState* s = c->sm;
+  const int n = c->mdl.n;
+  HIPCHK(hipMemsetAsync(s->d_ImatAdd, 0, (size_t)n * n * 8, c->stream));
+  HIPCHK(hipMemsetAsync(s->d_ivecAdd, 0, (size_t)n * 8, c->stream));
+  return info_addt(c, 0, c->T, 1.0);
+}
+
+// the (t-1) term leaves the suffix sums (:194-201)
+static int info_drop_term(rbpf_ctx* c, int t) { return info_addt(c, t - 1, t, -1.0); }
+
+// Arguments of the information-form ancestor-weight factorisation of the step about to run (t >= 1).  The kernel
+// also forms the information matrices of the current generation, Imat(:,:,i) = Imat(:,:,ai(i)) + dyi'/R*dyi
+// (:170,:253,:334), from the previous generation's bank (entry anc[i]; generation 0 starts from Imat0) and stores
+// them into the other bank: the gather `Imat = Imat(:,:,ai)` costs one extra write instead of a copy kernel.
+static CholArgs info_chol_args(rbpf_ctx* c, double* pant_log, const int* anc) {
+  SmootherState* s = c->sm;
+  const int n = c->mdl.n;
+  const int ni = s->imat_valid ? (s->imat_cur ^ 1) : 0;
+  CholArgs ca = chol_args(c, pant_log);
+  ca.mode = 1; ca.Msz = n; ca.Lbuf = s->d_L; ca.ldL = (long)chol_factor_doubles(n);
+  ca.Imat = s->imat_valid ? s->d_Imat[s->imat_cur] : s->d_Imat0;
+  ca.imat_stride = s->imat_valid ? (long)s->imat_len : 0;
+  ca.imat_anc = s->imat_valid ? anc : nullptr;
+  ca.ImatOut = s->d_Imat[ni]; ca.imat_out_stride = (long)s->imat_len; ca.imat_packed = s->imat_packed ? 1 : 0;
+  ca.Hb = s->d_Hb[s->icur]; ca.Rinv = s->d_Rinv; ca.ImatAdd = s->d_ImatAdd; ca.ivec = s->d_ivec[s->icur];
+  ca.ivecAdd = s->d_ivecAdd; ca.qf = s->d_qf[s->icur]; ca.hld = s->d_hld[s->icur];
+  s->imat_cur = ni;                 // after the launch the new bank is the current one
+  s->imat_valid = true;
+  // nothing reads the factors of this launch afterwards unless they are carried on (chol_refresh): let the 64-column kernel
+  // run persistent workgroups over one workspace slot each (rbpf_chol64.hpp); carried on, they are read back in that kernel's layout
+  ca.l_slots = (s->refresh > 1) ? 0 : chol64_workspace_slots(n);
+  if (s->refresh > 1) ca.variant = 64;
+  return ca;
+}
+
+// Carried factors, a step between two refreshes: one sweep per particle turns the ancestor's factor into this particle's and adds
+// logwMeas to pant_log (rbpf_chol_sweep.hpp).  Everything but where the ancestors are: anc / order / ref_slot, or the record fields.
+static SweepArgs info_sweep_args(rbpf_ctx* c, int t, double* pant_log) {
+  SmootherState* s = c->sm;
+  const int n = c->mdl.n, d = c->mdl.d;
+  SweepArgs sw;
+  sw.n = n; sw.d = d; sw.ldx = c->lay.ldx; sw.NS = sweep_slots(n); sw.tailc = sweep_tail_compact(n); sw.N = c->N;
+  sw.ref_slot = -1; sw.anc = nullptr; sw.order = nullptr;
+  sw.Lold = s->d_Lsw[s->sw_cur]; sw.Lnew = s->d_Lsw[s->sw_cur ^ 1]; sw.stride = sweep_factor_doubles(n);
+  sw.Hb = s->d_Hb[s->icur]; sw.Href = s->d_dyref + (size_t)(t - 1) * d * n;
+  sw.W = s->d_W; sw.yt = c->d_y + (size_t)(t - 1) * d; sw.qf = s->d_qf[s->icur]; sw.hld = s->d_hld[s->icur];
+  sw.pant_log = pant_log; sw.status = c->d_flags;
+  return sw;
+}
+
+static bool refresh_due(const SmootherState* s, int t) { return s->refresh > 1 && (t == 1 || ((t - 1) % s->refresh) == 0); }
+
+// sum of H' R^-1 H over `len` generations for each of `cnt` matrices: states Xp [cnt * len][nN] -> measModel -> whitened Jacobians
+// (d_G) -> G'G into Imat_out, block-lower as the factorisation reads it.  The epilogue adds what `gg` says (its add* fields).
+static int info_gram_product(rbpf_ctx* c, const double* Xp, int cnt, int len, double* Imat_out, GemmArgs gg) {
+  SmootherState* s = c->sm;
+  const int n = c->mdl.n, d = c->mdl.d;
   hipStream_t st = c->stream;
+  HIPCHK(launch_meas_model(c->mdl, cnt * len, Xp, s->d_G, st, 1));
+  const size_t rows = (size_t)cnt * len;
+  hipLaunchKernelGGL(sweep_whiten_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, st, rows, d, n, s->d_W, s->d_G);
+  HIPCHK(hipGetLastError());
+  const long Kd = (long)len * d;
+  gg.M = n; gg.N = n; gg.K = (int)Kd;
+  gg.A = s->d_G; gg.rsA = 1; gg.csA = n; gg.bsA = Kd * n;
+  gg.B = s->d_G; gg.rsB = n; gg.csB = 1; gg.bsB = Kd * n;
+  gg.C = Imat_out; gg.rsC = 1; gg.csC = n; gg.bsC = (long)s->imat_len;
+  gg.lower = 1; gg.packed = s->imat_packed ? 1 : 0;
+  HIPCHK(launch_gemm(gg, cnt, st));
+  return RBPF_OK;
+}
+
+// Refresh over the window since the last one: d_Xp holds the states of the Kp generations t0 + 1 .. t0 + Kp along every particle's
+// ancestral path, d_base_slot its ancestor's entry of generation t0 in the materialised bank (or, >= N, in add_rec: matrices
+// fetched from other ranks).  Imat = base + G'G into the other bank, chol(Imat + ImatAddt) out of it, the factors into the sweep layout.
+static int info_refresh_window(rbpf_ctx* c, int Kp, int t0, double* pant_log, const double* add_rec) {
+  SmootherState* s = c->sm;
+  const int N = c->N, ni = s->imat_valid ? (s->imat_cur ^ 1) : 0;
+  GemmArgs gg{};
+  gg.add = t0 < 0 ? s->d_Imat0 : s->d_Imat[s->imat_cur];             // + the base matrix, in the epilogue
+  gg.add_stride = t0 < 0 ? 0L : (long)s->imat_len;
+  gg.add_idx = t0 < 0 ? (const int*)nullptr : s->d_base_slot;
+  gg.add_rec = t0 < 0 ? (const double*)nullptr : add_rec; gg.add_nbank = N;
+  RB_TRY(info_gram_product(c, s->d_Xp, N, Kp, s->d_Imat[ni], gg));
+  s->imat_cur = ni; s->imat_valid = true; s->base_gen = t0 + Kp;
+  RB_TRY(refresh_factorise(c, pant_log, N));
+  s->sw_cur ^= 1;
+  return RBPF_OK;
+}
+
+// One chunk of a refresh from the origin, the particles p0 .. p0 + cnt - 1: Imat_i = Imat0 + sum over the generations 0 .. n_gen - 1
+// of the ancestral path of H' R^-1 H, accumulated segment by segment (seg_len generations, the latest first) into the chunk buffer,
+// then chol(Imat + ImatAddt) out of it.  Xp != null: the states are there already (one segment); otherwise every segment's walk
+// starts from its marks (single device).
+static int info_refresh_chunk(rbpf_ctx* c, int p0, int cnt, int n_gen, const double* Xp, double* pant_log) {
+  SmootherState* s = c->sm;
+  const int S = s->seg_len, n_seg = Xp ? 1 : (n_gen + S - 1) / S;        // segment j = [hi_j - len_j, hi_j), hi_0 = n_gen
+  for (int j = 0; j < n_seg; ++j) {
+    const int hi = n_gen - j * S, lo = Xp ? 0 : std::max(0, hi - S);
+    if (!Xp) {
+      hipLaunchKernelGGL(origin_segment_kernel, dim3((cnt + 127) / 128), dim3(128), 0, c->stream, c->N, c->mdl.nN, p0, cnt, lo, hi, c->A, c->X,
+                         s->d_marks + (size_t)j * c->N, s->d_Xp);
+      HIPCHK(hipGetLastError());
+    }
+    GemmArgs gg{};
+    if (j == 0) { gg.add = s->d_Imat0; gg.add_stride = 0L; gg.add_idx = nullptr; }
+    else gg.add_self = 1;
+    RB_TRY(info_gram_product(c, Xp ? Xp : s->d_Xp, cnt, hi - lo, s->d_Imat[0], gg));
+  }
+  return refresh_factorise(c, pant_log, cnt, p0, s->d_Imat[0]);
+}
+
+// Refresh from the origin (refresh-free runs, info_rebuild, long periods): no information matrix is stored, those of generation t - 1
+// are rebuilt along the WHOLE ancestral path (:334's terms, in another order of summation), chunk by chunk.  Cost grows with t; the
+// marks make every segment's walk O(seg_len).  Xp0 != null: the states of generation 0 of all particles (sharded: t = 1 only).
+static int info_refresh_origin(rbpf_ctx* c, int t, double* pant_log, const double* Xp0) {
+  SmootherState* s = c->sm;
+  const int N = c->N;
+  if (!Xp0) {
+    hipLaunchKernelGGL(origin_marks_kernel, dim3((N + 127) / 128), dim3(128), 0, c->stream, N, t - 1, s->seg_len, c->A, s->d_marks);
+    HIPCHK(hipGetLastError());
+  }
+  for (int p0 = 0; p0 < N; p0 += s->l_chunk)
+    RB_TRY(info_refresh_chunk(c, p0, std::min(s->l_chunk, N - p0), t, Xp0 ? Xp0 + (size_t)p0 * c->mdl.nN : nullptr, pant_log));
+  s->imat_valid = false; s->base_gen = t - 1;
+  s->sw_cur ^= 1;
+  return RBPF_OK;
+}
+
+// the extra ivec / halfLogDetP / qf / H state of the step t about to run (:170,:186,:253,:334): returns the bank it writes
+static int info_step_banks(const SmootherState* s, int t, int ldx, InfoStep& is) {
+  const int oc = s->icur, nc = (t == 0) ? 0 : (oc ^ 1);
+  if (t == 0) { is.ivec_old = s->d_ivec0; is.ivec_old_stride = 0; is.hld_old = s->d_hld0; is.hld_old_stride = 0; }
+  else { is.ivec_old = s->d_ivec[oc]; is.ivec_old_stride = (size_t)ldx; is.hld_old = s->d_hld[oc]; is.hld_old_stride = 1; }
+  is.ivec_new = s->d_ivec[nc]; is.hld_new = s->d_hld[nc]; is.qf_new = s->d_qf[nc]; is.Hb_new = s->d_Hb[nc];
+  return nc;
+}
+
+// ak = sample(w) and the new reference trajectory xnk = xn_traj(:,ak,:) into d_xnk (:346-354), from the normalised weights w and
+// their running sum wc of the last step and the history X / A of all N particles.
+static int draw_reference_index(rbpf_ctx* c, int N, double* w, double* wc, const double* X, const int* A, int k, int* ak) {
+  SmootherState* s = c->sm;
+  hipStream_t st = c->stream;
+  double* d_uf = c->d_scal;
+  if (c->rng_mode == RBPF_RNG_REPLAY) HIPCHK(hipMemcpyAsync(d_uf, &c->h_Ufin[k], 8, hipMemcpyHostToDevice, st));
+  SearchArgs sa;
+  sa.N = N; sa.n_draw = 1; sa.t = c->T; sa.wc = wc; sa.rng_mode = c->rng_mode; sa.k_iter = k; sa.slot0 = 0;
+  sa.U = d_uf; sa.seed = c->seed; sa.ai = s->d_ak; sa.overflow = c->d_flags + 1; sa.u_is_scalar = 1;
+  sa.approx = 1; sa.ambiguous = c->d_flags + 4; sa.w = w; sa.wc_exact = wc;
+  // (scan_depth stays 0: N / 1024 + 32, the depth of the multi-workgroup prefix that wrote wc)
+  HIPCHK(launch_search(sa, st));
+  HIPCHK(launch_resample_fixup(sa, st));
+  HIPCHK(launch_backtrace(N, c->mdl.nN, c->T, X, A, s->d_ak, 1, s->d_xnk, st));
+  HIPCHK(hipMemcpyAsync(ak, s->d_ak, 4, hipMemcpyDeviceToHost, st));
+  return ctx_check_flags(c);                           // synchronises
+}
+
+// =============================================================================================================
+// The single-device smoother, both forms
+// =============================================================================================================
+// sparse-visual family: the future observations of step t are M(t) stacked (time, output) pairs
+static int sparse_alloc(rbpf_ctx* c) {
+  SmootherState* s = c->sm;
+  SparsePairs& pr = s->pairs;
+  const int N = c->N, T = c->T, d = c->mdl.d;
+  std::vector<int> pair_t, pair_j;
+  pr.off.assign((size_t)T + 1, 0);
+  for (int ti = 0; ti < T; ++ti) {
+    pr.off[ti] = (int)pair_t.size();
+    for (int j = 0; j < d; ++j)
+      if (!std::isnan(c->h_y[ti + (size_t)T * j])) { pair_t.push_back(ti); pair_j.push_back(j); }
+  }
+  pr.off[T] = (int)pair_t.size();
+  const size_t Ms = (T > 1) ? (size_t)pr.future(1) : 0;
+  if (Ms > 1023) { set_error("sparse smoother: more than 1023 future observations (particleSmoother.m:197-212 stacks them all)"); return RBPF_ERR_UNSUPPORTED; }
+  s->Mmax = Ms;
+  RB_TRY(s->pool.alloc(&pr.d_t, std::max<size_t>(pair_t.size(), 1)));   // (kernel arguments: non-null without observations too)
+  RB_TRY(s->pool.alloc(&pr.d_j, std::max<size_t>(pair_j.size(), 1)));
+  if (!pair_t.empty()) {
+    HIPCHK(hipMemcpy(pr.d_t, pair_t.data(), pair_t.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(pr.d_j, pair_j.data(), pair_j.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  RB_TRY(s->pool.alloc(&s->d_S, std::max<size_t>((size_t)N * Ms * Ms, 1)));
+  RB_TRY(s->pool.alloc(&s->d_e, std::max<size_t>((size_t)N * Ms, 1)));
+  RB_TRY(s->pool.alloc(&s->d_L, (size_t)N * chol_factor_doubles((int)Ms)));
+  return RBPF_OK;
+}
+
+static int cov_alloc(rbpf_ctx* c) {
+  SmootherState* s = c->sm;
+  const size_t N = (size_t)c->N, n = (size_t)c->mdl.n, Mmax = s->Mmax;
+  RB_TRY(s->pool.alloc(&s->d_Pfull, N * n * n));
+  RB_TRY(s->pool.alloc(&s->d_G, N * Mmax * n));
+  RB_TRY(s->pool.alloc(&s->d_S, N * Mmax * Mmax));
+  RB_TRY(s->pool.alloc(&s->d_L, N * chol_factor_doubles((int)Mmax)));
+  if (Mmax > 1023) { set_error("covariance-form smoother supports ny*N_T <= 1023 (use the information form for long T)"); return RBPF_ERR_UNSUPPORTED; }
+  return RBPF_OK;
+}
+
+static int info_alloc(rbpf_ctx* c, const std::vector<double>& Rinv) {
+  SmootherState* s = c->sm;
+  const size_t N = (size_t)c->N, nN = (size_t)c->mdl.nN, n = (size_t)c->mdl.n, d = (size_t)c->mdl.d;
+  if (n > 1023) { set_error("information-form smoother supports nLin <= 1023"); return RBPF_ERR_UNSUPPORTED; }
+  if (c->x0_lin_cols != 1) {
+    // quirk Q5: the reference's repmat(x0_lin,1,N_P) (:109) only works for a single column
+    set_error("particleSmootherInformationForm: x0_lin must be nLin x 1 (the reference repmat's it, :109)");
+    return RBPF_ERR_INVALID_ARG;
+  }
+  info_resolve_options(c);
+  RB_TRY(info_state_create(c, Rinv, false));
+  if (!s->lazy_imat) return RBPF_OK;
+  if (s->refresh_free) {                                             // a chunk of particles x a segment of generations at a time
+    RB_TRY(s->pool.alloc(&s->d_Xp, (size_t)s->l_chunk * s->seg_len * nN));
+    RB_TRY(s->pool.alloc(&s->d_G, (size_t)s->l_chunk * s->seg_len * d * n));
+    RB_TRY(s->pool.alloc(&s->d_marks, (size_t)((c->T + s->seg_len - 1) / s->seg_len) * N));
+  } else {
+    RB_TRY(s->pool.alloc(&s->d_Xp, N * s->refresh * nN));          // generations a refresh walks back: K
+    RB_TRY(s->pool.alloc(&s->d_G, N * s->refresh * d * n));
+  }
+  return RBPF_OK;
+}
+
+// what the forms share: the checks of the model's dynamics residual, the reference trajectory and the ancestor probabilities
+static int smoother_setup(rbpf_ctx* c, int N_K, int info_form) {
+  const int N = c->N, T = c->T, nN = c->mdl.nN, n = c->mdl.n, d = c->mdl.d, nw = c->mdl.nw;
   SmootherState* s = new SmootherState();
   c->sm = s;
   if (!info_form && c->inplace) { set_error("inplace=1: the covariance-form smoother rewrites its covariances at every step (use the information form)"); return RBPF_ERR_UNSUPPORTED; }
@@ -946,423 +1290,219 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
     return RBPF_ERR_INVALID_ARG;
   }
   if (generic && !drn_cb && !c->cholQfull_ok) { set_error("isempty(dynResNorm): chol(dt*Q,'lower') failed (particleSmoother.m:177)"); return RBPF_ERR_CHOL_FAILED; }
-  DevicePool tmp;                                                    // scratch of this run
-  double* d_edyn = nullptr;
-  if (drn_cb) RB_TRY(tmp.alloc(&d_edyn, (size_t)N * nw));
-  std::vector<double> h_edyn;
-  const size_t Mmax = (size_t)d * T;
-  s->Mmax = Mmax;
+  if (drn_cb) RB_TRY(s->pool.alloc(&s->d_edyn, (size_t)N * nw));
+  s->Mmax = (size_t)d * T;
   RB_TRY(s->pool.alloc(&s->d_xnk, (size_t)T * nN));
   RB_TRY(s->pool.alloc(&s->d_dyref, (size_t)T * d * n));
   RB_TRY(s->pool.alloc(&s->d_pant_log, (size_t)N));
-  RB_TRY(s->pool.alloc(&s->d_pant, (size_t)N * (c->opt.trace ? (size_t)T * N_K : 1)));
-  {
-    const size_t cnt = (size_t)N * (c->opt.trace ? (size_t)T * N_K : 1);
-    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, cnt, (double)NAN, s->d_pant);
-    HIPCHK(hipGetLastError());
-  }
+  const size_t n_pant = (size_t)N * (c->opt.trace ? (size_t)T * N_K : 1);
+  RB_TRY(s->pool.alloc(&s->d_pant, n_pant));
+  hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n_pant + 255) / 256)), dim3(256), 0, c->stream, n_pant, (double)NAN, s->d_pant);
+  HIPCHK(hipGetLastError());
   RB_TRY(s->pool.alloc(&s->d_wc2, (size_t)N));
   RB_TRY(s->pool.alloc(&s->d_ak, 4));
-  std::vector<double> Rinv((size_t)d * d), Rh(c->h_R);
-  double halfLogDetR = 0.0;
-  RB_TRY(invert_R(Rh, d, Rinv, halfLogDetR));
-  double *d_R = nullptr, *d_Rinv = nullptr;
-  RB_TRY(tmp.alloc(&d_R, (size_t)d * d));
-  RB_TRY(tmp.alloc(&d_Rinv, (size_t)d * d));
-  HIPCHK(hipMemcpy(d_R, Rh.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_Rinv, Rinv.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
-
-  const bool sparse = c->mdl.kind == RBPF_MODEL_SPARSE_VISUAL_2D;
-  std::vector<int> pair_t, pair_j, pair_off((size_t)T + 1, 0);
-  int *d_pair_t = nullptr, *d_pair_j = nullptr;
-  if (sparse) {
+  std::vector<double> Rinv((size_t)d * d);
+  RB_TRY(invert_R(c->h_R, d, Rinv));
+  RB_TRY(s->pool.alloc(&s->d_R, (size_t)d * d));
+  HIPCHK(hipMemcpy(s->d_R, c->h_R.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
+  s->h_xnk.resize((size_t)nN * T);
+  if (c->mdl.kind == RBPF_MODEL_SPARSE_VISUAL_2D) {
     if (info_form) { set_error("This code has only been implemented for dense features"); return RBPF_ERR_UNSUPPORTED; }   // InformationForm.m:77-80
-    // observed (time, output) pairs, time-major: the future observations of step t are the suffix from pair_off[t]
-    for (int ti = 0; ti < T; ++ti) {
-      pair_off[ti] = (int)pair_t.size();
-      for (int j = 0; j < d; ++j)
-        if (!std::isnan(c->h_y[ti + (size_t)T * j])) { pair_t.push_back(ti); pair_j.push_back(j); }
-    }
-    pair_off[T] = (int)pair_t.size();
-    const size_t Ms = (T > 1) ? (size_t)(pair_off[T] - pair_off[1]) : 0;
-    if (Ms > 1023) { set_error("sparse smoother: more than 1023 future observations (particleSmoother.m:197-212 stacks them all)"); return RBPF_ERR_UNSUPPORTED; }
-    s->Mmax = Ms;
-    RB_TRY(tmp.alloc(&d_pair_t, std::max<size_t>(pair_t.size(), 1)));   // (kernel arguments: non-null without observations too)
-    RB_TRY(tmp.alloc(&d_pair_j, std::max<size_t>(pair_j.size(), 1)));
-    if (!pair_t.empty()) {
-      HIPCHK(hipMemcpy(d_pair_t, pair_t.data(), pair_t.size() * sizeof(int), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d_pair_j, pair_j.data(), pair_j.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    RB_TRY(s->pool.alloc(&s->d_S, std::max<size_t>((size_t)N * Ms * Ms, 1)));
-    RB_TRY(s->pool.alloc(&s->d_e, std::max<size_t>((size_t)N * Ms, 1)));
-    RB_TRY(s->pool.alloc(&s->d_L, (size_t)N * chol_factor_doubles((int)Ms)));
-  } else if (!info_form) {
-    RB_TRY(s->pool.alloc(&s->d_Pfull, (size_t)N * n * n));
-    RB_TRY(s->pool.alloc(&s->d_G, (size_t)N * Mmax * n));
-    RB_TRY(s->pool.alloc(&s->d_S, (size_t)N * Mmax * Mmax));
-    RB_TRY(s->pool.alloc(&s->d_L, (size_t)N * chol_factor_doubles((int)Mmax)));
-    if (Mmax > 1023) { set_error("covariance-form smoother supports ny*N_T <= 1023 (use the information form for long T)"); return RBPF_ERR_UNSUPPORTED; }
-  } else {
-    if (n > 1023) { set_error("information-form smoother supports nLin <= 1023"); return RBPF_ERR_UNSUPPORTED; }
-    if (c->x0_lin_cols != 1) {
-      // quirk Q5: the reference's repmat(x0_lin,1,N_P) (:109) only works for a single column
-      set_error("particleSmootherInformationForm: x0_lin must be nLin x 1 (the reference repmat's it, :109)");
-      return RBPF_ERR_INVALID_ARG;
-    }
-    {
-      const int K = resolve_chol_refresh(c->mdl.kind, n, d, effective_chol_refresh(c->opt));
-      s->refresh = K > 1 ? K : 0;
-    }
-    if (s->refresh && (sweep_slots(n) > kSweepMaxSlots || chol64_lds_bytes(n, d) > kC64MaxLds || (d != 1 && d != 3))) {
-      set_error("chol_refresh > 1 supports nLin <= 575 and n_y = 1 or 3"); return RBPF_ERR_UNSUPPORTED;
-    }
-    s->lazy_imat = s->refresh && c->mdl.kind != RBPF_MODEL_GENERIC_DENSE;     // needs measModel on the device
-    s->imat_packed = imat_storage_packed(n, d, s->refresh, s->lazy_imat);
-    s->imat_len = s->imat_packed ? imat_packed_doubles(n) : (size_t)n * n;
-    s->l_chunk = s->lazy_imat ? std::min(N, 4096) : N;
-    // Refresh-free (r05): with K >= N_T - 1 the factors are never refactorised after t = 1 -- against the extended-precision arbiter
-    // their ancestor probabilities are as close with K = 999 as with K = 32 or from scratch (6.8e-10 / 7.0e-10 / 6.7e-10 over T = 1000,
-    // DESIGN.md 9) -- so no information matrix is ever read again: none is stored, the first factorisation runs chunk by chunk over
-    // one buffer of l_chunk matrices.  3.6 MB of state per particle with one covariance bank (rbpf_options.inplace): the metric's full
-    // N_P = 65 536 fits one 288 GB MI355X.
-    if (c->opt.info_rebuild > 0 && !s->lazy_imat) {
-      set_error("info_rebuild = 1 needs carried factors (chol_refresh != 1) and a recognised model family: the information matrices are rebuilt from measModel along the state history");
-      return RBPF_ERR_UNSUPPORTED;
-    }
-    // (a window of more than 256 generations would need N_P x K x n_y x n doubles of Jacobians per refresh: such periods take the
-    //  rebuild from the origin as well, whose scratch is one chunk x one segment)
-    s->refresh_free = s->lazy_imat && (s->refresh >= T - 1 || c->opt.info_rebuild > 0 || s->refresh > 256);
-    s->seg_len = 32;
-    for (int b = 0; b < 2; ++b) {
-      const size_t n_mat = s->refresh_free ? (b == 0 ? (size_t)s->l_chunk : (size_t)0) : (size_t)N;
-      RB_TRY(s->pool.alloc(&s->d_Imat[b], std::max<size_t>(n_mat * s->imat_len, 1)));   // (refresh-free: bank 1 is a kernel argument nobody reads)
-      if (s->imat_packed && n_mat) HIPCHK(hipMemsetAsync(s->d_Imat[b], 0, n_mat * s->imat_len * 8, st));   // the never-written upper halves of the diagonal tiles
-      RB_TRY(s->pool.alloc(&s->d_Hb[b], (size_t)N * d * L.ldx));
-      RB_TRY(s->pool.alloc(&s->d_ivec[b], (size_t)N * L.ldx));
-      RB_TRY(s->pool.alloc(&s->d_hld[b], (size_t)N));
-      RB_TRY(s->pool.alloc(&s->d_qf[b], (size_t)N));
-    }
-    // factor workspaces of the 64-column kernel: one per particle -- or, with carried factors, per particle of a CHUNK of the
-    // refresh (they are converted to the sweep layout chunk by chunk): 2.2 MB per particle at nLin = 515 that N_P = 32 768 has no room for
-    RB_TRY(s->pool.alloc(&s->d_L, (size_t)s->l_chunk * chol_factor_doubles(n)));
-    RB_TRY(s->pool.alloc(&s->d_ImatAdd, (size_t)n * n));
-    RB_TRY(s->pool.alloc(&s->d_ivecAdd, (size_t)n));
-    RB_TRY(s->pool.alloc(&s->d_Imat0, (size_t)n * n));
-    if (s->refresh) {
-      for (int b = 0; b < 2; ++b) RB_TRY(s->pool.alloc(&s->d_Lsw[b], (size_t)N * sweep_factor_doubles(n)));
-      RB_TRY(s->pool.alloc(&s->d_W, (size_t)d * d));
-      std::vector<double> Wm;
-      whitening_factor(Rh, d, Wm);
-      HIPCHK(hipMemcpy(s->d_W, Wm.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
-      if (s->lazy_imat) {
-        RB_TRY(s->pool.alloc(&s->d_base_slot, (size_t)N));
-        if (s->refresh_free) {                                             // a chunk of particles x a segment of generations at a time
-          RB_TRY(s->pool.alloc(&s->d_Xp, (size_t)s->l_chunk * s->seg_len * nN));
-          RB_TRY(s->pool.alloc(&s->d_G, (size_t)s->l_chunk * s->seg_len * d * n));
-          RB_TRY(s->pool.alloc(&s->d_marks, (size_t)((T + s->seg_len - 1) / s->seg_len) * N));
-        } else {
-          RB_TRY(s->pool.alloc(&s->d_Xp, (size_t)N * s->refresh * nN));          // generations a refresh walks back: K
-          RB_TRY(s->pool.alloc(&s->d_G, (size_t)N * s->refresh * d * n));
-        }
-      }
-    }
+    s->form = SmootherForm::Sparse;
+    return sparse_alloc(c);
   }
-  // information-form initial values (quirk Q5: diagonal of P0 only, :110-115)
-  std::vector<double> ivec0(L.ldx, 0.0), Imat0((size_t)n * n, 0.0);
-  double hld0 = 0.0, qf0 = 0.0;
-  if (info_form) {
-    info_initial_values(c, ivec0, Imat0, hld0);
-    for (int r = 0; r < n; ++r) {                    // ivec0' * P0 * ivec0 (full P0, as :301 uses P)
-      double sacc = 0.0;
-      for (int cc = 0; cc < n; ++cc) sacc += c->h_P0[r + (size_t)n * cc] * ivec0[cc];
-      qf0 += ivec0[r] * sacc;
-    }
-    const std::vector<double> Imat0s = imat_host_storage(Imat0, n, s->imat_packed);
-    HIPCHK(hipMemcpy(s->d_Imat0, Imat0s.data(), Imat0s.size() * 8, hipMemcpyHostToDevice));
-  }
+  s->form = info_form ? SmootherForm::Info : SmootherForm::Cov;
+  return info_form ? info_alloc(c, Rinv) : cov_alloc(c);
+}
 
-  std::vector<double> xnk_h((size_t)nN * T);
+// dy_xnk = measModel(xnk)  (:120) into d_dyref [T][d][n]
+static int reference_jacobians(rbpf_ctx* c) {
+  SmootherState* s = c->sm;
+  const int T = c->T, n = c->mdl.n, d = c->mdl.d;
+  if (c->mdl.kind != RBPF_MODEL_GENERIC_DENSE) {
+    HIPCHK(launch_meas_model(c->mdl, T, s->d_xnk, s->d_dyref, c->stream, 1));
+    return RBPF_OK;
+  }
+  std::vector<double> dyT((size_t)T * d * n), Href((size_t)T * d * n);
+  if (c->cb.meas_model(c->cb.user, T, s->h_xnk.data(), dyT.data()) != 0) { set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK; }
+  for (int cc = 0; cc < n; ++cc)                   // dy(tt, a, cc) at tt + T*(a + d*cc) -> [T][d][n]
+    for (int a = 0; a < d; ++a)
+      for (int tt = 0; tt < T; ++tt) Href[((size_t)tt * d + a) * n + cc] = dyT[(size_t)tt + (size_t)T * (a + (size_t)d * cc)];
+  HIPCHK(hipMemcpy(s->d_dyref, Href.data(), Href.size() * 8, hipMemcpyHostToDevice));
+  return RBPF_OK;
+}
+
+// paNtLog = log(w) + logwDyn of the generation t - 1 against the reference state of step t (particleSmoother.m:175-182,232)
+static int anc_dyn_weights(rbpf_ctx* c, int t) {
+  SmootherState* s = c->sm;
+  const int N = c->N, nN = c->mdl.nN, nw = c->mdl.nw;
+  hipStream_t st = c->stream;
+  const double* w_prev = c->w + (c->opt.trace ? (size_t)(t - 1) * N : 0);
+  if (c->mdl.kind == RBPF_MODEL_GENERIC_DENSE && c->cb.dyn_res_norm) {
+    s->h_edyn.assign((size_t)N * nw, 0.0);
+    if (c->cb.dyn_res_norm(c->cb.user, t - 1, N, s->h_xnk.data() + (size_t)t * nN, c->h_xn.data(), s->h_edyn.data()) != 0) {
+      set_error("the dynResNorm callback failed"); return RBPF_ERR_CALLBACK;
+    }
+    HIPCHK(hipMemcpyAsync(s->d_edyn, s->h_edyn.data(), s->h_edyn.size() * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(anc_dyn_ext_kernel, dim3((N + 63) / 64), dim3(64), 0, st, N, nw, s->d_edyn, w_prev, s->d_pant_log);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return RBPF_OK;
+  }
+  const double* Lq = c->d_cholQfull + (size_t)((c->chol_pages > 1) ? t - 1 : 0) * nw * nw;
+  hipLaunchKernelGGL(anc_dyn_kernel, dim3((N + 63) / 64), dim3(64), 0, st, c->mdl, N, c->X + (size_t)(t - 1) * nN * N,
+                     s->d_xnk + (size_t)t * nN, c->d_odo + (size_t)(t - 1) * c->mdl.nodo, Lq, w_prev, s->d_pant_log);
+  HIPCHK(hipGetLastError());
+  return RBPF_OK;
+}
+
+// pant_log += logwMeas of step t, the three forms (Steps 9-10 of Alg. 2)
+static int sparse_anc_weights(rbpf_ctx* c, int t) {
+  SmootherState* s = c->sm;
+  const Layout& L = c->lay;
+  const int M = s->pairs.future(t), cur = c->cur;
+  SparseAncArgs aa;
+  aa.n = c->mdl.n; aa.d = c->mdl.d; aa.nN = c->mdl.nN; aa.ldx = L.ldx; aa.ldb = L.ldb; aa.M = M; aa.off = s->pairs.off[t]; aa.szB = L.szB;
+  aa.f = c->mdl.cam[0]; aa.fp = c->mdl.cam[1]; aa.pair_t = s->pairs.d_t; aa.pair_j = s->pairs.d_j; aa.xnk = s->d_xnk;
+  aa.y = c->d_y; aa.xl = c->xl[cur]; aa.Pb = c->Pb[cur]; aa.R = c->d_R; aa.rhs = s->d_e; aa.S = s->d_S;
+  HIPCHK(launch_sparse_anc(aa, c->N, c->stream));
+  if (M == 0) return RBPF_OK;                                          // no future observation: logwMeas = 0
+  CholArgs ca = chol_args(c, s->d_pant_log);
+  ca.mode = 0; ca.Msz = M; ca.Lbuf = s->d_L; ca.ldL = (long)chol_factor_doubles(M);
+  ca.S = s->d_S; ca.R = nullptr; ca.rhs = s->d_e; ca.jitter = c->mdl.jitter;
+  HIPCHK(launch_chol(ca, c->N, 0, c->stream));
+  return RBPF_OK;
+}
+
+static int cov_anc_weights(rbpf_ctx* c, int t) {
+  SmootherState* s = c->sm;
+  const int N = c->N, n = c->mdl.n, d = c->mdl.d, M = d * (c->T - t), cur = c->cur;
+  hipStream_t st = c->stream;
+  HIPCHK(launch_unpack_P(c->lay, d, c->Pt[cur], c->Pb[cur], c->F[cur], nullptr, N, s->d_Pfull, st));
+  const double* dyf = s->d_dyref + (size_t)t * d * n;              // [(T-t)*d x n] row-major (:163-166)
+  GemmArgs g1{M, n, n, dyf, n, 1, 0, s->d_Pfull, 1, n, (long)((size_t)n * n), s->d_G, n, 1, (long)((size_t)M * n)};
+  HIPCHK(launch_gemm(g1, N, st));                                  // G_j = dy * P_j
+  GemmArgs g2{M, M, n, s->d_G, n, 1, (long)((size_t)M * n), dyf, 1, n, 0, s->d_S, 1, M, (long)((size_t)M * M)};
+  HIPCHK(launch_gemm(g2, N, st));                                  // S_j = G_j * dy'
+  CholArgs ca = chol_args(c, s->d_pant_log);
+  ca.mode = 0; ca.Msz = M; ca.Lbuf = s->d_L; ca.ldL = (long)chol_factor_doubles(M);
+  ca.S = s->d_S; ca.R = s->d_R; ca.yf = c->d_y + (size_t)t * d; ca.dyf = dyf; ca.xl = c->xl[cur];
+  ca.jitter = c->mdl.jitter;
+  HIPCHK(launch_chol(ca, N, 0, st));
+  return RBPF_OK;
+}
+
+static int info_anc_weights(rbpf_ctx* c, int t) {
+  SmootherState* s = c->sm;
+  const int N = c->N, n = c->mdl.n, d = c->mdl.d;
+  hipStream_t st = c->stream;
+  const int* anc = c->A + (size_t)(t - 1) * N;                          // ancestors of the generation t-1
+  RB_TRY(info_drop_term(c, t));
+  if (s->refresh > 1 && !refresh_due(s, t)) {
+    // Host-callback models cannot rebuild Imat from the state history at a refresh, so for them the exactly carried Imat is
+    // advanced every step by a copy kernel.
+    if (!s->lazy_imat) {
+      const int ni = s->imat_cur ^ 1;
+      HIPCHK(launch_imat_gather(n, d, c->lay.ldx, N, s->d_Imat[s->imat_cur], (long)((size_t)n * n), anc, s->d_Hb[s->icur], s->d_Rinv,
+                                s->d_Imat[ni], st));
+      s->imat_cur = ni;
+    }
+    SweepArgs sw = info_sweep_args(c, t, s->d_pant_log);
+    sw.ref_slot = N - 1; sw.anc = anc;
+    sw.order = (c->order_step == t - 1) ? c->d_order : nullptr;     // generation t-1 in the order its step ran in
+    // (measured r05, diagnostic build of commit 31144f4: the sweep on a second stream beside the step kernels of the same time
+    //  step -- only slot N_P's ancestor depends on it -- 7.39 -> 7.15 ms per step: not worth splitting that slot out)
+    HIPCHK(launch_chol_sweep(sw, st));
+    s->sw_cur ^= 1;
+    return RBPF_OK;
+  }
+  if (s->lazy_imat && s->refresh_free) return info_refresh_origin(c, t, s->d_pant_log, nullptr);
+  if (s->lazy_imat) {
+    // refresh: Imat of generation t-1 from the base generation + G'G along the ancestral paths, then factorise it
+    const int t0 = s->base_gen, Kp = t - 1 - t0;
+    if (Kp < 1 || Kp > s->refresh) { set_error("internal: refresh window"); return RBPF_ERR_STATE; }
+    hipLaunchKernelGGL(sweep_path_kernel, dim3((N + 127) / 128), dim3(128), 0, st, N, c->mdl.nN, Kp, t - 1, t0, c->A, c->X, s->d_base_slot, s->d_Xp);
+    HIPCHK(hipGetLastError());
+    return info_refresh_window(c, Kp, t0, s->d_pant_log, nullptr);
+  }
+  // from scratch, every step -- or, host-callback models with carried factors, at their refreshes: fresh factors -> sweep layout
+  HIPCHK(launch_chol(info_chol_args(c, s->d_pant_log, anc), N, d, st));
+  if (s->refresh > 1) {
+    RB_TRY(sweep_bank_from_chol64(c, N, 0));
+    s->sw_cur ^= 1;
+  }
+  return RBPF_OK;
+}
+
+// One information-form time step: the fused step kernel with the extra ivec / halfLogDetP state
+static int info_step(rbpf_ctx* c, int k, int t, const double* xref, int n_draw) {
+  InfoStep is;
+  const int nc = info_step_banks(c->sm, t, c->lay.ldx, is);
+  RB_TRY(ctx_step(c, k, xref, n_draw, &is));
+  c->sm->icur = nc;
+  return RBPF_OK;
+}
+
+// ---- ak = sample(w); xnk = xn_traj(:,ak,:) (:346-354), and iteration k's outputs ----
+static int iteration_end(rbpf_ctx* c, int k, rbpf_smoother_out* out) {
+  SmootherState* s = c->sm;
+  const int N = c->N, T = c->T, nN = c->mdl.nN, n = c->mdl.n;
+  int ak = 0;
+  RB_TRY(draw_reference_index(c, N, c->w + (c->opt.trace ? (size_t)(T - 1) * N : 0), c->wc, c->X, c->A, k, &ak));
+  HIPCHK(hipMemcpy(s->h_xnk.data(), s->d_xnk, (size_t)nN * T * 8, hipMemcpyDeviceToHost));
+  if (out->XNK) std::memcpy(out->XNK + (size_t)k * nN * T, s->h_xnk.data(), (size_t)nN * T * 8);
+  if (out->XLK) HIPCHK(hipMemcpy(out->XLK + (size_t)k * n, c->xl[c->xcur] + (size_t)ak * c->lay.ldx, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (out->PK) {
+    DevicePool pk;
+    double* dP = nullptr;
+    RB_TRY(pk.alloc(&dP, (size_t)n * n));
+    RB_TRY(ctx_unpack(c, s->d_ak, 1, dP));                // pending downdates applied
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out->PK + (size_t)k * n * n, dP, (size_t)n * n * 8, hipMemcpyDeviceToHost));
+  }
+  if (out->trace_ak) out->trace_ak[k] = ak;
+  if (c->opt.trace) {
+    if (out->trace_logw) HIPCHK(hipMemcpy(out->trace_logw + (size_t)k * N * T, c->logw, (size_t)N * T * 8, hipMemcpyDeviceToHost));
+    if (out->trace_w) HIPCHK(hipMemcpy(out->trace_w + (size_t)k * N * T, c->w, (size_t)N * T * 8, hipMemcpyDeviceToHost));
+    if (out->trace_ai) HIPCHK(hipMemcpy(out->trace_ai + (size_t)k * N * T, c->A, (size_t)N * T * 4, hipMemcpyDeviceToHost));
+    if (out->trace_paNt && k > 0)
+      HIPCHK(hipMemcpy(out->trace_paNt + (size_t)k * N * T, s->d_pant + (size_t)k * T * N, (size_t)N * T * 8, hipMemcpyDeviceToHost));
+  }
+  return ctx_call_on_step(c, k, true);                  // particleSmoother.m:360-362
+}
+
+// CPF-AS (Alg. 2), N_K iterations.  The generic family evaluates its handles on the host, in the reference's call order:
+// ordinary ancestors + dynModel (:132-137), dynResNorm, then the reference slot and measModel.
+static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* out) {
+  RB_TRY(smoother_setup(c, N_K, info_form));
+  SmootherState* s = c->sm;
+  const int N = c->N, T = c->T, nN = c->mdl.nN;
+  const bool generic = c->mdl.kind == RBPF_MODEL_GENERIC_DENSE;
   for (int k = 0; k < N_K; ++k) {
     RB_TRY(ctx_reset(c));
-    if (info_form) {
-      RB_TRY(info_begin_iteration(c, ivec0.data(), hld0, qf0, halfLogDetR, d_Rinv));
-    }
-    if (k > 0 && !sparse) {
-      // dy_xnk = measModel(xnk)  (:120)
-      if (generic) {
-        std::vector<double> dyT((size_t)T * d * n), Href((size_t)T * d * n);
-        if (c->cb.meas_model(c->cb.user, T, xnk_h.data(), dyT.data()) != 0) { set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK; }
-        for (int cc = 0; cc < n; ++cc)                   // dy(tt, a, cc) at tt + T*(a + d*cc) -> [T][d][n]
-          for (int a = 0; a < d; ++a)
-            for (int tt = 0; tt < T; ++tt) Href[((size_t)tt * d + a) * n + cc] = dyT[(size_t)tt + (size_t)T * (a + (size_t)d * cc)];
-        HIPCHK(hipMemcpy(s->d_dyref, Href.data(), Href.size() * 8, hipMemcpyHostToDevice));
-      } else
-      HIPCHK(launch_meas_model(c->mdl, T, s->d_xnk, s->d_dyref, st, 1));
-      if (info_form) {                                                       // :132-146
-        HIPCHK(hipMemsetAsync(s->d_ImatAdd, 0, (size_t)n * n * 8, st));
-        HIPCHK(hipMemsetAsync(s->d_ivecAdd, 0, (size_t)n * 8, st));
-        hipLaunchKernelGGL(info_addt_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, st, n, d, 0, T,
-                           1.0, s->d_dyref, d_Rinv, c->d_y, s->d_ImatAdd, s->d_ivecAdd, s->imat_packed ? 1 : 0);
-        HIPCHK(hipGetLastError());
-      }
+    if (s->form == SmootherForm::Info) RB_TRY(info_begin_iteration(c));
+    if (k > 0 && s->form != SmootherForm::Sparse) {
+      RB_TRY(reference_jacobians(c));
+      if (s->form == SmootherForm::Info) RB_TRY(info_reference_sums(c));
     }
     for (int t = 0; t < T; ++t) {
       const double* xref = (k > 0) ? s->d_xnk + (size_t)t * nN : nullptr;
-      int n_draw = N;
-      if (k > 0 && t > 0) n_draw = N - 1;
-      // generic family: ordinary ancestors + dynModel on the host first, in the reference's call order (:132-137)
+      const int n_draw = (k > 0 && t > 0) ? N - 1 : N;
       if (generic) RB_TRY(generic_draw_propagate(c, k, n_draw));
       if (k > 0 && t > 0) {
-        // ---- ancestor weights of the reference trajectory (Steps 9-10 of Alg. 2) ----
-        const double* X_prev = c->X + (size_t)(t - 1) * nN * N;
-        const size_t tr_prev = c->opt.trace ? (size_t)(t - 1) * N : 0;
-        const double* w_prev = c->w + tr_prev;
-        const double* Lq = c->d_cholQfull + (size_t)((c->chol_pages > 1) ? t - 1 : 0) * nw * nw;
-        if (drn_cb) {
-          h_edyn.assign((size_t)N * nw, 0.0);
-          if (c->cb.dyn_res_norm(c->cb.user, t - 1, N, xnk_h.data() + (size_t)t * nN, c->h_xn.data(), h_edyn.data()) != 0) {
-            set_error("the dynResNorm callback failed"); return RBPF_ERR_CALLBACK;
-          }
-          HIPCHK(hipMemcpyAsync(d_edyn, h_edyn.data(), h_edyn.size() * 8, hipMemcpyHostToDevice, st));
-          hipLaunchKernelGGL(anc_dyn_ext_kernel, dim3((N + 63) / 64), dim3(64), 0, st, N, nw, d_edyn, w_prev, s->d_pant_log);
-          HIPCHK(hipGetLastError());
-          HIPCHK(hipStreamSynchronize(st));
-        } else {
-        hipLaunchKernelGGL(anc_dyn_kernel, dim3((N + 63) / 64), dim3(64), 0, st, c->mdl, N, X_prev, xref,
-                           c->d_odo + (size_t)(t - 1) * c->mdl.nodo, Lq, w_prev, s->d_pant_log);
-        HIPCHK(hipGetLastError());
-        }
-        const int cur = c->cur;
-        CholArgs ca;
-        std::memset(&ca, 0, sizeof(ca));
-        ca.d = d; ca.n = n; ca.ldx = L.ldx; ca.pant_log = s->d_pant_log; ca.status = c->d_flags;
-        ca.variant = c->opt.chol_variant;
-        bool skip_chol = false;
-        if (sparse) {
-          const int M = pair_off[T] - pair_off[t];
-          skip_chol = (M == 0);                                            // no future observation: logwMeas = 0
-          SparseAncArgs aa;
-          aa.n = n; aa.d = d; aa.nN = nN; aa.ldx = L.ldx; aa.ldb = L.ldb; aa.M = M; aa.off = pair_off[t]; aa.szB = L.szB;
-          aa.f = c->mdl.cam[0]; aa.fp = c->mdl.cam[1]; aa.pair_t = d_pair_t; aa.pair_j = d_pair_j; aa.xnk = s->d_xnk;
-          aa.y = c->d_y; aa.xl = c->xl[cur]; aa.Pb = c->Pb[cur]; aa.R = c->d_R; aa.rhs = s->d_e; aa.S = s->d_S;
-          HIPCHK(launch_sparse_anc(aa, N, st));
-          ca.mode = 0; ca.Msz = M; ca.Lbuf = s->d_L; ca.ldL = (long)chol_factor_doubles(M);
-          ca.S = s->d_S; ca.R = nullptr; ca.rhs = s->d_e; ca.jitter = c->mdl.jitter;
-        } else if (!info_form) {
-          const int M = d * (T - t);
-          HIPCHK(launch_unpack_P(L, d, c->Pt[cur], c->Pb[cur], c->F[cur], nullptr, N, s->d_Pfull, st));
-          const double* dyf = s->d_dyref + (size_t)t * d * n;              // [(T-t)*d x n] row-major (:163-166)
-          GemmArgs g1{M, n, n, dyf, n, 1, 0, s->d_Pfull, 1, n, (long)((size_t)n * n), s->d_G, n, 1, (long)((size_t)M * n)};
-          HIPCHK(launch_gemm(g1, N, st));                                  // G_j = dy * P_j
-          GemmArgs g2{M, M, n, s->d_G, n, 1, (long)((size_t)M * n), dyf, 1, n, 0, s->d_S, 1, M, (long)((size_t)M * M)};
-          HIPCHK(launch_gemm(g2, N, st));                                  // S_j = G_j * dy'
-          ca.mode = 0; ca.Msz = M; ca.Lbuf = s->d_L; ca.ldL = (long)chol_factor_doubles(M);
-          ca.S = s->d_S; ca.R = d_R; ca.yf = c->d_y + (size_t)t * d; ca.dyf = dyf; ca.xl = c->xl[cur];
-          ca.jitter = c->mdl.jitter;
-        } else {
-          // the (t-1) term leaves the suffix sums (:194-201)
-          hipLaunchKernelGGL(info_addt_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, st, n, d,
-                             t - 1, t, -1.0, s->d_dyref, d_Rinv, c->d_y, s->d_ImatAdd, s->d_ivecAdd, s->imat_packed ? 1 : 0);
-          HIPCHK(hipGetLastError());
-          const bool carry = s->refresh > 1;
-          const bool fresh = !carry || t == 1 || ((t - 1) % s->refresh) == 0;
-          if (carry && !fresh) {
-            // carried factors: one sweep per particle turns the ancestor's factor into this particle's and adds logwMeas
-            // (rbpf_chol_sweep.hpp).  Host-callback models cannot rebuild Imat from the state history at a refresh, so for
-            // them the exactly carried Imat is advanced every step by a copy kernel.
-            if (!s->lazy_imat) {
-              const int ni = s->imat_cur ^ 1;
-              HIPCHK(launch_imat_gather(n, d, L.ldx, N, s->d_Imat[s->imat_cur], (long)((size_t)n * n), c->A + (size_t)(t - 1) * N,
-                                        s->d_Hb[s->icur], d_Rinv, s->d_Imat[ni], st));
-              s->imat_cur = ni;
-            }
-            SweepArgs sw;
-            sw.n = n; sw.d = d; sw.ldx = L.ldx; sw.NS = sweep_slots(n); sw.tailc = sweep_tail_compact(n); sw.N = N; sw.ref_slot = N - 1;
-            sw.Lold = s->d_Lsw[s->sw_cur]; sw.Lnew = s->d_Lsw[s->sw_cur ^ 1]; sw.stride = sweep_factor_doubles(n);
-            sw.anc = c->A + (size_t)(t - 1) * N; sw.Hb = s->d_Hb[s->icur]; sw.Href = s->d_dyref + (size_t)(t - 1) * d * n;
-            sw.W = s->d_W; sw.yt = c->d_y + (size_t)(t - 1) * d; sw.qf = s->d_qf[s->icur]; sw.hld = s->d_hld[s->icur];
-            sw.pant_log = s->d_pant_log; sw.status = c->d_flags;
-            sw.order = (c->order_step == t - 1) ? c->d_order : nullptr;     // generation t-1 in the order its step ran in
-            // (measured r05, diagnostic build of commit 31144f4: the sweep on a second stream beside the step kernels of the same time
-            //  step -- only slot N_P's ancestor depends on it -- 7.39 -> 7.15 ms per step: not worth splitting that slot out)
-            HIPCHK(launch_chol_sweep(sw, st));
-            s->sw_cur ^= 1;
-            skip_chol = true;
-          } else if (carry && s->lazy_imat) {
-            // refresh: Imat of generation t-1 from the base generation + G'G along the ancestral paths, then factorise it
-            if (s->refresh_free) {
-              // No information matrix is stored: Imat_i(t-1) = Imat0 + sum over the WHOLE ancestral path of H' R^-1 H (:334's terms, in
-              // another order of summation), accumulated segment by segment into a chunk buffer, then chol(Imat + ImatAddt) out of it
-              // and the factors into the sweep layout.  Cost grows with t; the marks make every segment's walk O(seg_len).
-              const int S = s->seg_len, n_gen = t, n_seg = (n_gen + S - 1) / S;        // generations 0 .. t-1; segment j = [hi_j - len_j, hi_j), hi_0 = t
-              hipLaunchKernelGGL(origin_marks_kernel, dim3((N + 127) / 128), dim3(128), 0, st, N, t - 1, S, c->A, s->d_marks);
-              HIPCHK(hipGetLastError());
-              for (int p0 = 0; p0 < N; p0 += s->l_chunk) {
-                const int cnt = std::min(s->l_chunk, N - p0);
-                for (int j = 0; j < n_seg; ++j) {
-                  const int hi = n_gen - j * S, lo = std::max(0, hi - S), len = hi - lo;
-                  hipLaunchKernelGGL(origin_segment_kernel, dim3((cnt + 127) / 128), dim3(128), 0, st, N, nN, p0, cnt, lo, hi, c->A, c->X,
-                                     s->d_marks + (size_t)j * N, s->d_Xp);
-                  HIPCHK(hipGetLastError());
-                  HIPCHK(launch_meas_model(c->mdl, cnt * len, s->d_Xp, s->d_G, st, 1));
-                  const size_t rows = (size_t)cnt * len;
-                  hipLaunchKernelGGL(sweep_whiten_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, st, rows, d, n, s->d_W, s->d_G);
-                  HIPCHK(hipGetLastError());
-                  const long Kd = (long)len * d;
-                  GemmArgs gg{n, n, (int)Kd, s->d_G, 1, n, Kd * n, s->d_G, n, 1, Kd * n, s->d_Imat[0], 1, n, (long)s->imat_len};
-                  gg.lower = 1; gg.packed = s->imat_packed ? 1 : 0;
-                  if (j == 0) { gg.add = s->d_Imat0; gg.add_stride = 0L; gg.add_idx = nullptr; }
-                  else gg.add_self = 1;
-                  HIPCHK(launch_gemm(gg, cnt, st));
-                }
-                RB_TRY(refresh_factorise(c, d_Rinv, s->d_pant_log, cnt, st, p0, s->d_Imat[0]));
-              }
-              s->imat_valid = false; s->base_gen = t - 1;
-              s->sw_cur ^= 1;
-              skip_chol = true;
-            } else {
-            const int t0 = s->base_gen, Kp = t - 1 - t0;
-            if (Kp < 1 || Kp > s->refresh) { set_error("internal: refresh window"); return RBPF_ERR_STATE; }
-            const int ni = s->imat_valid ? (s->imat_cur ^ 1) : 0;
-            hipLaunchKernelGGL(sweep_path_kernel, dim3((N + 127) / 128), dim3(128), 0, st, N, nN, Kp, t - 1, t0, c->A, c->X, s->d_base_slot, s->d_Xp);
-            HIPCHK(hipGetLastError());
-            HIPCHK(launch_meas_model(c->mdl, N * Kp, s->d_Xp, s->d_G, st, 1));
-            const size_t rows = (size_t)N * Kp;
-            hipLaunchKernelGGL(sweep_whiten_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, st, rows, d, n, s->d_W, s->d_G);
-            HIPCHK(hipGetLastError());
-            const long Kd = (long)Kp * d;
-            GemmArgs gg{n, n, (int)Kd, s->d_G, 1, n, Kd * n, s->d_G, n, 1, Kd * n, s->d_Imat[ni], 1, n, (long)s->imat_len};
-            gg.lower = 1;                                                      // the factorisation reads the block-lower part
-            gg.packed = s->imat_packed ? 1 : 0;
-            gg.add = t0 < 0 ? s->d_Imat0 : s->d_Imat[s->imat_cur];             // + the base matrix, in the epilogue
-            gg.add_stride = t0 < 0 ? 0L : (long)s->imat_len;
-            gg.add_idx = t0 < 0 ? (const int*)nullptr : s->d_base_slot;
-            HIPCHK(launch_gemm(gg, N, st));                                   // Imat = base + G' G
-            s->imat_cur = ni; s->imat_valid = true; s->base_gen = t - 1;
-            RB_TRY(refresh_factorise(c, d_Rinv, s->d_pant_log, N, st));        // chol(Imat + ImatAddt), chunk by chunk -> sweep layout
-            s->sw_cur ^= 1;
-            skip_chol = true;
-            }
-          } else {
-            RB_TRY(info_fill_chol_args(c, ca, d_Rinv, c->A + (size_t)(t - 1) * N));   // ancestors of the generation t-1
-            if (carry) ca.variant = 64;            // the refresh reads the factor back in the 64-column kernel's layout
-          }
-        }
-        if (!skip_chol) HIPCHK(launch_chol(ca, N, ca.mode == 1 ? d : 0, st));
-        HIPCHK(hipGetLastError());
-        if (info_form && s->refresh > 1 && !skip_chol) {                    // fresh factors -> sweep layout (host-callback models)
-          HIPCHK(launch_sweep_from_chol64(n, N, s->d_L, chol_factor_doubles(n), s->d_Lsw[s->sw_cur ^ 1], sweep_factor_doubles(n), st));
-          s->sw_cur ^= 1;
-        }
-        // normalise (:236-238), sample ai(N_P) (:241)
+        // ancestor weights of the reference trajectory (Steps 9-10), normalise (:236-238), sample ai(N_P) (:241)
+        RB_TRY(anc_dyn_weights(c, t));
+        RB_TRY(s->form == SmootherForm::Sparse ? sparse_anc_weights(c, t) : s->form == SmootherForm::Cov ? cov_anc_weights(c, t) : info_anc_weights(c, t));
         RB_TRY(normalise_draw_one(c, N, t, k, s->d_pant_log, s->d_pant + (c->opt.trace ? ((size_t)k * T + t) * N : 0), s->d_wc2, N - 1,
-                                  c->d_U ? c->d_U + ((size_t)k * (T - 1) + (t - 1)) * N : nullptr, c->A + (size_t)t * N, st));
+                                  c->d_U ? c->d_U + ((size_t)k * (T - 1) + (t - 1)) * N : nullptr, c->A + (size_t)t * N, c->stream));
       }
-      if (generic) RB_TRY(generic_finish_inputs(c, k > 0 ? xnk_h.data() + (size_t)t * nN : nullptr));
-      const int st_step = info_form ? info_step(c, k, t, xref, n_draw, d_Rinv) : ctx_step(c, k, xref, n_draw, nullptr);
+      if (generic) RB_TRY(generic_finish_inputs(c, k > 0 ? s->h_xnk.data() + (size_t)t * nN : nullptr));
+      const int st_step = s->form == SmootherForm::Info ? info_step(c, k, t, xref, n_draw) : ctx_step(c, k, xref, n_draw, nullptr);
       if (generic) { c->ext_xn = nullptr; c->ext_H = nullptr; }
       RB_TRY(st_step);
     }
-    // ---- ak = sample(w); xnk = xn_traj(:,ak,:) (:346-354) ----
-    {
-      const size_t tr_last = c->opt.trace ? (size_t)(T - 1) * N : 0;
-      double* d_uf = c->d_scal;
-      if (c->rng_mode == RBPF_RNG_REPLAY) {
-        HIPCHK(hipMemcpyAsync(d_uf, &c->h_Ufin[k], 8, hipMemcpyHostToDevice, st));
-      }
-      SearchArgs sa;
-      sa.N = N; sa.n_draw = 1; sa.t = T; sa.wc = c->wc; sa.rng_mode = c->rng_mode; sa.k_iter = k; sa.slot0 = 0;
-      sa.U = d_uf; sa.seed = c->seed; sa.ai = s->d_ak; sa.overflow = c->d_flags + 1;
-      sa.u_is_scalar = 1;
-      sa.approx = 1; sa.ambiguous = c->d_flags + 4; sa.w = c->w + (c->opt.trace ? (size_t)(T - 1) * N : 0); sa.wc_exact = c->wc;
-      HIPCHK(launch_search(sa, st));
-      HIPCHK(launch_resample_fixup(sa, st));
-      (void)tr_last;
-      HIPCHK(launch_backtrace(N, nN, T, c->X, c->A, s->d_ak, 1, s->d_xnk, st));
-      int ak = 0;
-      HIPCHK(hipMemcpyAsync(&ak, s->d_ak, 4, hipMemcpyDeviceToHost, st));
-      RB_TRY(ctx_check_flags(c));
-      const int cur = c->cur;
-      HIPCHK(hipMemcpy(xnk_h.data(), s->d_xnk, (size_t)nN * T * 8, hipMemcpyDeviceToHost));
-      if (out->XNK) std::memcpy(out->XNK + (size_t)k * nN * T, xnk_h.data(), (size_t)nN * T * 8);
-      (void)cur;
-      if (out->XLK) HIPCHK(hipMemcpy(out->XLK + (size_t)k * n, c->xl[c->xcur] + (size_t)ak * L.ldx, (size_t)n * 8, hipMemcpyDeviceToHost));
-      if (out->PK) {
-        DevicePool pk;
-        double* dP = nullptr;
-        RB_TRY(pk.alloc(&dP, (size_t)n * n));
-        RB_TRY(ctx_unpack(c, s->d_ak, 1, dP));                // pending downdates applied
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipMemcpy(out->PK + (size_t)k * n * n, dP, (size_t)n * n * 8, hipMemcpyDeviceToHost));
-      }
-      if (out->trace_ak) out->trace_ak[k] = ak;
-      if (c->opt.trace) {
-        if (out->trace_logw) HIPCHK(hipMemcpy(out->trace_logw + (size_t)k * N * T, c->logw, (size_t)N * T * 8, hipMemcpyDeviceToHost));
-        if (out->trace_w) HIPCHK(hipMemcpy(out->trace_w + (size_t)k * N * T, c->w, (size_t)N * T * 8, hipMemcpyDeviceToHost));
-        if (out->trace_ai) HIPCHK(hipMemcpy(out->trace_ai + (size_t)k * N * T, c->A, (size_t)N * T * 4, hipMemcpyDeviceToHost));
-        if (out->trace_paNt && k > 0)
-          HIPCHK(hipMemcpy(out->trace_paNt + (size_t)k * N * T, s->d_pant + (size_t)k * T * N, (size_t)N * T * 8, hipMemcpyDeviceToHost));
-      }
-      RB_TRY(ctx_call_on_step(c, k, true));              // particleSmoother.m:360-362
-    }
+    RB_TRY(iteration_end(c, k, out));
   }
-  return RBPF_OK;
-}
-
-static int info_begin_iteration(rbpf_ctx* c, const double* ivec0, double hld0, double, double, const double*) {
-  SmootherState* s = c->sm;
-  const Layout& L = c->lay;
-  if (!s->d_ivec0) {
-    RB_TRY(s->pool.alloc(&s->d_ivec0, (size_t)L.ldx));
-    RB_TRY(s->pool.alloc(&s->d_hld0, 1));
-  }
-  HIPCHK(hipMemcpyAsync(s->d_ivec0, ivec0, (size_t)L.ldx * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(s->d_hld0, &hld0, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));       // host sources are stack / caller memory
-  s->icur = 0;
-  s->imat_cur = 0;
-  s->imat_valid = false;
-  s->base_gen = -1;
-  return RBPF_OK;
-}
-
-// Arguments of the information-form ancestor-weight factorisation of the step about to run (t >= 1).  The kernel
-// also forms the information matrices of the current generation, Imat(:,:,i) = Imat(:,:,ai(i)) + dyi'/R*dyi
-// (:170,:253,:334), from the previous generation's bank (entry anc[i]; generation 0 starts from Imat0) and stores
-// them into the other bank: the gather `Imat = Imat(:,:,ai)` costs one extra write instead of a copy kernel.
-static int info_fill_chol_args(rbpf_ctx* c, CholArgs& ca, const double* d_Rinv, const int* anc) {
-  SmootherState* s = c->sm;
-  const int n = c->mdl.n;
-  const int ni = s->imat_valid ? (s->imat_cur ^ 1) : 0;
-  ca.mode = 1; ca.Msz = n; ca.Lbuf = s->d_L; ca.ldL = (long)chol_factor_doubles(n);
-  ca.Imat = s->imat_valid ? s->d_Imat[s->imat_cur] : s->d_Imat0;
-  ca.imat_stride = s->imat_valid ? (long)s->imat_len : 0;
-  ca.imat_anc = s->imat_valid ? anc : nullptr;
-  ca.ImatOut = s->d_Imat[ni]; ca.imat_out_stride = (long)s->imat_len; ca.imat_packed = s->imat_packed ? 1 : 0;
-  ca.Hb = s->d_Hb[s->icur]; ca.Rinv = d_Rinv; ca.ImatAdd = s->d_ImatAdd; ca.ivec = s->d_ivec[s->icur];
-  ca.ivecAdd = s->d_ivecAdd; ca.qf = s->d_qf[s->icur]; ca.hld = s->d_hld[s->icur];
-  s->imat_cur = ni;                 // after the launch the new bank is the current one
-  s->imat_valid = true;
-  // nothing reads the factors of this launch afterwards unless they are carried on (chol_refresh): let the 64-column kernel
-  // run persistent workgroups over one workspace slot each (rbpf_chol64.hpp)
-  ca.l_slots = (s->refresh > 1) ? 0 : chol64_workspace_slots(n);
-  return RBPF_OK;
-}
-
-// One information-form time step: the fused step kernel with the extra ivec / halfLogDetP state,
-// followed (k>1) by the gather + pending update of the information matrices (:170,:186,:253,:334).
-static int info_step(rbpf_ctx* c, int k, int t, const double* xref, int n_draw, const double* d_Rinv) {
-  SmootherState* s = c->sm;
-  const int N = c->N, n = c->mdl.n, d = c->mdl.d;
-  const Layout& L = c->lay;
-  const int oc = s->icur, nc = (t == 0) ? 0 : (oc ^ 1);
-  InfoStep is;
-  if (t == 0) { is.ivec_old = s->d_ivec0; is.ivec_old_stride = 0; is.hld_old = s->d_hld0; is.hld_old_stride = 0; }
-  else { is.ivec_old = s->d_ivec[oc]; is.ivec_old_stride = (size_t)L.ldx; is.hld_old = s->d_hld[oc]; is.hld_old_stride = 1; }
-  is.ivec_new = s->d_ivec[nc]; is.hld_new = s->d_hld[nc]; is.qf_new = s->d_qf[nc]; is.Hb_new = s->d_Hb[nc];
-  RB_TRY(ctx_step(c, k, xref, n_draw, &is));
-  (void)N; (void)n; (void)d; (void)d_Rinv;
-  s->icur = nc;
   return RBPF_OK;
 }
 
@@ -1436,7 +1576,6 @@ int rbpf_shard_smoother_create(const rbpf_model* model, const rbpf_problem* prob
   RB_TRY(shard_create_impl(model, prob, rng, opt, rank, world, true, N_K, &c));
   std::unique_ptr<rbpf_ctx, void (*)(rbpf_ctx*)> guard(c, [](rbpf_ctx* p) { ctx_free(p); });
   const int N = c->N, T = c->T, nN = c->mdl.nN, n = c->mdl.n, d = c->mdl.d, nw = c->mdl.nw;
-  const Layout& L = c->lay;
   if (!c->mdl.use_dyn_res_norm && nw != nN) {
     set_error("isempty(dynResNorm): the additive default (particleSmoother.m:176) needs size(Q,1) == nNonLin");
     return RBPF_ERR_INVALID_ARG;
@@ -1444,59 +1583,21 @@ int rbpf_shard_smoother_create(const rbpf_model* model, const rbpf_problem* prob
   if (n > 1023) { set_error("information-form smoother supports nLin <= 1023"); return RBPF_ERR_UNSUPPORTED; }
   SmootherState* s = new SmootherState();
   c->sm = s;
-  {
-    const int K = resolve_chol_refresh(c->mdl.kind, n, d, effective_chol_refresh(c->opt));
-    s->refresh = K > 1 ? K : 0;
-  }
+  info_resolve_options(c);
   if (s->refresh && c->mdl.kind == RBPF_MODEL_GENERIC_DENSE) { set_error("chol_refresh > 1 in the sharded smoother needs measModel on the device"); return RBPF_ERR_UNSUPPORTED; }
   if (c->opt.info_rebuild > 0 && s->refresh < T - 1) { set_error("info_rebuild = 1 with refreshes is a single-device option (the sharded smoother exchanges stored information matrices at its refreshes; chol_refresh >= N_T - 1 never refreshes and stores none)"); return RBPF_ERR_UNSUPPORTED; }
   if (s->refresh > 256 && s->refresh < T - 1) { set_error("sharded smoother: chol_refresh between 257 and N_T - 2 is not supported (choose <= 256, or >= N_T - 1: never refresh)"); return RBPF_ERR_UNSUPPORTED; }
-  s->lazy_imat = s->refresh > 1;
-  // chol_refresh >= N_T - 1: the factors are never refactorised after t = 1 -- no information matrix is stored or exchanged, the first
-  // factorisation runs chunk by chunk (as in the single-device smoother, smoother_run)
-  s->refresh_free = s->lazy_imat && s->refresh >= T - 1;
-  s->seg_len = 32;
+  // (what is left: every step from scratch, a window of K <= 256 generations, or chol_refresh >= N_T - 1 -- the factors are never
+  //  refactorised after t = 1, no information matrix is stored or exchanged)
   RB_TRY(s->pool.alloc(&s->d_xnk, (size_t)T * nN));
   RB_TRY(s->pool.alloc(&s->d_dyref, (size_t)T * d * n));
   RB_TRY(s->pool.alloc(&s->d_ak, 4));
-  s->imat_packed = imat_storage_packed(n, d, s->refresh, true);
-  s->imat_len = s->imat_packed ? imat_packed_doubles(n) : (size_t)n * n;
-  s->l_chunk = s->lazy_imat ? std::min(N, 4096) : N;
-  for (int b = 0; b < 2; ++b) {
-    const size_t n_mat = s->refresh_free ? (b == 0 ? (size_t)s->l_chunk : (size_t)0) : (size_t)N;
-    RB_TRY(s->pool.alloc(&s->d_Imat[b], std::max<size_t>(n_mat * s->imat_len, 1)));   // (refresh-free: bank 1 is a kernel argument nobody reads)
-    if (s->imat_packed && n_mat) HIPCHK(hipMemset(s->d_Imat[b], 0, n_mat * s->imat_len * 8));
-    RB_TRY(s->pool.alloc(&s->d_Hb[b], (size_t)N * d * L.ldx));
-    RB_TRY(s->pool.alloc(&s->d_ivec[b], (size_t)N * L.ldx));
-    RB_TRY(s->pool.alloc(&s->d_hld[b], (size_t)N));
-    RB_TRY(s->pool.alloc(&s->d_qf[b], (size_t)N));
-  }
-  RB_TRY(s->pool.alloc(&s->d_L, (size_t)s->l_chunk * chol_factor_doubles(n)));
-  RB_TRY(s->pool.alloc(&s->d_ImatAdd, (size_t)n * n));
-  RB_TRY(s->pool.alloc(&s->d_ivecAdd, (size_t)n));
-  RB_TRY(s->pool.alloc(&s->d_Imat0, (size_t)n * n));
-  RB_TRY(s->pool.alloc(&s->d_Rinv, (size_t)d * d));
-  std::vector<double> Rinv((size_t)d * d), Imat0((size_t)n * n, 0.0);
-  double halfLogDetR = 0.0;
-  RB_TRY(invert_R(c->h_R, d, Rinv, halfLogDetR));
-  s->h_ivec0.assign(L.ldx, 0.0);
-  info_initial_values(c, s->h_ivec0, Imat0, s->hld0);
-  HIPCHK(hipMemcpy(s->d_Rinv, Rinv.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
-  {
-    const std::vector<double> Imat0s = imat_host_storage(Imat0, n, s->imat_packed);
-    HIPCHK(hipMemcpy(s->d_Imat0, Imat0s.data(), Imat0s.size() * 8, hipMemcpyHostToDevice));
-  }
+  std::vector<double> Rinv((size_t)d * d);
+  RB_TRY(invert_R(c->h_R, d, Rinv));
+  RB_TRY(info_state_create(c, Rinv, true));
   if (s->refresh) {
-    // carried ancestor-weight factors (rbpf_chol_sweep.hpp): factor banks, the buffers of the refresh from the state history,
-    // and the exchange buffers for base matrices that sit on another rank
-    if (sweep_slots(n) > kSweepMaxSlots || chol64_lds_bytes(n, d) > kC64MaxLds || (d != 1 && d != 3)) { set_error("chol_refresh > 1 supports nLin <= 575 and n_y = 1 or 3"); return RBPF_ERR_UNSUPPORTED; }
+    // the buffers of the refresh from the replicated state history, and the exchange buffers for base matrices that sit on another rank
     ShardState* sh = c->sh;
-    for (int b = 0; b < 2; ++b) RB_TRY(s->pool.alloc(&s->d_Lsw[b], (size_t)N * sweep_factor_doubles(n)));
-    RB_TRY(s->pool.alloc(&s->d_W, (size_t)d * d));
-    std::vector<double> Wm;
-    whitening_factor(c->h_R, d, Wm);
-    HIPCHK(hipMemcpy(s->d_W, Wm.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
-    RB_TRY(s->pool.alloc(&s->d_base_slot, (size_t)N));
     const size_t Kwin = s->refresh_free ? 1 : (size_t)s->refresh;        // generations a refresh walks back
     RB_TRY(s->pool.alloc(&s->d_Xp, (size_t)N * Kwin * nN));
     RB_TRY(s->pool.alloc(&s->d_G, (s->refresh_free ? (size_t)s->l_chunk : (size_t)N) * Kwin * d * n));
@@ -1533,20 +1634,15 @@ int rbpf_shard_smoother_begin(rbpf_ctx* c, int32_t k) {
   SmootherState* s = c->sm;
   ShardState* sh = c->sh;
   if (k < 0 || k >= c->N_K) { set_error("iteration out of range"); return RBPF_ERR_INVALID_ARG; }
-  const int T = c->T, n = c->mdl.n, d = c->mdl.d;
   RB_TRY(ctx_reset(c));
   sh->t_norm = 0; sh->placed = false; sh->plan_ready = false; sh->host_planned = false; sh->gid_cur = 0; sh->cur_gid = nullptr;
   sh->rec_used = 0; sh->plan_recv = 0; sh->k_iter = k;
   std::fill(sh->rec_used_all.begin(), sh->rec_used_all.end(), 0);
-  RB_TRY(info_begin_iteration(c, s->h_ivec0.data(), s->hld0, 0.0, 0.0, s->d_Rinv));
+  RB_TRY(info_begin_iteration(c));
   s->sw_valid = false; s->rf_stage = 0;
   if (k > 0) {
-    HIPCHK(launch_meas_model(c->mdl, T, s->d_xnk, s->d_dyref, c->stream, 1));           // :120
-    HIPCHK(hipMemsetAsync(s->d_ImatAdd, 0, (size_t)n * n * 8, c->stream));
-    HIPCHK(hipMemsetAsync(s->d_ivecAdd, 0, (size_t)n * 8, c->stream));
-    hipLaunchKernelGGL(info_addt_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, c->stream, n, d, 0, T,
-                       1.0, s->d_dyref, s->d_Rinv, c->d_y, s->d_ImatAdd, s->d_ivecAdd, s->imat_packed ? 1 : 0);   // :132-146
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_meas_model(c->mdl, c->T, s->d_xnk, s->d_dyref, c->stream, 1));        // :120
+    RB_TRY(info_reference_sums(c));
   }
   return RBPF_OK;
 }
@@ -1561,60 +1657,40 @@ int rbpf_shard_smoother_normalise(rbpf_ctx* c, int32_t want_draw) {
   return shard_normalise_impl(c, nullptr, want_draw ? draw_only_tag() : nullptr, sh->k_iter, n_draw);
 }
 
-// k > 1, t > 1: the measurement part of my particles' ancestor log-weights for the step about to run (:205-236) -> anc_local
-// [N_local] (physical order), BEFORE the all_gather of the forward bank, which carries it along.  Synchronises unless async.
 // Start of the MEASUREMENT part of my particles' ancestor log-weights (logwMeas, :205-236) in anc_local -- the extra row of the
 // forward bank, so that one all_gather carries it with the states and log-weights -- and the (t-1) term out of the suffix
 // sums.  It needs nothing from other ranks; the dynResNorm part and log w are added for all N particles after the gather
 // (rbpf_shard_smoother_anc_sample), in the reference's order of summation.
 static int shard_anc_meas_begin(rbpf_ctx* c) {
-  SmootherState* s = c->sm;
   ShardState* sh = c->sh;
-  const int t = c->t, k = sh->k_iter, n = c->mdl.n, d = c->mdl.d;
+  const int t = c->t, k = sh->k_iter;
   if (k < 1 || t < 1 || t >= c->T) { set_error("ancestor weights need k > 0 and 0 < t < N_T"); return RBPF_ERR_STATE; }
-  hipStream_t st = c->stream;
-  HIPCHK(hipMemsetAsync(sh->anc_local, 0, (size_t)sh->Nloc * sizeof(double), st));
-  // the (t-1) term leaves the suffix sums (:194-201)
-  hipLaunchKernelGGL(info_addt_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, st, n, d, t - 1, t, -1.0,
-                     s->d_dyref, s->d_Rinv, c->d_y, s->d_ImatAdd, s->d_ivecAdd, s->imat_packed ? 1 : 0);
-  HIPCHK(hipGetLastError());
-  return RBPF_OK;
+  HIPCHK(hipMemsetAsync(sh->anc_local, 0, (size_t)sh->Nloc * sizeof(double), c->stream));
+  return info_drop_term(c, t);
 }
-
-static bool shard_refresh_due(const SmootherState* s, int t) { return s->refresh > 1 && (t == 1 || ((t - 1) % s->refresh) == 0); }
 
 int rbpf_shard_smoother_anc_weights(rbpf_ctx* c) {
   if (!c || !c->sh || !c->sm) { set_error("not a sharded smoother context"); return RBPF_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
   SmootherState* s = c->sm;
   ShardState* sh = c->sh;
-  const int t = c->t, N = sh->Nloc, n = c->mdl.n, d = c->mdl.d;
+  const int t = c->t, N = sh->Nloc;
   hipStream_t st = c->stream;
-  if (shard_refresh_due(s, t)) { set_error("carried factors: this step refreshes them (rbpf_shard_smoother_refresh_begin / _pack / _end)"); return RBPF_ERR_STATE; }
+  if (refresh_due(s, t)) { set_error("carried factors: this step refreshes them (rbpf_shard_smoother_refresh_begin / _pack / _end)"); return RBPF_ERR_STATE; }
   RB_TRY(shard_anc_meas_begin(c));
   if (s->refresh > 1) {
     // carried factors: one sweep turns the ancestor's factor -- bank entry or received record -- into this particle's
     if (!s->sw_valid || !sh->placed) { set_error("carried factors: no factor bank for the previous generation"); return RBPF_ERR_STATE; }
-    SweepArgs sw;
-    sw.n = n; sw.d = d; sw.ldx = c->lay.ldx; sw.NS = sweep_slots(n); sw.tailc = sweep_tail_compact(n); sw.N = N; sw.ref_slot = -1;
-    sw.Lold = s->d_Lsw[s->sw_cur]; sw.Lnew = s->d_Lsw[s->sw_cur ^ 1]; sw.stride = sweep_factor_doubles(n);
-    sw.anc = sh->pb.anc_bank; sw.order = nullptr;             // the planner lays the generation out in ancestor order
-    sw.Hb = s->d_Hb[s->icur]; sw.Href = s->d_dyref + (size_t)(t - 1) * d * n;
-    sw.W = s->d_W; sw.yt = c->d_y + (size_t)(t - 1) * d; sw.qf = s->d_qf[s->icur]; sw.hld = s->d_hld[s->icur];
-    sw.pant_log = sh->anc_local; sw.status = c->d_flags;
+    SweepArgs sw = info_sweep_args(c, t, sh->anc_local);
+    sw.anc = sh->pb.anc_bank;                                 // no order: the planner lays the generation out in ancestor order
     sw.rec = sh->recv_rec; sw.rec_stride = sh->recsz; sw.rec_off = sh->rec_off_Imat; sw.n_bank = N;
     sw.slot_ids = sh->pb.slot_ids; sw.ref_logical = sh->Nglob - 1;
     HIPCHK(launch_chol_sweep(sw, st));
     s->sw_cur ^= 1;
   } else {
-    CholArgs ca;
-    std::memset(&ca, 0, sizeof(ca));
-    ca.d = d; ca.n = n; ca.ldx = c->lay.ldx; ca.pant_log = sh->anc_local; ca.status = c->d_flags;
-    ca.variant = c->opt.chol_variant;
-    RB_TRY(info_fill_chol_args(c, ca, s->d_Rinv, sh->pb.anc_bank));     // plan of the step that made this generation
+    CholArgs ca = info_chol_args(c, sh->anc_local, sh->pb.anc_bank);    // plan of the step that made this generation
     ca.n_bank_local = N; ca.rec = sh->recv_rec; ca.rec_stride = sh->recsz; ca.rec_off_Imat = sh->rec_off_Imat;
-    HIPCHK(launch_chol(ca, N, d, st));
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_chol(ca, N, c->mdl.d, st));
   }
   if (!sh->async) HIPCHK(hipStreamSynchronize(st));
   return RBPF_OK;
@@ -1632,7 +1708,7 @@ int rbpf_shard_smoother_refresh_begin(rbpf_ctx* c, int32_t* owner_now, int32_t* 
   SmootherState* s = c->sm;
   ShardState* sh = c->sh;
   const int t = c->t, nN = c->mdl.nN;
-  if (!shard_refresh_due(s, t)) { set_error("no refresh is due at this step"); return RBPF_ERR_STATE; }
+  if (!refresh_due(s, t)) { set_error("no refresh is due at this step"); return RBPF_ERR_STATE; }
   if (sh->t_norm < t) { set_error("a refresh walks the state history: gather + normalise the finished step first"); return RBPF_ERR_STATE; }
   RB_TRY(shard_anc_meas_begin(c));
   const int t0 = s->base_gen, Kp = t - 1 - t0;
@@ -1709,7 +1785,7 @@ int rbpf_shard_smoother_refresh_end(rbpf_ctx* c, const int32_t* base_index, int3
   SmootherState* s = c->sm;
   ShardState* sh = c->sh;
   if (s->rf_stage != 1) { set_error("refresh_end without refresh_begin"); return RBPF_ERR_STATE; }
-  const int t = c->t, N = sh->Nloc, n = c->mdl.n, d = c->mdl.d, Kp = s->rf_Kp, t0 = s->base_gen;
+  const int t = c->t, N = sh->Nloc, Kp = s->rf_Kp, t0 = s->base_gen;
   hipStream_t st = c->stream;
   if (t0 >= 0) {
     if (!base_index || n_recv < 0 || (size_t)n_recv > s->rf_cap) { set_error("refresh_end: base_index / n_recv"); return RBPF_ERR_INVALID_ARG; }
@@ -1717,44 +1793,14 @@ int rbpf_shard_smoother_refresh_end(rbpf_ctx* c, const int32_t* base_index, int3
     HIPCHK(hipMemcpyAsync(s->d_base_slot, base_index, (size_t)N * sizeof(int), hipMemcpyHostToDevice, st));
   }
   if (s->refresh_free) {
-    // the first (and only) factorisation, chunk by chunk: Imat = Imat0 + H' R^-1 H of generation 0 into the chunk buffer,
-    // chol(Imat + ImatAddt) out of it, factors into the sweep layout; nothing was fetched from other ranks
+    // the first (and only) factorisation: generation 0, whose states refresh_begin left in d_Xp; nothing was fetched from other ranks
     if (t != 1 || t0 >= 0 || Kp != 1) { set_error("internal: refresh-free sharded smoother refreshed after t = 1"); return RBPF_ERR_STATE; }
-    for (int p0 = 0; p0 < N; p0 += s->l_chunk) {
-      const int cnt = std::min(s->l_chunk, N - p0);
-      HIPCHK(launch_meas_model(c->mdl, cnt, s->d_Xp + (size_t)p0 * c->mdl.nN, s->d_G, st, 1));
-      hipLaunchKernelGGL(sweep_whiten_kernel, dim3((unsigned)(((size_t)cnt * n + 255) / 256)), dim3(256), 0, st, (size_t)cnt, d, n, s->d_W, s->d_G);
-      HIPCHK(hipGetLastError());
-      GemmArgs g1{n, n, d, s->d_G, 1, n, (long)d * n, s->d_G, n, 1, (long)d * n, s->d_Imat[0], 1, n, (long)s->imat_len};
-      g1.lower = 1; g1.packed = s->imat_packed ? 1 : 0;
-      g1.add = s->d_Imat0; g1.add_stride = 0L; g1.add_idx = nullptr;
-      HIPCHK(launch_gemm(g1, cnt, st));
-      RB_TRY(refresh_factorise(c, s->d_Rinv, sh->anc_local, cnt, st, p0, s->d_Imat[0]));
-    }
-    s->imat_valid = false; s->base_gen = t - 1;
-    HIPCHK(hipMemcpyAsync(s->d_base_gid, s->d_owner_now, (size_t)sh->Nglob * sizeof(int), hipMemcpyDeviceToDevice, st));
-    s->sw_cur ^= 1; s->sw_valid = true; s->rf_stage = 0;
-    HIPCHK(hipStreamSynchronize(st));
-    return RBPF_OK;
+    RB_TRY(info_refresh_origin(c, t, sh->anc_local, s->d_Xp));
+  } else {
+    RB_TRY(info_refresh_window(c, Kp, t0, sh->anc_local, s->d_rf_recv));     // base matrix: own bank entry or a fetched one
   }
-  const int ni = s->imat_valid ? (s->imat_cur ^ 1) : 0;
-  HIPCHK(launch_meas_model(c->mdl, N * Kp, s->d_Xp, s->d_G, st, 1));
-  const size_t rows = (size_t)N * Kp;
-  hipLaunchKernelGGL(sweep_whiten_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, st, rows, d, n, s->d_W, s->d_G);
-  HIPCHK(hipGetLastError());
-  const long Kd = (long)Kp * d;
-  GemmArgs gg{n, n, (int)Kd, s->d_G, 1, n, Kd * n, s->d_G, n, 1, Kd * n, s->d_Imat[ni], 1, n, (long)s->imat_len};
-  gg.lower = 1;
-  gg.packed = s->imat_packed ? 1 : 0;
-  gg.add = t0 < 0 ? s->d_Imat0 : s->d_Imat[s->imat_cur];               // base matrix: own bank entry or a fetched one
-  gg.add_stride = t0 < 0 ? 0L : (long)s->imat_len;
-  gg.add_idx = t0 < 0 ? (const int*)nullptr : s->d_base_slot;
-  gg.add_rec = t0 < 0 ? (const double*)nullptr : s->d_rf_recv; gg.add_nbank = N;
-  HIPCHK(launch_gemm(gg, N, st));                                      // Imat = base + G' G
-  s->imat_cur = ni; s->imat_valid = true; s->base_gen = t - 1;
   HIPCHK(hipMemcpyAsync(s->d_base_gid, s->d_owner_now, (size_t)sh->Nglob * sizeof(int), hipMemcpyDeviceToDevice, st));
-  RB_TRY(refresh_factorise(c, s->d_Rinv, sh->anc_local, N, st));
-  s->sw_cur ^= 1; s->sw_valid = true; s->rf_stage = 0;
+  s->sw_valid = true; s->rf_stage = 0;
   HIPCHK(hipStreamSynchronize(st));              // base_index is caller memory
   return RBPF_OK;
 }
@@ -1799,16 +1845,11 @@ int rbpf_shard_smoother_step(rbpf_ctx* c) {
   HIPCHK(hipSetDevice(c->device));
   SmootherState* s = c->sm;
   ShardState* sh = c->sh;
-  const int t = c->t, k = sh->k_iter, N = sh->Nloc, n = c->mdl.n, d = c->mdl.d, nN = c->mdl.nN;
-  const Layout& L = c->lay;
-  const double* xref = (k > 0) ? s->d_xnk + (size_t)t * nN : nullptr;
-  const int oc = s->icur, nc = (t == 0) ? 0 : (oc ^ 1);
+  const int t = c->t, k = sh->k_iter;
+  const double* xref = (k > 0) ? s->d_xnk + (size_t)t * c->mdl.nN : nullptr;
   InfoStep is;
-  if (t == 0) { is.ivec_old = s->d_ivec0; is.ivec_old_stride = 0; is.hld_old = s->d_hld0; is.hld_old_stride = 0; }
-  else { is.ivec_old = s->d_ivec[oc]; is.ivec_old_stride = (size_t)L.ldx; is.hld_old = s->d_hld[oc]; is.hld_old_stride = 1; }
-  is.ivec_new = s->d_ivec[nc]; is.hld_new = s->d_hld[nc]; is.qf_new = s->d_qf[nc]; is.Hb_new = s->d_Hb[nc];
+  const int nc = info_step_banks(s, t, c->lay.ldx, is);
   RB_TRY(shard_step_impl(c, nullptr, nullptr, k, xref, &is));
-  (void)N; (void)n; (void)d;
   s->icur = nc;
   return RBPF_OK;
 }
@@ -1821,23 +1862,10 @@ int rbpf_shard_smoother_end(rbpf_ctx* c, double* XNK_k, double* XLK_k, double* P
   HIPCHK(hipSetDevice(c->device));
   SmootherState* s = c->sm;
   ShardState* sh = c->sh;
-  const int T = c->T, k = sh->k_iter, N = sh->Nglob, nN = c->mdl.nN, n = c->mdl.n, d = c->mdl.d;
-  const Layout& L = c->lay;
-  hipStream_t st = c->stream;
+  const int T = c->T, nN = c->mdl.nN, n = c->mdl.n;
   if (c->t != T || sh->t_norm != T) { set_error("iteration not finished (run all steps, then gather + normalise)"); return RBPF_ERR_STATE; }
-  double* d_uf = c->d_scal;
-  if (c->rng_mode == RBPF_RNG_REPLAY) HIPCHK(hipMemcpyAsync(d_uf, &c->h_Ufin[k], 8, hipMemcpyHostToDevice, st));
-  SearchArgs sa;
-  sa.N = N; sa.n_draw = 1; sa.t = T; sa.wc = sh->wc_glob; sa.rng_mode = c->rng_mode; sa.k_iter = k; sa.slot0 = 0;
-  sa.U = d_uf; sa.seed = c->seed; sa.ai = s->d_ak; sa.overflow = c->d_flags + 1; sa.u_is_scalar = 1;
-  sa.approx = 1; sa.ambiguous = c->d_flags + 4; sa.w = sh->w_glob; sa.wc_exact = sh->wc_glob;
-  if (N > kSingleWgResampleMaxN) sa.scan_depth = (N + 1023) / 1024 + 32;
-  HIPCHK(launch_search(sa, st));
-  HIPCHK(launch_resample_fixup(sa, st));
-  HIPCHK(launch_backtrace(N, nN, T, sh->Xhist, sh->Ahist, s->d_ak, 1, s->d_xnk, st));
   int ak = 0;
-  HIPCHK(hipMemcpyAsync(&ak, s->d_ak, 4, hipMemcpyDeviceToHost, st));
-  RB_TRY(ctx_check_flags(c));
+  RB_TRY(draw_reference_index(c, sh->Nglob, sh->w_glob, sh->wc_glob, sh->Xhist, sh->Ahist, sh->k_iter, &ak));
   int gid = ak;
   if (sh->placed) HIPCHK(hipMemcpy(&gid, sh->cur_gid + ak, 4, hipMemcpyDeviceToHost));
   const int owner = gid / sh->Nloc, idx = gid % sh->Nloc;
@@ -1846,7 +1874,7 @@ int rbpf_shard_smoother_end(rbpf_ctx* c, double* XNK_k, double* XLK_k, double* P
   if (XNK_k) HIPCHK(hipMemcpy(XNK_k, s->d_xnk, (size_t)nN * T * 8, hipMemcpyDeviceToHost));
   if (XLK_k) {
     std::memset(XLK_k, 0, (size_t)n * 8);
-    if (owner == sh->rank) HIPCHK(hipMemcpy(XLK_k, c->xl[c->xcur] + (size_t)idx * L.ldx, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (owner == sh->rank) HIPCHK(hipMemcpy(XLK_k, c->xl[c->xcur] + (size_t)idx * c->lay.ldx, (size_t)n * 8, hipMemcpyDeviceToHost));
   }
   if (PK_k) {
     std::memset(PK_k, 0, (size_t)n * n * 8);
