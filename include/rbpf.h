@@ -326,6 +326,27 @@ int rbpf_particle_smoother(const rbpf_model* model, const rbpf_problem* prob, co
                            const rbpf_options* opt, int32_t N_K, int32_t info_form,
                            rbpf_smoother_out* out);
 
+/* Both smoothers for a generic model whose handles are device code (an addition to ABI 9: no struct changed).  model->kind is
+ * RBPF_MODEL_GENERIC_DENSE and model->callbacks NULL; device_callbacks are called in the reference's order with DEVICE pointers,
+ * valid in stream order on the context's stream (the callbacks enqueue there, or synchronise themselves):
+ *   dyn_model(user, t, n_cols, xn_anc, xn_new)   once per step t >= 1: n_cols = N_P in iteration 0, N_P - 1 (the ordinary slots,
+ *                in slot order, particleSmoother.m:132-137) afterwards; both [n_nonlin x n_cols] column-major
+ *   dyn_res_norm(user, t, N_P, xnk_t, xn, e_dyn)  iterations k >= 1, steps t >= 1: xn [n_nonlin x N_P] the states of generation
+ *                t - 1, e_dyn [n_w x N_P] column-major; NULL: the additive default on the device (needs n_w == n_nonlin)
+ *   meas_model(user, n_cols, xn, dy)              n_cols = N_P once per step; N_T once per iteration k >= 1 (the reference
+ *                trajectory, :120); with carried factors (chol_refresh > 1) any number of columns at a refresh, where the
+ *                information matrices are rebuilt from the state history through it -- so it must be a pure function of xn.
+ *                dy in dy_layout (rbpf_filter_step_device) for n_cols rows; layout 1: rows on the stride ldx >= n_lin, the
+ *                per-step call writes the step kernels' own buffer, every other call a staging buffer.
+ * Between two steps of an iteration no state, Jacobian or residual crosses to the host and the library adds no host
+ * synchronisation to those of the built-in families' smoother.  With device callbacks chol_refresh > 1 never stores or copies a
+ * per-particle information matrix between refreshes, and info_rebuild = 1, chol_refresh >= N_T - 1 and inplace = 1 are
+ * available as for the built-in families (chol_refresh = 0 still resolves to 1 for a generic model).  One GPU:
+ * rbpf_options.n_devices is RBPF_ERR_UNSUPPORTED.                                                                         */
+int rbpf_particle_smoother_device(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
+                                  const rbpf_options* opt, int32_t N_K, int32_t info_form,
+                                  const rbpf_callbacks* device_callbacks, int32_t dy_layout, rbpf_smoother_out* out);
+
 /* ---- resident-state API (what bench.py times: inputs already in HBM) --------------------------- */
 /* Uploads model, problem and RNG block to the current device and allocates the particle banks.    */
 int rbpf_filter_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
@@ -459,6 +480,9 @@ int rbpf_shard_trajectories(rbpf_ctx* ctx, double* traj_max, double* traj_mean);
 int rbpf_shard_xn_traj(rbpf_ctx* ctx, double* xn_traj);
 /* The HIP stream a context enqueues on (hipStream_t).  A caller that issues its collectives on this stream
  * (torch.cuda.ExternalStream) needs no host synchronisation between the library calls and the collectives.      */
+/* ctx == NULL inside a device callback of rbpf_particle_smoother_device (on the thread that made the call): the stream of the
+ * context that is calling back, which the caller never sees; likewise rbpf_filter_external_layout(NULL, &ldx) there.  NULL
+ * anywhere else stays RBPF_ERR_INVALID_ARG.                                                                                 */
 int rbpf_stream_get(rbpf_ctx* ctx, void** hip_stream);
 /* on = 1: rbpf_shard_pack / rbpf_shard_step / rbpf_shard_smoother_step return without synchronising the stream (the caller's
  * collectives are ordered behind them on the same stream); on = 0 (default): they synchronise (host / gloo transports).    */
@@ -602,6 +626,13 @@ int32_t rbpf_chol_refresh_resolve(int32_t model_kind, int32_t n_lin, int32_t n_y
  * terms).  d = 1 or 3, n <= 575.  *status bit 1: a downdate lost definiteness.  reps / *ms as in rbpf_chol_weights.        */
 int rbpf_chol_sweep_probe(int32_t n, int32_t d, int32_t batch, const double* L, const double* U, const double* V,
                           const double* eta, int32_t reps, double* L_out, double* logw, int32_t* status, double* ms);
+/* The pack-and-whiten kernel of the refreshes behind rbpf_particle_smoother_device on its own, for the kernel-level test:
+ * dy_host [rows x d x n] in dy_layout 0 (MATLAB order, dy(i, k, c) at i + rows * (k + d * c)) or 2 (C-contiguous), W_host
+ * [d x d] column-major; G_host [rows][d][n] receives G(i, a, c) = sum_b W(a, b) dy(i, b, c), accumulated as s = 0; for b
+ * ascending: s = fma(W(a, b), dy(i, b, c), s).  fused = 1: one kernel, from the layout straight to G; fused = 0: the pack kernel
+ * followed by the whitening kernel the built-in families' refreshes run -- the same bits.  d = 1 or 3.                      */
+int rbpf_ext_pack_whiten_probe(int32_t dy_layout, int32_t rows, int32_t d, int32_t n, const double* dy_host,
+                               const double* W_host, int32_t fused, double* G_host);
 /* Quaternion helpers of tools/ on the device, batched over n columns, for the parity tests:
  *   op 0  expq, scalar branch   tools/expq.m:22-31  (flip when q0 < 0)          in [3 x n]      -> out [4 x n]
  *   op 1  expq, batched branch  tools/expq.m:33-37  (flip when q0 <= 0)         in [3 x n]      -> out [4 x n]

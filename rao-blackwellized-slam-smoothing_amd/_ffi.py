@@ -144,12 +144,12 @@ ABI_STRUCTS = [rbpf_model, rbpf_problem, rbpf_rng, rbpf_options, rbpf_filter_out
 # every symbol include/rbpf.h declares (tests/test_abi.py checks the library exports all of them)
 EXPORTS = [
     "rbpf_abi_version", "rbpf_abi_sizeof", "rbpf_status_string", "rbpf_last_error", "rbpf_device_count", "rbpf_device_bytes_live",
-    "rbpf_particle_filter", "rbpf_particle_smoother",
+    "rbpf_particle_filter", "rbpf_particle_smoother", "rbpf_particle_smoother_device",
     "rbpf_filter_create", "rbpf_filter_workspace_bytes", "rbpf_filter_advance", "rbpf_filter_reset", "rbpf_sync",
     "rbpf_filter_finish", "rbpf_filter_tell", "rbpf_filter_schedule", "rbpf_filter_one_launch_flushes", "rbpf_filter_resample_fallbacks", "rbpf_plan_refresh", "rbpf_chol_refresh_resolve", "rbpf_shard_smoother_refresh_reserve", "rbpf_shard_xn_traj", "rbpf_filter_ancestors", "rbpf_filter_step_external", "rbpf_filter_external_layout", "rbpf_filter_ancestors_device",
     "rbpf_filter_step_device", "rbpf_filter_set_device_callbacks", "rbpf_timing_enable", "rbpf_timing_read", "rbpf_destroy",
     "rbpf_philox_fill", "rbpf_meas_model", "rbpf_dyn_model", "rbpf_dyn_res_norm", "rbpf_sample",
-    "rbpf_jacobian_phi3d", "rbpf_chol_weights", "rbpf_chol_sweep_probe", "rbpf_quat_helpers", "rbpf_probe_wave_reduce",
+    "rbpf_jacobian_phi3d", "rbpf_chol_weights", "rbpf_chol_sweep_probe", "rbpf_ext_pack_whiten_probe", "rbpf_quat_helpers", "rbpf_probe_wave_reduce",
     "rbpf_shard_create", "rbpf_shard_views_get", "rbpf_shard_normalise_search", "rbpf_shard_pack", "rbpf_shard_step",
     "rbpf_shard_trajectories", "rbpf_shard_plan", "rbpf_shard_plan_read", "rbpf_shard_normalise_plan",
     "rbpf_stream_get", "rbpf_shard_set_async", "rbpf_shard_finish", "rbpf_shard_set_ancestors",
@@ -224,6 +224,9 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_particle_smoother.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem), C.POINTER(rbpf_rng),
                                            C.POINTER(rbpf_options), C.c_int32, C.c_int32,
                                            C.POINTER(rbpf_smoother_out)]
+    lib.rbpf_particle_smoother_device.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem), C.POINTER(rbpf_rng),
+                                                  C.POINTER(rbpf_options), C.c_int32, C.c_int32, C.POINTER(rbpf_callbacks),
+                                                  C.c_int32, C.POINTER(rbpf_smoother_out)]
     lib.rbpf_filter_create.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem), C.POINTER(rbpf_rng),
                                        C.POINTER(rbpf_options), C.POINTER(C.c_void_p)]
     lib.rbpf_filter_workspace_bytes.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem),
@@ -260,6 +263,8 @@ def load_library(build_if_missing: bool = True):
                                       c_double_p, c_int32_p, c_double_p]
     lib.rbpf_chol_sweep_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32,
                                           c_double_p, c_double_p, c_int32_p, c_double_p]
+    lib.rbpf_ext_pack_whiten_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_int32,
+                                               c_double_p]
     lib.rbpf_quat_helpers.argtypes = [C.c_int32, C.c_int32, c_double_p, c_double_p]
     lib.rbpf_chol_refresh_resolve.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.rbpf_chol_refresh_resolve.restype = C.c_int32

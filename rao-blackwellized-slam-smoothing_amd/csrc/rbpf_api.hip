@@ -193,7 +193,8 @@ static size_t bank_bytes(const Layout& L, int d, int N) {
 }
 
 int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng, const rbpf_options* opt,
-               bool smoother, int N_K, rbpf_ctx** out, const CreateExtras* ex) {
+               bool smoother, int N_K, rbpf_ctx** out, const CreateExtras* ex, const rbpf_callbacks* device_callbacks,
+               int dy_layout) {
   if (!out) { set_error("ctx out pointer is NULL"); return RBPF_ERR_INVALID_ARG; }
   *out = nullptr;
   RB_TRY(validate_problem(prob));
@@ -237,6 +238,10 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     if (model->callbacks) {
       c->cb = *model->callbacks; c->has_cb = true;
       if (!c->cb.dyn_model || !c->cb.meas_model) { set_error("generic model: callbacks need dyn_model and meas_model"); return RBPF_ERR_INVALID_ARG; }
+      if (device_callbacks) { set_error("generic model: host callbacks (rbpf_model.callbacks) and device callbacks exclude each other"); return RBPF_ERR_INVALID_ARG; }
+    } else if (device_callbacks) {                     // rbpf_particle_smoother_device: the handles take device memory
+      if (!device_callbacks->dyn_model || !device_callbacks->meas_model) { set_error("generic model: callbacks need dyn_model and meas_model"); return RBPF_ERR_INVALID_ARG; }
+      c->dev_cb = *device_callbacks; c->has_dev_cb = true; c->dev_dy_layout = dy_layout;
     } else if (smoother) { set_error("generic (host-callback) smoothers need rbpf_model.callbacks"); return RBPF_ERR_INVALID_ARG; }
     RB_TRY(c->pool.alloc(&c->d_xn_ext, (size_t)prob->n_nonlin * prob->N_P));
     RB_TRY(c->pool.alloc(&c->d_H_ext, (size_t)prob->N_P * prob->n_y * c->lay.ldx));
@@ -573,6 +578,42 @@ static int generic_device_inputs(rbpf_ctx* c) {
   double* dy = (c->dev_dy_layout == 1) ? c->d_H_ext : c->d_dy_stage;
   if (c->dev_cb.meas_model(c->dev_cb.user, N, c->d_xn_cm, dy) != 0) { set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK; }
   return ext_set_inputs(c, c->d_xn_cm, dy, c->dev_dy_layout);
+}
+
+static thread_local rbpf_ctx* tl_callback_ctx = nullptr;
+rbpf_ctx* callback_context() { return tl_callback_ctx; }
+void set_callback_context(rbpf_ctx* c) { tl_callback_ctx = c; }
+
+// The smoothers with device callbacks (rbpf_particle_smoother_device), the two halves of generic_device_inputs around the
+// ancestor weights of the reference trajectory: ordinary ancestors + dynModel for the slots [0, n_draw) -- N_P in iteration 0,
+// N_P - 1 later (particleSmoother.m:132-137) -- then (device_finish_inputs) the reference slot, measModel and the re-layouts.
+int device_draw_propagate(rbpf_ctx* c, int k_iter, int n_draw) {
+  const int t = c->t, N = c->N, nN = c->mdl.nN;
+  if (!c->has_dev_cb || !c->d_xn_anc || !c->d_xn_cm) { set_error("generic model without device callbacks"); return RBPF_ERR_STATE; }
+  if (t >= c->T) { set_error("advance past N_T"); return RBPF_ERR_STATE; }
+  if (t == 0) {                                        // particleSmoother.m:104: the slab ctx_reset filled with x0_nonLin
+    HIPCHK(launch_ext_gather_states(N, nN, c->X, nullptr, c->d_xn_cm, c->stream));
+    return RBPF_OK;
+  }
+  if (n_draw <= 0) return RBPF_OK;
+  if (c->ready_step != t && c->drawn_step != t) { RB_TRY(ctx_draw_ancestors(c, k_iter, n_draw)); c->drawn_step = t; }
+  const bool hist = c->opt.keep_history != 0;
+  const int* A_t = c->A + (hist ? (size_t)t * N : 0);
+  const double* X_old = c->X + (size_t)(hist ? t - 1 : ((t - 1) & 1)) * nN * N;
+  HIPCHK(launch_ext_gather_columns(n_draw, N, nN, X_old, A_t, c->d_xn_anc, c->stream));
+  if (c->dev_cb.dyn_model(c->dev_cb.user, t - 1, n_draw, c->d_xn_anc, c->d_xn_cm) != 0) { set_error("the dynModel callback failed"); return RBPF_ERR_CALLBACK; }
+  return RBPF_OK;
+}
+
+// xref_dev != null: slot N-1 is the conditioned reference trajectory (particleSmoother.m:242), a device pointer.
+int device_finish_inputs(rbpf_ctx* c, const double* xref_dev) {
+  const int N = c->N, nN = c->mdl.nN, d = c->mdl.d, n = c->mdl.n, ldx = c->lay.ldx;
+  HIPCHK(launch_ext_states_to_soa_ref(N, nN, c->d_xn_cm, c->d_xn_ext, xref_dev, c->stream));
+  double* dy = (c->dev_dy_layout == 1) ? c->d_H_ext : c->d_dy_stage;
+  if (c->dev_cb.meas_model(c->dev_cb.user, N, c->d_xn_cm, dy) != 0) { set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK; }
+  if (c->dev_dy_layout != 1) HIPCHK(launch_ext_pack_dy(c->dev_dy_layout, N, d, n, ldx, dy, c->d_H_ext, c->stream));
+  c->ext_xn = c->d_xn_ext; c->ext_H = c->d_H_ext;
+  return RBPF_OK;
 }
 
 // Bytes a timed launch of the step kernel has to move (rbpf_timing.scheduled_bytes_per_launch): the stored covariance in
@@ -1096,6 +1137,7 @@ int rbpf_filter_step_external(rbpf_ctx* c, const double* xn_new, const double* d
 }
 
 int rbpf_filter_external_layout(const rbpf_ctx* c, int32_t* ldx) {
+  if (!c && ldx && callback_context()) { *ldx = callback_context()->lay.ldx; return RBPF_OK; }   // inside a device callback of a one-shot call
   if (!c || !ldx) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(ext_device_ctx_ok(c));
   *ldx = c->lay.ldx;

@@ -150,7 +150,8 @@ namespace rbpf {
 int fill_model_dev(const rbpf_model* model, int nN, int n, int d, int nw, int nodo, const double* R, double jitter,
                    ModelDev& M, std::vector<int>& nn_axis_major);
 int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng, const rbpf_options* opt,
-               bool smoother, int N_K, rbpf_ctx** out, const CreateExtras* ex = nullptr);
+               bool smoother, int N_K, rbpf_ctx** out, const CreateExtras* ex = nullptr,
+               const rbpf_callbacks* device_callbacks = nullptr, int dy_layout = 0);   // device_callbacks: rbpf_particle_smoother_device
 int ctx_reset(rbpf_ctx* c);
 void ctx_free(rbpf_ctx* c);
 int ctx_step(rbpf_ctx* c, int k_iter, const double* xref_t, int n_draw, const InfoStep* info);
@@ -159,6 +160,14 @@ int ctx_check_flags(rbpf_ctx* c);
 // host for slots [0, n_draw); then (generic_finish_inputs) the reference slot, measModel and the upload
 int generic_draw_propagate(rbpf_ctx* c, int k_iter, int n_draw);
 int generic_finish_inputs(rbpf_ctx* c, const double* xref_host);
+// the same two halves with device callbacks (rbpf_particle_smoother_device): everything stays on the device, in stream order
+int device_draw_propagate(rbpf_ctx* c, int k_iter, int n_draw);
+int device_finish_inputs(rbpf_ctx* c, const double* xref_dev);
+// The context whose device callbacks are being called on this thread by a one-shot entry point (rbpf_particle_smoother_device),
+// null otherwise: the callbacks have no other way to the stream they must enqueue on (rbpf_stream_get(NULL, ...)) and to the
+// row stride of the native dy layout (rbpf_filter_external_layout(NULL, ...)).
+rbpf_ctx* callback_context();
+void set_callback_context(rbpf_ctx* c);
 int ctx_call_on_step(rbpf_ctx* c, int t, bool is_smoother);
 void ctx_account_launch(rbpf_ctx* c, const StepArgs& a);
 int ctx_arm_distinct(rbpf_ctx* c, StepArgs& a, size_t keys);

@@ -280,6 +280,14 @@ hipError_t launch_transpose_soa(int N, int nN, const double* soa, double* aos, h
 hipError_t launch_ext_gather_states(int N, int nN, const double* soa, const int* ai, double* cm, hipStream_t s);
 hipError_t launch_ext_states_to_soa(int N, int nN, const double* cm, double* soa, hipStream_t s);
 hipError_t launch_ext_pack_dy(int layout, int N, int d, int n, int ldx, const double* dy, double* H, hipStream_t s);
+// ... for the smoothers: the first `count` slots only (ancestors clamped to N - 1); the reference state xref [nN] (null: none)
+// written to column N - 1 of cm on the way to soa; G [rows][d][n] = W * dy in one pass, dy in layout 0 (MATLAB order) or as
+// rows on the stride ld (layout 2: ld = n, layout 1: ld = ldx); rows on the stride ld -> back to back
+hipError_t launch_ext_gather_columns(int count, int N, int nN, const double* soa, const int* ai, double* cm, hipStream_t s);
+hipError_t launch_ext_states_to_soa_ref(int N, int nN, double* cm, double* soa, const double* xref, hipStream_t s);
+hipError_t launch_ext_pack_whiten(int layout, int rows, int d, int n, int ld, const double* dy, const double* W, double* G,
+                                  hipStream_t s);
+hipError_t launch_ext_compact_rows(size_t rows, int n, int ld, const double* src, double* dst, hipStream_t s);
 hipError_t launch_pack_records(const Layout& lay, int d, const int* idx, int count, const double* Pt, const double* Pb,
                                const double* F, const double* xl, double* rec, hipStream_t s, size_t rec_stride = 0,
                                int fp32 = 0);

@@ -418,6 +418,7 @@ int rbpf_shard_plan_read(rbpf_ctx* c, int32_t* slot_ids, int32_t* anc_bank, int3
 }
 
 int rbpf_stream_get(rbpf_ctx* c, void** hip_stream) {
+  if (!c) c = callback_context();                      // inside a device callback of a one-shot call
   if (!c || !hip_stream) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   *hip_stream = reinterpret_cast<void*>(c->stream);
   return RBPF_OK;

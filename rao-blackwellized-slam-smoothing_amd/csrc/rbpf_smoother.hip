@@ -79,6 +79,8 @@ struct SmootherState {
   SmootherForm form = SmootherForm::Info;
   double* d_R = nullptr;        // [d*d] (the covariance form reads it)
   double* d_edyn = nullptr;     // [N][nw] generic family with a dynResNorm handle: its values
+  double* d_xprev = nullptr;    // [N][nN] device callbacks: generation t - 1 column-major, what the dynResNorm handle reads
+  size_t stage_rows = 0;        // device callbacks: columns per measModel call of a refresh (the staging buffer holds that many rows of H)
   std::vector<double> h_xnk, h_edyn;   // host copies of d_xnk (the callbacks read it) and d_edyn
   SparsePairs pairs;
   // sharded smoother with carried factors: where every logical slot's particle lives now / lived when the Imat bank was
@@ -962,7 +964,7 @@ static void info_resolve_options(rbpf_ctx* c) {
   const int N = c->N, T = c->T, n = c->mdl.n, d = c->mdl.d;
   const int K = resolve_chol_refresh(c->mdl.kind, n, d, effective_chol_refresh(c->opt));
   s->refresh = K > 1 ? K : 0;
-  s->lazy_imat = s->refresh && c->mdl.kind != RBPF_MODEL_GENERIC_DENSE;     // needs measModel on the device
+  s->lazy_imat = s->refresh && (c->mdl.kind != RBPF_MODEL_GENERIC_DENSE || c->has_dev_cb);     // needs measModel on the device
   s->imat_packed = imat_storage_packed(n, d, s->refresh, s->lazy_imat);
   s->imat_len = s->imat_packed ? imat_packed_doubles(n) : (size_t)n * n;
   s->l_chunk = s->lazy_imat ? std::min(N, 4096) : N;
@@ -975,6 +977,16 @@ static void info_resolve_options(rbpf_ctx* c) {
   //  rebuild from the origin as well, whose scratch is one chunk x one segment)
   s->refresh_free = s->lazy_imat && (s->refresh >= T - 1 || c->opt.info_rebuild > 0 || s->refresh > 256);
   s->seg_len = 32;
+  if (c->has_dev_cb) s->seg_len = std::min(32, std::max(T - 1, 1));   // a path is never longer than N_T - 1 generations: what is staged is sized by it
+  // device callbacks, refresh from the origin: a chunk is a quarter of the particles at the most, below N_P = 16 384 too.  What a
+  // chunk particle holds (its matrix, its factor workspace, its staged Jacobians) is more than the two carried factors of a
+  // particle; over a quarter of them it is less than the workspace per particle that the from-scratch run keeps, so the mode's
+  // footprint is below that run's at every N_P, not only where 4096 is a small part of it.  Same launches per particle.
+  if (c->has_dev_cb && s->refresh_free) s->l_chunk = std::min(s->l_chunk, (N + 3) / 4);
+  // device callbacks: one measModel call per chunk of a refresh -- a chunk of particles x a segment of generations, or the whole
+  // window where that is less -- so the staging buffer of its result does not grow with N_P x K
+  const size_t chunk_rows = (size_t)s->l_chunk * s->seg_len;
+  s->stage_rows = !s->lazy_imat ? 0 : s->refresh_free ? chunk_rows : std::min(chunk_rows, (size_t)N * s->refresh);
 }
 
 // The information-form state of this context's particles, after info_resolve_options: the banks, the factor workspaces, the suffix
@@ -1110,10 +1122,20 @@ static int info_gram_product(rbpf_ctx* c, const double* Xp, int cnt, int len, do
   SmootherState* s = c->sm;
   const int n = c->mdl.n, d = c->mdl.d;
   hipStream_t st = c->stream;
-  HIPCHK(launch_meas_model(c->mdl, cnt * len, Xp, s->d_G, st, 1));
   const size_t rows = (size_t)cnt * len;
-  hipLaunchKernelGGL(sweep_whiten_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, st, rows, d, n, s->d_W, s->d_G);
-  HIPCHK(hipGetLastError());
+  if (c->has_dev_cb) {
+    // the measModel handle on the states, stage by stage, each packed from its layout and whitened in one pass
+    const int layout = c->dev_dy_layout, ld = layout == 1 ? c->lay.ldx : n;
+    for (size_t r0 = 0; r0 < rows; r0 += s->stage_rows) {
+      const int nr = (int)std::min(s->stage_rows, rows - r0);
+      if (c->dev_cb.meas_model(c->dev_cb.user, nr, Xp + r0 * c->mdl.nN, c->d_dy_stage) != 0) { set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK; }
+      HIPCHK(launch_ext_pack_whiten(layout, nr, d, n, ld, c->d_dy_stage, s->d_W, s->d_G + r0 * d * n, st));
+    }
+  } else {
+    HIPCHK(launch_meas_model(c->mdl, cnt * len, Xp, s->d_G, st, 1));
+    hipLaunchKernelGGL(sweep_whiten_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, st, rows, d, n, s->d_W, s->d_G);
+    HIPCHK(hipGetLastError());
+  }
   const long Kd = (long)len * d;
   gg.M = n; gg.N = n; gg.K = (int)Kd;
   gg.A = s->d_G; gg.rsA = 1; gg.csA = n; gg.bsA = Kd * n;
@@ -1274,6 +1296,24 @@ static int info_alloc(rbpf_ctx* c, const std::vector<double>& Rinv) {
   return RBPF_OK;
 }
 
+// Device callbacks: what the handles read and write.  The ancestors' states and the new states [nN x N] column-major, generation
+// t - 1 for the dynResNorm handle, and one staging buffer for measModel's results that are not consumed in place: the per-step
+// call of layouts 0 / 2 (N columns), the call along the reference trajectory (T columns, every layout) and the calls of a
+// refresh (stage_rows columns, every layout); layout 1 is staged on its row stride ldx.
+static int device_handle_buffers(rbpf_ctx* c, bool drn_cb) {
+  SmootherState* s = c->sm;
+  const size_t N = (size_t)c->N, T = (size_t)c->T, nN = (size_t)c->mdl.nN, n = (size_t)c->mdl.n, d = (size_t)c->mdl.d, ldx = (size_t)c->lay.ldx;
+  const int layout = c->dev_dy_layout;
+  RB_TRY(c->pool.alloc(&c->d_xn_anc, nN * N));
+  RB_TRY(c->pool.alloc(&c->d_xn_cm, nN * N));
+  if (drn_cb) RB_TRY(s->pool.alloc(&s->d_xprev, nN * N));
+  const size_t rows = std::max(std::max(T, layout == 1 ? (size_t)0 : N), s->stage_rows);
+  RB_TRY(c->pool.alloc(&c->d_dy_stage, rows * d * (layout == 1 ? ldx : n)));
+  // layout 1: the handle fills columns 0..nLin-1 of the context's own buffer at every step; the pad is zeroed here, once
+  if (layout == 1) HIPCHK(hipMemsetAsync(c->d_H_ext, 0, N * d * ldx * sizeof(double), c->stream));
+  return RBPF_OK;
+}
+
 // what the forms share: the checks of the model's dynamics residual, the reference trajectory and the ancestor probabilities
 static int smoother_setup(rbpf_ctx* c, int N_K, int info_form) {
   const int N = c->N, T = c->T, nN = c->mdl.nN, n = c->mdl.n, d = c->mdl.d, nw = c->mdl.nw;
@@ -1283,7 +1323,7 @@ static int smoother_setup(rbpf_ctx* c, int N_K, int info_form) {
   if (!info_form) c->lazy_depth = 1;          // the covariance form reads the flushed covariances of every particle every step
   c->sort_steps = true;
   const bool generic = c->mdl.kind == RBPF_MODEL_GENERIC_DENSE;
-  const bool drn_cb = generic && c->cb.dyn_res_norm != nullptr;      // the handle; otherwise isempty(dynResNorm)
+  const bool drn_cb = generic && (c->has_dev_cb ? c->dev_cb.dyn_res_norm : c->cb.dyn_res_norm) != nullptr;      // the handle; otherwise isempty(dynResNorm)
   if (generic) c->mdl.use_dyn_res_norm = 0;                          // device side: only the additive default exists
   if (!c->mdl.use_dyn_res_norm && !drn_cb && nw != nN) {
     set_error("isempty(dynResNorm): the additive default (particleSmoother.m:176) needs size(Q,1) == nNonLin");
@@ -1312,7 +1352,8 @@ static int smoother_setup(rbpf_ctx* c, int N_K, int info_form) {
     return sparse_alloc(c);
   }
   s->form = info_form ? SmootherForm::Info : SmootherForm::Cov;
-  return info_form ? info_alloc(c, Rinv) : cov_alloc(c);
+  RB_TRY(info_form ? info_alloc(c, Rinv) : cov_alloc(c));
+  return c->has_dev_cb ? device_handle_buffers(c, drn_cb) : RBPF_OK;
 }
 
 // dy_xnk = measModel(xnk)  (:120) into d_dyref [T][d][n]
@@ -1321,6 +1362,15 @@ static int reference_jacobians(rbpf_ctx* c) {
   const int T = c->T, n = c->mdl.n, d = c->mdl.d;
   if (c->mdl.kind != RBPF_MODEL_GENERIC_DENSE) {
     HIPCHK(launch_meas_model(c->mdl, T, s->d_xnk, s->d_dyref, c->stream, 1));
+    return RBPF_OK;
+  }
+  if (c->has_dev_cb) {
+    // the handle on d_xnk ([T][nN] = column-major nN x T) into the staging buffer, from there into [T][d][n]: the pack kernels
+    // at row stride n (no pad columns, T in place of N); the native layout's rows lose their pad
+    const int layout = c->dev_dy_layout;
+    if (c->dev_cb.meas_model(c->dev_cb.user, T, s->d_xnk, c->d_dy_stage) != 0) { set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK; }
+    if (layout == 1) HIPCHK(launch_ext_compact_rows((size_t)T * d, n, c->lay.ldx, c->d_dy_stage, s->d_dyref, c->stream));
+    else HIPCHK(launch_ext_pack_dy(layout, T, d, n, n, c->d_dy_stage, s->d_dyref, c->stream));
     return RBPF_OK;
   }
   std::vector<double> dyT((size_t)T * d * n), Href((size_t)T * d * n);
@@ -1338,6 +1388,16 @@ static int anc_dyn_weights(rbpf_ctx* c, int t) {
   const int N = c->N, nN = c->mdl.nN, nw = c->mdl.nw;
   hipStream_t st = c->stream;
   const double* w_prev = c->w + (c->opt.trace ? (size_t)(t - 1) * N : 0);
+  if (c->has_dev_cb && c->dev_cb.dyn_res_norm) {
+    // the handle reads generation t - 1 column-major and writes e_dyn [nw x N] where the kernel reads it, all in stream order
+    HIPCHK(launch_ext_gather_states(N, nN, c->X + (size_t)(t - 1) * nN * N, nullptr, s->d_xprev, st));
+    if (c->dev_cb.dyn_res_norm(c->dev_cb.user, t - 1, N, s->d_xnk + (size_t)t * nN, s->d_xprev, s->d_edyn) != 0) {
+      set_error("the dynResNorm callback failed"); return RBPF_ERR_CALLBACK;
+    }
+    hipLaunchKernelGGL(anc_dyn_ext_kernel, dim3((N + 63) / 64), dim3(64), 0, st, N, nw, s->d_edyn, w_prev, s->d_pant_log);
+    HIPCHK(hipGetLastError());
+    return RBPF_OK;
+  }
   if (c->mdl.kind == RBPF_MODEL_GENERIC_DENSE && c->cb.dyn_res_norm) {
     s->h_edyn.assign((size_t)N * nw, 0.0);
     if (c->cb.dyn_res_norm(c->cb.user, t - 1, N, s->h_xnk.data() + (size_t)t * nN, c->h_xn.data(), s->h_edyn.data()) != 0) {
@@ -1472,12 +1532,14 @@ static int iteration_end(rbpf_ctx* c, int k, rbpf_smoother_out* out) {
 }
 
 // CPF-AS (Alg. 2), N_K iterations.  The generic family evaluates its handles on the host, in the reference's call order:
-// ordinary ancestors + dynModel (:132-137), dynResNorm, then the reference slot and measModel.
+// ordinary ancestors + dynModel (:132-137), dynResNorm, then the reference slot and measModel.  With device callbacks the
+// same calls in the same order hand out device memory, and nothing of a step crosses to the host.
 static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* out) {
   RB_TRY(smoother_setup(c, N_K, info_form));
   SmootherState* s = c->sm;
   const int N = c->N, T = c->T, nN = c->mdl.nN;
-  const bool generic = c->mdl.kind == RBPF_MODEL_GENERIC_DENSE;
+  const bool device = c->has_dev_cb;
+  const bool generic = c->mdl.kind == RBPF_MODEL_GENERIC_DENSE && !device;
   for (int k = 0; k < N_K; ++k) {
     RB_TRY(ctx_reset(c));
     if (s->form == SmootherForm::Info) RB_TRY(info_begin_iteration(c));
@@ -1489,6 +1551,7 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
       const double* xref = (k > 0) ? s->d_xnk + (size_t)t * nN : nullptr;
       const int n_draw = (k > 0 && t > 0) ? N - 1 : N;
       if (generic) RB_TRY(generic_draw_propagate(c, k, n_draw));
+      if (device) RB_TRY(device_draw_propagate(c, k, n_draw));
       if (k > 0 && t > 0) {
         // ancestor weights of the reference trajectory (Steps 9-10), normalise (:236-238), sample ai(N_P) (:241)
         RB_TRY(anc_dyn_weights(c, t));
@@ -1497,8 +1560,9 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
                                   c->d_U ? c->d_U + ((size_t)k * (T - 1) + (t - 1)) * N : nullptr, c->A + (size_t)t * N, c->stream));
       }
       if (generic) RB_TRY(generic_finish_inputs(c, k > 0 ? s->h_xnk.data() + (size_t)t * nN : nullptr));
+      if (device) RB_TRY(device_finish_inputs(c, xref));
       const int st_step = s->form == SmootherForm::Info ? info_step(c, k, t, xref, n_draw) : ctx_step(c, k, xref, n_draw, nullptr);
-      if (generic) { c->ext_xn = nullptr; c->ext_H = nullptr; }
+      if (generic || device) { c->ext_xn = nullptr; c->ext_H = nullptr; }
       RB_TRY(st_step);
     }
     RB_TRY(iteration_end(c, k, out));
@@ -1506,18 +1570,14 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
   return RBPF_OK;
 }
 
-extern "C" int32_t rbpf_chol_refresh_resolve(int32_t model_kind, int32_t n_lin, int32_t n_y, int32_t requested) {
-  return resolve_chol_refresh(model_kind, n_lin, n_y, requested);
-}
-
-extern "C" int rbpf_particle_smoother(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
-                                      const rbpf_options* opt, int32_t N_K, int32_t info_form, rbpf_smoother_out* out) {
-  if (!out || N_K < 1) { set_error("bad smoother arguments"); return RBPF_ERR_INVALID_ARG; }
-  RB_TRY(options_ok(opt));
-  if (wants_multi(opt)) return multi_particle_smoother(model, prob, rng, opt, N_K, info_form, out);   // sharded over several GPUs
-  rbpf_ctx* c = nullptr;
-  int st = ctx_create(model, prob, rng, opt, true, N_K, &c);
-  if (st == RBPF_OK) st = smoother_run(c, N_K, info_form, out);
+// what the one-shot entry points share: run on the context just created (st: ctx_create's status), explain a smoother that did
+// not fit, wait for the stream and free the context
+static int smoother_run_and_free(int st, rbpf_ctx* c, const rbpf_problem* prob, int N_K, int info_form, rbpf_smoother_out* out) {
+  if (st == RBPF_OK) {
+    if (c->has_dev_cb) set_callback_context(c);        // the callbacks ask for the stream and the native row stride
+    st = smoother_run(c, N_K, info_form, out);
+    set_callback_context(nullptr);
+  }
   if (st == RBPF_ERR_OUT_OF_MEMORY && info_form && prob) {
     // say what would fit: the information-form state without stored information matrices and with one covariance bank
     const double n = (double)prob->n_lin, mb = (8.0 * (0.57 * n * n + 2.0 * 0.52 * (n + 1) * (n + 1))) / 1e6;
@@ -1533,6 +1593,36 @@ extern "C" int rbpf_particle_smoother(const rbpf_model* model, const rbpf_proble
   }
   ctx_free(c);
   return st;
+}
+
+extern "C" int32_t rbpf_chol_refresh_resolve(int32_t model_kind, int32_t n_lin, int32_t n_y, int32_t requested) {
+  return resolve_chol_refresh(model_kind, n_lin, n_y, requested);
+}
+
+extern "C" int rbpf_particle_smoother(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
+                                      const rbpf_options* opt, int32_t N_K, int32_t info_form, rbpf_smoother_out* out) {
+  if (!out || N_K < 1) { set_error("bad smoother arguments"); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(options_ok(opt));
+  if (wants_multi(opt)) return multi_particle_smoother(model, prob, rng, opt, N_K, info_form, out);   // sharded over several GPUs
+  rbpf_ctx* c = nullptr;
+  const int st = ctx_create(model, prob, rng, opt, true, N_K, &c);
+  return smoother_run_and_free(st, c, prob, N_K, info_form, out);
+}
+
+extern "C" int rbpf_particle_smoother_device(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
+                                             const rbpf_options* opt, int32_t N_K, int32_t info_form,
+                                             const rbpf_callbacks* device_callbacks, int32_t dy_layout, rbpf_smoother_out* out) {
+  if (!out || N_K < 1) { set_error("bad smoother arguments"); return RBPF_ERR_INVALID_ARG; }
+  if (!device_callbacks || !device_callbacks->dyn_model || !device_callbacks->meas_model) { set_error("NULL argument (the callbacks need dyn_model and meas_model)"); return RBPF_ERR_INVALID_ARG; }
+  if (dy_layout < 0 || dy_layout > 2) { set_error("dy_layout must be 0 (MATLAB order), 1 (native) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
+  if (!model || model->kind != RBPF_MODEL_GENERIC_DENSE || model->callbacks) {
+    set_error("rbpf_particle_smoother_device takes a generic model (RBPF_MODEL_GENERIC_DENSE) with rbpf_model.callbacks == NULL"); return RBPF_ERR_INVALID_ARG;
+  }
+  RB_TRY(options_ok(opt));
+  if (wants_multi(opt)) { set_error("device handles in the smoothers: one GPU only (rbpf_options.n_devices is not supported)"); return RBPF_ERR_UNSUPPORTED; }
+  rbpf_ctx* c = nullptr;
+  const int st = ctx_create(model, prob, rng, opt, true, N_K, &c, nullptr, device_callbacks, dy_layout);
+  return smoother_run_and_free(st, c, prob, N_K, info_form, out);
 }
 
 // =============================================================================================================
@@ -2057,5 +2147,30 @@ int rbpf_chol_sweep_probe(int32_t n, int32_t d, int32_t batch, const double* L, 
   return RBPF_OK;
 }
 
+// G [rows][d][n] = W * dy for dy [rows x d x n] in dy_layout 0 (MATLAB order) or 2 (C-contiguous), W [d x d] column-major: the
+// fused pack-and-whiten kernel of the refreshes with device callbacks (fused = 1), or the pack kernel followed by
+// sweep_whiten_kernel (fused = 0) -- the path the built-in families' refreshes take after their measModel.
+int rbpf_ext_pack_whiten_probe(int32_t dy_layout, int32_t rows, int32_t d, int32_t n, const double* dy_host, const double* W_host,
+                               int32_t fused, double* G_host) {
+  if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
+  if (!dy_host || !W_host || !G_host || rows < 1 || n < 1 || (d != 1 && d != 3) || (dy_layout != 0 && dy_layout != 2)) {
+    set_error("bad argument (dy_layout 0 or 2, d = 1 or 3)"); return RBPF_ERR_INVALID_ARG;
+  }
+  const size_t len = (size_t)rows * d * n;
+  double *dy = nullptr, *dW = nullptr, *dG = nullptr;
+  DevicePool tmp;
+  RB_TRY(tmp.upload(&dy, dy_host, len));
+  RB_TRY(tmp.upload(&dW, W_host, (size_t)d * d));
+  RB_TRY(tmp.alloc(&dG, len));
+  if (fused) {
+    HIPCHK(launch_ext_pack_whiten(dy_layout, rows, d, n, n, dy, dW, dG, nullptr));
+  } else {
+    HIPCHK(launch_ext_pack_dy(dy_layout, rows, d, n, n, dy, dG, nullptr));
+    hipLaunchKernelGGL(sweep_whiten_kernel, dim3((unsigned)(((size_t)rows * n + 255) / 256)), dim3(256), 0, nullptr, (size_t)rows, d, n, dW, dG);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpy(G_host, dG, len * 8, hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
 
 }  // extern "C"

@@ -332,10 +332,130 @@ class DeviceHandles:
         self.dy_layout, self.native_out = dy_layout, bool(native_out)
 
 
+class DeviceSmootherHandles(DeviceHandles):
+    """Device handles for particleSmoother / particleSmootherInformationForm (and, as its base class, for the filter): batched
+    callables on torch float64 tensors of the library's device, run inside torch.cuda.stream(the library's stream), handed in
+    place of the three handles -- the object as dynModel, None as measModel and dynResNorm.  Between two steps of an iteration
+    no state, Jacobian or residual is copied to the host and nothing waits for it (rbpf_particle_smoother_device).
+
+    A filter handle is written for exactly N_P columns; the smoothers' contract is wider, hence the separate class:
+
+        xn_new (n_nonlin, n_cols) = dynModel(xn_anc (n_nonlin, n_cols), dx (n_odo,), dt, Q (n_w, n_w))
+            n_cols = N_P in iteration 0, N_P - 1 at the steps t >= 1 of later iterations: the ordinary slots, in slot order
+            (particleSmoother.m:132-137).  Draws its own random numbers.  Called once per step, N_T - 1 times per iteration.
+        dy (n_cols, n_y, nLin) = measModel(xn (n_nonlin, n_cols))            ((n_cols, nLin) is accepted for n_y = 1)
+            must be a PURE function of xn.  n_cols = N_P once per step; N_T once per iteration k >= 1, for the reference
+            trajectory (particleSmoother.m:120); with chol_refresh > 1, any chunk size at a refresh, where the information
+            matrices are rebuilt from the state history through it.
+        e (n_w, N_P) = dynResNorm(xnk_t (n_nonlin,), xn (n_nonlin, N_P), dx, dt, Q)
+            the reference's handle (particleSmoother.m:178-180) batched over the particles of generation t - 1.  None: the
+            additive default (:175-177) on the device, as for host handles; it needs n_w == n_nonlin.
+
+    dy_layout 0 / 1 / 2 mean what they mean for the filter (DeviceHandles): the layout of the library buffer measModel's result
+    is copied into unless it is that buffer.  native_out=True: measModel(xn, out) with `out` (n_cols, n_y, nLin) a view of that
+    buffer; with dy_layout=1 its strides are (n_y ldx, ldx, 1) in EVERY call -- the per-step call fills the buffer the step
+    kernels read, the others a staging buffer that a copy kernel compacts.
+    A handle that raises, or returns a wrong shape, dtype or device, surfaces as that exception; the library stays usable.
+    One GPU (no n_devices), dense features only."""
+
+    def __init__(self, dynModel, measModel, dynResNorm=None, dy_layout=0, native_out=False):
+        if dy_layout not in (0, 1, 2):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "dy_layout must be 0 (MATLAB order), 1 (native) or 2 (C-contiguous)")
+        super().__init__(dynModel, measModel, dy_layout=dy_layout, native_out=native_out)
+        if not _is_empty_handle(dynResNorm) and not callable(dynResNorm):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "dynResNorm must be callable or None")
+        self.dynResNorm = None if _is_empty_handle(dynResNorm) else dynResNorm
+
+
 def _refuse_device_handles(what, *handles):
     if any(isinstance(h, DeviceHandles) for h in handles):
         raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceHandles are not supported by %s: the filter on one GPU only "
-                                                   "(particleFilter, FilterSession)" % what)
+                                                   "(particleFilter, FilterSession); the smoothers take a "
+                                                   "DeviceSmootherHandles as dynModel, whose handles accept any number of columns" % what)
+
+
+class _DeviceSmootherCallbacks:
+    """The rbpf_callbacks of a DeviceSmootherHandles object: the ctypes wrappers of _DeviceDriver._register with views of the
+    passed pointers sized by n_cols, plus dynResNorm.  The stream and the native row stride are the calling context's, asked
+    for inside the first callback (the one-shot entry point creates the context itself)."""
+
+    def __init__(self, lib, handles, model, prob):
+        import torch
+        from .multigpu import _view
+        self.torch, self._view = torch, _view
+        self.lib, self.h = lib, handles
+        self.nN, self.n, self.d, self.nw, self.N = model.nNonLin, model.nLin, model.ny, model.nw, prob.N_P
+        self.layout = int(handles.dy_layout)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.odo = torch.as_tensor(np.ascontiguousarray(model._odo), device=self.device)
+        self.Q = torch.as_tensor(np.ascontiguousarray(np.moveaxis(model._Q, 2, 0)), device=self.device)     # [pages][nw][nw]
+        self.dt = model._dt
+        self.error = None
+        self.stream = None
+        self.ldx = 0
+        torch.cuda.current_stream(self.device).synchronize()           # the constants above, before the library's stream reads them
+
+        def guarded(fn):
+            def call(*a):
+                try:
+                    self._enter()
+                    with torch.cuda.stream(self.stream):
+                        fn(*a)
+                    return 0
+                except Exception as exc:                                                  # noqa: BLE001
+                    self.error = self.error or exc
+                    return 1
+            return call
+
+        cb = _ffi.rbpf_callbacks()
+        self._fns = (_ffi.DYN_MODEL_FN(guarded(self._dyn)), _ffi.MEAS_MODEL_FN(guarded(self._meas)),
+                     _ffi.DYN_RES_NORM_FN(guarded(self._drn)) if handles.dynResNorm is not None else _ffi.DYN_RES_NORM_FN())
+        cb.dyn_model, cb.meas_model, cb.dyn_res_norm = self._fns
+        cb.user = None
+        self.cb = cb
+
+    def _enter(self):
+        if self.stream is None:
+            sp, ldx = C.c_void_p(), C.c_int32(0)
+            check(self.lib.rbpf_stream_get(None, C.byref(sp)))
+            check(self.lib.rbpf_filter_external_layout(None, C.byref(ldx)))
+            self.stream, self.ldx = self.torch.cuda.ExternalStream(sp.value, device=self.device), ldx.value
+
+    def _args(self, t):
+        return self.odo[t], float(self.dt[t if self.dt.size > 1 else 0]), self.Q[t if self.Q.shape[0] > 1 else 0]
+
+    def _checked(self, what, x, shape):
+        if tuple(x.shape) != shape or x.dtype != self.torch.float64 or not x.is_cuda:
+            raise ValueError(f"{what} returned {tuple(x.shape)} {x.dtype} on {x.device}, expected a float64 device tensor of "
+                             f"shape {shape}")
+        return x
+
+    def _dyn(self, _user, t, n_cols, xn_anc, xn_new):
+        anc = self._view(self.torch, xn_anc, (n_cols, self.nN), self.device).t()
+        xn = self._checked("dynModel", self.h.dynModel(anc, *self._args(t)), (self.nN, n_cols))
+        self._view(self.torch, xn_new, (n_cols, self.nN), self.device).t().copy_(xn)
+
+    def _drn(self, _user, t, n_cols, xnk_t, xn, e_dyn):
+        xk = self._view(self.torch, xnk_t, (self.nN,), self.device)
+        X = self._view(self.torch, xn, (n_cols, self.nN), self.device).t()
+        e = self._checked("dynResNorm", self.h.dynResNorm(xk, X, *self._args(t)), (self.nw, n_cols))
+        self._view(self.torch, e_dyn, (n_cols, self.nw), self.device).t().copy_(e)
+
+    def _meas(self, _user, n_cols, xn, dy_p):
+        n, d = self.n, self.d
+        if self.layout == 0:
+            target = self._view(self.torch, dy_p, (n, d, n_cols), self.device).permute(2, 1, 0)
+        elif self.layout == 1:
+            target = self._view(self.torch, dy_p, (n_cols, d, self.ldx), self.device)[:, :, :n]
+        else:
+            target = self._view(self.torch, dy_p, (n_cols, d, n), self.device)
+        X = self._view(self.torch, xn, (n_cols, self.nN), self.device).t()
+        dy = self.h.measModel(X, target) if self.h.native_out else self.h.measModel(X)
+        if dy.dim() == 2 and d == 1:
+            dy = dy.unsqueeze(1)
+        self._checked("measModel", dy, (n_cols, d, n))
+        if not _DeviceDriver._same(dy, target):
+            target.copy_(dy)
 
 
 class _DeviceDriver:
@@ -899,12 +1019,25 @@ def model_dyn_res_norm(dynModel):
 def _smoother(info_form, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, N_K, dt,
               sparseFeatures, makePlots, rng, extras, chol_variant=0, lazy_depth=0, chol_refresh=0, n_devices=0, device_ids=None,
               storage="fp64", exchange_capacity=0, inplace=0, info_rebuild=0):
-    _refuse_device_handles("the smoothers", dynModel, measModel, dynResNorm)
+    handles = dynModel if isinstance(dynModel, DeviceSmootherHandles) else None
+    if handles is None:
+        _refuse_device_handles("the smoothers", dynModel, measModel, dynResNorm)
+    else:                                                     # device code: no host callbacks (see DeviceSmootherHandles)
+        if (measModel is not None and measModel is not handles) or not (_is_empty_handle(dynResNorm) or dynResNorm is handles):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "DeviceSmootherHandles replace the three handles: pass the object as "
+                                                       "dynModel and None as measModel and dynResNorm")
+        if int(n_devices) > 1 or (int(n_devices) == 1 and device_ids is not None):
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceSmootherHandles are not supported by sharded sessions (n_devices): "
+                                                       "the smoothers with device handles run on one GPU only")
+        if sparseFeatures:
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceSmootherHandles: sparseFeatures=true is implemented for the "
+                                                       "sparse-visual family only")
+        dynModel = measModel = dynResNorm = None
     if sparseFeatures:
         if info_form:
             # particleSmootherInformationForm.m:77-80 prints and returns with outputs unassigned
             raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "This code has only been implemented for dense features")
-    model, use_drn = _recognise(dynModel, measModel, dynResNorm)
+    model, use_drn = (None, False) if handles is not None else _recognise(dynModel, measModel, dynResNorm)
     if model is None:
         # arbitrary handles (particleSmoother.m:134-136,175-180,264 accept any): the generic family through callbacks
         if sparseFeatures:
@@ -951,13 +1084,19 @@ def _smoother(info_form, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin
                 return 1
         hook = _ffi.ON_STEP_FN(on_iter)
         opt.on_step = hook
+    driver = None
     try:
-        check(lib.rbpf_particle_smoother(C.byref(mdesc), C.byref(prob.c), C.byref(blk), C.byref(opt), N_K,
-                                         1 if info_form else 0, C.byref(o)))
+        if handles is not None:
+            driver = _DeviceSmootherCallbacks(lib, handles, model, prob)
+            check(lib.rbpf_particle_smoother_device(C.byref(mdesc), C.byref(prob.c), C.byref(blk), C.byref(opt), N_K,
+                                                    1 if info_form else 0, C.byref(driver.cb), driver.layout, C.byref(o)))
+        else:
+            check(lib.rbpf_particle_smoother(C.byref(mdesc), C.byref(prob.c), C.byref(blk), C.byref(opt), N_K,
+                                             1 if info_form else 0, C.byref(o)))
     except RBPFError as exc:
         if exc.status == _ffi.RBPF_ERR_CALLBACK and hook_error:
             raise hook_error[0] from exc
-        _raise_callback_error(model, exc)
+        _raise_callback_error(driver if driver is not None else model, exc)
     res = (b["XNK"], b["XLK"], b["PK"])
     if extras:
         ex = dict(logw=np.transpose(b["trace_logw"], (2, 1, 0)).copy(), w=np.transpose(b["trace_w"], (2, 1, 0)).copy(),
@@ -1067,6 +1206,21 @@ def chol_sweep_probe(L, U, V, eta, batch=1, reps=1):
     ms = np.zeros(1)
     check(lib.rbpf_chol_sweep_probe(n, d, int(batch), _dp(L), _dp(U), _dp(V), _dp(eta), int(reps), _dp(Lo), _dp(logw), _ip(status), _dp(ms)))
     return Lo, float(logw[0]), int(status[0]), float(ms[0])
+
+
+def pack_whiten_probe(dy, W, dy_layout=0, fused=True):
+    """rbpf_ext_pack_whiten_probe: G (rows, n_y, nLin) = W @ dy[i] for dy (rows, n_y, nLin), handed to the device in dy_layout 0
+    (MATLAB order) or 2 (C-contiguous).  fused=True: the pack-and-whiten kernel of the refreshes with device handles; False: the
+    pack kernel followed by the whitening kernel of the built-in families' refreshes -- the same bits."""
+    lib = load_library()
+    dy = np.asarray(dy, dtype=np.float64)
+    rows, d, n = dy.shape
+    W = np.asfortranarray(np.asarray(W, dtype=np.float64))
+    assert W.shape == (d, d)
+    mem = np.asfortranarray(dy) if int(dy_layout) == 0 else np.ascontiguousarray(dy)
+    G = np.empty((rows, d, n))
+    check(lib.rbpf_ext_pack_whiten_probe(int(dy_layout), rows, d, n, _dp(mem), _dp(W), 1 if fused else 0, _dp(G)))
+    return G
 
 
 # ------------------------------------------------------------------------------------------------
