@@ -63,7 +63,16 @@ typedef enum {
   /* Arbitrary dense model (any dynModel / measModel handles, sparseFeatures = false): the caller evaluates the handles
    * itself -- dynModel per particle (particleFilter.m:108), measModel on the whole batch (:124) -- and hands states and
    * Jacobians to rbpf_filter_step_external; everything else of the step (weights, normalisation, resampling, Kalman
-   * update, ancestry) runs on the device.  n_y must be 1 or 3.  The slow path behind unrecognised handles.         */
+   * update, ancestry) runs on the device.  The slow path behind unrecognised handles.
+   * Measurement width: with host callbacks (rbpf_model.callbacks != NULL; the MEX gateway) n_y must be 1 or 3 -- a known
+   * limit of the slow path.  Without them (callbacks == NULL: rbpf_filter_step_external, the device entry points
+   * rbpf_filter_ancestors_device / rbpf_filter_step_device / rbpf_filter_set_device_callbacks, and
+   * rbpf_particle_smoother_device) every n_y from 1 to 8 runs, on one GPU.  At n_y other than 1 and 3 the covariances are
+   * fp64 full squares rewritten every step and the ancestor weights are factorised from scratch: storage != 0,
+   * lazy_depth >= 2, inplace, chol_refresh > 1 and info_rebuild return RBPF_ERR_UNSUPPORTED before any device memory is
+   * taken (chol_refresh = 0 resolves to 1), as does an nLin whose step-kernel LDS plan exceeds 160 KB (DESIGN.md has the
+   * admitted nLin per n_y; n_y = 8: nLin <= 383 and 512..639, the filter also 1024..1117), and a smoother whose nLin x nLin
+   * ancestor-weight factorisation has no kernel that fits (n_y = 7 at nLin >= 1024).                                  */
   RBPF_MODEL_GENERIC_DENSE = 4
 } rbpf_model_kind;
 
@@ -342,7 +351,8 @@ int rbpf_particle_smoother(const rbpf_model* model, const rbpf_problem* prob, co
  * synchronisation to those of the built-in families' smoother.  With device callbacks chol_refresh > 1 never stores or copies a
  * per-particle information matrix between refreshes, and info_rebuild = 1, chol_refresh >= N_T - 1 and inplace = 1 are
  * available as for the built-in families (chol_refresh = 0 still resolves to 1 for a generic model).  One GPU:
- * rbpf_options.n_devices is RBPF_ERR_UNSUPPORTED.                                                                         */
+ * rbpf_options.n_devices is RBPF_ERR_UNSUPPORTED.  n_y from 1 to 8; at n_y other than 1 and 3 both forms run with the
+ * from-scratch factorisation only (chol_refresh <= 1) on fp64 full squares: see RBPF_MODEL_GENERIC_DENSE.                 */
 int rbpf_particle_smoother_device(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
                                   const rbpf_options* opt, int32_t N_K, int32_t info_form,
                                   const rbpf_callbacks* device_callbacks, int32_t dy_layout, rbpf_smoother_out* out);
@@ -405,7 +415,9 @@ int rbpf_filter_step_external(rbpf_ctx* ctx, const double* xn_new, const double*
  *        them device pointers: dyn_model(user, t, N_P, xn_anc_dev, xn_new_dev), meas_model(user, N_P, xn_dev, dy_dev) with
  *        dy_dev in dy_layout -- layout 1: the context's own Jacobian buffer (its pad zeroed here, once), 0 / 2: a staging
  *        buffer of the context.  The callbacks enqueue on rbpf_stream_get(ctx) or synchronise themselves; a non-zero
- *        return is RBPF_ERR_CALLBACK; dyn_res_norm is ignored.                                                        */
+ *        return is RBPF_ERR_CALLBACK; dyn_res_norm is ignored.
+ * n_y from 1 to 8 (see RBPF_MODEL_GENERIC_DENSE for what the widths other than 1 and 3 run with); every layout above is
+ * written for any of them.                                                                                            */
 int rbpf_filter_external_layout(const rbpf_ctx* ctx, int32_t* ldx);
 int rbpf_filter_ancestors_device(rbpf_ctx* ctx, const int32_t** ai_dev, const double** xn_anc_dev);
 int rbpf_filter_step_device(rbpf_ctx* ctx, const double* xn_new_dev, const double* dy_dev, int32_t dy_layout);

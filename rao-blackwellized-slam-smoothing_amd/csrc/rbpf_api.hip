@@ -86,17 +86,20 @@ static int build_chol_factors(const rbpf_model* model, const rbpf_problem* p, st
   return RBPF_OK;
 }
 
-// inv(R) and 0.5*log(det(R)) for the information-form recursions (particleSmootherInformationForm.m:292,298,304), d <= 3.
+// inv(R) and 0.5*log(det(R)) for the information-form recursions (particleSmootherInformationForm.m:292,298,304), d <= 8: the
+// built-in families and the generic one up to 3 x 3 keep them in ModelDev (kernel arguments), wider generic models in device memory
+// (ModelDev::Rdev).  Rinv holds d x d doubles.
 // Only the information-form smoother needs them; the filter accepts any R whose innovation covariance passes chol
 // (with the jitter retry), so a failure here only leaves NaNs behind.
+constexpr int kMaxNy = 8;
 static void invert_R_small(const double* R, int d, double* Rinv, double& halfLogDetR) {
-  double Lr[9] = {0};
-  const bool pd = R && d <= 3 && chol_lower_host(R, d, d, Lr, d);
+  double Lr[kMaxNy * kMaxNy] = {0};
+  const bool pd = R && d <= kMaxNy && chol_lower_host(R, d, d, Lr, d);
   halfLogDetR = pd ? 0.0 : std::nan("");
-  for (int q = 0; q < d * d && q < 9; ++q) Rinv[q] = std::nan("");
+  for (int q = 0; q < d * d && q < kMaxNy * kMaxNy; ++q) Rinv[q] = std::nan("");
   for (int j = 0; pd && j < d; ++j) halfLogDetR += std::log(Lr[j + d * j]);
   for (int col = 0; pd && col < d; ++col) {
-    double y[3], x[3];
+    double y[kMaxNy], x[kMaxNy];
     for (int i = 0; i < d; ++i) { double v = (i == col); for (int k = 0; k < i; ++k) v -= Lr[i + d * k] * y[k]; y[i] = v / Lr[i + d * i]; }
     for (int i = d - 1; i >= 0; --i) { double v = y[i]; for (int k = i + 1; k < d; ++k) v -= Lr[k + d * i] * x[k]; x[i] = v / Lr[i + d * i]; }
     for (int i = 0; i < d; ++i) Rinv[i + d * col] = x[i];
@@ -123,12 +126,21 @@ int fill_model_dev(const rbpf_model* model, int nN, int n, int d, int nw, int no
       return RBPF_ERR_INVALID_ARG;
     }
   } else if (model->kind == RBPF_MODEL_GENERIC_DENSE) {
-    if ((d != 1 && d != 3) || nN < 1 || nN > 8 || nw < 1 || nw > 8 || n < 1) {
+    // host callbacks (rbpf_model.callbacks, the MEX gateway): the two widths of the built-in families.  Device code
+    // (DeviceHandles / DeviceSmootherHandles / step_external): every width the step kernel is instantiated for, 1 .. 8.
+    if ((model->callbacks && d != 1 && d != 3) || nN < 1 || nN > 8 || nw < 1 || nw > 8 || n < 1) {
       set_error("generic dense family: n_y must be 1 or 3, n_nonlin and n_w <= 8"); return RBPF_ERR_UNSUPPORTED;
     }
+    if (d < 1 || d > kMaxNy) {
+      set_error("generic dense family without host callbacks: n_y must be 1 .. 8 (with host callbacks: 1 or 3)"); return RBPF_ERR_UNSUPPORTED;
+    }
     M.m = n; M.dim = 0; M.ktot = 0;
-    for (int q = 0; q < d * d; ++q) M.R[q] = R ? R[q] : 0.0;
-    invert_R_small(R, d, M.Rinv, M.halfLogDetR);
+    if (d <= 3) {
+      for (int q = 0; q < d * d; ++q) M.R[q] = R ? R[q] : 0.0;
+      invert_R_small(R, d, M.Rinv, M.halfLogDetR);
+    } else {                                // too wide for the kernel arguments: ctx_create inverts R once, into device memory
+      M.halfLogDetR = std::nan("");         // (ModelDev::Rdev), and sets halfLogDetR from the same factorisation
+    }
     M.jitter = jitter;
     M.logconst = -0.5 * d * std::log(2.0 * 3.14159265358979323846);
     nn_axis_major.clear();
@@ -213,6 +225,19 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
   const bool sparse = model->kind == RBPF_MODEL_SPARSE_VISUAL_2D;
   c->fp32 = c->opt.storage == 1 || c->opt.storage == 3;
   if (c->opt.storage < 0 || c->opt.storage > 3) { set_error("options.storage must be 0 (fp64), 1 (fp32), 2 (fp64, symmetric) or 3 (fp32, symmetric)"); return RBPF_ERR_INVALID_ARG; }
+  if (model->kind == RBPF_MODEL_GENERIC_DENSE && prob->n_y != 1 && prob->n_y != 3) {
+    // The generic family's other widths (2, 4 .. 8; device code only, fill_model_dev): the full-square fp64 step kernel with one
+    // pending set rewritten every step, ancestor weights factorised from scratch.  What they do not have is refused here, before
+    // any device memory is taken.
+    const char* who = "generic models with n_y other than 1 or 3: ";
+    if (c->opt.storage != 0) { set_error(std::string(who) + "options.storage must be 0 (fp64 full squares; fp32 and block-lower storage are instantiated for n_y = 3 and 1)"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->opt.lazy_depth >= 2) { set_error(std::string(who) + "lazy_depth >= 2 is not supported (the multi-step lazy update is instantiated for n_y = 1 and 3)"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->opt.inplace > 0) { set_error(std::string(who) + "inplace = 1 is not supported (one covariance bank needs lazy_depth >= 2)"); return RBPF_ERR_UNSUPPORTED; }
+    if (smoother && (c->opt.chol_refresh > 1 || c->opt.info_rebuild > 0)) { set_error(std::string(who) + "chol_refresh > 1 and info_rebuild are not supported (the carried-factor sweep is instantiated for n_y = 1 and 3; chol_refresh = 0 resolves to 1)"); return RBPF_ERR_UNSUPPORTED; }
+    if (step_lds_bytes(c->mdl, c->lay, smoother ? 1 : 0) > 160 * 1024) { set_error(std::string(who) + "nLin too large for the LDS plan of the step kernel at this n_y (160 KB per workgroup)"); return RBPF_ERR_UNSUPPORTED; }
+    // the information form factorises Imat + ImatAddt (nLin x nLin, n_y pending rows in LDS) at every step: some kernel must take it
+    if (smoother && !info_chol_variant_fits(prob->n_lin, prob->n_y)) { set_error(std::string(who) + "nLin too large for the ancestor-weight factorisation of the smoothers at this n_y (the 64-column kernel's LDS grows with n_y, the 16-column kernel takes nLin <= 1023)"); return RBPF_ERR_UNSUPPORTED; }
+  }
   if (c->opt.storage == 2 || c->opt.storage == 3) {
     // symmetric storage (lower block triangle, rbpf_step_sym.hip): the ny = 3 dense families at the sizes its wave decomposition
     // takes (4 to 16 tile rows of 64: 256 <= nLin - nb < 1024 + 128), ny = 1 at nLin = 128
@@ -276,6 +301,13 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
   c->mdl.NN = c->d_NN;
   if (sparse) {
     RB_TRY(c->pool.upload(&c->d_R, prob->R, (size_t)d * d));
+    c->mdl.Rdev = c->d_R;
+  }
+  if (model->kind == RBPF_MODEL_GENERIC_DENSE && d > 3) {     // [R | inv(R)]: too wide for the kernel arguments (fill_model_dev)
+    std::vector<double> rr((size_t)2 * d * d);
+    for (int q = 0; q < d * d; ++q) rr[q] = prob->R[q];
+    invert_R_small(prob->R, d, rr.data() + (size_t)d * d, c->mdl.halfLogDetR);
+    RB_TRY(c->pool.upload(&c->d_R, rr.data(), rr.size()));
     c->mdl.Rdev = c->d_R;
   }
   {

@@ -227,6 +227,9 @@ inline int options_ok(const rbpf_options* o) {
 }
 // the K rbpf_options.chol_refresh stands for (rbpf_chol_refresh_resolve; rbpf_smoother.hip)
 int resolve_chol_refresh(int model_kind, int n, int d, int requested);
+// is there a from-scratch factorisation kernel for the information form's n x n matrices with d pending rows kept in LDS?
+// (rbpf_smoother.hip: the 64-column kernel while its LDS fits, else the 16-column kernel up to 64 row tiles)
+bool info_chol_variant_fits(int n, int d);
 // an explicit kernel choice (chol_variant) names the kernel of the from-scratch factorisation: with chol_refresh left at 0
 // (automatic) it selects that factorisation at every step
 inline int effective_chol_refresh(const rbpf_options& o) { return (o.chol_refresh == 0 && o.chol_variant != 0) ? 1 : o.chol_refresh; }

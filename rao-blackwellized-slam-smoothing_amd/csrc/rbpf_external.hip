@@ -179,6 +179,7 @@ hipError_t launch_ext_states_to_soa_ref(int N, int nN, double* cm, double* soa, 
 
 hipError_t launch_ext_pack_whiten(int layout, int rows, int d, int n, int ld, const double* dy, const double* W, double* G,
                                   hipStream_t s) {
+  if (d < 1 || d > 3) return hipErrorInvalidValue;   // tile[3], w[9], v[3] below: the refreshes of carried factors, n_y = 1 and 3 only
   if (rows <= 0) return hipSuccess;
   if (layout == 0) {
     const dim3 grid((n + kPackTile - 1) / kPackTile, (rows + kWhitenCols - 1) / kWhitenCols);

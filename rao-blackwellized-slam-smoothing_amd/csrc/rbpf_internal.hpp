@@ -73,6 +73,7 @@ struct ModelDev {
   double halfLogDetR;  // 0.5*log(det(R))
   double cam[3];       // sparse-visual family: f, fp, fw
   const double* Rdev;  // sparse-visual family: full R [d x d] in device memory (d may exceed 3)
+                       // generic family with d > 3: [R | inv(R)], d x d column-major each (R / Rinv above stay zero)
 };
 
 // HBM layout of one particle's covariance ("bank" entry).  Natural state order is kept for the
@@ -223,6 +224,13 @@ hipError_t launch_probe_wave_reduce(const double* in, double* out, hipStream_t s
 // dynModel for all slots (must run before launch_step of the same StepArgs)
 hipError_t launch_propagate(const StepArgs& a, hipStream_t s);
 hipError_t launch_step(const StepArgs& a, hipStream_t s);
+// the generic family at n_y = 2, 4 .. 8 (rbpf_step_wide_*.hip; launch_step dispatches to them)
+hipError_t launch_step_wide_d2(const StepArgs& a, hipStream_t s);
+hipError_t launch_step_wide_d4(const StepArgs& a, hipStream_t s);
+hipError_t launch_step_wide_d5(const StepArgs& a, hipStream_t s);
+hipError_t launch_step_wide_d6(const StepArgs& a, hipStream_t s);
+hipError_t launch_step_wide_d7(const StepArgs& a, hipStream_t s);
+hipError_t launch_step_wide_d8(const StepArgs& a, hipStream_t s);
 hipError_t launch_normalise_scan(const NormArgs& a, hipStream_t s);
 hipError_t launch_search(const SearchArgs& a, hipStream_t s);
 hipError_t launch_cumsum(int N, const double* w, double* wc, hipStream_t s);

@@ -658,11 +658,12 @@ __global__ __launch_bounds__(W * 64, 4) void chol_solve_kernel(CholArgs a_in) {
   }
 }
 
+constexpr size_t kChol16MaxLds = 150 * 1024;      // the 16-column kernel's opt-in (launch_chol_w)
 static size_t chol_lds_bytes(int M, int d) { return ((size_t)256 + 256 + 32 + M + 2 + (d ? 2 * (size_t)d * M : (size_t)M)) * sizeof(double); }
 template <int W, int NTMAX>
 static hipError_t launch_chol_w(const CholArgs& ca, int batch, size_t lds, hipStream_t st) {
   static std::atomic<uint64_t> attr{0};
-  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&chol_solve_kernel<W, NTMAX>), 150 * 1024, attr)) return e;
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&chol_solve_kernel<W, NTMAX>), (int)kChol16MaxLds, attr)) return e;
   hipLaunchKernelGGL((chol_solve_kernel<W, NTMAX>), dim3(batch), dim3(W * 64), lds, st, ca);
   return hipGetLastError();
 }
@@ -691,6 +692,9 @@ static hipError_t launch_chol16(const CholArgs& ca, int batch, int d_lds, hipStr
   if ((w_force == 4 || w_force == 8 || w_force == 16) && (RT + w_force - 1) / w_force <= 4) W = w_force;
   const size_t lds = chol_lds_bytes(ca.Msz, d_lds);
   const int ntmax = (RT + W - 1) / W;
+  // sixteen waves own at most four row tiles each: a larger matrix would leave its bottom row tiles (the right-hand side among
+  // them) uncomputed.  The 64-column kernel takes those sizes whenever its LDS fits; info_chol_variant_fits refuses the rest.
+  if (ntmax > 4 || lds > kChol16MaxLds) return hipErrorInvalidValue;
   if (W == 4) return launch_chol_nt<4>(ca, batch, lds, ntmax, st);
   if (W == 8) return launch_chol_nt<8>(ca, batch, lds, ntmax, st);
   return launch_chol_nt<16>(ca, batch, lds, ntmax, st);
@@ -824,6 +828,14 @@ using namespace rbpf;
 // every step by the copy kernel on full squares.
 static bool imat_storage_packed(int n, int d, int refresh, bool lazy) {
   return (refresh <= 1 || lazy) && ((n + 1 + 15) >> 4) > 11 && chol64_lds_bytes(n, d) <= kC64MaxLds;
+}
+
+// launch_chol's automatic choice for an information-form matrix, as a yes / no before anything is allocated: the 64-column kernel
+// (LDS 5120 + 32 + n + 2 + 2 d n doubles: grows with d), else the register-resident or the 16-column kernel, whose sixteen waves
+// take at most 64 row tiles (n <= 1023).  Every built-in width passes wherever its step kernel does; n_y = 7 at nLin >= 1024 does not.
+bool rbpf::info_chol_variant_fits(int n, int d) {
+  if (chol64_lds_bytes(n, d) <= kC64MaxLds) return true;
+  return ((n + 1 + 15) >> 4) <= 64 && chol_lds_bytes(n, d) <= kChol16MaxLds;
 }
 
 // rbpf_options.chol_refresh -> the K in use.  0 = automatic: the carried factors (K = 32) for the recognised dense families from

@@ -19,7 +19,13 @@ Per N_P the tool records
 Timing: a warm-up, then the median of WINDOWS windows of STEPS steps, each window a host clock around work that ends in a
 synchronise.  Writes one JSON document (default profiles/generic_device_bench.json).
 
-Usage: generic_device_bench.py [--out FILE] [--particles N ...] [--windows 5] [--steps 20] [--host-steps 2]"""
+Usage: generic_device_bench.py [--out FILE] [--particles N ...] [--windows 5] [--steps 20] [--host-steps 2]
+
+--ny 3 4 6 8: the measurement-width sweep instead -- per n_y a DeviceHandles filter (native view filled in place) on fp64 full
+squares rewritten every step (lazy_depth 0: what every n_y from 1 to 8 has), at --ny-particles (8192) and --ny-nlin (256);
+records the ms per step, the bytes a step must move, N_P (2 nLin^2 + (5 n_y + 2) ldx) 8 (the covariance read and written, H
+read, both pending factor pairs read and written, the mean read and written), and that traffic's share of the HBM peak.
+Default output profiles/generic_device_ny_bench.json."""
 import argparse
 import ctypes as C
 import importlib
@@ -41,6 +47,8 @@ host = importlib.import_module("rao-blackwellized-slam-smoothing_amd.host")
 
 SHAPE = (4, 3, 4, 3, 515)                       # (n_nonlin, n_w, n_odo, n_y, nLin)
 OPTS = dict(storage="fp64sym", lazy_depth=4)
+NY_OPTS = dict(storage="fp64", lazy_depth=0)    # the --ny sweep: the schedule every width has
+HBM_PEAK_GBPS = 8000.0                          # MI355X: HBM3E 8 TB/s (as bench.py)
 
 
 def median_ms_per_step(advance, sync, warmup, windows, steps):
@@ -80,8 +88,8 @@ def device_handles(torch, gmt, m, p, layout):
     return rbpf.DeviceHandles(tm.dynModel, tm.measModel, native_out=(layout == 1))
 
 
-def bench_device(torch, gmt, m, p, N, layout, a):
-    with rbpf.FilterSession(device_handles(torch, gmt, m, p, layout), *filter_args(p, N), rng=rbpf.PhiloxRNG(1), **OPTS) as s:
+def bench_device(torch, gmt, m, p, N, layout, a, opts=OPTS):
+    with rbpf.FilterSession(device_handles(torch, gmt, m, p, layout), *filter_args(p, N), rng=rbpf.PhiloxRNG(1), **opts) as s:
         med, ms = median_ms_per_step(s.advance, s.sync, a.warmup, a.windows, a.steps)
     return {"ms_per_step": med, "windows_ms": ms}
 
@@ -194,9 +202,39 @@ def bench_pack(torch, m, p, N, a):
     return out
 
 
+def ny_sweep(a):
+    """--ny: ms per step of the DeviceHandles filter per measurement width, with the bytes a step must move."""
+    import torch
+    import generic_model as gm
+    import generic_model_torch as gmt
+    N, n = a.ny_particles, a.ny_nlin
+    ldx = (n + 1) & ~1
+    T = a.warmup + a.windows * a.steps + 4
+    doc = {"tool": "tools/generic_device_bench.py --ny", "device": torch.cuda.get_device_name(0), "N_P": N, "nLin": n, "options": NY_OPTS,
+           "handles": "rbpf.DeviceHandles, measModel fills the native view (dy layout 1)",
+           "timing": f"warm-up {a.warmup} steps, median of {a.windows} windows of {a.steps} steps (host clock, synchronised)",
+           "bytes_per_step": "N_P (2 nLin^2 + (5 n_y + 2) ldx) 8", "hbm_peak_GBps": HBM_PEAK_GBPS, "runs": []}
+    for ny in a.ny:
+        m = gm.GenericModel(4, 3, 4, ny, n, seed=1)
+        p = gm.problem(m, 1, T, seed=1)
+        run = dict(bench_device(torch, gmt, m, p, N, 1, a, NY_OPTS), n_y=ny)
+        run["bytes_per_step"] = float(N) * (2 * n * n + (5 * ny + 2) * ldx) * 8
+        run["GBps"] = run["bytes_per_step"] / (run["ms_per_step"] * 1e-3) / 1e9
+        run["frac_hbm_peak"] = run["GBps"] / HBM_PEAK_GBPS
+        doc["runs"].append(run)
+        print(json.dumps(run), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generic_device_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/generic_device_bench.json (--ny: profiles/generic_device_ny_bench.json)")
+    ap.add_argument("--ny", type=int, nargs="+", default=None, help="measurement widths of the n_y sweep (1 .. 8); replaces the default runs")
+    ap.add_argument("--ny-particles", type=int, default=8192)
+    ap.add_argument("--ny-nlin", type=int, default=256)
     ap.add_argument("--particles", type=int, nargs="*", default=None, help="default: 8192 and the largest power of two up to 65536 that fits")
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
@@ -210,6 +248,10 @@ def main():
         ap.error("at least 5 windows of at least 20 steps")
     if rbpf.device_count() < 1:
         raise SystemExit("generic_device_bench: no HIP device visible (nothing is measured without one)")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "generic_device_ny_bench.json" if a.ny else "generic_device_bench.json")
+    if a.ny:
+        return ny_sweep(a)
     import torch
     import generic_model as gm
     import generic_model_torch as gmt

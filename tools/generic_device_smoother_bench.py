@@ -24,7 +24,11 @@ criterion of anything: the partners are different code.
 
 Writes one JSON document (default profiles/generic_device_smoother_bench.json).
 
-Usage: generic_device_smoother_bench.py [--out FILE] [--particles 8192] [--windows 5] [--steps 40] [--host-steps 4]"""
+Usage: generic_device_smoother_bench.py [--out FILE] [--particles 8192] [--windows 5] [--steps 40] [--host-steps 4]
+
+--ny 3 4 8: the measurement-width sweep instead -- per n_y the device handles alone, chol_refresh = 1, on fp64 full squares
+rewritten every step (what every n_y from 1 to 8 has), nLin = --ny-nlin (256).  Default output
+profiles/generic_device_smoother_ny_bench.json."""
 import argparse
 import importlib
 import json
@@ -44,6 +48,7 @@ dg = importlib.import_module("rao-blackwellized-slam-smoothing_amd.datagen")
 
 SHAPE = (4, 3, 4, 3, 515)                       # (n_nonlin, n_w, n_odo, n_y, nLin)
 OPTS = dict(storage="fp64sym", lazy_depth=3)
+NY_OPTS = dict(storage="fp64", lazy_depth=0)    # the --ny sweep
 N_K = 2
 
 
@@ -86,12 +91,12 @@ def device_handles(torch, gms, m, p):
     return rbpf.DeviceSmootherHandles(tm.dynModel, tm.measModel, tm.dynResNorm, dy_layout=2)
 
 
-def bench_device(torch, gms, m, p, N, chol_refresh, a):
+def bench_device(torch, gms, m, p, N, chol_refresh, a, opts=OPTS):
     handles = device_handles(torch, gms, m, p)
 
     def run(T, hook):
         return rbpf.particleSmootherInformationForm(handles, None, None, *generic_args(p, N, T), makePlots=hook, rng=rbpf.PhiloxRNG(1),
-                                                    chol_refresh=chol_refresh, **OPTS)
+                                                    chol_refresh=chol_refresh, **opts)
     return per_step(run, a.steps, a.windows)
 
 
@@ -120,7 +125,9 @@ def bench_builtin(N, a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generic_device_smoother_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/generic_device_smoother_bench.json (--ny: ..._smoother_ny_bench.json)")
+    ap.add_argument("--ny", type=int, nargs="+", default=None, help="measurement widths of the n_y sweep (1 .. 8); replaces the default runs")
+    ap.add_argument("--ny-nlin", type=int, default=256)
     ap.add_argument("--particles", type=int, default=8192)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--steps", type=int, default=40)
@@ -136,6 +143,23 @@ def main():
     import generic_model_torch_smoother as gms
     N = a.particles
     free, _total = torch.cuda.mem_get_info()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "generic_device_smoother_ny_bench.json" if a.ny else "generic_device_smoother_bench.json")
+    if a.ny:
+        doc = {"tool": "tools/generic_device_smoother_bench.py --ny", "device": torch.cuda.get_device_name(0), "N_P": N, "N_K": N_K,
+               "nLin": a.ny_nlin, "options": dict(NY_OPTS, chol_refresh=1), "form": "information form, DeviceSmootherHandles, dy layout 2",
+               "timing": f"per step = host clock between the makePlots hooks of iterations 0 and 1 / N_T; N_T = {a.steps}, a warm-up run, "
+                         f"then the median of {a.windows} runs", "runs": []}
+        for ny in a.ny:
+            m = gm.GenericModel(4, 3, 4, ny, a.ny_nlin, seed=1)
+            p = gm.problem(m, 1, a.steps, N_K=N_K, seed=1)
+            doc["runs"].append(dict(bench_device(torch, gms, m, p, N, 1, a, NY_OPTS), n_y=ny))
+            print(json.dumps(doc["runs"][-1]), flush=True)
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(doc, f, indent=1)
+                f.write("\n")
+        return
     m = gm.GenericModel(*SHAPE, seed=1)
     p = gm.problem(m, 1, a.steps, N_K=N_K, seed=1)
     doc = {"tool": "tools/generic_device_smoother_bench.py", "device": torch.cuda.get_device_name(0), "free_bytes_at_start": free,
