@@ -73,7 +73,16 @@ typedef enum {
    * taken (chol_refresh = 0 resolves to 1), as does an nLin whose step-kernel LDS plan exceeds 160 KB (DESIGN.md has the
    * admitted nLin per n_y; n_y = 8: nLin <= 383 and 512..639, the filter also 1024..1117), and a smoother whose nLin x nLin
    * ancestor-weight factorisation has no kernel that fits (n_y = 7 at nLin >= 1024).                                  */
-  RBPF_MODEL_GENERIC_DENSE = 4
+  RBPF_MODEL_GENERIC_DENSE = 4,
+  /* Arbitrary model with sparseFeatures = true (particleFilter.m:127-137,165-181): [yhat, dy] = measModel(xn_i, xl_i) is
+   * linearised per particle at the particle's own map and NaN in y marks an output that was not observed.  The caller's
+   * device code evaluates both handles; the library hands it the resampled linear states and runs the EKF step
+   * (rbpf_filter_sparse_gathered_device / rbpf_filter_step_sparse_device below).  The filter on one GPU only.
+   * rbpf_model.callbacks must be NULL (RBPF_ERR_INVALID_ARG); m_basis, dim, NN, L, cam are not read.
+   * Admitted: n_y 1 .. 32, n_lin 1 .. 96 (the border-only bank layout; the step kernel's LDS plan stays within 150 KB),
+   * n_nonlin and n_w <= 8.  Anything larger, storage != 0, lazy_depth >= 2, inplace, n_devices and the smoothers return
+   * RBPF_ERR_UNSUPPORTED with a message that names the rule, before any device memory is taken.                           */
+  RBPF_MODEL_GENERIC_SPARSE = 5
 } rbpf_model_kind;
 
 /* Host callbacks of the generic family = the reference's handle contracts, batched over columns so that a binding
@@ -417,11 +426,38 @@ int rbpf_filter_step_external(rbpf_ctx* ctx, const double* xn_new, const double*
  *        buffer of the context.  The callbacks enqueue on rbpf_stream_get(ctx) or synchronise themselves; a non-zero
  *        return is RBPF_ERR_CALLBACK; dyn_res_norm is ignored.
  * n_y from 1 to 8 (see RBPF_MODEL_GENERIC_DENSE for what the widths other than 1 and 3 run with); every layout above is
- * written for any of them.                                                                                            */
+ * written for any of them.  rbpf_filter_external_layout and rbpf_filter_ancestors_device also serve a context of
+ * RBPF_MODEL_GENERIC_SPARSE (below), unchanged.                                                                         */
 int rbpf_filter_external_layout(const rbpf_ctx* ctx, int32_t* ldx);
 int rbpf_filter_ancestors_device(rbpf_ctx* ctx, const int32_t** ai_dev, const double** xn_anc_dev);
 int rbpf_filter_step_device(rbpf_ctx* ctx, const double* xn_new_dev, const double* dy_dev, int32_t dy_layout);
 int rbpf_filter_set_device_callbacks(rbpf_ctx* ctx, const rbpf_callbacks* callbacks, int32_t dy_layout);
+/* The sparseFeatures branch with handles that live on the device (RBPF_MODEL_GENERIC_SPARSE; any other context:
+ * RBPF_ERR_STATE, NULL arguments and unknown layouts: RBPF_ERR_INVALID_ARG before anything touches a device).  One step, in
+ * stream order on rbpf_stream_get(ctx), nothing crosses to the host:
+ *   t > 0:  rbpf_filter_ancestors_device(ctx, &ai, &xn_anc);  xn = dynModel(xn_anc, ...)        (t = 0: xn = x0_nonlin repeated)
+ *           rbpf_filter_sparse_gathered_device(ctx, &xl, &ldx)
+ *           [yhat, dy] = measModel(xn, xl)                                                       one call for all particles
+ *           rbpf_filter_step_sparse_device(ctx, xn, yhat, yhat_layout, dy, dy_layout)
+ *   rbpf_filter_sparse_gathered_device  *xl_dev [N_P][ldx]: row i holds xl(:,ai(i)) of the step about to run
+ *        (particleFilter.m:112), columns n_lin..ldx-1 zero; at t = 0 the initial linear states (x0_lin n x 1 repeated, or
+ *        n x N_P).  Owned by the context, valid in stream order until the next step call.  RBPF_ERR_STATE after the last step.
+ *   rbpf_filter_step_sparse_device  xn_new_dev [n_nonlin x N_P] column-major.
+ *        yhat_layout 0: yhat(i,k) at i + N_P*k (MATLAB order); 2: C-contiguous [N_P][n_y].
+ *        dy_layout 0: dy(i,k,c) at i + N_P*(k + n_y*c) (MATLAB order, packed by a kernel first); 2: C-contiguous
+ *        [N_P][n_y][n_lin]; 1: rows on the stride ldx, [N_P][n_y][ldx].  dy is dense: no structure is assumed.
+ *        Rows of yhat / dy that belong to outputs not observed at this step (NaN in y) are not read by the step; they may hold
+ *        anything.  Per particle: e = (y - yhat)(ind), S = dy(ind,:) P dy(ind,:)' + R(ind,ind), chol with the one jitter retry
+ *        of particleFilter.m:145-148 (a second failure: RBPF_ERR_CHOL_FAILED at the next rbpf_sync / rbpf_filter_finish), the
+ *        weight (:150), xl + K e and P - K S K' (:181,197-198); nothing observed: weight 0, state carried over.  Then the
+ *        weights are normalised and the next ancestors drawn as for every other family.  Returns without waiting unless an
+ *        on_step hook is set.  rbpf_filter_advance and device callbacks are not available for this kind (RBPF_ERR_STATE).
+ *   rbpf_filter_sparse_yhattraj  yhattraj [n_y x N_T] column-major (particleFilter.m:94,201-203): column t is the whole yhat
+ *        of step t's maximum-weight particle as the caller handed it in, NaN for steps not yet run.  Waits for the stream.    */
+int rbpf_filter_sparse_gathered_device(rbpf_ctx* ctx, const double** xl_dev, int32_t* ldx);
+int rbpf_filter_step_sparse_device(rbpf_ctx* ctx, const double* xn_new_dev, const double* yhat_dev, int32_t yhat_layout,
+                                   const double* dy_dev, int32_t dy_layout);
+int rbpf_filter_sparse_yhattraj(rbpf_ctx* ctx, double* yhattraj);
 /* Enable (1) / disable (0) per-launch HIP-event timing of the stream kernel; read / reset it.     */
 int rbpf_timing_enable(rbpf_ctx* ctx, int32_t on);
 int rbpf_timing_read(rbpf_ctx* ctx, rbpf_timing* out, int32_t reset);

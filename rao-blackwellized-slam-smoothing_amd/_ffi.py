@@ -25,6 +25,7 @@ RBPF_MODEL_DENSE_MAG_6D = 1
 RBPF_MODEL_DENSE_RADIO_2DH = 2
 RBPF_MODEL_SPARSE_VISUAL_2D = 3
 RBPF_MODEL_GENERIC_DENSE = 4
+RBPF_MODEL_GENERIC_SPARSE = 5
 RBPF_RNG_REPLAY = 0
 RBPF_RNG_PHILOX = 1
 
@@ -147,7 +148,8 @@ EXPORTS = [
     "rbpf_particle_filter", "rbpf_particle_smoother", "rbpf_particle_smoother_device",
     "rbpf_filter_create", "rbpf_filter_workspace_bytes", "rbpf_filter_advance", "rbpf_filter_reset", "rbpf_sync",
     "rbpf_filter_finish", "rbpf_filter_tell", "rbpf_filter_schedule", "rbpf_filter_one_launch_flushes", "rbpf_filter_resample_fallbacks", "rbpf_plan_refresh", "rbpf_chol_refresh_resolve", "rbpf_shard_smoother_refresh_reserve", "rbpf_shard_xn_traj", "rbpf_filter_ancestors", "rbpf_filter_step_external", "rbpf_filter_external_layout", "rbpf_filter_ancestors_device",
-    "rbpf_filter_step_device", "rbpf_filter_set_device_callbacks", "rbpf_timing_enable", "rbpf_timing_read", "rbpf_destroy",
+    "rbpf_filter_step_device", "rbpf_filter_set_device_callbacks",
+    "rbpf_filter_sparse_gathered_device", "rbpf_filter_step_sparse_device", "rbpf_filter_sparse_yhattraj", "rbpf_timing_enable", "rbpf_timing_read", "rbpf_destroy",
     "rbpf_philox_fill", "rbpf_meas_model", "rbpf_dyn_model", "rbpf_dyn_res_norm", "rbpf_sample",
     "rbpf_jacobian_phi3d", "rbpf_chol_weights", "rbpf_chol_sweep_probe", "rbpf_ext_pack_whiten_probe", "rbpf_quat_helpers", "rbpf_probe_wave_reduce",
     "rbpf_shard_create", "rbpf_shard_views_get", "rbpf_shard_normalise_search", "rbpf_shard_pack", "rbpf_shard_step",
@@ -245,6 +247,9 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_filter_ancestors_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.rbpf_filter_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.rbpf_filter_set_device_callbacks.argtypes = [C.c_void_p, C.POINTER(rbpf_callbacks), C.c_int32]
+    lib.rbpf_filter_sparse_gathered_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p]
+    lib.rbpf_filter_step_sparse_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+    lib.rbpf_filter_sparse_yhattraj.argtypes = [C.c_void_p, c_double_p]
     lib.rbpf_stream_get.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.rbpf_timing_enable.argtypes = [C.c_void_p, C.c_int32]
     lib.rbpf_timing_read.argtypes = [C.c_void_p, C.POINTER(rbpf_timing), C.c_int32]

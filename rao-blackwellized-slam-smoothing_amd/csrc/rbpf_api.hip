@@ -64,8 +64,8 @@ static int build_chol_factors(const rbpf_model* model, const rbpf_problem* p, st
     double* Lb = &blk[(size_t)t * nw * nw];
     double* Lf = &full[(size_t)t * nw * nw];
     bool ok = true;
-    if (model->kind == RBPF_MODEL_GENERIC_DENSE) {
-      // dynModel runs on the host: Q is its business.  Only the additive default of an empty dynResNorm
+    if (model->kind == RBPF_MODEL_GENERIC_DENSE || model->kind == RBPF_MODEL_GENERIC_SPARSE) {
+      // dynModel is the caller's: Q is its business.  Only the additive default of an empty dynResNorm
       // (particleSmoother.m:175-177) needs chol(dt*Q,'lower'); a failure is reported when a smoother asks for it.
       if (!chol_lower_host(A.data(), nw, nw, Lf, nw) && full_ok) *full_ok = false;
       continue;
@@ -108,7 +108,7 @@ static void invert_R_small(const double* R, int d, double* Rinv, double& halfLog
 
 int fill_model_dev(const rbpf_model* model, int nN, int n, int d, int nw, int nodo, const double* R, double jitter,
                    ModelDev& M, std::vector<int>& nn_axis_major) {
-  if (!model || (!model->NN && model->kind != RBPF_MODEL_SPARSE_VISUAL_2D && model->kind != RBPF_MODEL_GENERIC_DENSE)) { set_error("model / model->NN is NULL"); return RBPF_ERR_INVALID_ARG; }
+  if (!model || (!model->NN && model->kind != RBPF_MODEL_SPARSE_VISUAL_2D && model->kind != RBPF_MODEL_GENERIC_DENSE && model->kind != RBPF_MODEL_GENERIC_SPARSE)) { set_error("model / model->NN is NULL"); return RBPF_ERR_INVALID_ARG; }
   std::memset(&M, 0, sizeof(M));
   M.kind = model->kind;
   M.m = model->m_basis;
@@ -157,6 +157,18 @@ int fill_model_dev(const rbpf_model* model, int nN, int n, int d, int nw, int no
     M.logconst = -0.5 * d * std::log(2.0 * 3.14159265358979323846);
     nn_axis_major.clear();
     return RBPF_OK;                       // R lives in device memory (ModelDev::Rdev, set by ctx_create)
+  } else if (model->kind == RBPF_MODEL_GENERIC_SPARSE) {
+    // any measModel with sparseFeatures = true, evaluated by the caller's device code (rbpf_filter_step_sparse_device)
+    if (model->callbacks) { set_error("generic sparse family: rbpf_model.callbacks must be NULL (the caller's device code drives the steps)"); return RBPF_ERR_INVALID_ARG; }
+    if (d < 1 || d > 32) { set_error("generic sparse family: n_y must be 1 .. 32"); return RBPF_ERR_UNSUPPORTED; }
+    if (n < 1 || n > 96) { set_error("generic sparse family: nLin must be 1 .. 96 (the border-only bank layout)"); return RBPF_ERR_UNSUPPORTED; }
+    if (nN < 1 || nw < 1) { set_error("generic sparse family: n_nonlin and n_w must be 1 .. 8"); return RBPF_ERR_INVALID_ARG; }
+    if (sparse_ext_step_lds_bytes(n, d) > 150 * 1024) { set_error("generic sparse family: the step kernel's LDS plan exceeds 150 KB at this n_y and nLin"); return RBPF_ERR_UNSUPPORTED; }
+    M.m = n; M.dim = 0; M.ktot = 0;
+    M.jitter = jitter;
+    M.logconst = -0.5 * d * std::log(2.0 * 3.14159265358979323846);
+    nn_axis_major.clear();
+    return RBPF_OK;                       // R lives in device memory, as for the sparse-visual family
   } else {
     set_error("unknown model family");
     return RBPF_ERR_UNSUPPORTED;
@@ -222,7 +234,17 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
   RB_TRY(fill_model_dev(model, prob->n_nonlin, prob->n_lin, prob->n_y, prob->n_w, prob->n_odo, prob->R, jitter, c->mdl, nn));
   c->lay = make_layout(prob->n_lin, prob->n_y);
   c->lay_low = make_layout_low_regs(prob->n_lin, prob->n_y);
-  const bool sparse = model->kind == RBPF_MODEL_SPARSE_VISUAL_2D;
+  const bool gsparse = model->kind == RBPF_MODEL_GENERIC_SPARSE;
+  const bool sparse = model->kind == RBPF_MODEL_SPARSE_VISUAL_2D || gsparse;
+  if (gsparse) {
+    // what this family does not have is refused here, before any device memory is taken
+    const char* who = "generic sparse family (sparseFeatures = true with device handles): ";
+    if (smoother) { set_error(std::string(who) + "the filter only (the smoothers' sparse branch linearises N_P x (N_T - t) times per step: another kernel and another handle contract)"); return RBPF_ERR_UNSUPPORTED; }
+    if (ex || wants_multi(&c->opt)) { set_error(std::string(who) + "n_devices is not supported (the sparseFeatures branch is not sharded)"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->opt.storage != 0) { set_error(std::string(who) + "options.storage must be 0 (fp64 full squares)"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->opt.lazy_depth >= 2) { set_error(std::string(who) + "lazy_depth >= 2 is not supported (the EKF update rewrites every covariance at every step)"); return RBPF_ERR_UNSUPPORTED; }
+    if (c->opt.inplace > 0) { set_error(std::string(who) + "inplace = 1 is not supported (one covariance bank needs lazy_depth >= 2)"); return RBPF_ERR_UNSUPPORTED; }
+  }
   c->fp32 = c->opt.storage == 1 || c->opt.storage == 3;
   if (c->opt.storage < 0 || c->opt.storage > 3) { set_error("options.storage must be 0 (fp64), 1 (fp32), 2 (fp64, symmetric) or 3 (fp32, symmetric)"); return RBPF_ERR_INVALID_ARG; }
   if (model->kind == RBPF_MODEL_GENERIC_DENSE && prob->n_y != 1 && prob->n_y != 3) {
@@ -276,7 +298,9 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     c->h_dt.assign(prob->dt, prob->dt + prob->dt_len);
     c->q_pages = prob->q_pages; c->dt_len = prob->dt_len;
   }
-  if (sparse) {
+  if (gsparse) {
+    if (c->lay.mc != 0) { set_error("generic sparse family: nLin must be 1 .. 96 (the border-only bank layout)"); return RBPF_ERR_UNSUPPORTED; }
+  } else if (sparse) {
     if (c->lay.mc != 0 || sparse_step_lds_bytes(prob->n_lin, prob->n_y) > 150 * 1024) { set_error("sparse-visual-2D supports nLin <= 96"); return RBPF_ERR_UNSUPPORTED; }
     if (ex) { set_error("the sparseFeatures branch is not sharded"); return RBPF_ERR_UNSUPPORTED; }
   } else if (step_lds_bytes(c->mdl, c->lay, smoother ? 1 : 0) > 160 * 1024) { set_error("nLin too large for the LDS plan of the step kernel"); return RBPF_ERR_UNSUPPORTED; }
@@ -442,6 +466,11 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
   RB_TRY(c->pool.alloc(&c->d_counts, (size_t)2 * N + 128));
   RB_TRY(c->pool.alloc(&c->d_flags, 16));
   HIPCHK(hipMemsetAsync(c->d_flags, 0, 16 * sizeof(int), c->stream));
+  if (gsparse) {
+    RB_TRY(c->pool.alloc(&c->d_xl_g, (size_t)N * L.ldx));
+    const std::vector<double> nans((size_t)T * d, std::nan(""));                          // particleFilter.m:94
+    RB_TRY(c->pool.upload(&c->d_yhattraj, nans.data(), nans.size()));
+  }
   RB_TRY(ctx_reset(c));
   HIPCHK(hipStreamSynchronize(c->stream));
   guard.release();
@@ -471,6 +500,7 @@ int ctx_reset(rbpf_ctx* c) {
   c->ready_step = -1;
   c->drawn_step = -1;
   c->order_step = -1;
+  c->gathered_step = -1;
   if (c->mdl.kind == RBPF_MODEL_GENERIC_DENSE) {              // particleFilter.m:59: xn = repmat(x0_nonLin, 1, N_P)
     c->h_xn.resize((size_t)c->mdl.nN * c->N);
     for (int i = 0; i < c->N; ++i) for (int q = 0; q < c->mdl.nN; ++q) c->h_xn[q + (size_t)c->mdl.nN * i] = c->h_x0n[q];
@@ -558,7 +588,8 @@ int generic_finish_inputs(rbpf_ctx* c, const double* xref_host) {
 // The same contracts with device pointers: the ancestors' states are gathered by a kernel, the handles' results are brought
 // into the step kernels' layouts by kernels (rbpf_external.hip), everything in stream order.  No copy to or from the host,
 // no host synchronisation.
-static int ext_device_ctx_ok(const rbpf_ctx* c) {
+static int ext_device_ctx_ok(const rbpf_ctx* c, bool sparse_too = false) {
+  if (sparse_too && c->mdl.kind == RBPF_MODEL_GENERIC_SPARSE && !c->smoother && !c->sh) return RBPF_OK;
   if (c->mdl.kind != RBPF_MODEL_GENERIC_DENSE || c->has_cb || c->smoother || c->sh || !c->d_xn_ext || !c->d_H_ext) {
     set_error("the device entry points of the generic family need a filter context created with rbpf_model.callbacks == NULL");
     return RBPF_ERR_STATE;
@@ -829,12 +860,51 @@ static int ctx_step_diagnostics(rbpf_ctx* c, StepArgs& a, const int* A_t) {
   return RBPF_OK;
 }
 
+// Weights of step t from its log-weights (particleFilter.m:154-161) and, on the filter's fast path, the ancestors of step t + 1
+// with their ancestor-sorted processing order in the same launch.  sort_remap: the stored-matrix slot of every lineage (the sort
+// key of the next step) or null; u_pre_drawn: propagate_kernel left the Philox uniforms of step t + 1 in d_unext.
+static int ctx_normalise_resample(rbpf_ctx* c, int t, int k_iter, const int* sort_remap, bool u_pre_drawn) {
+  const int N = c->N, nN = c->mdl.nN;
+  const bool hist = c->opt.keep_history != 0;
+  double* X_new = c->X + (size_t)(hist ? t : (t & 1)) * nN * N;
+  const size_t tr = c->opt.trace ? (size_t)t * N : 0;
+  const size_t rng_page = (size_t)k_iter * N * std::max(c->T - 1, 0);
+  NormArgs nm;
+  nm.N = N; nm.nN = nN; nm.t = t; nm.logw = c->logw + tr; nm.w = c->w + tr; nm.wc = c->wc; nm.xn = X_new;
+  nm.traj_max = c->traj_max + (size_t)t * nN; nm.traj_mean = c->traj_mean + (size_t)t * nN;
+  nm.iw_max = c->d_flags + 2; nm.lse_out = nullptr;
+  nm.parallel_scan = 1;
+  if (c->fuse_resample && t + 1 < c->T) {
+    // filter fast path: one single-workgroup kernel normalises step t and draws step t+1's ancestors and
+    // their ancestor-sorted processing order
+    int* A_next = c->A + (hist ? (size_t)(t + 1) * N : 0);
+    SearchArgs s;
+    s.N = N; s.n_draw = N; s.t = t + 1; s.wc = c->wc; s.rng_mode = c->rng_mode; s.k_iter = k_iter;
+    s.U = c->d_U ? c->d_U + rng_page + (size_t)t * N : nullptr;
+    if (u_pre_drawn) { s.rng_mode = RBPF_RNG_REPLAY; s.U = c->d_unext; }     // pre-drawn by propagate_kernel (same Philox values)
+    s.seed = c->seed; s.ai = A_next; s.overflow = c->d_flags + 1; s.slot0 = 0; s.u_is_scalar = 0;
+    s.approx = 1; s.ambiguous = c->d_flags + 4; s.w = c->w + tr; s.wc_exact = c->wc;
+    // sort key of the next step: the slot of the stored matrix each ancestor's lineage refers to
+    if (N > kSingleWgResampleMaxN)
+      HIPCHK(launch_resample_pipeline(nm, &s, c->d_order, c->d_counts, sort_remap, c->d_rs, c->stream));
+    else
+      HIPCHK(launch_normalise_resample(nm, s, c->d_order, c->d_counts, c->stream, sort_remap));
+    c->ready_step = t + 1;
+  } else if (N > kSingleWgResampleMaxN) {
+    HIPCHK(launch_resample_pipeline(nm, nullptr, nullptr, nullptr, nullptr, c->d_rs, c->stream));
+  } else {
+    HIPCHK(launch_normalise_scan(nm, c->stream));
+  }
+  return RBPF_OK;
+}
+
 // One time step of particleFilter.m:100-218 / particleSmoother.m:124-341 (iteration k_iter).
 // xref != nullptr: slot N-1 is the conditioned reference trajectory (its ancestor index has
 // already been written to A_t[N-1] by the ancestor-sampling kernels).
 int ctx_step(rbpf_ctx* c, int k_iter, const double* xref_t, int n_draw, const InfoStep* info) {
   const int t = c->t, N = c->N, nN = c->mdl.nN, d = c->mdl.d, nw = c->mdl.nw;
   if (t >= c->T) { set_error("advance past N_T"); return RBPF_ERR_STATE; }
+  if (c->mdl.kind == RBPF_MODEL_GENERIC_SPARSE) { set_error("generic sparse model: advance with rbpf_filter_step_sparse_device"); return RBPF_ERR_STATE; }
   const Layout& L = c->lay;
   const bool hist = c->opt.keep_history != 0;
   int* A_t = c->A + (hist ? (size_t)t * N : 0);
@@ -876,7 +946,13 @@ int ctx_step(rbpf_ctx* c, int k_iter, const double* xref_t, int n_draw, const In
     sa.rng_mode = c->rng_mode; sa.k_iter = k_iter; sa.seed = c->seed;
     sa.Z = (c->d_Z && t > 0) ? c->d_Z + (rng_page + (size_t)(t - 1) * N) * nw : nullptr;
     sa.xref = xref_t; sa.jitter = c->mdl.jitter; sa.logw = c->logw + tr; sa.status = c->d_flags;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->timing_on) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, c->stream)); }
     HIPCHK(launch_sparse_step(sa, c->stream));
+    if (c->timing_on) {                                  // covariance in and out, means in and out
+      HIPCHK(hipEventRecord(e1, c->stream)); c->events.emplace_back(e0, e1);
+      c->sched_bytes += 8.0 * (double)N * (2.0 * sa.n * sa.n + 2.0 * sa.n + 2.0 * nN);
+    }
     NormArgs nm;
     nm.N = N; nm.nN = nN; nm.t = t; nm.logw = c->logw + tr; nm.w = c->w + tr; nm.wc = c->wc; nm.xn = X_new;
     nm.traj_max = c->traj_max + (size_t)t * nN; nm.traj_mean = c->traj_mean + (size_t)t * nN;
@@ -934,34 +1010,7 @@ int ctx_step(rbpf_ctx* c, int k_iter, const double* xref_t, int n_draw, const In
   RB_TRY(ctx_arm_distinct(c, a, (size_t)N + 1));
   HIPCHK(launch_propagate(a, c->stream));
   RB_TRY(ctx_launch_step(c, a, bk, mode));
-
-  NormArgs nm;
-  nm.N = N; nm.nN = nN; nm.t = t; nm.logw = c->logw + tr; nm.w = c->w + tr; nm.wc = c->wc; nm.xn = X_new;
-  nm.traj_max = c->traj_max + (size_t)t * nN; nm.traj_mean = c->traj_mean + (size_t)t * nN;
-  nm.iw_max = c->d_flags + 2; nm.lse_out = nullptr;
-  nm.parallel_scan = 1;
-  if (c->fuse_resample && t + 1 < c->T) {
-    // filter fast path: one single-workgroup kernel normalises step t and draws step t+1's ancestors and
-    // their ancestor-sorted processing order
-    int* A_next = c->A + (hist ? (size_t)(t + 1) * N : 0);
-    SearchArgs s;
-    s.N = N; s.n_draw = N; s.t = t + 1; s.wc = c->wc; s.rng_mode = c->rng_mode; s.k_iter = k_iter;
-    s.U = c->d_U ? c->d_U + rng_page + (size_t)t * N : nullptr;
-    if (a.u_next) { s.rng_mode = RBPF_RNG_REPLAY; s.U = c->d_unext; }     // pre-drawn by propagate_kernel (same Philox values)
-    s.seed = c->seed; s.ai = A_next; s.overflow = c->d_flags + 1; s.slot0 = 0; s.u_is_scalar = 0;
-    s.approx = 1; s.ambiguous = c->d_flags + 4; s.w = c->w + tr; s.wc_exact = c->wc;
-    // sort key of the next step: the slot of the stored matrix each ancestor's lineage refers to
-    if (N > kSingleWgResampleMaxN)
-      HIPCHK(launch_resample_pipeline(nm, &s, c->d_order, c->d_counts, lazy ? c->base[bk.tnew] : nullptr, c->d_rs, c->stream));
-    else
-      HIPCHK(launch_normalise_resample(nm, s, c->d_order, c->d_counts, c->stream, lazy ? c->base[bk.tnew] : nullptr));
-    c->ready_step = t + 1;
-  } else if (N > kSingleWgResampleMaxN) {
-    HIPCHK(launch_resample_pipeline(nm, nullptr, nullptr, nullptr, nullptr, c->d_rs, c->stream));
-  } else {
-    HIPCHK(launch_normalise_scan(nm, c->stream));
-  }
-  return RBPF_OK;
+  return ctx_normalise_resample(c, t, k_iter, lazy ? c->base[bk.tnew] : nullptr, a.u_next != nullptr);
 }
 
 // Flushed covariances of `count` particles (index: device list or null = 0..count-1) in MATLAB layout.
@@ -1171,14 +1220,14 @@ int rbpf_filter_step_external(rbpf_ctx* c, const double* xn_new, const double* d
 int rbpf_filter_external_layout(const rbpf_ctx* c, int32_t* ldx) {
   if (!c && ldx && callback_context()) { *ldx = callback_context()->lay.ldx; return RBPF_OK; }   // inside a device callback of a one-shot call
   if (!c || !ldx) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
-  RB_TRY(ext_device_ctx_ok(c));
+  RB_TRY(ext_device_ctx_ok(c, true));
   *ldx = c->lay.ldx;
   return RBPF_OK;
 }
 
 int rbpf_filter_ancestors_device(rbpf_ctx* c, const int32_t** ai_dev, const double** xn_anc_dev) {
   if (!c || !ai_dev || !xn_anc_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
-  RB_TRY(ext_device_ctx_ok(c));
+  RB_TRY(ext_device_ctx_ok(c, true));
   if (c->t < 1 || c->t >= c->T || c->ready_step != c->t) { set_error("no ancestors drawn for the next step (run a step first)"); return RBPF_ERR_STATE; }
   HIPCHK(hipSetDevice(c->device));
   RB_TRY(ext_device_buffers(c, false, false));
@@ -1216,6 +1265,97 @@ int rbpf_filter_set_device_callbacks(rbpf_ctx* c, const rbpf_callbacks* cb, int3
   c->dev_cb = *cb; c->dev_cb.dyn_res_norm = nullptr;
   c->dev_dy_layout = dy_layout;
   c->has_dev_cb = true;
+  return RBPF_OK;
+}
+
+// ---- generic sparse family: sparseFeatures = true with handles on the device --------------------------------------------
+static int sparse_device_ctx_ok(const rbpf_ctx* c) {
+  if (c->mdl.kind != RBPF_MODEL_GENERIC_SPARSE || c->smoother || c->sh || !c->d_xl_g) {
+    set_error("the sparse device entry points need a filter context of RBPF_MODEL_GENERIC_SPARSE");
+    return RBPF_ERR_STATE;
+  }
+  if (c->t >= c->T) { set_error("advance past N_T"); return RBPF_ERR_STATE; }
+  return RBPF_OK;
+}
+
+// xl(:,ai) of the step about to run (particleFilter.m:112) into d_xl_g
+static int sparse_gather_xl(rbpf_ctx* c) {
+  const int t = c->t, N = c->N, ldx = c->lay.ldx;
+  if (c->gathered_step == t) return RBPF_OK;
+  if (t == 0) {
+    HIPCHK(launch_sparse_ext_gather_xl(N, ldx, c->d_x0l, c->x0_lin_cols > 1 ? (size_t)ldx : 0, nullptr, c->d_xl_g, c->stream));
+  } else {
+    if (c->ready_step != t) { set_error("no ancestors drawn for the next step (run a step first)"); return RBPF_ERR_STATE; }
+    const int* A_t = c->A + (c->opt.keep_history ? (size_t)t * N : 0);
+    HIPCHK(launch_sparse_ext_gather_xl(N, ldx, c->xl[c->xcur], (size_t)ldx, A_t, c->d_xl_g, c->stream));
+  }
+  c->gathered_step = t;
+  return RBPF_OK;
+}
+
+int rbpf_filter_sparse_gathered_device(rbpf_ctx* c, const double** xl_dev, int32_t* ldx) {
+  if (!c || !xl_dev || !ldx) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(sparse_device_ctx_ok(c));
+  HIPCHK(hipSetDevice(c->device));
+  RB_TRY(sparse_gather_xl(c));
+  *xl_dev = c->d_xl_g;
+  *ldx = c->lay.ldx;
+  return RBPF_OK;
+}
+
+int rbpf_filter_step_sparse_device(rbpf_ctx* c, const double* xn_new_dev, const double* yhat_dev, int32_t yhat_layout,
+                                   const double* dy_dev, int32_t dy_layout) {
+  if (!c || !xn_new_dev || !yhat_dev || !dy_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (yhat_layout != 0 && yhat_layout != 2) { set_error("yhat_layout must be 0 (MATLAB order) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
+  if (dy_layout < 0 || dy_layout > 2) { set_error("dy_layout must be 0 (MATLAB order), 1 (rows on the stride ldx) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(sparse_device_ctx_ok(c));
+  HIPCHK(hipSetDevice(c->device));
+  const int t = c->t, N = c->N, nN = c->mdl.nN, n = c->mdl.n, d = c->mdl.d;
+  const Layout& L = c->lay;
+  const bool hist = c->opt.keep_history != 0;
+  RB_TRY(sparse_gather_xl(c));
+  double* X_new = c->X + (size_t)(hist ? t : (t & 1)) * nN * N;
+  HIPCHK(launch_ext_states_to_soa(N, nN, xn_new_dev, X_new, c->stream));
+  if (dy_layout == 0) {                               // the lines of one particle lie N_P doubles apart: pack them into rows first
+    if (!c->d_H_ext) RB_TRY(c->pool.alloc(&c->d_H_ext, (size_t)N * d * L.ldx));
+    HIPCHK(launch_ext_pack_dy(0, N, d, n, L.ldx, dy_dev, c->d_H_ext, c->stream));
+  }
+  const size_t tr = c->opt.trace ? (size_t)t * N : 0;
+  const int ob = c->cur, nb = (t == 0) ? 0 : (c->cur ^ 1);
+  SparseExtStepArgs sa;
+  sa.N = N; sa.n = n; sa.d = d; sa.ldx = L.ldx; sa.ldb = L.ldb; sa.szB = L.szB;
+  sa.ai = (t > 0) ? c->A + (hist ? (size_t)t * N : 0) : nullptr;
+  sa.xl_g = c->d_xl_g; sa.xl_new = c->xl[nb];
+  if (t == 0) { sa.Pb_old = c->d_P0b; sa.Pb_old_stride = 0; }
+  else { sa.Pb_old = c->Pb[ob]; sa.Pb_old_stride = L.szB; }
+  sa.Pb_new = c->Pb[nb];
+  sa.yhat = yhat_dev; sa.yhat_si = yhat_layout == 0 ? 1 : (size_t)d; sa.yhat_sk = yhat_layout == 0 ? (size_t)N : 1;
+  sa.dy = dy_layout == 0 ? c->d_H_ext : dy_dev;
+  sa.dy_sr = dy_layout == 2 ? n : L.ldx; sa.dy_sp = (size_t)d * sa.dy_sr;
+  sa.y = c->d_y + (size_t)t * d; sa.R = c->d_R; sa.jitter = c->mdl.jitter; sa.logw = c->logw + tr; sa.status = c->d_flags;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (c->timing_on) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, c->stream)); }
+  HIPCHK(launch_sparse_ext_step(sa, c->stream));
+  if (c->timing_on) {                                 // covariance in and out, Jacobian and yhat in, means in and out
+    HIPCHK(hipEventRecord(e1, c->stream)); c->events.emplace_back(e0, e1);
+    c->sched_bytes += 8.0 * (double)N * (2.0 * n * n + (double)d * n + d + 2.0 * n);
+  }
+  c->cur = nb; c->xcur = nb;
+  c->t = t + 1;
+  c->fuse_resample = true;
+  RB_TRY(ctx_normalise_resample(c, t, 0, nullptr, false));
+  HIPCHK(launch_sparse_ext_yhat_of_max(d, yhat_dev, sa.yhat_si, sa.yhat_sk, c->d_flags + 2, c->d_yhattraj + (size_t)t * d, c->stream));
+  if (!c->opt.on_step) return RBPF_OK;
+  HIPCHK(hipStreamSynchronize(c->stream));          // as rbpf_filter_step_device: the hook sees a finished step
+  return ctx_call_on_step(c, c->t - 1, false);
+}
+
+int rbpf_filter_sparse_yhattraj(rbpf_ctx* c, double* yhattraj) {
+  if (!c || !yhattraj) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (c->mdl.kind != RBPF_MODEL_GENERIC_SPARSE || !c->d_yhattraj) { set_error("the sparse device entry points need a filter context of RBPF_MODEL_GENERIC_SPARSE"); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(yhattraj, c->d_yhattraj, (size_t)c->T * c->mdl.d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return RBPF_OK;
 }
 

@@ -94,6 +94,10 @@ struct rbpf_ctx {
   bool has_dev_cb = false;
   int dev_dy_layout = 0;
   double *d_xn_anc = nullptr, *d_xn_cm = nullptr, *d_dy_stage = nullptr;
+  // generic sparse family (RBPF_MODEL_GENERIC_SPARSE): xl(:,ai) of the step about to run [N][ldx] and the step it was gathered
+  // for, yhat of every step's maximum-weight particle [T][d]
+  double *d_xl_g = nullptr, *d_yhattraj = nullptr;
+  int gathered_step = -1;
   std::vector<double> h_xn;      // generic family: states of the last step [nN x N] column-major (host evaluates dynModel)
   std::vector<double> h_xn_new, h_dy;   // scratch of the callbacks
   std::vector<int> h_ai;

@@ -282,7 +282,7 @@ int create(Multi& M, const rbpf_model* model, const rbpf_problem* prob, const rb
   const int W = opt->n_devices;
   if (W < 1 || W > 64) { set_error("options.n_devices must be in 1..64"); return RBPF_ERR_INVALID_ARG; }
   if (prob->N_P % W) { set_error("N_P must be a multiple of options.n_devices"); return RBPF_ERR_INVALID_ARG; }
-  if (model->kind == RBPF_MODEL_GENERIC_DENSE || model->kind == RBPF_MODEL_SPARSE_VISUAL_2D) {
+  if (model->kind == RBPF_MODEL_GENERIC_DENSE || model->kind == RBPF_MODEL_SPARSE_VISUAL_2D || model->kind == RBPF_MODEL_GENERIC_SPARSE) {
     set_error("options.n_devices: the recognised dense model families only (host callbacks are not sharded)"); return RBPF_ERR_UNSUPPORTED;
   }
   if (opt->on_step && !smoother) { set_error("options.n_devices: the per-step hook (makePlots) is not available in the sharded filter"); return RBPF_ERR_UNSUPPORTED; }

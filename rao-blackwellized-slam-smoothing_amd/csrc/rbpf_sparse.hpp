@@ -37,6 +37,28 @@ struct SparseAncArgs {
   double* S;                          // [N][M*M] column-major
 };
 
+// The same step for RBPF_MODEL_GENERIC_SPARSE (rbpf_sparse_ext.hip): measModel was evaluated by the caller's device code
+struct SparseExtStepArgs {
+  int N, n, d, ldx, ldb;
+  size_t szB;
+  const int* ai;                      // ancestors of this step (null: identity): whose covariance slot i starts from
+  const double* xl_g;                 // [N][ldx] xl(:,ai), gathered before measModel ran (particleFilter.m:112)
+  double* xl_new;                     // [N][ldx]
+  const double* Pb_old; size_t Pb_old_stride; double* Pb_new;                         // [N][n][ldb] row-major
+  const double* yhat; size_t yhat_si, yhat_sk;       // yhat(i, k) at i*si + k*sk
+  const double* dy; size_t dy_sp; int dy_sr;         // dy(i, k, c) at i*sp + k*sr + c
+  const double* y;                    // [d] outputs of this step, NaN = not observed
+  const double* R;                    // [d x d] column-major
+  double jitter;
+  double* logw;
+  int* status;
+};
+
+size_t sparse_ext_step_lds_bytes(int n, int d);
+hipError_t launch_sparse_ext_step(const SparseExtStepArgs& a, hipStream_t s);
+hipError_t launch_sparse_ext_gather_xl(int N, int ldx, const double* src, size_t src_stride, const int* ai, double* out, hipStream_t s);
+hipError_t launch_sparse_ext_yhat_of_max(int d, const double* yhat, size_t si, size_t sk, const int* iw_max, double* out, hipStream_t s);
+
 size_t sparse_step_lds_bytes(int n, int d);
 hipError_t launch_sparse_step(const SparseStepArgs& a, hipStream_t s);
 hipError_t launch_sparse_anc(const SparseAncArgs& a, int N, hipStream_t s);

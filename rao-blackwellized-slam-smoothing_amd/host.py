@@ -302,6 +302,25 @@ class GenericDenseModel:
         return d
 
 
+class GenericSparseModel:
+    """Descriptor behind a DeviceSparseHandles object: an arbitrary model with sparseFeatures = true, sized from the problem arrays
+    (RBPF_MODEL_GENERIC_SPARSE).  It carries no handles -- the binding drives the steps -- only the sizes and the per-step arguments
+    of dynModel.  Admitted: ny <= 32, nLin <= 96, nNonLin and nw <= 8; the filter on one GPU, fp64 storage."""
+    kind = _ffi.RBPF_MODEL_GENERIC_SPARSE
+    sparse = True
+
+    def __init__(self, nNonLin, nLin, ny, nw, n_odo, odometry=None, Q=None, dt=None):
+        self.nNonLin, self.nLin, self.ny, self.nw, self.n_odo = int(nNonLin), int(nLin), int(ny), int(nw), int(n_odo)
+        self._odo, self._Q, self._dt = odometry, Q, dt
+        self.error = None
+
+    def descriptor(self, use_dyn_res_norm=False):
+        d = _ffi.rbpf_model()
+        d.kind, d.m_basis, d.dim, d.use_dyn_res_norm = self.kind, self.nLin, 0, 0
+        d.NN = None
+        return d
+
+
 class DeviceHandles:
     """An arbitrary (unrecognised) dense model whose handles are device code: batched callables on torch float64 tensors of
     the library's device,
@@ -365,6 +384,29 @@ class DeviceSmootherHandles(DeviceHandles):
         if not _is_empty_handle(dynResNorm) and not callable(dynResNorm):
             raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "dynResNorm must be callable or None")
         self.dynResNorm = None if _is_empty_handle(dynResNorm) else dynResNorm
+
+
+class DeviceSparseHandles(DeviceHandles):
+    """An arbitrary model with sparseFeatures = true (particleFilter.m:127-137,165-181) whose handles are device code: batched
+    callables on torch float64 tensors of the library's device, run inside torch.cuda.stream(the library's stream),
+
+        xn_new (n_nonlin, N_P)               = dynModel(xn_anc (n_nonlin, N_P), dx (n_odo,), dt, Q (n_w, n_w))   -- draws its own random numbers
+        yhat (N_P, n_y), dy (N_P, n_y, nLin) = measModel(xn (n_nonlin, N_P), xl (N_P, nLin))
+
+    handed to particleFilter(handles, None, ..., sparseFeatures=True) or FilterSession in place of the handle pair.  xl is a view of
+    library memory: the linear states after the resampling gather, xl(:,ai) (:112); row i is the map measModel linearises
+    particle i at.  measModel is called once per step (the reference's second call at :167 is at the same point).  NaN in y marks
+    an output that was not observed: the rows of yhat / dy that belong to such outputs are never read by the step and may hold
+    anything, NaN included; dy is dense, no structure is assumed.
+    The layouts are read off the strides of what measModel returns: dy C-contiguous or in MATLAB order (strides
+    (1, N_P, N_P n_y), packed by a kernel first), yhat contiguous or transposed; anything else costs one contiguous().
+    extras=True adds yhattraj (n_y, N_T): every step's yhat of the maximum-weight particle (:201-203).
+    n_y <= 32, nLin <= 96, n_nonlin and n_w <= 8; the filter on one GPU with fp64 storage.  Not taken by the smoothers, by sharded
+    sessions, with sparseFeatures=False, or with lazy_depth / inplace / another storage (see GenericSparseModel).
+    A handle that raises, or returns a wrong shape, dtype or device, surfaces as that exception; the library stays usable."""
+
+    def __init__(self, dynModel, measModel):
+        super().__init__(dynModel, measModel)
 
 
 def _refuse_device_handles(what, *handles):
@@ -595,6 +637,56 @@ class _DeviceDriver:
             raise
 
 
+class _SparseDeviceDriver(_DeviceDriver):
+    """Runs the steps of a generic sparse filter context with DeviceSparseHandles (see there)."""
+
+    def _meas_sparse(self, xn, xl):
+        torch = self.torch
+        out = self.h.measModel(xn, xl)
+        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(v) for v in out)):
+            raise ValueError("measModel must return (yhat, dy), two device tensors")
+        for what, v, shape in (("yhat", out[0], (self.N, self.d)), ("dy", out[1], (self.N, self.d, self.n))):
+            if tuple(v.shape) != shape or v.dtype != torch.float64 or not v.is_cuda:
+                raise ValueError(f"measModel returned {what} {tuple(v.shape)} {v.dtype} on {v.device}, expected a float64 device "
+                                 f"tensor of shape {shape}")
+        return out
+
+    def _step(self, t):
+        torch, lib = self.torch, self.lib
+        with torch.cuda.stream(self.stream):
+            if t == 0:
+                xn_cm = self.x0
+            else:
+                ai, anc = C.c_void_p(), C.c_void_p()
+                check(lib.rbpf_filter_ancestors_device(self.ctx, C.byref(ai), C.byref(anc)))
+                xn = self._dyn(t - 1, self._view(torch, anc, (self.N, self.nN), self.device).t())
+                xn_cm = xn.t().contiguous()                               # [n_nonlin x N_P] column-major (no copy if it is)
+            xlp, ldx = C.c_void_p(), C.c_int32(0)
+            check(lib.rbpf_filter_sparse_gathered_device(self.ctx, C.byref(xlp), C.byref(ldx)))
+            xl = self._view(torch, xlp, (self.N, ldx.value), self.device)[:, :self.n]       # xl(:,ai), particleFilter.m:112
+            yhat, dy = self._meas_sparse(xn_cm.t(), xl)
+            if yhat.is_contiguous():
+                yl = 2
+            elif yhat.t().is_contiguous():
+                yl = 0
+            else:
+                yhat, yl = yhat.contiguous(), 2
+            if dy.is_contiguous():
+                dl = 2
+            elif dy.permute(2, 1, 0).is_contiguous():
+                dl = 0
+            else:
+                dy, dl = dy.contiguous(), 2
+            self._keep = (xn_cm, yhat, dy)                                # read in stream order by the step just enqueued
+            check(lib.rbpf_filter_step_sparse_device(self.ctx, C.c_void_p(xn_cm.data_ptr()), C.c_void_p(yhat.data_ptr()), yl,
+                                                     C.c_void_p(dy.data_ptr()), dl))
+
+    def yhattraj(self):
+        out = np.empty((self.d, self.T), order="F")
+        check(self.lib.rbpf_filter_sparse_yhattraj(self.ctx, _dp(out)))
+        return out
+
+
 def dense_mag_prior(m, LL, theta):
     """GP prior of run_dense3D_magfield.m:83-107,122-131 -> (model, x0_lin, P0_lin, R)."""
     L, NN = domain_cartesian_dx(m, 3, LL)
@@ -803,8 +895,9 @@ def _device_handles(dynModel, measModel):
     return dynModel
 
 
-def _generic_model(dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, Q, dt):
-    """GenericDenseModel for arbitrary callables, sized from the problem arrays."""
+def _generic_model(dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, Q, dt, sparse=False):
+    """GenericDenseModel for arbitrary callables (sparse=True: GenericSparseModel for DeviceSparseHandles), sized from the problem
+    arrays."""
     y2 = np.asarray(y, dtype=np.float64)
     y2 = y2.reshape(-1, 1) if y2.ndim == 1 else y2
     Qa = np.asarray(Q, dtype=np.float64)
@@ -814,6 +907,8 @@ def _generic_model(dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_l
     odo = np.asarray(odometry, dtype=np.float64)
     odo = odo.reshape(1, -1) if odo.ndim == 1 else odo
     dtv = np.atleast_1d(np.asarray(dt, dtype=np.float64)).ravel()
+    if sparse:
+        return GenericSparseModel(np.asarray(x0_nonLin).size, x0l.shape[0], y2.shape[1], Q3.shape[0], odo.shape[1], odo, Q3, dtv)
     return GenericDenseModel(np.asarray(x0_nonLin).size, x0l.shape[0], y2.shape[1], Q3.shape[0], odo.shape[1], dynModel, measModel,
                              None if _is_empty_handle(dynResNorm) else dynResNorm, odo, Q3, dtv)
 
@@ -860,9 +955,13 @@ def particleFilter(dynModel, measModel, odometry, y, x0_nonLin, x0_lin, P0_lin, 
         model, _ = _recognise(dynModel, measModel, model_dyn_res_norm(dynModel))
     generic = model is None
     if generic:
-        if sparseFeatures:
+        if isinstance(handles, DeviceSparseHandles):
+            if not sparseFeatures:
+                raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "DeviceSparseHandles need sparseFeatures=True: their measModel returns "
+                                                           "(yhat, dy) at every particle's own map")
+        elif sparseFeatures:
             raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "sparseFeatures=true is implemented for the sparse-visual family only")
-        model = _generic_model(dynModel, measModel, None, odometry, y, x0_nonLin, x0_lin, Q, dt)
+        model = _generic_model(dynModel, measModel, None, odometry, y, x0_nonLin, x0_lin, Q, dt, sparse=bool(sparseFeatures))
     _check_sparse_flag(model, sparseFeatures)
     lib = load_library()
     prob = _Problem(model, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, dt)
@@ -944,7 +1043,7 @@ def particleFilter(dynModel, measModel, odometry, y, x0_nonLin, x0_lin, P0_lin, 
     try:
         try:
             if handles is not None:
-                driver = _DeviceDriver(lib, ctx, handles, model, prob)    # (alive until the context is gone: it owns what the last step reads)
+                driver = (_SparseDeviceDriver if model.sparse else _DeviceDriver)(lib, ctx, handles, model, prob)    # (alive until the context is gone: it owns what the last step reads)
                 driver.advance(T)
             else:
                 check(lib.rbpf_filter_advance(ctx, T))
@@ -955,8 +1054,11 @@ def particleFilter(dynModel, measModel, odometry, y, x0_nonLin, x0_lin, P0_lin, 
         o, b = alloc_out(T, full=True)
         check(lib.rbpf_filter_finish(ctx, C.byref(o)))
         n_fallbacks = C.c_int64(0)
+        yhattraj = None
         if extras:
             check(lib.rbpf_filter_resample_fallbacks(ctx, C.byref(n_fallbacks)))
+            if isinstance(handles, DeviceSparseHandles):
+                yhattraj = driver.yhattraj()
     finally:
         lib.rbpf_destroy(ctx)
     xn_traj = b.get("xn_traj")
@@ -966,6 +1068,8 @@ def particleFilter(dynModel, measModel, odometry, y, x0_nonLin, x0_lin, P0_lin, 
         ex = dict(logw=b["trace_logw"].T.copy(), w=b["trace_w"].T.copy(), ai=b["trace_ai"].T.copy(),
                   xn=b["final_xn"], xl=b["final_xl"], P=b["final_P"], iw_max=int(b["iw_max"][0]),
                   resample_fallbacks=int(n_fallbacks.value))
+        if yhattraj is not None:
+            ex["yhattraj"] = yhattraj
         return res + (ex,)
     return res
 
@@ -1234,7 +1338,8 @@ class FilterSession:
         self.lib = load_library()
         handles = model if isinstance(model, DeviceHandles) else None
         if handles is not None:                                # device code in place of a model: the generic family, caller-driven
-            model = _generic_model(None, None, None, odometry, y, x0_nonLin, x0_lin, Q, dt)
+            model = _generic_model(None, None, None, odometry, y, x0_nonLin, x0_lin, Q, dt,
+                                   sparse=isinstance(handles, DeviceSparseHandles))
             if isinstance(rng, ReplayRNG) and (rng.Z is None or rng.Z.size == 0):
                 rng = ReplayRNG(rng.U, np.zeros(rng.U.shape + (model.nw,)), rng.Ufin)
         self.model = model
@@ -1250,7 +1355,7 @@ class FilterSession:
                                           C.byref(self.opt), C.byref(self.ctx)))
         if handles is not None:
             try:
-                self._driver = _DeviceDriver(self.lib, self.ctx, handles, model, self.prob)
+                self._driver = (_SparseDeviceDriver if model.sparse else _DeviceDriver)(self.lib, self.ctx, handles, model, self.prob)
             except Exception:
                 self.close()
                 raise
@@ -1305,7 +1410,8 @@ class FilterSession:
 
     def finish(self, want=("traj_max", "traj_mean", "xl_max", "P_max")):
         """Any subset of the reference's outputs (particleFilter.m:220-233) and of the extras of rbpf_filter_out, as of the
-        last finished step.  trace_* need trace=True, traj_sample_iwmax / xn_traj / trace_ai need keep_history=True."""
+        last finished step.  trace_* need trace=True, traj_sample_iwmax / xn_traj / trace_ai need keep_history=True; yhattraj
+        (n_y, N_T) is kept for DeviceSparseHandles only."""
         m = self.model
         nN, n, N, T, Td = m.nNonLin, m.nLin, self.prob.N_P, self.prob.N_T, self.tell()
         shapes = dict(traj_max=(nN, T), traj_mean=(nN, T), xl_max=(n,), xl_mean=(n,), P_max=(n, n), P_mean=(n, n),
@@ -1314,11 +1420,17 @@ class FilterSession:
         o = _ffi.rbpf_filter_out()
         b = {}
         for k in want:
+            if k == "yhattraj":
+                continue
             b[k] = np.empty(shapes[k], dtype=np.int32 if k == "trace_ai" else np.float64, order="F")
             setattr(o, k, _ip(b[k]) if k == "trace_ai" else _dp(b[k]))
         b["iw_max"] = np.zeros(1, dtype=np.int32)
         o.iw_max = _ip(b["iw_max"])
         check(self.lib.rbpf_filter_finish(self.ctx, C.byref(o)))
+        if "yhattraj" in want:
+            if not isinstance(self._driver, _SparseDeviceDriver):
+                raise RBPFError(_ffi.RBPF_ERR_STATE, "yhattraj is kept for DeviceSparseHandles only")
+            b["yhattraj"] = self._driver.yhattraj()
         return b
 
     def close(self):
