@@ -366,6 +366,56 @@ int rbpf_particle_smoother_device(const rbpf_model* model, const rbpf_problem* p
                                   const rbpf_options* opt, int32_t N_K, int32_t info_form,
                                   const rbpf_callbacks* device_callbacks, int32_t dy_layout, rbpf_smoother_out* out);
 
+/* The covariance-form smoother's sparseFeatures branch (src/particleSmoother.m:194-217,267-277,306-321) for an ARBITRARY model whose
+ * handles are device code (an addition to ABI 9: no struct changed).  model->kind is RBPF_MODEL_GENERIC_SPARSE and
+ * model->callbacks NULL; rbpf_callbacks.meas_model cannot carry xl and yhat, so the three callbacks and `user` are plain arguments.
+ * They are called in the reference's order with DEVICE pointers, valid in stream order on the context's stream
+ * (rbpf_stream_get(NULL, ...) inside a callback; the callbacks enqueue there, or synchronise themselves):
+ *   dyn_model(user, t, n_cols, xn_anc, xn_new)    as for rbpf_particle_smoother_device: once per step t >= 1, n_cols = N_P in
+ *                iteration 0, N_P - 1 (the ordinary slots, in slot order, :132-137) afterwards
+ *   dyn_res_norm(user, t, N_P, xnk_t, xn, e_dyn)  as for rbpf_particle_smoother_device; NULL: the additive default on the device
+ *                (:175-177, needs n_w == n_nonlin)
+ *   meas_model(user, n_cols, xn, xl, ldx, yhat, dy)  [yhat, dy] = measModel(xn, xl) for n_cols columns: xn [n_nonlin x n_cols]
+ *                column-major, xl [n_cols][ldx] (row c: the map column c is linearised at; columns n_lin..ldx-1 zero), results
+ *                into yhat / dy, library buffers for n_cols columns in yhat_layout / dy_layout.  It must be a PURE function of
+ *                its arguments and accept any n_cols:
+ *                  n_cols = N_P once per step: xl the maps after the resampling gather, the reference slot's sampled map
+ *                      included (:243), as rbpf_filter_sparse_gathered_device hands them to the filter's caller;
+ *                  n_cols = F N_P at the steps t >= 1 of the iterations k >= 1, for the ancestor weights (:194-217): a chunk of F
+ *                      future times ti_f of t .. N_T-1; column f N_P + i carries xn = xnk(:,ti_f) and xl = xl(:,i) of generation
+ *                      t - 1 -- the map BEFORE the resampling gather, the one :206 linearises at -- both materialised in device
+ *                      memory by the library.  Times without an observed output are skipped (the handle is pure: the
+ *                      reference's call for them has no effect).
+ *                Rows of yhat / dy that belong to outputs not observed at that time are never read.  dy is dense.
+ *   yhat_layout / dy_layout  as in rbpf_filter_step_sparse_device with N_P replaced by n_cols: yhat 0 (MATLAB order, yhat(c,k) at
+ *                c + n_cols k) or 2 (C-contiguous); dy 0 (MATLAB order, dy(c,k,q) at c + n_cols (k + n_y q)), 2 (C-contiguous) or
+ *                1 (rows on the stride ldx, [n_cols][n_y][ldx]).
+ *   max_future_per_call  the largest F; 0: chosen so that the chunk's staging buffers (dy: F N_P n_y n_lin doubles, and the
+ *                replicated xl) stay within 256 MB.
+ * Per particle the stacked future observations give D [M x n_lin] (time-major, outputs ascending within a time), e = y - yhat
+ * and S = D P D' + blkdiag(R(ind,ind)) (:207-215), formed on the fp64 matrix cores (rbpf_sparse_ext_anc.hip), then the batched
+ * Cholesky with the one jitter retry (:221-229; jitter 1e-2, :70).  The step itself is rbpf_filter_step_sparse_device's.  Between two
+ * steps nothing crosses to the host and the library adds no host synchronisation to those of the built-in sparse smoother.
+ * Refused before anything touches a device: NULL arguments (dyn_res_norm and user may be NULL), N_K < 1, unknown layouts, a model
+ * of another kind or with callbacks (RBPF_ERR_INVALID_ARG); rbpf_options.n_devices, storage other than 0, lazy_depth >= 2,
+ * inplace, n_y > 32, n_lin > 96, more than 1023 stacked future observations at step 1 (RBPF_ERR_UNSUPPORTED).  The largest
+ * workspace is S, N_P M^2 doubles with M the observations after step 0.  Not available: the information form (the reference
+ * returns nothing for sparseFeatures, particleSmootherInformationForm.m:77-80), host closures, sharding, the MEX gateway.   */
+typedef int (*rbpf_sparse_dyn_fn)(void* user, int32_t t, int32_t n_cols, const double* xn_anc, double* xn_new);
+typedef int (*rbpf_sparse_meas_fn)(void* user, int32_t n_cols, const double* xn, const double* xl, int32_t ldx, double* yhat, double* dy);
+typedef int (*rbpf_sparse_dyn_res_norm_fn)(void* user, int32_t t, int32_t n_cols, const double* xnk_t, const double* xn, double* e_dyn);
+int rbpf_particle_smoother_sparse_device(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
+                                         const rbpf_options* opt, int32_t N_K, rbpf_sparse_dyn_fn dyn_model,
+                                         rbpf_sparse_meas_fn meas_model, rbpf_sparse_dyn_res_norm_fn dyn_res_norm, void* user,
+                                         int32_t yhat_layout, int32_t dy_layout, int32_t max_future_per_call,
+                                         rbpf_smoother_out* out);
+/* Per-step timing of that smoother's ancestor weights, for tools/sparse_device_smoother_bench.py: enable = 1 makes every later
+ * call in this process put HIP events around the build kernel and around the batched factorisation of every step with future
+ * observations (read once per iteration, where the library waits for the stream anyway); 0 switches it off.  The non-NULL outputs
+ * receive the totals accumulated since the last call -- milliseconds in the build kernel, in the factorisation, and the number of
+ * timed steps -- and the totals are reset.  Never touches a device.                                                       */
+int rbpf_sparse_smoother_timing(int32_t enable, double* build_ms, double* chol_ms, int64_t* steps);
+
 /* ---- resident-state API (what bench.py times: inputs already in HBM) --------------------------- */
 /* Uploads model, problem and RNG block to the current device and allocates the particle banks.    */
 int rbpf_filter_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
@@ -681,6 +731,15 @@ int rbpf_chol_sweep_probe(int32_t n, int32_t d, int32_t batch, const double* L, 
  * followed by the whitening kernel the built-in families' refreshes run -- the same bits.  d = 1 or 3.                      */
 int rbpf_ext_pack_whiten_probe(int32_t dy_layout, int32_t rows, int32_t d, int32_t n, const double* dy_host,
                                const double* W_host, int32_t fused, double* G_host);
+/* The build kernel of rbpf_particle_smoother_sparse_device's ancestor weights on its own, for the kernel-level test and the
+ * bench, on caller-supplied DEVICE arrays: P_dev [N][n][n] (symmetric), D_dev [N][M][n] row-major, pair_t_dev / pair_j_dev [M] the
+ * time and the output (0 .. d-1) of every stacked row, R_dev [d x d] column-major; S_dev [N][M*M] column-major receives
+ * S_i(a, b) = (D_i P_i D_i')(a, b) + (pair_t[a] == pair_t[b] ? R(pair_j[a], pair_j[b]) : 0) in the 16 x 16 tiles on and below the
+ * diagonal (what the batched Cholesky reads); the tiles above are not written.  n <= 96, M <= 1023.  Runs on the null stream and
+ * waits for it; reps >= 1 repeats the launch, *ms (may be NULL) = mean kernel time (HIP events).                           */
+int rbpf_sparse_ext_build_probe(int32_t N, int32_t n, int32_t M, int32_t d, const double* P_dev, const double* D_dev,
+                                const int32_t* pair_t_dev, const int32_t* pair_j_dev, const double* R_dev, int32_t reps,
+                                double* S_dev, double* ms);
 /* Quaternion helpers of tools/ on the device, batched over n columns, for the parity tests:
  *   op 0  expq, scalar branch   tools/expq.m:22-31  (flip when q0 < 0)          in [3 x n]      -> out [4 x n]
  *   op 1  expq, batched branch  tools/expq.m:33-37  (flip when q0 <= 0)         in [3 x n]      -> out [4 x n]

@@ -12,8 +12,8 @@ from ._ffi import (RBPFError, load_library, EXPORTS,                  # noqa: F4
                    RBPF_ERR_OUT_OF_MEMORY, RBPF_ERR_CHOL_FAILED, RBPF_ERR_STATE, RBPF_ERR_CALLBACK)
 from .host import (particleFilter, particleSmoother, particleSmootherInformationForm,   # noqa: F401
                    DenseMagModel, DenseRadioModel, SparseVisualModel, dense_mag_prior, dense_radio_prior,
-                   domain_cartesian_dx, eigenval, PhiloxRNG, ReplayRNG, FilterSession, sample, chol_weights, chol_sweep_probe, pack_whiten_probe, quat_helper,
-                   GenericDenseModel, GenericSparseModel, DeviceHandles, DeviceSmootherHandles, DeviceSparseHandles, particle_filter_external, chol_refresh_in_use,
+                   domain_cartesian_dx, eigenval, PhiloxRNG, ReplayRNG, FilterSession, sample, chol_weights, chol_sweep_probe, pack_whiten_probe, sparse_ext_build_probe, sparse_smoother_timing, quat_helper,
+                   GenericDenseModel, GenericSparseModel, DeviceHandles, DeviceSmootherHandles, DeviceSparseHandles, DeviceSparseSmootherHandles, particle_filter_external, chol_refresh_in_use,
                    DenseMagMap, particleFilterLocalization, LocalizationSession, loc_workspace_bytes,
                    particleSmootherLocalization, loc_backward_step, loc_backward_workspace_bytes)
 

@@ -34,6 +34,8 @@ RBPF_RNG_PHILOX = 1
 DYN_MODEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, c_double_p, c_double_p)
 MEAS_MODEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, c_double_p, c_double_p)
 DYN_RES_NORM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p)
+# rbpf_sparse_meas_fn: (user, n_cols, xn, xl, ldx, yhat, dy) -- the measModel of rbpf_particle_smoother_sparse_device
+SPARSE_MEAS_MODEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p)
 
 
 class rbpf_callbacks(C.Structure):
@@ -149,7 +151,7 @@ EXPORTS = [
     "rbpf_filter_create", "rbpf_filter_workspace_bytes", "rbpf_filter_advance", "rbpf_filter_reset", "rbpf_sync",
     "rbpf_filter_finish", "rbpf_filter_tell", "rbpf_filter_schedule", "rbpf_filter_one_launch_flushes", "rbpf_filter_resample_fallbacks", "rbpf_plan_refresh", "rbpf_chol_refresh_resolve", "rbpf_shard_smoother_refresh_reserve", "rbpf_shard_xn_traj", "rbpf_filter_ancestors", "rbpf_filter_step_external", "rbpf_filter_external_layout", "rbpf_filter_ancestors_device",
     "rbpf_filter_step_device", "rbpf_filter_set_device_callbacks",
-    "rbpf_filter_sparse_gathered_device", "rbpf_filter_step_sparse_device", "rbpf_filter_sparse_yhattraj", "rbpf_timing_enable", "rbpf_timing_read", "rbpf_destroy",
+    "rbpf_filter_sparse_gathered_device", "rbpf_filter_step_sparse_device", "rbpf_filter_sparse_yhattraj", "rbpf_particle_smoother_sparse_device", "rbpf_sparse_smoother_timing", "rbpf_sparse_ext_build_probe", "rbpf_timing_enable", "rbpf_timing_read", "rbpf_destroy",
     "rbpf_philox_fill", "rbpf_meas_model", "rbpf_dyn_model", "rbpf_dyn_res_norm", "rbpf_sample",
     "rbpf_jacobian_phi3d", "rbpf_chol_weights", "rbpf_chol_sweep_probe", "rbpf_ext_pack_whiten_probe", "rbpf_quat_helpers", "rbpf_probe_wave_reduce",
     "rbpf_shard_create", "rbpf_shard_views_get", "rbpf_shard_normalise_search", "rbpf_shard_pack", "rbpf_shard_step",
@@ -229,6 +231,13 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_particle_smoother_device.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem), C.POINTER(rbpf_rng),
                                                   C.POINTER(rbpf_options), C.c_int32, C.c_int32, C.POINTER(rbpf_callbacks),
                                                   C.c_int32, C.POINTER(rbpf_smoother_out)]
+    lib.rbpf_particle_smoother_sparse_device.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem), C.POINTER(rbpf_rng),
+                                                         C.POINTER(rbpf_options), C.c_int32, DYN_MODEL_FN, SPARSE_MEAS_MODEL_FN,
+                                                         DYN_RES_NORM_FN, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                         C.POINTER(rbpf_smoother_out)]
+    lib.rbpf_sparse_smoother_timing.argtypes = [C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int64)]
+    lib.rbpf_sparse_ext_build_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, c_double_p]
     lib.rbpf_filter_create.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem), C.POINTER(rbpf_rng),
                                        C.POINTER(rbpf_options), C.POINTER(C.c_void_p)]
     lib.rbpf_filter_workspace_bytes.argtypes = [C.POINTER(rbpf_model), C.POINTER(rbpf_problem),

@@ -218,7 +218,7 @@ static size_t bank_bytes(const Layout& L, int d, int N) {
 
 int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng, const rbpf_options* opt,
                bool smoother, int N_K, rbpf_ctx** out, const CreateExtras* ex, const rbpf_callbacks* device_callbacks,
-               int dy_layout) {
+               int dy_layout, const SparseSmootherHandles* sparse_handles) {
   if (!out) { set_error("ctx out pointer is NULL"); return RBPF_ERR_INVALID_ARG; }
   *out = nullptr;
   RB_TRY(validate_problem(prob));
@@ -239,7 +239,7 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
   if (gsparse) {
     // what this family does not have is refused here, before any device memory is taken
     const char* who = "generic sparse family (sparseFeatures = true with device handles): ";
-    if (smoother) { set_error(std::string(who) + "the filter only (the smoothers' sparse branch linearises N_P x (N_T - t) times per step: another kernel and another handle contract)"); return RBPF_ERR_UNSUPPORTED; }
+    if (smoother && !sparse_handles) { set_error(std::string(who) + "the filter, and the covariance-form smoother through rbpf_particle_smoother_sparse_device (its sparse branch linearises N_P x (N_T - t) times per step: another handle contract)"); return RBPF_ERR_UNSUPPORTED; }
     if (ex || wants_multi(&c->opt)) { set_error(std::string(who) + "n_devices is not supported (the sparseFeatures branch is not sharded)"); return RBPF_ERR_UNSUPPORTED; }
     if (c->opt.storage != 0) { set_error(std::string(who) + "options.storage must be 0 (fp64 full squares)"); return RBPF_ERR_UNSUPPORTED; }
     if (c->opt.lazy_depth >= 2) { set_error(std::string(who) + "lazy_depth >= 2 is not supported (the EKF update rewrites every covariance at every step)"); return RBPF_ERR_UNSUPPORTED; }
@@ -297,6 +297,14 @@ int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng
     c->h_Q.assign(prob->Q, prob->Q + (size_t)prob->n_w * prob->n_w * prob->q_pages);
     c->h_dt.assign(prob->dt, prob->dt + prob->dt_len);
     c->q_pages = prob->q_pages; c->dt_len = prob->dt_len;
+  }
+  if (gsparse && smoother) {
+    // rbpf_particle_smoother_sparse_device: dyn_model and dyn_res_norm have rbpf_callbacks' signatures and travel in dev_cb, so
+    // that device_draw_propagate and anc_dyn_weights serve this family unchanged; meas_model has its own
+    c->dev_cb.dyn_model = sparse_handles->dyn_model; c->dev_cb.meas_model = nullptr; c->dev_cb.dyn_res_norm = sparse_handles->dyn_res_norm;
+    c->dev_cb.user = sparse_handles->user; c->has_dev_cb = true;
+    c->sparse_meas = sparse_handles->meas_model; c->sparse_user = sparse_handles->user;
+    c->sparse_yhat_layout = sparse_handles->yhat_layout; c->sparse_dy_layout = sparse_handles->dy_layout; c->sparse_max_future = sparse_handles->max_future;
   }
   if (gsparse) {
     if (c->lay.mc != 0) { set_error("generic sparse family: nLin must be 1 .. 96 (the border-only bank layout)"); return RBPF_ERR_UNSUPPORTED; }
@@ -1278,14 +1286,17 @@ static int sparse_device_ctx_ok(const rbpf_ctx* c) {
   return RBPF_OK;
 }
 
+}  // extern "C"
+
 // xl(:,ai) of the step about to run (particleFilter.m:112) into d_xl_g
-static int sparse_gather_xl(rbpf_ctx* c) {
+int rbpf::sparse_ext_gather_xl(rbpf_ctx* c) {
   const int t = c->t, N = c->N, ldx = c->lay.ldx;
   if (c->gathered_step == t) return RBPF_OK;
   if (t == 0) {
     HIPCHK(launch_sparse_ext_gather_xl(N, ldx, c->d_x0l, c->x0_lin_cols > 1 ? (size_t)ldx : 0, nullptr, c->d_xl_g, c->stream));
   } else {
-    if (c->ready_step != t) { set_error("no ancestors drawn for the next step (run a step first)"); return RBPF_ERR_STATE; }
+    // (the smoother draws its ancestors in device_draw_propagate and the ancestor weights, not in the step before)
+    if (!c->smoother && c->ready_step != t) { set_error("no ancestors drawn for the next step (run a step first)"); return RBPF_ERR_STATE; }
     const int* A_t = c->A + (c->opt.keep_history ? (size_t)t * N : 0);
     HIPCHK(launch_sparse_ext_gather_xl(N, ldx, c->xl[c->xcur], (size_t)ldx, A_t, c->d_xl_g, c->stream));
   }
@@ -1293,11 +1304,13 @@ static int sparse_gather_xl(rbpf_ctx* c) {
   return RBPF_OK;
 }
 
+extern "C" {
+
 int rbpf_filter_sparse_gathered_device(rbpf_ctx* c, const double** xl_dev, int32_t* ldx) {
   if (!c || !xl_dev || !ldx) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(sparse_device_ctx_ok(c));
   HIPCHK(hipSetDevice(c->device));
-  RB_TRY(sparse_gather_xl(c));
+  RB_TRY(sparse_ext_gather_xl(c));
   *xl_dev = c->d_xl_g;
   *ldx = c->lay.ldx;
   return RBPF_OK;
@@ -1310,12 +1323,23 @@ int rbpf_filter_step_sparse_device(rbpf_ctx* c, const double* xn_new_dev, const 
   if (dy_layout < 0 || dy_layout > 2) { set_error("dy_layout must be 0 (MATLAB order), 1 (rows on the stride ldx) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(sparse_device_ctx_ok(c));
   HIPCHK(hipSetDevice(c->device));
+  return sparse_ext_ctx_step(c, 0, xn_new_dev, false, yhat_dev, yhat_layout, dy_dev, dy_layout);
+}
+
+}  // extern "C"
+
+// The step behind rbpf_filter_step_sparse_device, shared with the smoother of this family (smoother_run): there the new states are
+// already in the history slab (states_done), the next ancestors are not drawn here (the smoother's own pieces do that, with
+// the reference slot's) and the hook is the iteration's.
+int rbpf::sparse_ext_ctx_step(rbpf_ctx* c, int k_iter, const double* xn_new_dev, bool states_done, const double* yhat_dev, int yhat_layout,
+                              const double* dy_dev, int dy_layout) {
   const int t = c->t, N = c->N, nN = c->mdl.nN, n = c->mdl.n, d = c->mdl.d;
+  if (t >= c->T) { set_error("advance past N_T"); return RBPF_ERR_STATE; }
   const Layout& L = c->lay;
   const bool hist = c->opt.keep_history != 0;
-  RB_TRY(sparse_gather_xl(c));
+  RB_TRY(sparse_ext_gather_xl(c));
   double* X_new = c->X + (size_t)(hist ? t : (t & 1)) * nN * N;
-  HIPCHK(launch_ext_states_to_soa(N, nN, xn_new_dev, X_new, c->stream));
+  if (!states_done) HIPCHK(launch_ext_states_to_soa(N, nN, xn_new_dev, X_new, c->stream));
   if (dy_layout == 0) {                               // the lines of one particle lie N_P doubles apart: pack them into rows first
     if (!c->d_H_ext) RB_TRY(c->pool.alloc(&c->d_H_ext, (size_t)N * d * L.ldx));
     HIPCHK(launch_ext_pack_dy(0, N, d, n, L.ldx, dy_dev, c->d_H_ext, c->stream));
@@ -1342,13 +1366,16 @@ int rbpf_filter_step_sparse_device(rbpf_ctx* c, const double* xn_new_dev, const 
   }
   c->cur = nb; c->xcur = nb;
   c->t = t + 1;
-  c->fuse_resample = true;
-  RB_TRY(ctx_normalise_resample(c, t, 0, nullptr, false));
+  c->fuse_resample = !c->smoother;
+  RB_TRY(ctx_normalise_resample(c, t, k_iter, nullptr, false));
+  if (c->smoother) return RBPF_OK;
   HIPCHK(launch_sparse_ext_yhat_of_max(d, yhat_dev, sa.yhat_si, sa.yhat_sk, c->d_flags + 2, c->d_yhattraj + (size_t)t * d, c->stream));
   if (!c->opt.on_step) return RBPF_OK;
   HIPCHK(hipStreamSynchronize(c->stream));          // as rbpf_filter_step_device: the hook sees a finished step
   return ctx_call_on_step(c, c->t - 1, false);
 }
+
+extern "C" {
 
 int rbpf_filter_sparse_yhattraj(rbpf_ctx* c, double* yhattraj) {
   if (!c || !yhattraj) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }

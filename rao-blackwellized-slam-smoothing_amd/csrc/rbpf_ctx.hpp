@@ -32,6 +32,12 @@ struct SmootherState;   // rbpf_smoother.hip
 struct ShardState;      // rbpf_shard.hip
 struct LocState;        // rbpf_loc.hip
 
+// the handles of rbpf_particle_smoother_sparse_device (the generic sparse family's smoother) on their way into a context
+struct SparseSmootherHandles {
+  rbpf_sparse_dyn_fn dyn_model; rbpf_sparse_meas_fn meas_model; rbpf_sparse_dyn_res_norm_fn dyn_res_norm; void* user;
+  int yhat_layout, dy_layout, max_future;
+};
+
 // extra capacity requested by the sharded filter
 struct CreateExtras {
   size_t bank_extra = 0;   // particles appended to every bank (recv region of remote ancestors)
@@ -98,6 +104,11 @@ struct rbpf_ctx {
   // for, yhat of every step's maximum-weight particle [T][d]
   double *d_xl_g = nullptr, *d_yhattraj = nullptr;
   int gathered_step = -1;
+  // ... in the smoother (rbpf_particle_smoother_sparse_device): the measModel callback, which rbpf_callbacks cannot carry (dyn_model
+  // and dyn_res_norm are dev_cb's), the layouts of its results and the largest number of future times per call (0: automatic)
+  rbpf_sparse_meas_fn sparse_meas = nullptr;
+  void* sparse_user = nullptr;
+  int sparse_yhat_layout = 2, sparse_dy_layout = 2, sparse_max_future = 0;
   std::vector<double> h_xn;      // generic family: states of the last step [nN x N] column-major (host evaluates dynModel)
   std::vector<double> h_xn_new, h_dy;   // scratch of the callbacks
   std::vector<int> h_ai;
@@ -155,7 +166,8 @@ int fill_model_dev(const rbpf_model* model, int nN, int n, int d, int nw, int no
                    ModelDev& M, std::vector<int>& nn_axis_major);
 int ctx_create(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng, const rbpf_options* opt,
                bool smoother, int N_K, rbpf_ctx** out, const CreateExtras* ex = nullptr,
-               const rbpf_callbacks* device_callbacks = nullptr, int dy_layout = 0);   // device_callbacks: rbpf_particle_smoother_device
+               const rbpf_callbacks* device_callbacks = nullptr, int dy_layout = 0,    // device_callbacks: rbpf_particle_smoother_device
+               const SparseSmootherHandles* sparse_handles = nullptr);                 // rbpf_particle_smoother_sparse_device
 int ctx_reset(rbpf_ctx* c);
 void ctx_free(rbpf_ctx* c);
 int ctx_step(rbpf_ctx* c, int k_iter, const double* xref_t, int n_draw, const InfoStep* info);
@@ -167,6 +179,11 @@ int generic_finish_inputs(rbpf_ctx* c, const double* xref_host);
 // the same two halves with device callbacks (rbpf_particle_smoother_device): everything stays on the device, in stream order
 int device_draw_propagate(rbpf_ctx* c, int k_iter, int n_draw);
 int device_finish_inputs(rbpf_ctx* c, const double* xref_dev);
+// generic sparse family: xl(:,ai) of the step about to run into d_xl_g, and the step itself on the caller's (or the callback's)
+// yhat / dy (rbpf_filter_step_sparse_device; the smoother's states are already in the history slab: states_done)
+int sparse_ext_gather_xl(rbpf_ctx* c);
+int sparse_ext_ctx_step(rbpf_ctx* c, int k_iter, const double* xn_new_dev, bool states_done, const double* yhat_dev, int yhat_layout,
+                        const double* dy_dev, int dy_layout);
 // The context whose device callbacks are being called on this thread by a one-shot entry point (rbpf_particle_smoother_device),
 // null otherwise: the callbacks have no other way to the stream they must enqueue on (rbpf_stream_get(NULL, ...)) and to the
 // row stride of the native dy layout (rbpf_filter_external_layout(NULL, ...)).

@@ -15,17 +15,24 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 namespace rbpf {
 
-enum class SmootherForm { Sparse, Cov, Info };   // covariance form with sparse features / with dense features, information form
+// covariance form with sparse features (the built-in camera) / with dense features, information form, covariance form with sparse
+// features of an arbitrary model whose handles are device code (RBPF_MODEL_GENERIC_SPARSE)
+enum class SmootherForm { Sparse, Cov, Info, GenericSparse };
 
 // sparse-visual family: the observed (time, output) pairs, time-major -- the future observations of step t are the suffix from off[t]
 struct SparsePairs {
   std::vector<int> off;                    // [T + 1]
   int *d_t = nullptr, *d_j = nullptr;      // the pairs' times and outputs
   int future(int t) const { return off.back() - off[t]; }
+  // generic sparse family: the times with at least one observed output, ascending (a handle call covers a chunk of them), and
+  // every time's index in that table (a time without observations: the index of the next one that has some)
+  std::vector<int> obs_times, time_slot;
+  int *d_obs_times = nullptr, *d_time_slot = nullptr;
 };
 
 struct SmootherState {
@@ -83,6 +90,11 @@ struct SmootherState {
   size_t stage_rows = 0;        // device callbacks: columns per measModel call of a refresh (the staging buffer holds that many rows of H)
   std::vector<double> h_xnk, h_edyn;   // host copies of d_xnk (the callbacks read it) and d_edyn
   SparsePairs pairs;
+  // generic sparse family: at most future_chunk future times per measModel call; the handle's operands and results of a call
+  // (xn [nN x C], xl [C][ldx], yhat [C x d], dy [C x d x nLin or ldx] for C = future_chunk N columns)
+  int future_chunk = 1;
+  std::vector<hipEvent_t> sparse_events;   // rbpf_sparse_smoother_timing: three per timed step (before the build, between, after the factorisation)
+  double *d_rep_xn = nullptr, *d_rep_xl = nullptr, *d_yhat_stage = nullptr, *d_dy_stage = nullptr;
   // sharded smoother with carried factors: where every logical slot's particle lives now / lived when the Imat bank was
   // materialised, and the base matrices fetched from (packed for) other ranks at a refresh
   int* d_owner_now = nullptr;   // [Nglob] rank * Nloc + physical slot
@@ -100,6 +112,7 @@ struct SmootherState {
 void smoother_free(rbpf_ctx* c) {
   SmootherState* s = c->sm;
   if (!s) return;
+  for (hipEvent_t e : s->sparse_events) hipEventDestroy(e);
   delete s;
   c->sm = nullptr;
 }
@@ -1274,6 +1287,65 @@ static int sparse_alloc(rbpf_ctx* c) {
   return RBPF_OK;
 }
 
+// Generic sparse family (device handles): sparse_alloc's pair table, S, e and factor workspaces, plus the stacked Jacobians
+// D [N][M(1)][n], the table of observed times and what the handles read and write.  A measModel call covers at most future_chunk
+// future times: the caller's figure, or as many as keep the chunk's staging buffers -- dy and the replicated xl, the two that grow
+// with the chunk -- within kSparseStageBudget (the figure the sharded driver uses for its chunked traces).
+constexpr size_t kSparseStageBudget = (size_t)256 << 20;
+
+// rbpf_sparse_smoother_timing: process-wide totals of the timed ancestor-weight steps of this family's smoother
+static std::atomic<int> g_sparse_timing{0};
+static std::mutex g_sparse_timing_mutex;
+static double g_sparse_build_ms = 0.0, g_sparse_chol_ms = 0.0;
+static long long g_sparse_timed_steps = 0;
+
+// the events of the steps timed since the last call -> the totals (the stream has been waited for: iteration_end)
+static void sparse_timing_collect(SmootherState* s) {
+  std::lock_guard<std::mutex> lock(g_sparse_timing_mutex);
+  for (size_t q = 0; q + 2 < s->sparse_events.size(); q += 3) {
+    float b = 0.f, f = 0.f;
+    if (hipEventElapsedTime(&b, s->sparse_events[q], s->sparse_events[q + 1]) == hipSuccess &&
+        hipEventElapsedTime(&f, s->sparse_events[q + 1], s->sparse_events[q + 2]) == hipSuccess) {
+      g_sparse_build_ms += b; g_sparse_chol_ms += f; ++g_sparse_timed_steps;
+    }
+  }
+  for (hipEvent_t e : s->sparse_events) hipEventDestroy(e);
+  s->sparse_events.clear();
+}
+
+static int generic_sparse_alloc(rbpf_ctx* c, bool drn_cb) {
+  SmootherState* s = c->sm;
+  SparsePairs& pr = s->pairs;
+  RB_TRY(sparse_alloc(c));
+  const size_t N = (size_t)c->N, nN = (size_t)c->mdl.nN, n = (size_t)c->mdl.n, d = (size_t)c->mdl.d, ldx = (size_t)c->lay.ldx;
+  const int T = c->T;
+  pr.time_slot.assign((size_t)T + 1, 0);
+  for (int ti = 0; ti < T; ++ti) {
+    pr.time_slot[ti] = (int)pr.obs_times.size();
+    if (pr.off[ti + 1] > pr.off[ti]) pr.obs_times.push_back(ti);
+  }
+  pr.time_slot[T] = (int)pr.obs_times.size();
+  RB_TRY(s->pool.upload(&pr.d_time_slot, pr.time_slot.data(), pr.time_slot.size()));
+  RB_TRY(s->pool.alloc(&pr.d_obs_times, std::max<size_t>(pr.obs_times.size(), 1)));
+  if (!pr.obs_times.empty()) HIPCHK(hipMemcpy(pr.d_obs_times, pr.obs_times.data(), pr.obs_times.size() * sizeof(int), hipMemcpyHostToDevice));
+  const size_t dy_w = c->sparse_dy_layout == 1 ? ldx : n;
+  const size_t future_max = std::max<size_t>(T > 1 ? pr.obs_times.size() - (size_t)pr.time_slot[1] : 0, 1);   // the most step 1 can ask for
+  size_t F = c->sparse_max_future > 0 ? (size_t)c->sparse_max_future : std::max<size_t>(kSparseStageBudget / (N * (d * dy_w + ldx) * sizeof(double)), 1);
+  F = std::min(F, future_max);
+  s->future_chunk = (int)F;
+  RB_TRY(s->pool.alloc(&s->d_G, std::max<size_t>(N * s->Mmax * n, 1)));
+  RB_TRY(s->pool.alloc(&s->d_rep_xn, F * N * nN));
+  RB_TRY(s->pool.alloc(&s->d_rep_xl, F * N * ldx));
+  RB_TRY(s->pool.alloc(&s->d_yhat_stage, F * N * d));
+  RB_TRY(s->pool.alloc(&s->d_dy_stage, F * N * d * dy_w));
+  RB_TRY(c->pool.alloc(&c->d_xn_anc, nN * N));
+  RB_TRY(c->pool.alloc(&c->d_xn_cm, nN * N));
+  if (drn_cb) RB_TRY(s->pool.alloc(&s->d_xprev, nN * N));
+  if (c->sparse_dy_layout == 0 && !c->d_H_ext) RB_TRY(c->pool.alloc(&c->d_H_ext, N * d * ldx));   // the step packs MATLAB order into rows
+  if (c->sparse_dy_layout == 1) HIPCHK(hipMemsetAsync(s->d_dy_stage, 0, F * N * d * dy_w * sizeof(double), c->stream));   // the rows' pad
+  return RBPF_OK;
+}
+
 static int cov_alloc(rbpf_ctx* c) {
   SmootherState* s = c->sm;
   const size_t N = (size_t)c->N, n = (size_t)c->mdl.n, Mmax = s->Mmax;
@@ -1334,7 +1406,8 @@ static int smoother_setup(rbpf_ctx* c, int N_K, int info_form) {
   if (!info_form && c->inplace) { set_error("inplace=1: the covariance-form smoother rewrites its covariances at every step (use the information form)"); return RBPF_ERR_UNSUPPORTED; }
   if (!info_form) c->lazy_depth = 1;          // the covariance form reads the flushed covariances of every particle every step
   c->sort_steps = true;
-  const bool generic = c->mdl.kind == RBPF_MODEL_GENERIC_DENSE;
+  const bool gsparse = c->mdl.kind == RBPF_MODEL_GENERIC_SPARSE;
+  const bool generic = c->mdl.kind == RBPF_MODEL_GENERIC_DENSE || gsparse;
   const bool drn_cb = generic && (c->has_dev_cb ? c->dev_cb.dyn_res_norm : c->cb.dyn_res_norm) != nullptr;      // the handle; otherwise isempty(dynResNorm)
   if (generic) c->mdl.use_dyn_res_norm = 0;                          // device side: only the additive default exists
   if (!c->mdl.use_dyn_res_norm && !drn_cb && nw != nN) {
@@ -1354,7 +1427,7 @@ static int smoother_setup(rbpf_ctx* c, int N_K, int info_form) {
   RB_TRY(s->pool.alloc(&s->d_wc2, (size_t)N));
   RB_TRY(s->pool.alloc(&s->d_ak, 4));
   std::vector<double> Rinv((size_t)d * d);
-  RB_TRY(invert_R(c->h_R, d, Rinv));
+  if (!gsparse) RB_TRY(invert_R(c->h_R, d, Rinv));     // (the generic sparse family runs the covariance form only: R itself, any sign)
   RB_TRY(s->pool.alloc(&s->d_R, (size_t)d * d));
   HIPCHK(hipMemcpy(s->d_R, c->h_R.data(), (size_t)d * d * 8, hipMemcpyHostToDevice));
   s->h_xnk.resize((size_t)nN * T);
@@ -1362,6 +1435,12 @@ static int smoother_setup(rbpf_ctx* c, int N_K, int info_form) {
     if (info_form) { set_error("This code has only been implemented for dense features"); return RBPF_ERR_UNSUPPORTED; }   // InformationForm.m:77-80
     s->form = SmootherForm::Sparse;
     return sparse_alloc(c);
+  }
+  if (gsparse) {
+    if (info_form) { set_error("This code has only been implemented for dense features (use particleSmoother)"); return RBPF_ERR_UNSUPPORTED; }   // InformationForm.m:77-80
+    if (!c->sparse_meas || !c->has_dev_cb) { set_error("generic sparse smoother without device handles"); return RBPF_ERR_STATE; }
+    s->form = SmootherForm::GenericSparse;
+    return generic_sparse_alloc(c, drn_cb);
   }
   s->form = info_form ? SmootherForm::Info : SmootherForm::Cov;
   RB_TRY(info_form ? info_alloc(c, Rinv) : cov_alloc(c));
@@ -1446,6 +1525,66 @@ static int sparse_anc_weights(rbpf_ctx* c, int t) {
   return RBPF_OK;
 }
 
+// Generic sparse family: measModel at (xnk(:,ti), xl(:,i)) for every future time ti with observations and every particle i, a
+// chunk of future times per call of the handle; the observed rows are packed into the stacked D and e, then S = D P D' +
+// blkdiag(R(ind,ind)) and the batched factorisation (rbpf_sparse_ext_anc.hip).  xl and P are those of generation t - 1.
+static int generic_sparse_anc_weights(rbpf_ctx* c, int t) {
+  SmootherState* s = c->sm;
+  const SparsePairs& pr = s->pairs;
+  const Layout& L = c->lay;
+  const int N = c->N, nN = c->mdl.nN, n = c->mdl.n, d = c->mdl.d, cur = c->cur;
+  const int M = pr.future(t);
+  if (M == 0) return RBPF_OK;                                          // no future observation: logwMeas = 0
+  hipStream_t st = c->stream;
+  const int n_obs = (int)pr.obs_times.size();
+  for (int c0 = pr.time_slot[t]; c0 < n_obs; c0 += s->future_chunk) {
+    const int F = std::min(s->future_chunk, n_obs - c0);
+    HIPCHK(launch_sparse_ext_replicate(N, F, nN, L.ldx, pr.d_obs_times + c0, s->d_xnk, c->xl[c->xcur], s->d_rep_xn, s->d_rep_xl, st));
+    if (c->sparse_meas(c->sparse_user, F * N, s->d_rep_xn, s->d_rep_xl, L.ldx, s->d_yhat_stage, s->d_dy_stage) != 0) {
+      set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK;
+    }
+    SparseExtPackArgs pa;
+    pa.N = N; pa.F = F; pa.n = n; pa.d = d; pa.M = M; pa.slot0 = c0; pa.time_slot = pr.d_time_slot;
+    pa.m0 = pr.off[pr.obs_times[c0]] - pr.off[t]; pa.Mc = pr.off[pr.obs_times[c0 + F - 1] + 1] - pr.off[pr.obs_times[c0]];
+    pa.pair_t = pr.d_t + pr.off[t]; pa.pair_j = pr.d_j + pr.off[t]; pa.y = c->d_y;
+    pa.yhat = s->d_yhat_stage; pa.yhat_layout = c->sparse_yhat_layout;
+    pa.dy = s->d_dy_stage; pa.dy_layout = c->sparse_dy_layout; pa.dy_ld = c->sparse_dy_layout == 1 ? L.ldx : n;
+    pa.D = s->d_G; pa.rhs = s->d_e;
+    HIPCHK(launch_sparse_ext_pack(pa, st));
+  }
+  const bool timed = g_sparse_timing.load() != 0;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  if (timed) {
+    for (hipEvent_t& e : ev) { HIPCHK(hipEventCreate(&e)); s->sparse_events.push_back(e); }
+    HIPCHK(hipEventRecord(ev[0], st));
+  }
+  SparseExtBuildArgs ba;
+  ba.n = n; ba.M = M; ba.d = d; ba.ldb = L.ldb; ba.ldn = n; ba.szB = L.szB; ba.szD = (size_t)M * n;
+  ba.Pb = c->Pb[cur]; ba.D = s->d_G; ba.pair_t = pr.d_t + pr.off[t]; ba.pair_j = pr.d_j + pr.off[t]; ba.R = s->d_R; ba.S = s->d_S;
+  HIPCHK(launch_sparse_ext_build(ba, N, st));
+  if (timed) HIPCHK(hipEventRecord(ev[1], st));
+  CholArgs ca = chol_args(c, s->d_pant_log);
+  ca.mode = 0; ca.Msz = M; ca.Lbuf = s->d_L; ca.ldL = (long)chol_factor_doubles(M);
+  ca.S = s->d_S; ca.R = nullptr; ca.rhs = s->d_e; ca.jitter = c->mdl.jitter;
+  HIPCHK(launch_chol(ca, N, 0, st));
+  if (timed) HIPCHK(hipEventRecord(ev[2], st));
+  return RBPF_OK;
+}
+
+// One step of the generic sparse family: the reference slot's state, the gathered maps (the reference slot's sampled one
+// included, :243), ONE measModel call for the N_P particles, and the filter's step on its results (jitter: the smoother's, :70)
+static int generic_sparse_step(rbpf_ctx* c, int k, const double* xref) {
+  SmootherState* s = c->sm;
+  const int t = c->t, N = c->N, nN = c->mdl.nN;
+  if (t >= c->T) { set_error("advance past N_T"); return RBPF_ERR_STATE; }
+  HIPCHK(launch_ext_states_to_soa_ref(N, nN, c->d_xn_cm, c->X + (size_t)t * nN * N, xref, c->stream));
+  RB_TRY(sparse_ext_gather_xl(c));
+  if (c->sparse_meas(c->sparse_user, N, c->d_xn_cm, c->d_xl_g, c->lay.ldx, s->d_yhat_stage, s->d_dy_stage) != 0) {
+    set_error("the measModel callback failed"); return RBPF_ERR_CALLBACK;
+  }
+  return sparse_ext_ctx_step(c, k, c->d_xn_cm, true, s->d_yhat_stage, c->sparse_yhat_layout, s->d_dy_stage, c->sparse_dy_layout);
+}
+
 static int cov_anc_weights(rbpf_ctx* c, int t) {
   SmootherState* s = c->sm;
   const int N = c->N, n = c->mdl.n, d = c->mdl.d, M = d * (c->T - t), cur = c->cur;
@@ -1521,6 +1660,7 @@ static int iteration_end(rbpf_ctx* c, int k, rbpf_smoother_out* out) {
   const int N = c->N, T = c->T, nN = c->mdl.nN, n = c->mdl.n;
   int ak = 0;
   RB_TRY(draw_reference_index(c, N, c->w + (c->opt.trace ? (size_t)(T - 1) * N : 0), c->wc, c->X, c->A, k, &ak));
+  if (!s->sparse_events.empty()) sparse_timing_collect(s);
   HIPCHK(hipMemcpy(s->h_xnk.data(), s->d_xnk, (size_t)nN * T * 8, hipMemcpyDeviceToHost));
   if (out->XNK) std::memcpy(out->XNK + (size_t)k * nN * T, s->h_xnk.data(), (size_t)nN * T * 8);
   if (out->XLK) HIPCHK(hipMemcpy(out->XLK + (size_t)k * n, c->xl[c->xcur] + (size_t)ak * c->lay.ldx, (size_t)n * 8, hipMemcpyDeviceToHost));
@@ -1552,10 +1692,11 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
   const int N = c->N, T = c->T, nN = c->mdl.nN;
   const bool device = c->has_dev_cb;
   const bool generic = c->mdl.kind == RBPF_MODEL_GENERIC_DENSE && !device;
+  const bool gsparse = s->form == SmootherForm::GenericSparse;       // device handles too: measModel takes the maps, per step and per future time
   for (int k = 0; k < N_K; ++k) {
     RB_TRY(ctx_reset(c));
     if (s->form == SmootherForm::Info) RB_TRY(info_begin_iteration(c));
-    if (k > 0 && s->form != SmootherForm::Sparse) {
+    if (k > 0 && s->form != SmootherForm::Sparse && !gsparse) {
       RB_TRY(reference_jacobians(c));
       if (s->form == SmootherForm::Info) RB_TRY(info_reference_sums(c));
     }
@@ -1567,13 +1708,14 @@ static int smoother_run(rbpf_ctx* c, int N_K, int info_form, rbpf_smoother_out* 
       if (k > 0 && t > 0) {
         // ancestor weights of the reference trajectory (Steps 9-10), normalise (:236-238), sample ai(N_P) (:241)
         RB_TRY(anc_dyn_weights(c, t));
-        RB_TRY(s->form == SmootherForm::Sparse ? sparse_anc_weights(c, t) : s->form == SmootherForm::Cov ? cov_anc_weights(c, t) : info_anc_weights(c, t));
+        RB_TRY(s->form == SmootherForm::Sparse ? sparse_anc_weights(c, t) : gsparse ? generic_sparse_anc_weights(c, t) :
+               s->form == SmootherForm::Cov ? cov_anc_weights(c, t) : info_anc_weights(c, t));
         RB_TRY(normalise_draw_one(c, N, t, k, s->d_pant_log, s->d_pant + (c->opt.trace ? ((size_t)k * T + t) * N : 0), s->d_wc2, N - 1,
                                   c->d_U ? c->d_U + ((size_t)k * (T - 1) + (t - 1)) * N : nullptr, c->A + (size_t)t * N, c->stream));
       }
       if (generic) RB_TRY(generic_finish_inputs(c, k > 0 ? s->h_xnk.data() + (size_t)t * nN : nullptr));
-      if (device) RB_TRY(device_finish_inputs(c, xref));
-      const int st_step = s->form == SmootherForm::Info ? info_step(c, k, t, xref, n_draw) : ctx_step(c, k, xref, n_draw, nullptr);
+      if (device && !gsparse) RB_TRY(device_finish_inputs(c, xref));
+      const int st_step = s->form == SmootherForm::Info ? info_step(c, k, t, xref, n_draw) : gsparse ? generic_sparse_step(c, k, xref) : ctx_step(c, k, xref, n_draw, nullptr);
       if (generic || device) { c->ext_xn = nullptr; c->ext_H = nullptr; }
       RB_TRY(st_step);
     }
@@ -1596,6 +1738,11 @@ static int smoother_run_and_free(int st, rbpf_ctx* c, const rbpf_problem* prob, 
     set_error(std::string(rbpf_last_error()) + " -- the information-form smoother did not fit this device with these options.  Its smallest "
               "footprint: storage = 2 (nLin 256..767), lazy_depth >= 2, inplace = 1 and chol_refresh >= N_T (or info_rebuild = 1): about " +
               std::to_string((int)(mb * 10) / 10.0).substr(0, 4) + " MB of state per particle at this nLin (include/rbpf.h, rbpf_options)");
+  }
+  if (st == RBPF_ERR_OUT_OF_MEMORY && c && c->mdl.kind == RBPF_MODEL_GENERIC_SPARSE) {
+    set_error(std::string(rbpf_last_error()) + " -- the sparse smoother with device handles did not fit this device.  Its largest workspace is S, "
+              "N_P * M^2 doubles with M the observed outputs after step 0 (then the factors, as many again, the stacked Jacobians N_P * M * nLin "
+              "and the staging buffers of a measModel call, bounded by max_future_per_call): fewer particles or a shorter data set");
   }
   if (!c) return st;
   if (st != RBPF_OK) { ctx_free(c); return st; }
@@ -1635,6 +1782,51 @@ extern "C" int rbpf_particle_smoother_device(const rbpf_model* model, const rbpf
   rbpf_ctx* c = nullptr;
   const int st = ctx_create(model, prob, rng, opt, true, N_K, &c, nullptr, device_callbacks, dy_layout);
   return smoother_run_and_free(st, c, prob, N_K, info_form, out);
+}
+
+extern "C" int rbpf_particle_smoother_sparse_device(const rbpf_model* model, const rbpf_problem* prob, const rbpf_rng* rng,
+                                                    const rbpf_options* opt, int32_t N_K, rbpf_sparse_dyn_fn dyn_model,
+                                                    rbpf_sparse_meas_fn meas_model, rbpf_sparse_dyn_res_norm_fn dyn_res_norm, void* user,
+                                                    int32_t yhat_layout, int32_t dy_layout, int32_t max_future_per_call,
+                                                    rbpf_smoother_out* out) {
+  // everything that can be refused is refused here, before anything touches a device
+  if (!out || N_K < 1) { set_error("bad smoother arguments"); return RBPF_ERR_INVALID_ARG; }
+  if (!model || !prob || !rng || !dyn_model || !meas_model) { set_error("NULL argument (model, prob, rng, dyn_model and meas_model are needed)"); return RBPF_ERR_INVALID_ARG; }
+  if (yhat_layout != 0 && yhat_layout != 2) { set_error("yhat_layout must be 0 (MATLAB order) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
+  if (dy_layout < 0 || dy_layout > 2) { set_error("dy_layout must be 0 (MATLAB order), 1 (rows on the stride ldx) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
+  if (max_future_per_call < 0) { set_error("max_future_per_call must be >= 0 (0: automatic)"); return RBPF_ERR_INVALID_ARG; }
+  if (model->kind != RBPF_MODEL_GENERIC_SPARSE || model->callbacks) {
+    set_error("rbpf_particle_smoother_sparse_device takes a generic sparse model (RBPF_MODEL_GENERIC_SPARSE) with rbpf_model.callbacks == NULL"); return RBPF_ERR_INVALID_ARG;
+  }
+  RB_TRY(options_ok(opt));
+  const char* who = "generic sparse family (sparseFeatures = true with device handles): ";
+  if (wants_multi(opt)) { set_error(std::string(who) + "n_devices is not supported (the sparseFeatures branch is not sharded)"); return RBPF_ERR_UNSUPPORTED; }
+  if (opt && opt->storage != 0) { set_error(std::string(who) + "options.storage must be 0 (fp64 full squares)"); return RBPF_ERR_UNSUPPORTED; }
+  if (opt && opt->lazy_depth >= 2) { set_error(std::string(who) + "lazy_depth >= 2 is not supported (the EKF update rewrites every covariance at every step)"); return RBPF_ERR_UNSUPPORTED; }
+  if (opt && opt->inplace > 0) { set_error(std::string(who) + "inplace = 1 is not supported (one covariance bank needs lazy_depth >= 2)"); return RBPF_ERR_UNSUPPORTED; }
+  if (prob->n_y < 1 || prob->n_y > 32) { set_error("generic sparse family: n_y must be 1 .. 32"); return RBPF_ERR_UNSUPPORTED; }
+  if (prob->n_lin < 1 || prob->n_lin > 96) { set_error("generic sparse family: nLin must be 1 .. 96 (the border-only bank layout)"); return RBPF_ERR_UNSUPPORTED; }
+  if (prob->y && prob->N_T >= 1) {                       // the future observations of step 1, as sparse_alloc counts them
+    size_t Ms = 0;
+    for (int ti = 1; ti < prob->N_T; ++ti)
+      for (int j = 0; j < prob->n_y; ++j) Ms += std::isnan(prob->y[ti + (size_t)prob->N_T * j]) ? 0 : 1;
+    if (Ms > 1023) { set_error("sparse smoother: more than 1023 future observations (particleSmoother.m:197-212 stacks them all)"); return RBPF_ERR_UNSUPPORTED; }
+  }
+  const SparseSmootherHandles sh{dyn_model, meas_model, dyn_res_norm, user, yhat_layout, dy_layout, max_future_per_call};
+  rbpf_ctx* c = nullptr;
+  const int st = ctx_create(model, prob, rng, opt, true, N_K, &c, nullptr, nullptr, 0, &sh);
+  return smoother_run_and_free(st, c, prob, N_K, 0, out);
+}
+
+extern "C" int rbpf_sparse_smoother_timing(int32_t enable, double* build_ms, double* chol_ms, int64_t* steps) {
+  std::lock_guard<std::mutex> lock(g_sparse_timing_mutex);
+  if (build_ms) *build_ms = g_sparse_build_ms;
+  if (chol_ms) *chol_ms = g_sparse_chol_ms;
+  if (steps) *steps = g_sparse_timed_steps;
+  g_sparse_build_ms = g_sparse_chol_ms = 0.0;
+  g_sparse_timed_steps = 0;
+  g_sparse_timing.store(enable ? 1 : 0);
+  return RBPF_OK;
 }
 
 // =============================================================================================================
@@ -2182,6 +2374,37 @@ int rbpf_ext_pack_whiten_probe(int32_t dy_layout, int32_t rows, int32_t d, int32
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipMemcpy(G_host, dG, len * 8, hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+// The build kernel of the generic sparse family's ancestor weights (rbpf_sparse_ext_anc.hip) on caller-supplied device arrays.
+int rbpf_sparse_ext_build_probe(int32_t N, int32_t n, int32_t M, int32_t d, const double* P_dev, const double* D_dev,
+                                const int32_t* pair_t_dev, const int32_t* pair_j_dev, const double* R_dev, int32_t reps,
+                                double* S_dev, double* ms) {
+  if (!P_dev || !D_dev || !pair_t_dev || !pair_j_dev || !R_dev || !S_dev || N < 1 || n < 1 || n > 96 || M < 1 || M > 1023 || d < 1 || reps < 1) {
+    set_error("bad argument (NULL pointer, or outside 1 <= n <= 96, 1 <= M <= 1023, N, d, reps >= 1)"); return RBPF_ERR_INVALID_ARG;
+  }
+  if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
+  SparseExtBuildArgs ba;
+  ba.n = n; ba.M = M; ba.d = d; ba.ldb = n; ba.ldn = n; ba.szB = (size_t)n * n; ba.szD = (size_t)M * n;
+  ba.Pb = P_dev; ba.D = D_dev; ba.pair_t = pair_t_dev; ba.pair_j = pair_j_dev; ba.R = R_dev; ba.S = S_dev;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipError_t err = hipEventCreate(&e0);
+  if (err == hipSuccess) err = hipEventCreate(&e1);
+  float total = 0.f;
+  for (int r = 0; r < reps && err == hipSuccess; ++r) {
+    err = hipEventRecord(e0, nullptr);
+    if (err == hipSuccess) err = launch_sparse_ext_build(ba, N, nullptr);
+    if (err == hipSuccess) err = hipEventRecord(e1, nullptr);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    float t = 0.f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
+    total += t;
+  }
+  if (e0) hipEventDestroy(e0);
+  if (e1) hipEventDestroy(e1);
+  if (err != hipSuccess) return hip_fail(err, "rbpf_sparse_ext_build_probe", __FILE__, __LINE__);
+  if (ms) *ms = (double)total / reps;
   return RBPF_OK;
 }
 

@@ -59,6 +59,35 @@ hipError_t launch_sparse_ext_step(const SparseExtStepArgs& a, hipStream_t s);
 hipError_t launch_sparse_ext_gather_xl(int N, int ldx, const double* src, size_t src_stride, const int* ai, double* out, hipStream_t s);
 hipError_t launch_sparse_ext_yhat_of_max(int d, const double* yhat, size_t si, size_t sk, const int* iw_max, double* out, hipStream_t s);
 
+// Ancestor weights of the smoother for RBPF_MODEL_GENERIC_SPARSE (rbpf_sparse_ext_anc.hip)
+struct SparseExtPackArgs {
+  int N, F, n, d, M, m0, Mc;          // particles, future times of the chunk, nLin, n_y; pairs [m0, m0 + Mc) of the step's M
+  int slot0;                          // index of the chunk's first time in the table of observed times
+  const int* time_slot;               // [T] index of every time in that table
+  const int* pair_t; const int* pair_j;     // the step's stacked (time, output) pairs
+  const double* y;                    // [T][d]
+  const double* yhat; int yhat_layout;      // of the handle's F N columns: 0 MATLAB order, 2 C-contiguous
+  const double* dy; int dy_layout, dy_ld;   // 0 MATLAB order; 1 / 2: rows on the stride dy_ld
+  double* D;                          // [N][M][n]
+  double* rhs;                        // [N][M]
+};
+
+struct SparseExtBuildArgs {
+  int n, M, d, ldb, ldn;
+  size_t szB, szD;                    // doubles between two particles' P and D
+  const double* Pb;                   // [N][n][ldb] row-major (symmetric)
+  const double* D;                    // [N][M][ldn]
+  const int* pair_t; const int* pair_j;     // [M] time and output of every stacked row
+  const double* R;                    // [d x d] column-major
+  double* S;                          // [N][M*M] column-major: the 16 x 16 tiles on and below the diagonal
+};
+
+hipError_t launch_sparse_ext_replicate(int N, int F, int nN, int ldx, const int* times, const double* xnk, const double* xl_bank,
+                                       double* xn, double* xl, hipStream_t s);
+hipError_t launch_sparse_ext_pack(const SparseExtPackArgs& a, hipStream_t s);
+size_t sparse_ext_build_lds_bytes(int n, int M);
+hipError_t launch_sparse_ext_build(const SparseExtBuildArgs& a, int N, hipStream_t s);
+
 size_t sparse_step_lds_bytes(int n, int d);
 hipError_t launch_sparse_step(const SparseStepArgs& a, hipStream_t s);
 hipError_t launch_sparse_anc(const SparseAncArgs& a, int N, hipStream_t s);

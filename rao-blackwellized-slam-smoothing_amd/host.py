@@ -303,9 +303,10 @@ class GenericDenseModel:
 
 
 class GenericSparseModel:
-    """Descriptor behind a DeviceSparseHandles object: an arbitrary model with sparseFeatures = true, sized from the problem arrays
+    """Descriptor behind a DeviceSparseHandles / DeviceSparseSmootherHandles object: an arbitrary model with sparseFeatures = true, sized from the problem arrays
     (RBPF_MODEL_GENERIC_SPARSE).  It carries no handles -- the binding drives the steps -- only the sizes and the per-step arguments
-    of dynModel.  Admitted: ny <= 32, nLin <= 96, nNonLin and nw <= 8; the filter on one GPU, fp64 storage."""
+    of dynModel.  Admitted: ny <= 32, nLin <= 96, nNonLin and nw <= 8; the filter (DeviceSparseHandles) and the covariance-form
+    smoother (DeviceSparseSmootherHandles) on one GPU, fp64 storage."""
     kind = _ffi.RBPF_MODEL_GENERIC_SPARSE
     sparse = True
 
@@ -401,12 +402,50 @@ class DeviceSparseHandles(DeviceHandles):
     The layouts are read off the strides of what measModel returns: dy C-contiguous or in MATLAB order (strides
     (1, N_P, N_P n_y), packed by a kernel first), yhat contiguous or transposed; anything else costs one contiguous().
     extras=True adds yhattraj (n_y, N_T): every step's yhat of the maximum-weight particle (:201-203).
-    n_y <= 32, nLin <= 96, n_nonlin and n_w <= 8; the filter on one GPU with fp64 storage.  Not taken by the smoothers, by sharded
-    sessions, with sparseFeatures=False, or with lazy_depth / inplace / another storage (see GenericSparseModel).
+    n_y <= 32, nLin <= 96, n_nonlin and n_w <= 8; the filter on one GPU with fp64 storage.  Not taken by the smoothers (a filter
+    handle is written for exactly N_P columns: particleSmoother takes a DeviceSparseSmootherHandles, whose contract is wider), by
+    sharded sessions, with sparseFeatures=False, or with lazy_depth / inplace / another storage (see GenericSparseModel).
     A handle that raises, or returns a wrong shape, dtype or device, surfaces as that exception; the library stays usable."""
 
     def __init__(self, dynModel, measModel):
         super().__init__(dynModel, measModel)
+
+
+class DeviceSparseSmootherHandles(DeviceSparseHandles):
+    """Device handles for particleSmoother(..., sparseFeatures=True) with an arbitrary model (particleSmoother.m:194-217,267-277,
+    306-321), and, as its base class, for the filter: batched callables on torch float64 tensors of the library's device, run inside
+    torch.cuda.stream(the library's stream), handed in place of the three handles -- the object as dynModel, None as measModel and
+    dynResNorm.  Between two steps of an iteration nothing is copied to the host and nothing waits for it
+    (rbpf_particle_smoother_sparse_device).
+
+        xn_new (n_nonlin, C) = dynModel(xn_anc (n_nonlin, C), dx (n_odo,), dt, Q (n_w, n_w))
+            C = N_P in iteration 0, N_P - 1 at the steps t >= 1 of later iterations: the ordinary slots, in slot order (:132-137).
+            Draws its own random numbers.
+        yhat (C, n_y), dy (C, n_y, nLin) = measModel(xn (n_nonlin, C), xl (C, nLin))
+            must be a PURE function of its arguments and accept any C.  C = N_P once per step: xl the gathered maps as in the filter,
+            the reference slot's sampled map included (:243).  C = F N_P at the steps t >= 1 of the iterations k >= 1, for the
+            ancestor weights: F is a chunk of the future times ti of t .. N_T-1 that have an observed output; column f N_P + i carries
+            xn = xnk(:,ti_f) and xl row = xl(:,i) of generation t - 1, the map before the resampling gather (the one :206 linearises
+            at).  Rows of yhat / dy of outputs not observed at that time are never read; dy is dense, no structure is assumed.
+        e (n_w, N_P) = dynResNorm(xnk_t (n_nonlin,), xn (n_nonlin, N_P), dx, dt, Q), or None
+            exactly DeviceSmootherHandles' contract; None: the additive default (:175-177) on the device, needs n_w == n_nonlin.
+
+    future_chunk: the largest F per call.  None: as many future times as keep the chunk's staging buffers (dy, F N_P n_y nLin
+    doubles, and the replicated xl) within 256 MB; an integer >= 1 forces it.  The results do not depend on it, bit for bit.
+    The layouts are read off the strides of what measModel returns, as for DeviceSparseHandles, once, in a call with C = N_P at the
+    initial states before the run: dy C-contiguous, in MATLAB order (strides (1, C, C n_y)) or rows on a wider stride (a slice
+    [:, :, :nLin]); yhat contiguous or transposed.  The library's buffers then have that layout, and every result is copied into them.
+    One GPU, fp64 storage; n_y <= 32, nLin <= 96 and at most 1023 observed outputs after step 0.  Not built: the information form
+    (the reference's returns nothing for sparseFeatures: use particleSmoother), host closures, sharding, the MEX gateway."""
+
+    def __init__(self, dynModel, measModel, dynResNorm=None, future_chunk=None):
+        super().__init__(dynModel, measModel)
+        if not _is_empty_handle(dynResNorm) and not callable(dynResNorm):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "dynResNorm must be callable or None")
+        if future_chunk is not None and (isinstance(future_chunk, bool) or not isinstance(future_chunk, (int, np.integer)) or future_chunk < 1):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "future_chunk must be None (automatic) or an integer >= 1")
+        self.dynResNorm = None if _is_empty_handle(dynResNorm) else dynResNorm
+        self.future_chunk = None if future_chunk is None else int(future_chunk)
 
 
 def _refuse_device_handles(what, *handles):
@@ -498,6 +537,80 @@ class _DeviceSmootherCallbacks:
         self._checked("measModel", dy, (n_cols, d, n))
         if not _DeviceDriver._same(dy, target):
             target.copy_(dy)
+
+
+class _SparseSmootherCallbacks(_DeviceSmootherCallbacks):
+    """The callbacks of a DeviceSparseSmootherHandles object for rbpf_particle_smoother_sparse_device: dynModel and dynResNorm as
+    for DeviceSmootherHandles; measModel takes the maps and returns (yhat, dy), copied into the library's buffers of the layouts
+    read off its strides in one call at the initial states (C = N_P) before the run."""
+
+    def __init__(self, lib, handles, model, prob):
+        import torch
+        from .multigpu import _view
+        self.torch, self._view = torch, _view
+        self.lib, self.h = lib, handles
+        self.nN, self.n, self.d, self.nw, self.N = model.nNonLin, model.nLin, model.ny, model.nw, prob.N_P
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.odo = torch.as_tensor(np.ascontiguousarray(model._odo), device=self.device)
+        self.Q = torch.as_tensor(np.ascontiguousarray(np.moveaxis(model._Q, 2, 0)), device=self.device)     # [pages][nw][nw]
+        self.dt = model._dt
+        self.error = None
+        self.stream = None
+        self.ldx = 0
+        self.future = 0 if handles.future_chunk is None else int(handles.future_chunk)
+        x0 = torch.as_tensor(prob.x0n, device=self.device).repeat(self.N, 1).t()
+        xl0 = torch.as_tensor(np.ascontiguousarray(prob.x0l.T), device=self.device)
+        yhat, dy = self._meas_sparse(x0, xl0.expand(self.N, self.n).contiguous() if xl0.shape[0] == 1 else xl0, self.N)
+        self.yhat_layout = 0 if (not yhat.is_contiguous() and yhat.t().is_contiguous()) else 2
+        if dy.is_contiguous():
+            self.dy_layout = 2
+        elif dy.permute(2, 1, 0).is_contiguous():
+            self.dy_layout = 0
+        else:                                             # rows on a wider stride: the library's buffer has its own, ldx
+            self.dy_layout = 1 if (dy.stride(2) == 1 and dy.stride(0) == self.d * dy.stride(1)) else 2
+        del yhat, dy
+        torch.cuda.current_stream(self.device).synchronize()           # the constants above, before the library's stream reads them
+
+        def guarded(fn):
+            def call(*a):
+                try:
+                    self._enter()
+                    with torch.cuda.stream(self.stream):
+                        fn(*a)
+                    return 0
+                except Exception as exc:                                                  # noqa: BLE001
+                    self.error = self.error or exc
+                    return 1
+            return call
+
+        self._fns = (_ffi.DYN_MODEL_FN(guarded(self._dyn)), _ffi.SPARSE_MEAS_MODEL_FN(guarded(self._meas)),
+                     _ffi.DYN_RES_NORM_FN(guarded(self._drn)) if handles.dynResNorm is not None else _ffi.DYN_RES_NORM_FN())
+
+    def _meas_sparse(self, xn, xl, n_cols):
+        torch = self.torch
+        out = self.h.measModel(xn, xl)
+        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(v) for v in out)):
+            raise ValueError("measModel must return (yhat, dy), two device tensors")
+        self._checked("measModel (yhat)", out[0], (n_cols, self.d))
+        self._checked("measModel (dy)", out[1], (n_cols, self.d, self.n))
+        return out
+
+    def _meas(self, _user, n_cols, xn, xl, ldx, yhat_p, dy_p):
+        n, d = self.n, self.d
+        X = self._view(self.torch, xn, (n_cols, self.nN), self.device).t()
+        XL = self._view(self.torch, xl, (n_cols, ldx), self.device)[:, :n]
+        yhat, dy = self._meas_sparse(X, XL, n_cols)
+        if self.yhat_layout == 0:
+            self._view(self.torch, yhat_p, (d, n_cols), self.device).t().copy_(yhat)
+        else:
+            self._view(self.torch, yhat_p, (n_cols, d), self.device).copy_(yhat)
+        if self.dy_layout == 0:
+            target = self._view(self.torch, dy_p, (n, d, n_cols), self.device).permute(2, 1, 0)
+        elif self.dy_layout == 1:
+            target = self._view(self.torch, dy_p, (n_cols, d, ldx), self.device)[:, :, :n]
+        else:
+            target = self._view(self.torch, dy_p, (n_cols, d, n), self.device)
+        target.copy_(dy)
 
 
 class _DeviceDriver:
@@ -1120,12 +1233,51 @@ def model_dyn_res_norm(dynModel):
     return mdl.dynResNorm if isinstance(mdl, _ModelFamily) else None
 
 
+def _refuse_sparse_smoother(model, y, lazy_depth, inplace, storage):
+    """The refusals of rbpf_particle_smoother_sparse_device that depend on the options and the sizes, made here as well: the binding
+    calls measModel once before the run (the layouts), and a refused run calls no handle."""
+    who = "generic sparse family (sparseFeatures = true with device handles): "
+    if _storage_code(storage) != 0:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, who + "options.storage must be 0 (fp64 full squares)")
+    if int(lazy_depth) >= 2:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, who + "lazy_depth >= 2 is not supported (the EKF update rewrites every covariance "
+                                                         "at every step)")
+    if int(inplace) > 0:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, who + "inplace = 1 is not supported (one covariance bank needs lazy_depth >= 2)")
+    if not 1 <= model.ny <= 32:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "generic sparse family: n_y must be 1 .. 32")
+    if not 1 <= model.nLin <= 96:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "generic sparse family: nLin must be 1 .. 96 (the border-only bank layout)")
+    y2 = np.asarray(y, dtype=np.float64)
+    y2 = y2.reshape(-1, 1) if y2.ndim == 1 else y2
+    if int(np.count_nonzero(~np.isnan(y2[1:]))) > 1023:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "sparse smoother: more than 1023 future observations (particleSmoother.m:197-212 "
+                                                   "stacks them all)")
+
+
 def _smoother(info_form, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, N_K, dt,
               sparseFeatures, makePlots, rng, extras, chol_variant=0, lazy_depth=0, chol_refresh=0, n_devices=0, device_ids=None,
               storage="fp64", exchange_capacity=0, inplace=0, info_rebuild=0):
-    handles = dynModel if isinstance(dynModel, DeviceSmootherHandles) else None
+    handles = dynModel if isinstance(dynModel, (DeviceSmootherHandles, DeviceSparseSmootherHandles)) else None
+    sparse_handles = isinstance(handles, DeviceSparseSmootherHandles)
     if handles is None:
         _refuse_device_handles("the smoothers", dynModel, measModel, dynResNorm)
+    elif sparse_handles:                                      # sparseFeatures = true with device code (see DeviceSparseSmootherHandles)
+        if (measModel is not None and measModel is not handles) or not (_is_empty_handle(dynResNorm) or dynResNorm is handles):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "DeviceSparseSmootherHandles replace the three handles: pass the object as "
+                                                       "dynModel and None as measModel and dynResNorm")
+        if info_form:
+            # particleSmootherInformationForm.m:77-80 prints and returns with outputs unassigned (oracle quirk Q5)
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceSparseSmootherHandles: the information form has only been implemented for "
+                                                       "dense features (the reference's returns nothing for sparseFeatures): use "
+                                                       "particleSmoother")
+        if not sparseFeatures:
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "DeviceSparseSmootherHandles need sparseFeatures=True: their measModel returns "
+                                                       "(yhat, dy) at every particle's own map")
+        if int(n_devices) > 1 or (int(n_devices) == 1 and device_ids is not None):
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceSparseSmootherHandles are not supported by sharded sessions (n_devices): "
+                                                       "the sparseFeatures branch is not sharded")
+        dynModel = measModel = dynResNorm = None
     else:                                                     # device code: no host callbacks (see DeviceSmootherHandles)
         if (measModel is not None and measModel is not handles) or not (_is_empty_handle(dynResNorm) or dynResNorm is handles):
             raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "DeviceSmootherHandles replace the three handles: pass the object as "
@@ -1142,6 +1294,9 @@ def _smoother(info_form, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin
             # particleSmootherInformationForm.m:77-80 prints and returns with outputs unassigned
             raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "This code has only been implemented for dense features")
     model, use_drn = (None, False) if handles is not None else _recognise(dynModel, measModel, dynResNorm)
+    if sparse_handles:
+        model = _generic_model(None, None, None, odometry, y, x0_nonLin, x0_lin, Q, dt, sparse=True)
+        _refuse_sparse_smoother(model, y, lazy_depth, inplace, storage)      # what the library would refuse, before a handle is called
     if model is None:
         # arbitrary handles (particleSmoother.m:134-136,175-180,264 accept any): the generic family through callbacks
         if sparseFeatures:
@@ -1152,7 +1307,7 @@ def _smoother(info_form, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin
     prob = _Problem(model, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, dt)
     N_K = int(N_K)
     nN, n, N, T = model.nNonLin, model.nLin, prob.N_P, prob.N_T
-    if isinstance(model, GenericDenseModel) and isinstance(rng, ReplayRNG) and (rng.Z is None or rng.Z.size == 0):
+    if isinstance(model, (GenericDenseModel, GenericSparseModel)) and isinstance(rng, ReplayRNG) and (rng.Z is None or rng.Z.size == 0):
         rng = ReplayRNG(rng.U, np.zeros(rng.U.shape + (model.nw,)), rng.Ufin)
     blk, _keep = _rng_block(rng, prob.N_P, prob.N_T, model.nw, N_K)
     opt = _ffi.rbpf_options(keep_history=1, trace=1 if extras else 0, fix_p_mean=0, lazy_depth=int(lazy_depth), jitter=0.0,
@@ -1190,7 +1345,12 @@ def _smoother(info_form, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin
         opt.on_step = hook
     driver = None
     try:
-        if handles is not None:
+        if sparse_handles:
+            driver = _SparseSmootherCallbacks(lib, handles, model, prob)
+            check(lib.rbpf_particle_smoother_sparse_device(C.byref(mdesc), C.byref(prob.c), C.byref(blk), C.byref(opt), N_K,
+                                                           driver._fns[0], driver._fns[1], driver._fns[2], None,
+                                                           driver.yhat_layout, driver.dy_layout, driver.future, C.byref(o)))
+        elif handles is not None:
             driver = _DeviceSmootherCallbacks(lib, handles, model, prob)
             check(lib.rbpf_particle_smoother_device(C.byref(mdesc), C.byref(prob.c), C.byref(blk), C.byref(opt), N_K,
                                                     1 if info_form else 0, C.byref(driver.cb), driver.layout, C.byref(o)))
@@ -1211,10 +1371,15 @@ def _smoother(info_form, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin
 
 
 def particleSmoother(dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, N_K, dt,
-                     sparseFeatures=False, makePlots=None, *, rng=None, extras=False, chol_variant=0, storage="fp64"):
-    """Mirror of src/particleSmoother.m:1-2 (covariance-form ancestor weights) -> (XNK, XLK, PK)."""
+                     sparseFeatures=False, makePlots=None, *, rng=None, extras=False, chol_variant=0, storage="fp64",
+                     lazy_depth=0, inplace=0, n_devices=0, device_ids=None):
+    """Mirror of src/particleSmoother.m:1-2 (covariance-form ancestor weights) -> (XNK, XLK, PK).
+    sparseFeatures=True runs for the sparse-visual family, and for ANY model whose handles are device code: a
+    DeviceSparseSmootherHandles object as dynModel (see there).  The covariance form rewrites every covariance at every step, so
+    lazy_depth is ignored and inplace refused; n_devices is what it is for particleSmootherInformationForm."""
     return _smoother(False, dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R, N_P, N_K,
-                     dt, sparseFeatures, makePlots, rng, extras, chol_variant, storage=storage)
+                     dt, sparseFeatures, makePlots, rng, extras, chol_variant, lazy_depth=lazy_depth, n_devices=n_devices,
+                     device_ids=device_ids, storage=storage, inplace=inplace)
 
 
 def particleSmootherInformationForm(dynModel, measModel, dynResNorm, odometry, y, x0_nonLin, x0_lin, P0_lin, Q, R,
@@ -1325,6 +1490,42 @@ def pack_whiten_probe(dy, W, dy_layout=0, fused=True):
     G = np.empty((rows, d, n))
     check(lib.rbpf_ext_pack_whiten_probe(int(dy_layout), rows, d, n, _dp(mem), _dp(W), 1 if fused else 0, _dp(G)))
     return G
+
+
+def sparse_smoother_timing(enable):
+    """Switch the per-step HIP-event timing of particleSmoother with DeviceSparseSmootherHandles on or off
+    (rbpf_sparse_smoother_timing) and return the totals since the last call: dict(build_ms, chol_ms, steps) -- milliseconds in the
+    build kernel and in the batched factorisation of the ancestor weights, and the number of timed steps."""
+    lib = load_library()
+    b, f, n = C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
+    check(lib.rbpf_sparse_smoother_timing(1 if enable else 0, C.byref(b), C.byref(f), C.byref(n)))
+    return dict(build_ms=float(b.value), chol_ms=float(f.value), steps=int(n.value))
+
+
+def sparse_ext_build_probe(P, D, pair_t, pair_j, R, reps=1, out=None):
+    """The build kernel of the sparse smoother with device handles on its own (rbpf_sparse_ext_build_probe), on torch device tensors:
+    P (N, n, n) symmetric, D (N, M, n), pair_t / pair_j (M,) int32 -- the time and the output of every stacked row -- and R (d, d)
+    -> (S (N, M, M) with S[i, a, b] = (D_i P_i D_i')(a, b) + (pair_t[a] == pair_t[b]) R[pair_j[a], pair_j[b]] in the 16 x 16 tiles on
+    and below the diagonal, mean kernel time in ms).  The tiles above the diagonal are not written: they keep what `out`
+    (N, M, M), viewed as the kernel's column-major matrices, held (NaN when out is None)."""
+    import torch
+    lib = load_library()
+    N, M, n = (int(v) for v in D.shape)
+    d = int(R.shape[0])
+    f64 = dict(dtype=torch.float64, device=D.device)
+    Pc, Dc = P.to(**f64).contiguous(), D.to(**f64).contiguous()
+    Rc = R.to(**f64).t().contiguous()                                  # column-major
+    pt = pair_t.to(dtype=torch.int32, device=D.device).contiguous()
+    pj = pair_j.to(dtype=torch.int32, device=D.device).contiguous()
+    if tuple(Pc.shape) != (N, n, n) or tuple(pt.shape) != (M,) or tuple(pj.shape) != (M,) or tuple(R.shape) != (d, d):
+        raise ValueError("P (N, n, n), D (N, M, n), pair_t / pair_j (M,), R (d, d)")
+    S = torch.full((N, M, M), float("nan"), **f64) if out is None else out     # [i][b][a]: column-major matrices
+    torch.cuda.synchronize(D.device)                                   # the kernel runs on the null stream
+    ms = C.c_double(0.0)
+    check(lib.rbpf_sparse_ext_build_probe(N, n, M, d, C.c_void_p(Pc.data_ptr()), C.c_void_p(Dc.data_ptr()), C.c_void_p(pt.data_ptr()),
+                                          C.c_void_p(pj.data_ptr()), C.c_void_p(Rc.data_ptr()), int(reps), C.c_void_p(S.data_ptr()),
+                                          C.byref(ms)))
+    return S.transpose(1, 2), float(ms.value)
 
 
 # ------------------------------------------------------------------------------------------------
