@@ -858,6 +858,46 @@ int rbpf_loc_backward_workspace_bytes(int32_t N_P, int32_t N_T, int32_t n_traj, 
 int rbpf_loc_backward_step(int32_t N, int32_t M, const double* xn, const double* w, const double* xs_next, const double* odo,
                            double dt, const double* Q, const double* u, int32_t* index, double* logp, int32_t reps, double* ms);
 
+/* ---- localisation in the fixed map of a generic device-code model --------------------------------
+ * particleFilter.m:100-161 with the map frozen: xl = mean and P = V'V (V lower n_lin x n_lin, column-major, lower triangle read:
+ * the rbpf_loc_map convention) are the same for every particle and never updated (:163-204 are left out).  The model is the
+ * caller's device code, as for rbpf_filter_step_device: per step, with dy(i,:,:) = H_i [n_y x n_lin] from the caller's measModel,
+ *     e_i = y_t' - H_i mean,   S_i = H_i P H_i' + R,   logw_i = -sum log diag chol S_i - |chol(S_i) \ e_i|^2 / 2 - n_y log(2 pi) / 2
+ * (:139-150, a proper Gaussian; the jitter retry of :145-148 is left out: S_i is a Gram matrix plus R, and an R that is not
+ * positive definite is RBPF_ERR_CHOL_FAILED at creation).  Normalisation, traj_max / traj_mean, the ancestors ai(i) = sample(w) on
+ * the library's uniforms, xn_traj and log(sum(w)) are those of rbpf_loc_create's filter; dynModel draws its own normals (rng->Z is
+ * not read).  n_y 1 .. 8, n_lin 1 .. 1151, n_nonlin 1 .. 8 (above: RBPF_ERR_UNSUPPORTED).  No new struct: the scalars and arrays
+ * below, rbpf_rng, rbpf_options (keep_history, trace, on_step are read, any other non-zero field is RBPF_ERR_UNSUPPORTED) and
+ * rbpf_loc_out, whose 7 rows are n_nonlin rows for such a context.  NULL arguments and bad sizes are refused before any device
+ * is touched; without a device: RBPF_ERR_NO_DEVICE.
+ *   rbpf_loc_generic_create   mean [n_lin], V, R [n_y x n_y] column-major, y [N_T x n_y] column-major, x0_nonlin
+ *        [n_nonlin x x0_cols], x0_cols 1 or N_P.  rbpf_loc_finish, rbpf_loc_history, rbpf_filter_tell, rbpf_sync, rbpf_stream_get and
+ *        rbpf_destroy work on the context; rbpf_loc_advance is RBPF_ERR_STATE (the handles are the caller's) and
+ *        rbpf_loc_backward_simulate RBPF_ERR_UNSUPPORTED (it needs dynModel's transition density; a generic dynModel is a sampler).
+ *   rbpf_loc_generic_layout   ldx >= n_lin, the row stride of dy layout 1.
+ *   rbpf_loc_generic_ancestors_device   before every step, in stream order on rbpf_stream_get(ctx): *xn_anc_dev
+ *        [n_nonlin x N_P] column-major = the states of the resampled ancestors, xn_{t-1}(:, ai(i)), and *ai_dev [N_P] the 0-based
+ *        ancestors; at t = 0 the initial states (x0_nonlin repeated) and *ai_dev = NULL.  Owned by the context, valid until the
+ *        next step call.  RBPF_ERR_STATE after the last step.
+ *   rbpf_loc_generic_step_device   xn_new_dev [n_nonlin x N_P] column-major = dynModel(xn_anc, ...) (t = 0: xn_anc itself),
+ *        dy_dev = measModel(xn_new) in dy_layout 0 (MATLAB order, dy(i,k,c) at i + N_P*(k + n_y*c), packed by a kernel first),
+ *        2 (C-contiguous [N_P][n_y][n_lin]) or 1 ([N_P][n_y][ldx] rows, consumed in place; columns n_lin .. ldx-1 are never
+ *        read and may hold anything).  RBPF_ERR_STATE at t >= 1 without the ancestors call.  Returns without waiting unless an
+ *        on_step hook is set (then: synchronise, call the hook; view->ctx is valid for rbpf_loc_finish).
+ *   rbpf_loc_generic_weights   the weight kernel on its own, host arrays: dy for n_p particles in dy_layout (ldx: the row stride
+ *        of layout 1, otherwise ignored), y [n_y] -> yhat [n_y x n_p] = H_i mean, S [n_y x n_y x n_p] = H_i P H_i' (before R is
+ *        added), logw [n_p]; NULL outputs are skipped.  reps >= 1 repeats the launch; *ms (may be NULL) = median kernel time by
+ *        device events.                                                                                                          */
+int rbpf_loc_generic_create(int32_t n_nonlin, int32_t n_y, int32_t n_lin, const double* mean, const double* V, const double* R,
+                            int32_t N_P, int32_t N_T, const double* y, const double* x0_nonlin, int32_t x0_cols,
+                            const rbpf_rng* rng, const rbpf_options* opt, rbpf_ctx** ctx);
+int rbpf_loc_generic_layout(const rbpf_ctx* ctx, int32_t* ldx);
+int rbpf_loc_generic_ancestors_device(rbpf_ctx* ctx, const int32_t** ai_dev, const double** xn_anc_dev);
+int rbpf_loc_generic_step_device(rbpf_ctx* ctx, const double* xn_new_dev, const double* dy_dev, int32_t dy_layout);
+int rbpf_loc_generic_weights(int32_t n_y, int32_t n_lin, int32_t n_p, const double* dy, int32_t dy_layout, int32_t ldx,
+                             const double* mean, const double* V, const double* R, const double* y, double* yhat, double* S,
+                             double* logw, int32_t reps, double* ms);
+
 /* ---- the EKF comparison baseline of examples/slam-dense-mag, batched over data sets ---------------
  * ekf_dense.m:41-102 with the closures measModel_ekf / dynModel_ekf of run_dense3D_magfield.m:281-299,310-316, on the device:
  * one Gaussian state [position(3); orientation deviation(3); map(nLin = m_basis + 3)], n = 6 + nLin, per run.  The n_runs runs

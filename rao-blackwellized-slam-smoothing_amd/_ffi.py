@@ -164,6 +164,8 @@ EXPORTS = [
     "rbpf_particle_filter_localization", "rbpf_loc_create", "rbpf_loc_advance", "rbpf_loc_finish", "rbpf_loc_workspace_bytes",
     "rbpf_loc_predict", "rbpf_loc_dyn_model",
     "rbpf_loc_backward_simulate", "rbpf_loc_history", "rbpf_loc_backward_workspace_bytes", "rbpf_loc_backward_step",
+    "rbpf_loc_generic_create", "rbpf_loc_generic_layout", "rbpf_loc_generic_ancestors_device", "rbpf_loc_generic_step_device",
+    "rbpf_loc_generic_weights",
     "rbpf_ekf_dense", "rbpf_ekf_workspace_bytes",
 ]
 
@@ -297,6 +299,14 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_loc_backward_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
     lib.rbpf_loc_backward_step.argtypes = [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p,
                                            c_double_p, c_int32_p, c_double_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_generic_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32,
+                                            c_double_p, c_double_p, C.c_int32, C.POINTER(rbpf_rng), C.POINTER(rbpf_options),
+                                            C.POINTER(C.c_void_p)]
+    lib.rbpf_loc_generic_layout.argtypes = [C.c_void_p, c_int32_p]
+    lib.rbpf_loc_generic_ancestors_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.rbpf_loc_generic_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.rbpf_loc_generic_weights.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p,
+                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
     lib.rbpf_ekf_dense.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(rbpf_ekf_out)]
     lib.rbpf_ekf_workspace_bytes.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(C.c_size_t)]
     _lib = lib

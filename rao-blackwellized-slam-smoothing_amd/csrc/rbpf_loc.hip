@@ -390,7 +390,7 @@ static int loc_validate_problem(const rbpf_loc_problem* p) {
   return RBPF_OK;
 }
 
-static int loc_validate_options(const rbpf_options* o) {
+int loc_validate_options(const rbpf_options* o) {
   RB_TRY(options_ok(o));
   if (!o) return RBPF_OK;
   if (o->fix_p_mean || o->lazy_depth || o->inplace || o->storage || o->chol_variant || o->chol_refresh || o->exchange_capacity ||
@@ -582,6 +582,7 @@ int rbpf_loc_create(const rbpf_loc_map* map, const rbpf_loc_problem* prob, const
 
 int rbpf_loc_advance(rbpf_ctx* c, int32_t n_steps) {
   if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (c->loc->generic) { set_error("a generic localisation context is driven step by step (rbpf_loc_generic_step_device): its handles are the caller's"); return RBPF_ERR_STATE; }
   HIPCHK(hipSetDevice(c->device));
   for (int s = 0; s < n_steps; ++s) {
     RB_TRY(loc_step(c));
@@ -594,7 +595,7 @@ int rbpf_loc_finish(rbpf_ctx* c, rbpf_loc_out* o) {
   if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(loc_size_ok(o, "rbpf_loc_out"));
   HIPCHK(hipSetDevice(c->device));
-  const int N = c->N, Td = c->t;
+  const int N = c->N, Td = c->t, nN = c->loc->nN;
   const bool hist = c->opt.keep_history != 0, trace = c->opt.trace != 0;
   if ((o->trace_logw || o->trace_w) && !trace) { set_error("trace_logw / trace_w need rbpf_options.trace"); return RBPF_ERR_STATE; }
   if ((o->trace_ai || o->xn_traj) && !hist) { set_error("trace_ai / xn_traj need rbpf_options.keep_history"); return RBPF_ERR_STATE; }
@@ -607,25 +608,25 @@ int rbpf_loc_finish(rbpf_ctx* c, rbpf_loc_out* o) {
   for (int t = 0; t < Td; ++t)
     if (!(lse[t] > std::log(1e-12))) { o->first_degenerate_step = t; break; }                    // sum(w) <= 1e-12 (:113)
   if (o->log_sum_w) std::memcpy(o->log_sum_w, lse.data(), (size_t)Td * sizeof(double));
-  if (o->traj_max) HIPCHK(hipMemcpy(o->traj_max, c->traj_max, (size_t)Td * 7 * sizeof(double), hipMemcpyDeviceToHost));
-  if (o->traj_mean) HIPCHK(hipMemcpy(o->traj_mean, c->traj_mean, (size_t)Td * 7 * sizeof(double), hipMemcpyDeviceToHost));
+  if (o->traj_max) HIPCHK(hipMemcpy(o->traj_max, c->traj_max, (size_t)Td * nN * sizeof(double), hipMemcpyDeviceToHost));
+  if (o->traj_mean) HIPCHK(hipMemcpy(o->traj_mean, c->traj_mean, (size_t)Td * nN * sizeof(double), hipMemcpyDeviceToHost));
   if (o->trace_logw) HIPCHK(hipMemcpy(o->trace_logw, c->logw, (size_t)Td * N * sizeof(double), hipMemcpyDeviceToHost));
   if (o->trace_w) HIPCHK(hipMemcpy(o->trace_w, c->w, (size_t)Td * N * sizeof(double), hipMemcpyDeviceToHost));
   if (o->trace_ai) HIPCHK(hipMemcpy(o->trace_ai, c->A, (size_t)Td * N * sizeof(int), hipMemcpyDeviceToHost));
-  const double* X_last = c->X + (size_t)(hist ? Td - 1 : ((Td - 1) & 1)) * 7 * N;
+  const double* X_last = c->X + (size_t)(hist ? Td - 1 : ((Td - 1) & 1)) * nN * N;
   if (o->final_xn || o->xn_traj) {
     DevicePool tmp;
     double* d_tmp = nullptr;
-    const size_t cnt = (size_t)7 * N * (o->xn_traj ? Td : 1);
+    const size_t cnt = (size_t)nN * N * (o->xn_traj ? Td : 1);
     RB_TRY(tmp.alloc(&d_tmp, cnt));
     if (o->final_xn) {
-      HIPCHK(launch_transpose_soa(N, 7, X_last, d_tmp, c->stream));
+      HIPCHK(launch_transpose_soa(N, nN, X_last, d_tmp, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(hipMemcpy(o->final_xn, d_tmp, (size_t)7 * N * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(o->final_xn, d_tmp, (size_t)nN * N * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (o->xn_traj) {
       // xn_traj(:,:,1:t-1) = xn_traj(:,ai,1:t-1) of every step (:101-104) = every slot's path through the ancestor table
-      HIPCHK(launch_backtrace(N, 7, Td, c->X, c->A, nullptr, N, d_tmp, c->stream, 0));
+      HIPCHK(launch_backtrace(N, nN, Td, c->X, c->A, nullptr, N, d_tmp, c->stream, 0));
       HIPCHK(hipStreamSynchronize(c->stream));
       HIPCHK(hipMemcpy(o->xn_traj, d_tmp, cnt * sizeof(double), hipMemcpyDeviceToHost));
     }

@@ -320,20 +320,24 @@ int rbpf_loc_history(rbpf_ctx* c, double* xn_fwd) {
   if (!xn_fwd) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   if (!c->opt.keep_history) { set_error("rbpf_loc_history needs rbpf_options.keep_history"); return RBPF_ERR_STATE; }
   HIPCHK(hipSetDevice(c->device));
-  const int N = c->N, Td = c->t;
+  const int N = c->N, Td = c->t, nN = c->loc->nN;
   if (Td == 0) return RBPF_OK;
   DevicePool tmp;
   double* d_tmp = nullptr;
-  RB_TRY(tmp.alloc(&d_tmp, (size_t)7 * N * Td));
-  for (int t = 0; t < Td; ++t) HIPCHK(launch_transpose_soa(N, 7, c->X + (size_t)t * 7 * N, d_tmp + (size_t)t * 7 * N, c->stream));
+  RB_TRY(tmp.alloc(&d_tmp, (size_t)nN * N * Td));
+  for (int t = 0; t < Td; ++t) HIPCHK(launch_transpose_soa(N, nN, c->X + (size_t)t * nN * N, d_tmp + (size_t)t * nN * N, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy(xn_fwd, d_tmp, (size_t)7 * N * Td * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(xn_fwd, d_tmp, (size_t)nN * N * Td * sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
 int rbpf_loc_backward_simulate(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, double* xs_traj, int32_t* index,
                                double* traj_smooth_mean) {
   if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (c->loc->generic) {
+    set_error("backward simulation needs the transition density of dynModel: a generic map's dynModel is a sampler (its handles carry no density)");
+    return RBPF_ERR_UNSUPPORTED;
+  }
   if (n_traj < 1) { set_error("n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
   if (!c->opt.keep_history || !c->opt.trace) {
     set_error("rbpf_loc_backward_simulate reads the stored particles and weights: create the context with keep_history = 1 and trace = 1");

@@ -617,29 +617,34 @@ class _DeviceDriver:
     """Runs the steps of a generic-family filter context with DeviceHandles (see there)."""
 
     def __init__(self, lib, ctx, handles, model, prob):
+        self._setup(lib, ctx, handles, (model.nNonLin, model.nLin, model.ny, prob.N_P, prob.N_T), lib.rbpf_filter_external_layout, model)
+        self.x0 = self.torch.as_tensor(prob.x0n, device=self.device).repeat(self.N, 1)                       # particleFilter.m:59
+        self.torch.cuda.current_stream(self.device).synchronize()      # the constants above, before the library's stream reads them
+        if handles.dy_layout is not None:
+            self._register(int(handles.dy_layout))
+
+    def _setup(self, lib, ctx, handles, sizes, layout_fn, args):
+        """The context's stream and native row stride (layout_fn), and the handles' per-step arguments (args._odo, ._Q, ._dt) as
+        device constants; the caller synchronises before the library's stream reads them."""
         import torch
         from .multigpu import _view
         self.torch, self._view = torch, _view
         self.lib, self.ctx, self.h = lib, ctx, handles
-        self.nN, self.n, self.d, self.N, self.T = model.nNonLin, model.nLin, model.ny, prob.N_P, prob.N_T
+        self.nN, self.n, self.d, self.N, self.T = sizes
         self.device = torch.device("cuda", torch.cuda.current_device())
         sp = C.c_void_p()
         check(lib.rbpf_stream_get(ctx, C.byref(sp)))
         self.stream = torch.cuda.ExternalStream(sp.value, device=self.device)
         ldx = C.c_int32(0)
-        check(lib.rbpf_filter_external_layout(ctx, C.byref(ldx)))
+        check(layout_fn(ctx, C.byref(ldx)))
         self.ldx = ldx.value
-        self.odo = torch.as_tensor(np.ascontiguousarray(model._odo), device=self.device)
-        self.Q = torch.as_tensor(np.ascontiguousarray(np.moveaxis(model._Q, 2, 0)), device=self.device)     # [pages][nw][nw]
-        self.dt = model._dt
-        self.x0 = torch.as_tensor(prob.x0n, device=self.device).repeat(self.N, 1)                            # particleFilter.m:59
+        self.odo = torch.as_tensor(np.ascontiguousarray(args._odo), device=self.device)
+        self.Q = torch.as_tensor(np.ascontiguousarray(np.moveaxis(args._Q, 2, 0)), device=self.device)      # [pages][nw][nw]
+        self.dt = args._dt
         self.error = None
         self._keep = None
         self._native = None
         self._cb = None
-        torch.cuda.current_stream(self.device).synchronize()           # the constants above, before the library's stream reads them
-        if handles.dy_layout is not None:
-            self._register(int(handles.dy_layout))
 
     # -- the handles ------------------------------------------------------------------------------------
     def _dyn(self, t, xn_anc):
@@ -683,22 +688,28 @@ class _DeviceDriver:
                 check(lib.rbpf_filter_ancestors_device(self.ctx, C.byref(ai), C.byref(anc)))
                 xn = self._dyn(t - 1, self._view(torch, anc, (self.N, self.nN), self.device).t())
                 xn_cm = xn.t().contiguous()                               # [n_nonlin x N_P] column-major (no copy if it is)
-            out = None
-            if self.h.native_out:
-                if self._native is None:
-                    self._native = torch.zeros((self.N, self.d, self.ldx), dtype=torch.float64, device=self.device)
-                out = self._native[:, :, :self.n]
-            dy = self._meas(xn_cm.t(), out)
-            if self._same(dy, out):
-                layout = 1
-            elif dy.is_contiguous():
-                layout = 2
-            elif dy.permute(2, 1, 0).is_contiguous():
-                layout = 0
-            else:
-                dy, layout = dy.contiguous(), 2
+            out = self._native_out()
+            dy, layout = self._layout_of(self._meas(xn_cm.t(), out), out)
             self._keep = (xn_cm, dy)                                      # read in stream order by the step just enqueued
             check(lib.rbpf_filter_step_device(self.ctx, C.c_void_p(xn_cm.data_ptr()), C.c_void_p(dy.data_ptr()), layout))
+
+    def _native_out(self):
+        """The (N, n_y, nLin) view of the native buffer a native_out measModel fills, or None."""
+        if not self.h.native_out:
+            return None
+        if self._native is None:
+            self._native = self.torch.zeros((self.N, self.d, self.ldx), dtype=self.torch.float64, device=self.device)
+        return self._native[:, :, :self.n]
+
+    def _layout_of(self, dy, out):
+        """(dy, dy_layout of the C ABI) read off the strides of what measModel returned; anything else costs one contiguous()."""
+        if self._same(dy, out):
+            return dy, 1
+        if dy.is_contiguous():
+            return dy, 2
+        if dy.permute(2, 1, 0).is_contiguous():
+            return dy, 0
+        return dy.contiguous(), 2
 
     # -- device callbacks: rbpf_filter_advance runs the steps ---------------------------------------------
     def _register(self, layout):
@@ -1673,6 +1684,18 @@ def _grad_rows(NN, L, x):
     return rows
 
 
+def _lower_factor(P):
+    """V lower with V'V = P (symmetrised first): the transposed Cholesky factor of the index-reversed matrix, reversed back.
+    ValueError when P is not positive definite."""
+    P = np.asarray(P, dtype=np.float64)
+    P = 0.5 * (P + P.T)
+    try:
+        Cr = np.linalg.cholesky(P[::-1, ::-1])
+    except np.linalg.LinAlgError as exc:
+        raise ValueError("P is not positive definite") from exc
+    return Cr.T[::-1, ::-1]
+
+
 class DenseMagMap:
     """A fixed map of the dense-mag family: the posterior N(mean, V'V) over the m + 3 basis coefficients, as the SLAM filter /
     smoothers return it (xl_max, P_max / XLK, PK) or as the batch regression of run_localization.m:134-151 computes it.  Its
@@ -1702,13 +1725,7 @@ class DenseMagMap:
     def from_posterior(cls, model, xl, P, sigma2, var_points=None):
         """From a map posterior (mean xl, covariance P).  V = lower factor with V'V = P: the transposed Cholesky factor of the
         index-reversed matrix, reversed back."""
-        P = np.asarray(P, dtype=np.float64)
-        P = 0.5 * (P + P.T)
-        try:
-            Cr = np.linalg.cholesky(P[::-1, ::-1])
-        except np.linalg.LinAlgError as exc:
-            raise ValueError("P is not positive definite") from exc
-        return cls(model, xl, Cr.T[::-1, ::-1], sigma2, var_points)
+        return cls(model, xl, _lower_factor(P), sigma2, var_points)
 
     @classmethod
     def from_data(cls, model, x, y, theta, var_points=None):
@@ -1812,20 +1829,195 @@ class _LocProblem:
 def _recognise_map(dynModel, measModel):
     mp = getattr(dynModel, "model", None)
     if not isinstance(mp, DenseMagMap) or getattr(measModel, "model", None) is not mp:
-        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleFilterLocalization runs the handles of a DenseMagMap; a host-callback "
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleFilterLocalization runs the handles of a DenseMagMap, or a DeviceMap as dynModel; a host-callback "
                         "family for arbitrary localisation handles is not implemented")
     return mp
 
 
-def _loc_out(N, T, Td, extras, hist=True, trace=True):
+def device_map_weights(dy, mean, V, R, y, dy_layout=2, ldx=None, pad=0.0, reps=1):
+    """rbpf_loc_generic_weights, the kernel-level probe of localisation in a generic map: dy [N x n_y x nLin] (the Jacobians of N
+    particles), mean [nLin], V [nLin x nLin] lower with V'V = P, R [n_y x n_y], y [n_y] ->
+    (yhat [N x n_y] = H_i mean, S [N x n_y x n_y] = H_i P H_i' before R is added, logw [N], median kernel ms over `reps` launches).
+    dy_layout: the memory layout dy is handed to the library in -- 0 MATLAB order, 2 C-contiguous, 1 rows on the stride ldx
+    (default: the next multiple of 16), the columns behind nLin filled with `pad` (the kernel does not read them)."""
+    lib = load_library()
+    dy = np.asarray(dy, dtype=np.float64)
+    if dy.ndim != 3:
+        raise ValueError("dy must be [N x n_y x nLin]")
+    N, d, n = dy.shape
+    if dy_layout == 0:
+        buf = np.asfortranarray(dy)
+    elif dy_layout == 1:
+        ldx = (n + 15) // 16 * 16 if ldx is None else int(ldx)
+        buf = np.full((N, d, max(ldx, n)), float(pad))
+        buf[:, :, :n] = dy
+    else:
+        buf = np.ascontiguousarray(dy)
+    mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).ravel())
+    V = np.asfortranarray(np.tril(np.asarray(V, dtype=np.float64)))
+    R = np.asfortranarray(np.asarray(R, dtype=np.float64).reshape(d, d))
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
+    if mean.size != n or V.shape != (n, n) or y.size != d:
+        raise ValueError("mean must be [nLin], V [nLin x nLin] and y [n_y]")
+    yhat, S, logw = np.empty((N, d)), np.empty((N, d, d)), np.empty(N)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_generic_weights(d, n, N, _dp(buf), int(dy_layout), int(ldx or 0), _dp(mean), _dp(V), _dp(R), _dp(y), _dp(yhat),
+                                       _dp(S), _dp(logw), int(reps), C.byref(ms)))
+    return yhat, S, logw, ms.value
+
+
+class DeviceMap:
+    """A fixed map of an arbitrary model whose handles are device code: the posterior N(mean, V'V) over the nLin linear states, V
+    lower (the DenseMagMap convention), as a SLAM filter or smoother run with the same DeviceHandles returns it (xl_max, P_max /
+    XLK, PK: from_posterior), and the measurement noise R [n_y x n_y], symmetric positive definite.  Handed to
+    particleFilterLocalization(device_map, None, ...) or LocalizationSession, it localises a run in that map: the RBPF with the map
+    frozen (particleFilter.m:100-161 with xl, P shared by all particles and never updated),
+
+        e_i = y_t' - H_i mean,   S_i = H_i P H_i' + R,   logw_i = -sum log diag chol S_i - |chol(S_i) \\ e_i|^2 / 2 - n_y log(2 pi) / 2
+
+    with H_i = dy(i,:,:) of handles.measModel(xn), called once per step with N_P columns; handles.dynModel draws its own random
+    numbers, as for DeviceHandles.  The layout of every dy is read off its strides (MATLAB-order strides, C-contiguous, or the native
+    view of a native_out handle, consumed in place); handles.dy_layout is not used.  n_y 1 .. 8, nLin 1 .. 1151, n_nonlin 1 .. 8; one
+    GPU.  Not built: backward simulation / particleSmootherLocalization (they need dynModel's transition density; a generic
+    dynModel is a sampler), host closures, sharding, sparse-feature maps."""
+
+    def __init__(self, handles, mean, V, R):
+        if not isinstance(handles, DeviceHandles):
+            raise TypeError("DeviceMap needs a DeviceHandles object")
+        if isinstance(handles, DeviceSparseHandles):
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceMap is built for dense models: a DeviceSparseHandles measModel "
+                                                       "linearises at every particle's own map, and a fixed map has none")
+        self.handles = handles
+        self.mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).ravel())
+        n = self.mean.size
+        self.V = np.asfortranarray(np.tril(np.asarray(V, dtype=np.float64)))
+        R = np.asarray(R, dtype=np.float64)
+        self.R = np.asfortranarray(R.reshape(1, 1) if R.ndim == 0 else R)
+        if self.V.shape != (n, n):
+            raise ValueError("mean must be [nLin] and V [nLin x nLin]")
+        if self.R.ndim != 2 or self.R.shape[0] != self.R.shape[1]:
+            raise ValueError("R must be [n_y x n_y]")
+
+    @property
+    def nLin(self):
+        return self.mean.size
+
+    @property
+    def ny(self):
+        return self.R.shape[0]
+
+    @classmethod
+    def from_posterior(cls, handles, xl, P, R):
+        """From a map posterior (mean xl, covariance P), factored as DenseMagMap.from_posterior factors it."""
+        return cls(handles, xl, _lower_factor(P), R)
+
+    def predict(self, xn, reps=1):
+        """The map's prediction at the states xn [n_nonlin x n_pred] (numpy or a device tensor), through the weight kernel on its
+        own: (yhat [n_pred x n_y] = H mean, cov [n_pred x n_y x n_y] = H P H', without R).  measModel is called once, with n_pred
+        columns."""
+        import torch
+        lib = load_library()
+        if lib.rbpf_device_count() < 1:
+            raise RBPFError(_ffi.RBPF_ERR_NO_DEVICE, "no HIP device: the localisation filter has no CPU fallback")
+        device = torch.device("cuda", torch.cuda.current_device())
+        xn = torch.as_tensor(xn, dtype=torch.float64, device=device)
+        xn = xn.reshape(-1, 1) if xn.dim() == 1 else xn
+        npred, d, n = xn.shape[1], self.ny, self.nLin
+        if self.handles.native_out:
+            dy = self.handles.measModel(xn, torch.zeros((npred, d, (n + 15) // 16 * 16), dtype=torch.float64, device=device)[:, :, :n])
+        else:
+            dy = self.handles.measModel(xn)
+        if dy.dim() == 2 and d == 1:
+            dy = dy.unsqueeze(1)
+        if tuple(dy.shape) != (npred, d, n) or dy.dtype != torch.float64 or not dy.is_cuda:
+            raise ValueError(f"measModel returned {tuple(dy.shape)} {dy.dtype} on {dy.device}, expected a float64 device tensor of "
+                             f"shape {(npred, d, n)}")
+        yhat, S, _, _ = device_map_weights(dy.cpu().numpy(), self.mean, self.V, self.R, np.zeros(d), reps=reps)
+        return yhat, S
+
+
+class _DeviceMapProblem:
+    """The problem arrays of a localisation run in a DeviceMap, sized from the map and the arrays themselves."""
+
+    def __init__(self, mp, odometry, y, x0_nonLin, Q, N_P, dt):
+        y = np.asarray(y, dtype=np.float64)
+        y = y.reshape(-1, 1) if y.ndim == 1 else y
+        self.N_T, self.N_P, self.ny = y.shape[0], int(N_P), mp.ny
+        if y.ndim != 2 or y.shape[1] != mp.ny:
+            raise ValueError(f"y must be [N_T x {mp.ny}]")
+        self.y = np.asfortranarray(y)
+        x0 = np.asarray(x0_nonLin, dtype=np.float64)
+        self.x0 = np.asfortranarray(x0.reshape(-1, 1) if x0.ndim == 1 else x0)
+        self.nNonLin = self.x0.shape[0]
+        if self.x0.shape[1] not in (1, self.N_P):
+            raise ValueError("x0_nonLin must be [n_nonlin] or [n_nonlin x N_P]")
+        odo = np.asarray(odometry, dtype=np.float64)
+        self._odo = odo.reshape(1, -1) if odo.ndim == 1 else odo
+        Qa = np.asarray(Q, dtype=np.float64)
+        Qa = Qa.reshape(1, 1) if Qa.ndim == 0 else Qa
+        self._Q = Qa[:, :, None] if Qa.ndim == 2 else Qa
+        self._dt = np.atleast_1d(np.asarray(dt, dtype=np.float64)).ravel()
+        if self.N_T > 1 and (self._odo.shape[0] < self.N_T - 1 or (self._Q.shape[2] > 1 and self._Q.shape[2] < self.N_T - 1)
+                             or (self._dt.size > 1 and self._dt.size < self.N_T - 1)):
+            raise ValueError("odometry must have >= N_T-1 rows, Q and dt one or >= N_T-1 pages / entries")
+
+
+class _DeviceMapDriver(_DeviceDriver):
+    """Runs the steps of a generic localisation context (rbpf_loc_generic_create) with the handles of a DeviceMap: the pair
+    rbpf_loc_generic_ancestors_device / rbpf_loc_generic_step_device, the layout of every dy read off its strides."""
+
+    def __init__(self, lib, ctx, mp, prob):                       # (the initial states are the context's; handles.dy_layout is not used)
+        self._setup(lib, ctx, mp.handles, (prob.nNonLin, mp.nLin, mp.ny, prob.N_P, prob.N_T), lib.rbpf_loc_generic_layout, prob)
+        self.torch.cuda.current_stream(self.device).synchronize()      # the constants, before the library's stream reads them
+
+    def _step(self, t):
+        torch, lib = self.torch, self.lib
+        with torch.cuda.stream(self.stream):
+            ai, anc = C.c_void_p(), C.c_void_p()
+            check(lib.rbpf_loc_generic_ancestors_device(self.ctx, C.byref(ai), C.byref(anc)))
+            xn_cm = self._view(torch, anc, (self.N, self.nN), self.device)    # [n_nonlin x N_P] column-major; t = 0: the initial states
+            if t > 0:
+                xn_cm = self._dyn(t - 1, xn_cm.t()).t().contiguous()
+            out = self._native_out()
+            dy, layout = self._layout_of(self._meas(xn_cm.t(), out), out)
+            self._keep = (xn_cm, dy)                                      # read in stream order by the step just enqueued
+            check(lib.rbpf_loc_generic_step_device(self.ctx, C.c_void_p(xn_cm.data_ptr()), C.c_void_p(dy.data_ptr()), layout))
+
+
+def _device_map(dynModel, measModel):
+    """The DeviceMap given in place of the handle pair (as dynModel, measModel None or the same object), or None."""
+    if not isinstance(dynModel, DeviceMap) and not isinstance(measModel, DeviceMap):
+        return None
+    if not isinstance(dynModel, DeviceMap) or (measModel is not None and measModel is not dynModel):
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "a DeviceMap replaces the handle pair: pass the object as dynModel and None "
+                                                   "(or the same object) as measModel")
+    return dynModel
+
+
+_NO_BACKWARD_IN_DEVICE_MAP = ("backward simulation needs the transition density of dynModel: the dynModel of a DeviceMap is a "
+                              "sampler that draws its own random numbers (its handles carry no density)")
+
+
+def _device_map_create(lib, mp, prob, rng, opt):
+    """rbpf_loc_generic_create -> (ctx, what must stay alive with it)."""
+    if isinstance(rng, ReplayRNG):                                # the handles draw their own normals: Z is not read
+        rng = ReplayRNG(rng.U, np.zeros(rng.U.shape + (1,)))
+    blk, keep = _rng_block(rng, prob.N_P, prob.N_T, 1, 1)
+    ctx = C.c_void_p()
+    check(lib.rbpf_loc_generic_create(prob.nNonLin, mp.ny, mp.nLin, _dp(mp.mean), _dp(mp.V), _dp(mp.R), prob.N_P, prob.N_T, _dp(prob.y),
+                                      _dp(prob.x0), prob.x0.shape[1], C.byref(blk), C.byref(opt), C.byref(ctx)))
+    return ctx, (blk, keep)
+
+
+def _loc_out(N, T, Td, extras, hist=True, trace=True, nN=7):
     o = _ffi.rbpf_loc_out()
-    b = dict(traj_max=np.full((7, T), np.nan, order="F"), traj_mean=np.full((7, T), np.nan, order="F"))
+    b = dict(traj_max=np.full((nN, T), np.nan, order="F"), traj_mean=np.full((nN, T), np.nan, order="F"))
     if extras:
-        b.update(final_xn=np.empty((7, N), order="F"), log_sum_w=np.empty(Td))
+        b.update(final_xn=np.empty((nN, N), order="F"), log_sum_w=np.empty(Td))
         if trace:
             b.update(trace_logw=np.empty((N, Td), order="F"), trace_w=np.empty((N, Td), order="F"))
         if hist:
-            b.update(trace_ai=np.zeros((N, Td), dtype=np.int32, order="F"), xn_traj=np.empty((7, N, Td), order="F"))
+            b.update(trace_ai=np.zeros((N, Td), dtype=np.int32, order="F"), xn_traj=np.empty((nN, N, Td), order="F"))
     for k, v in b.items():
         setattr(o, k, _ip(v) if v.dtype == np.int32 else _dp(v))
     return o, b
@@ -1836,8 +2028,13 @@ def particleFilterLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R
     """Mirror of examples/mag-localization-mapping/particleFilterLocalization.m:1-2 -> (traj_max, traj_mean[, extras]).
     dynModel / measModel are the handles of a DenseMagMap; R is accepted and not used (:19).  makePlots(xn, traj_max, yhattraj,
     xn_traj, traj_mean) is called after every step (:129-131).  A step whose weights sum to <= 1e-12 raises a RuntimeWarning
-    with the reference's text (:113-115) and the run carries on."""
+    with the reference's text (:113-115) and the run carries on.
+    A DeviceMap as dynModel (measModel None) localises in the fixed map of an arbitrary device-code model (see DeviceMap): the same
+    outputs with n_nonlin rows in place of 7, yhattraj [n_y x N_T]; R is accepted and not used there either (the map's R counts)."""
     import warnings
+    dmap = _device_map(dynModel, measModel)
+    if dmap is not None:
+        return _device_map_localization(dmap, odometry, y, x0_nonLin, Q, N_P, dt, makePlots, rng, extras, n_devices, lazy_depth)
     mp = _recognise_map(dynModel, measModel)
     lib = load_library()
     prob = _LocProblem(odometry, y, x0_nonLin, Q, N_P, dt)
@@ -1889,6 +2086,54 @@ def particleFilterLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R
     return b["traj_max"], b["traj_mean"]
 
 
+def _device_map_localization(mp, odometry, y, x0_nonLin, Q, N_P, dt, makePlots, rng, extras, n_devices, lazy_depth):
+    """particleFilterLocalization in a DeviceMap: the binding drives a generic localisation context with the map's handles."""
+    import warnings
+    lib = load_library()
+    prob = _DeviceMapProblem(mp, odometry, y, x0_nonLin, Q, N_P, dt)
+    N, T, nN = prob.N_P, prob.N_T, prob.nNonLin
+    if lib.rbpf_device_count() < 1:
+        raise RBPFError(_ffi.RBPF_ERR_NO_DEVICE, "no HIP device: the localisation filter has no CPU fallback")
+    opt = _ffi.rbpf_options(keep_history=1, trace=1 if extras else 0, n_devices=int(n_devices), lazy_depth=int(lazy_depth))
+    hook_error = []
+    if makePlots is not None:
+        def on_step(view_p, _user):
+            try:
+                v = view_p.contents
+                t = int(v.t)
+                o, b = _loc_out(N, T, t + 1, True, trace=False, nN=nN)
+                check(lib.rbpf_loc_finish(C.c_void_p(v.ctx), C.byref(o)))
+                xn_traj = np.zeros((nN, N, T))
+                xn_traj[:, :, :t + 1] = b["xn_traj"]
+                makePlots(b["final_xn"], b["traj_max"], np.full((prob.ny, T), np.nan), xn_traj, b["traj_mean"])
+                return 0
+            except Exception as exc:                                                      # noqa: BLE001
+                hook_error.append(exc)
+                return 1
+        hook = _ffi.ON_STEP_FN(on_step)
+        opt.on_step = hook
+    ctx, _keep = _device_map_create(lib, mp, prob, rng, opt)      # (n_devices / lazy_depth: refused here, before anything is computed)
+    try:
+        try:
+            driver = _DeviceMapDriver(lib, ctx, mp, prob)          # (alive until the context is gone: it owns what the last step reads)
+            driver.advance(T)
+        except RBPFError as exc:
+            if exc.status == _ffi.RBPF_ERR_CALLBACK and hook_error:
+                raise hook_error[0] from exc
+            raise
+        o, b = _loc_out(N, T, T, extras, nN=nN)
+        check(lib.rbpf_loc_finish(ctx, C.byref(o)))
+    finally:
+        lib.rbpf_destroy(ctx)
+    if o.first_degenerate_step >= 0:
+        warnings.warn(f"Weights filter close to zero at t={o.first_degenerate_step + 1} !!!", RuntimeWarning, stacklevel=3)
+    if extras:
+        ex = dict(logw=b["trace_logw"].T.copy(), w=b["trace_w"].T.copy(), ai=b["trace_ai"].T.copy(), xn=b["final_xn"],
+                  xn_traj=b["xn_traj"], log_sum_w=b["log_sum_w"], first_degenerate_step=int(o.first_degenerate_step))
+        return b["traj_max"], b["traj_mean"], ex
+    return b["traj_max"], b["traj_mean"]
+
+
 def loc_workspace_bytes(map_struct, prob_struct, opt=None):
     """rbpf_loc_workspace_bytes (no device access)."""
     lib = load_library()
@@ -1904,16 +2149,31 @@ class LocalizationSession:
     def __init__(self, loc_map, odometry, y, x0_nonLin, Q, N_P, dt, rng=None, keep_history=False, trace=False):
         self.lib = load_library()
         self.map = loc_map
-        self.prob = _LocProblem(odometry, y, x0_nonLin, Q, N_P, dt)
-        self.mstruct = loc_map._loc_map(self.prob.N_P)
-        self.blk, self._rng = _rng_block(rng, self.prob.N_P, self.prob.N_T, 6, 1)
         self.opt = _ffi.rbpf_options(keep_history=1 if keep_history else 0, trace=1 if trace else 0)
         self.hist = bool(keep_history)
         self.ctx = C.c_void_p()
+        self.driver = None
+        if isinstance(loc_map, DeviceMap):                        # a generic map: the binding drives the context with the map's handles
+            self.prob = _DeviceMapProblem(loc_map, odometry, y, x0_nonLin, Q, N_P, dt)
+            self.nN = self.prob.nNonLin
+            self.ctx, self._rng = _device_map_create(self.lib, loc_map, self.prob, rng, self.opt)
+            try:
+                self.driver = _DeviceMapDriver(self.lib, self.ctx, loc_map, self.prob)
+            except Exception:
+                self.close()
+                raise
+            return
+        self.nN = 7
+        self.prob = _LocProblem(odometry, y, x0_nonLin, Q, N_P, dt)
+        self.mstruct = loc_map._loc_map(self.prob.N_P)
+        self.blk, self._rng = _rng_block(rng, self.prob.N_P, self.prob.N_T, 6, 1)
         check(self.lib.rbpf_loc_create(C.byref(self.mstruct), C.byref(self.prob.c), C.byref(self.blk), C.byref(self.opt),
                                        C.byref(self.ctx)))
 
     def advance(self, n_steps):
+        if self.driver is not None:
+            self.driver.advance(n_steps)
+            return
         check(self.lib.rbpf_loc_advance(self.ctx, int(n_steps)))
 
     def sync(self):
@@ -1925,14 +2185,15 @@ class LocalizationSession:
         return t.value
 
     def finish(self, extras=False):
-        o, b = _loc_out(self.prob.N_P, self.prob.N_T, self.tell(), extras, self.hist, bool(self.opt.trace))
+        o, b = _loc_out(self.prob.N_P, self.prob.N_T, self.tell(), extras, self.hist, bool(self.opt.trace), nN=self.nN)
         check(self.lib.rbpf_loc_finish(self.ctx, C.byref(o)))
         b["first_degenerate_step"] = int(o.first_degenerate_step)
         return b
 
     def history(self):
-        """rbpf_loc_history: the forward particles as propagated, NOT traced back, [7 x N_P x T_done] (needs keep_history)."""
-        X = np.empty((7, self.prob.N_P, self.tell()), order="F")
+        """rbpf_loc_history: the forward particles as propagated, NOT traced back, [7 x N_P x T_done] (needs keep_history;
+        n_nonlin rows in a DeviceMap)."""
+        X = np.empty((self.nN, self.prob.N_P, self.tell()), order="F")
         check(self.lib.rbpf_loc_history(self.ctx, _dp(X)))
         return X
 
@@ -1940,7 +2201,9 @@ class LocalizationSession:
         """rbpf_loc_backward_simulate: n_traj trajectories drawn backwards through the stored particles (keep_history and trace,
         every step done).  rng: None / PhiloxRNG(seed): the device generator (PhiloxRNG.backward_uniforms(n_traj, N_T) are its
         draws); an array u [N_T x n_traj] of uniforms in (0, 1]: replay.  Returns a dict of the arrays named in `want`:
-        xs_traj [7 x n_traj x N_T], index [n_traj x N_T] (0-based), traj_smooth_mean [7 x N_T]."""
+        xs_traj [7 x n_traj x N_T], index [n_traj x N_T] (0-based), traj_smooth_mean [7 x N_T].  Not available in a DeviceMap."""
+        if self.driver is not None:
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, _NO_BACKWARD_IN_DEVICE_MAP)
         M, T = int(n_traj), self.prob.N_T
         seed, u = 0, None
         if rng is None:
@@ -2016,6 +2279,8 @@ def particleSmootherLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q,
     backward draws, on disjoint counters) or ReplayRNG(U, Z, Uback=u) with the backward uniforms u [N_T x N_S].
     extras: the filter's outputs (traj_max, traj_mean, first_degenerate_step, ...) and the drawn `index` [N_S x N_T]."""
     import warnings
+    if _device_map(dynModel, measModel) is not None:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleSmootherLocalization: " + _NO_BACKWARD_IN_DEVICE_MAP)
     mp = _recognise_map(dynModel, measModel)
     if isinstance(rng, ReplayRNG):
         if rng.Uback is None:
