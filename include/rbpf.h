@@ -874,6 +874,8 @@ int rbpf_loc_backward_step(int32_t N, int32_t M, const double* xn, const double*
  *        [n_nonlin x x0_cols], x0_cols 1 or N_P.  rbpf_loc_finish, rbpf_loc_history, rbpf_filter_tell, rbpf_sync, rbpf_stream_get and
  *        rbpf_destroy work on the context; rbpf_loc_advance is RBPF_ERR_STATE (the handles are the caller's) and
  *        rbpf_loc_backward_simulate RBPF_ERR_UNSUPPORTED (it needs dynModel's transition density; a generic dynModel is a sampler).
+ *        A caller that can state the density as Gaussian in a wrapped difference has the rbpf_loc_generic_backward_* entry points
+ *        below; without one the refusal is the open end.
  *   rbpf_loc_generic_layout   ldx >= n_lin, the row stride of dy layout 1.
  *   rbpf_loc_generic_ancestors_device   before every step, in stream order on rbpf_stream_get(ctx): *xn_anc_dev
  *        [n_nonlin x N_P] column-major = the states of the resampled ancestors, xn_{t-1}(:, ai(i)), and *ai_dev [N_P] the 0-based
@@ -897,6 +899,44 @@ int rbpf_loc_generic_step_device(rbpf_ctx* ctx, const double* xn_new_dev, const 
 int rbpf_loc_generic_weights(int32_t n_y, int32_t n_lin, int32_t n_p, const double* dy, int32_t dy_layout, int32_t ldx,
                              const double* mean, const double* V, const double* R, const double* y, double* yhat, double* S,
                              double* logw, int32_t reps, double* ms);
+
+/* ---- backward simulation in the fixed map of a generic device-code model: Gaussian transitions ----
+ * The recursion of rbpf_loc_backward_simulate on a context of rbpf_loc_generic_create (keep_history = 1, trace = 1, every step
+ * done, no degenerate forward step), for a dynModel that is a drift plus Gaussian noise on n_res of the n_nonlin rows:
+ *     r = wrap(x'(rows) - mu_i),   z = L \ r  (L L' = cov, lower),   logp = -z'z / 2        (constants omitted, particleSmoother.m:181-182)
+ * rows [n_res] 0-based, distinct, each < n_nonlin, n_res 1 .. 8; rows not listed take no part in the density.  Bit k of angle_mask
+ * marks residual row k (state row rows[k]) as an angle: wrap(r) = r - 2 pi rint(r / (2 pi)), 2 pi the fp64 constant, applied before L.
+ * mu_i = mean(X(:, i, t)) is the caller's device code, so the pass is driven step by step, t = N_T-1 .. 0:
+ *   rbpf_loc_generic_backward_begin   takes the workspace from the context's pool; u [N_T x n_traj] (row t = step t) or NULL: Philox
+ *        keyed by `seed` on the counters of rbpf_loc_backward_simulate.  RBPF_ERR_STATE: a pass is open already, steps missing, no
+ *        keep_history / trace, a degenerate forward step.
+ *   rbpf_loc_generic_backward_particles_device   *t = the step the next step call processes, *xn_dev = its stored particles
+ *        [n_nonlin][N_P] (rows contiguous over the particles: a C-contiguous (n_nonlin, N_P) array), library memory, read only.
+ *   rbpf_loc_generic_backward_step_device   mu_dev [n_res][N_P] on rbpf_stream_get(ctx), cov [n_res x n_res] on the host (symmetric;
+ *        the lower triangle is read); both may be NULL at t = N_T-1, whose draw reads log w only.  With odometry row t, dt(t),
+ *        Q(:,:,t): the arguments dynModel got when it made step t+1.  A cov that is not positive definite: RBPF_ERR_CHOL_FAILED, the
+ *        step named, before anything is launched.  Enqueues prologue, all-pairs pass, locate and mean without waiting.
+ *   rbpf_loc_generic_backward_finish   synchronises, copies out (NULL outputs are skipped) xs_traj [n_nonlin x n_traj x N_T],
+ *        index [n_traj x N_T] 0-based, traj_smooth_mean [n_nonlin x N_T] (plain means of all rows) and returns the workspace.  With
+ *        steps left undone it returns the workspace all the same: RBPF_OK when every output is NULL (the way out after a failed
+ *        handle), RBPF_ERR_STATE otherwise.  rbpf_destroy releases an open pass too.
+ *   rbpf_loc_generic_backward_workspace_bytes   what begin takes from the pool (no device access).
+ *   rbpf_loc_generic_backward_step   one step on host arrays, the kernel-level probe: mu [n_res][N], w [N], xs_next [n_nonlin x M]
+ *        column-major, cov [n_res x n_res], u [M] -> index [M]; logp [N x M] column-major (may be NULL) without log(w).  reps >= 1
+ *        repeats the step's launches; *ms (may be NULL) = median time of one step by device events.
+ * RBPF_ERR_STATE out of order (step without begin, begin twice, a step after the last); NULL arguments and bad sizes are
+ * RBPF_ERR_INVALID_ARG before any device is touched; without a device RBPF_ERR_NO_DEVICE; the context stays usable after any
+ * refusal.  rbpf_loc_backward_simulate keeps refusing a generic context.  Not built: densities that are not Gaussian in a wrapped
+ * difference, n_res > 8, sharding.                                                                                              */
+int rbpf_loc_generic_backward_begin(rbpf_ctx* ctx, int32_t n_traj, const double* u, uint64_t seed, int32_t n_res, const int32_t* rows,
+                                    uint32_t angle_mask);
+int rbpf_loc_generic_backward_particles_device(rbpf_ctx* ctx, int32_t* t, const double** xn_dev);
+int rbpf_loc_generic_backward_step_device(rbpf_ctx* ctx, const double* mu_dev, const double* cov);
+int rbpf_loc_generic_backward_finish(rbpf_ctx* ctx, double* xs_traj, int32_t* index, double* traj_smooth_mean);
+int rbpf_loc_generic_backward_workspace_bytes(int32_t n_nonlin, int32_t n_res, int32_t N_P, int32_t N_T, int32_t n_traj, size_t* bytes);
+int rbpf_loc_generic_backward_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_res, const int32_t* rows, uint32_t angle_mask,
+                                   const double* mu, const double* w, const double* xs_next, const double* cov, const double* u,
+                                   int32_t* index, double* logp, int32_t reps, double* ms);
 
 /* ---- the EKF comparison baseline of examples/slam-dense-mag, batched over data sets ---------------
  * ekf_dense.m:41-102 with the closures measModel_ekf / dynModel_ekf of run_dense3D_magfield.m:281-299,310-316, on the device:

@@ -166,6 +166,8 @@ EXPORTS = [
     "rbpf_loc_backward_simulate", "rbpf_loc_history", "rbpf_loc_backward_workspace_bytes", "rbpf_loc_backward_step",
     "rbpf_loc_generic_create", "rbpf_loc_generic_layout", "rbpf_loc_generic_ancestors_device", "rbpf_loc_generic_step_device",
     "rbpf_loc_generic_weights",
+    "rbpf_loc_generic_backward_begin", "rbpf_loc_generic_backward_particles_device", "rbpf_loc_generic_backward_step_device",
+    "rbpf_loc_generic_backward_finish", "rbpf_loc_generic_backward_workspace_bytes", "rbpf_loc_generic_backward_step",
     "rbpf_ekf_dense", "rbpf_ekf_workspace_bytes",
 ]
 
@@ -307,6 +309,13 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_loc_generic_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.rbpf_loc_generic_weights.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p,
                                              c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_generic_backward_begin.argtypes = [C.c_void_p, C.c_int32, c_double_p, C.c_uint64, C.c_int32, c_int32_p, C.c_uint32]
+    lib.rbpf_loc_generic_backward_particles_device.argtypes = [C.c_void_p, c_int32_p, C.POINTER(C.c_void_p)]
+    lib.rbpf_loc_generic_backward_step_device.argtypes = [C.c_void_p, C.c_void_p, c_double_p]
+    lib.rbpf_loc_generic_backward_finish.argtypes = [C.c_void_p, c_double_p, c_int32_p, c_double_p]
+    lib.rbpf_loc_generic_backward_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_generic_backward_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, c_double_p, c_double_p,
+                                                   c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, C.c_int32, c_double_p]
     lib.rbpf_ekf_dense.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(rbpf_ekf_out)]
     lib.rbpf_ekf_workspace_bytes.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(C.c_size_t)]
     _lib = lib

@@ -1,0 +1,538 @@
+// Backward-simulation smoother in the fixed map of a generic device-code model (forward filter, backward simulation: Godsill,
+// Doucet & West 2004), for a dynModel that is a drift plus Gaussian noise on some rows of the state:
+//     x'[rows] = mean(x) + L z,   L L' = cov,   z ~ N(0, I)
+// The recursion is that of rbpf_loc_smooth.hip on the stored particles X [T][n_nonlin][N] and weights w [T][N] of a generic
+// localisation context (keep_history = 1, trace = 1):
+//     b[T-1][j] = sample(w[T-1], u[T-1][j]);   t = T-2 .. 0:  l_i = log w[t][i] + logp(xs[t+1][j] | X[t][:, i]),  b[t][j] = sample(p, u[t][j])
+// with the density, constants omitted (particleSmoother.m:181-182),
+//     r = wrap(x'[rows] - mu_i),   z = L \ r = W r,   logp = -z'z / 2,        wrap(r) = r - 2 pi rint(r / (2 pi)) on the angle rows
+// mu_i = mean(X[t][:, i]) comes from the caller's device code, one call per step with N columns: the pass is driven step by step
+// (begin / particles_device / step_device / finish), as the forward filter of such a context is.  W = inv(L) is lower triangular,
+// inverted on the host in fp64, and travels in the kernel arguments (n_res (n_res + 1) / 2 values, uniform: SGPRs).
+//
+// Kernels of one step t (all in stream order), siblings of the bs_* kernels of rbpf_loc_smooth.hip:
+//   gs_prologue_kernel        Xhat[t] = (mu rows .., log w_i): n_res + 1 doubles per particle, SoA, shared by all M trajectories.
+//   gs_pass_kernel<NR, ANG>   all pairs.  Grid = (trajectory blocks of 256) x (particle chunks of C); a lane owns one trajectory,
+//                             keeps its selected rows in registers and a running (max, sum) pair; the particles come in tiles of 256
+//                             through LDS as [particle][NR + 1] and are read as broadcasts.  No cross-lane operation.  The partial
+//                             sums of z_k^2 only lower l, so after the first NR / 2 rows of W a pair more than 746 below the
+//                             running max skips the rest: its exp is exactly 0, wherever the test sits.
+//   gs_locate_kernel<NR, ANG> per j: merge the chunk partials, find the chunk that holds u * total, walk it with the SAME terms
+//                             (gs_term, explicit fma throughout: no contraction is left to the compiler), gather all n_nonlin rows.
+//   gs_mean_kernel            traj_smooth_mean[:, t] = plain means over j of all n_nonlin rows.
+//   gs_logp_kernel<NR, ANG>   the probe's second output.
+//
+// SUMMATION ORDER: that of rbpf_loc_smooth.hip's header, statement by statement -- chunk size from (N, M) only, ascending i inside
+// a chunk, chunk partials merged in ascending c, the walk and its carry-over, the clamped-draw counter, w_i = 0 never selected.
+// PHILOX COUNTERS: u[t][j] = first uniform of philox_uniform2(seed, slot = j, step = t, lane = 0x42530000, iter = 0), as there.
+#include "../../include/rbpf.h"
+#include "rbpf_internal.hpp"
+#include "rbpf_device.hpp"
+#include "rbpf_ctx.hpp"
+#include "rbpf_loc_state.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace rbpf {
+
+constexpr int kGsTile = 256;               // particles per LDS tile = threads per workgroup
+constexpr int kGsMaxChunk = 2048;          // largest chunk (particles)
+constexpr int kGsMaxRes = 8, kGsMaxNonlin = 8;
+constexpr uint32_t kGsPhiloxLane = 0x42530000u;
+constexpr double kGsSkip = 746.0;          // exp(x) == 0 for x < -745.14
+constexpr double kGsTwoPi = 6.283185307179586476925286766559;
+
+// chunk of the all-pairs pass: enough (trajectory block) x (chunk) workgroups to give every CU four, in whole tiles
+static int gs_chunk_size(int N, int M) {
+  const int bx = (M + kGsTile - 1) / kGsTile;
+  const int want = std::max(1, (1024 + bx - 1) / bx);
+  int C = ((N + want - 1) / want + kGsTile - 1) / kGsTile * kGsTile;
+  return std::min(std::max(C, kGsTile), kGsMaxChunk);
+}
+
+struct GsW { double w[kGsMaxRes * (kGsMaxRes + 1) / 2]; };   // W = inv(L), lower: W(k, c) at w[k (k + 1) / 2 + c], c <= k
+
+struct GsArgs {
+  int N, M, C, nchunks;
+  int nN;                          // rows of a state
+  int first;                       // 1: the draw of step T-1, l_i = log w_i
+  unsigned angle_mask;             // bit k: residual row k is an angle
+  int rows[kGsMaxRes];             // the state rows that carry noise
+  const double* Xhat;              // [NR + 1][N]
+  const double* X;                 // [nN][N] particles of this step (gather)
+  const double* xs_next;           // [M][nN]
+  const double* u;                 // [M]
+  double* part_m; double* part_s;  // [nchunks][M]
+  int* index;                      // [M]
+  double* xs;                      // [M][nN] or null
+  int* clamped;                    // device counter
+  GsW W;
+};
+
+__global__ void gs_prologue_kernel(int N, int NR, const double* __restrict__ mu, const double* __restrict__ w, double* __restrict__ Xhat) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  for (int k = 0; k < NR; ++k) Xhat[(size_t)k * N + i] = mu ? mu[(size_t)k * N + i] : 0.0;
+  const double wi = w[i];
+  Xhat[(size_t)NR * N + i] = wi > 0.0 ? log(wi) : -INFINITY;
+}
+
+// l <- l - z'z / 2 of one pair; h: the particle's NR + 1 doubles (predicted rows, log w), x: the trajectory's selected rows.
+// false: after NR / 2 rows the pair already lies below `bound` (l is then not final).  Every product-sum is an explicit fma.
+template <int NR, bool ANG>
+__device__ __forceinline__ bool gs_term(const GsW& W, unsigned amask, const double* h, const double (&x)[NR], double bound, double& l) {
+  constexpr int KT = NR / 2;
+  double r[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    double d = x[k] - h[k];
+    if (ANG && ((amask >> k) & 1u)) d = fma(-kGsTwoPi, rint(d / kGsTwoPi), d);
+    r[k] = d;
+  }
+  double q = 0.0;
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    double z = W.w[k * (k + 1) / 2] * r[0];
+#pragma unroll
+    for (int c = 1; c <= k; ++c) z = fma(W.w[k * (k + 1) / 2 + c], r[c], z);
+    q = fma(z, z, q);
+    if (k + 1 == KT && fma(-0.5, q, l) < bound) return false;
+  }
+  l = fma(-0.5, q, l);
+  return true;
+}
+
+template <int NR, bool ANG>
+__global__ __launch_bounds__(kGsTile) void gs_pass_kernel(const GsArgs a) {
+  constexpr int S = NR + 1;
+  __shared__ double tile[kGsTile * S];     // [particle][NR + 1]
+  const int tid = threadIdx.x;
+  const int j = blockIdx.x * kGsTile + tid;
+  const int jl = min(j, a.M - 1);          // lanes past the end recompute the last trajectory; nothing of theirs is stored
+  const int c = blockIdx.y;
+  const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
+  double x[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) x[k] = a.first ? 0.0 : a.xs_next[(size_t)jl * a.nN + a.rows[k]];
+  double m = -INFINITY, s = 0.0;
+  for (int base = i0; base < i1; base += kGsTile) {
+    const int cnt = min(kGsTile, i1 - base);
+    __syncthreads();
+    if (tid < cnt) {
+#pragma unroll
+      for (int r = 0; r < S; ++r) tile[tid * S + r] = a.Xhat[(size_t)r * a.N + base + tid];
+    }
+    __syncthreads();
+    for (int k = 0; k < cnt; ++k) {
+      const double* h = tile + k * S;
+      double l = h[NR];
+      if (!a.first) {
+        if (!gs_term<NR, ANG>(a.W, a.angle_mask, h, x, m - kGsSkip, l)) continue;
+      }
+      if (l == -INFINITY) continue;
+      const double d = l - m;
+      const double ex = exp(-fabs(d));
+      if (d > 0.0) { s = s * ex + 1.0; m = l; }
+      else s += ex;
+    }
+  }
+  if (j < a.M) {
+    a.part_m[(size_t)c * a.M + j] = m;
+    a.part_s[(size_t)c * a.M + j] = s;
+  }
+}
+
+template <int NR, bool ANG>
+__global__ void gs_locate_kernel(const GsArgs a) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.M) return;
+  double x[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) x[k] = a.first ? 0.0 : a.xs_next[(size_t)j * a.nN + a.rows[k]];
+  double Mx = -INFINITY;
+  for (int c = 0; c < a.nchunks; ++c) Mx = fmax(Mx, a.part_m[(size_t)c * a.M + j]);
+  int idx = -1;
+  if (Mx > -INFINITY) {
+    double total = 0.0;
+    for (int c = 0; c < a.nchunks; ++c) {
+      const double sc = a.part_s[(size_t)c * a.M + j];
+      if (sc > 0.0) total += sc * exp(a.part_m[(size_t)c * a.M + j] - Mx);
+    }
+    const double target = a.u[j] * total;
+    double acc = 0.0;
+    int c0 = 0;
+    for (; c0 < a.nchunks; ++c0) {
+      const double sc = a.part_s[(size_t)c0 * a.M + j];
+      if (!(sc > 0.0)) continue;
+      const double nxt = acc + sc * exp(a.part_m[(size_t)c0 * a.M + j] - Mx);
+      if (nxt >= target) break;
+      acc = nxt;
+    }
+    int last_nz = -1;
+    for (int c = c0; c < a.nchunks && idx < 0; ++c) {
+      if (!(a.part_s[(size_t)c * a.M + j] > 0.0)) continue;
+      const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
+      for (int i = i0; i < i1; ++i) {
+        double h[NR + 1];
+        h[NR] = a.Xhat[(size_t)NR * a.N + i];
+        if (h[NR] == -INFINITY) continue;
+        double l = h[NR];
+        if (!a.first) {
+#pragma unroll
+          for (int r = 0; r < NR; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
+          if (!gs_term<NR, ANG>(a.W, a.angle_mask, h, x, Mx - kGsSkip, l)) continue;
+        }
+        const double term = exp(l - Mx);
+        if (!(term > 0.0)) continue;
+        last_nz = i;
+        acc += term;
+        if (acc >= target) { idx = i; break; }
+      }
+    }
+    if (idx < 0) idx = last_nz;
+    if (idx < 0 || !(acc >= target)) atomicAdd(a.clamped, 1);
+  } else {
+    atomicAdd(a.clamped, 1);
+  }
+  if (idx < 0) {                                   // no non-zero term at all: the last particle with a non-zero weight
+    for (int i = a.N - 1; i >= 0 && idx < 0; --i)
+      if (a.Xhat[(size_t)NR * a.N + i] > -INFINITY) idx = i;
+    if (idx < 0) idx = a.N - 1;
+  }
+  a.index[j] = idx;
+  if (a.xs) {
+    for (int r = 0; r < a.nN; ++r) a.xs[(size_t)j * a.nN + r] = a.X[(size_t)r * a.N + idx];
+  }
+}
+
+// mean over the M trajectories of xs [M][nN] -> out [nN]: one workgroup, strided partial sums, then a fixed tree
+__global__ __launch_bounds__(256) void gs_mean_kernel(int M, int nN, const double* __restrict__ xs, double* __restrict__ out) {
+  __shared__ double red[kGsMaxNonlin][256];
+  const int tid = threadIdx.x;
+  double acc[kGsMaxNonlin];
+#pragma unroll
+  for (int r = 0; r < kGsMaxNonlin; ++r) acc[r] = 0.0;
+  for (int j = tid; j < M; j += 256)
+#pragma unroll
+    for (int r = 0; r < kGsMaxNonlin; ++r)
+      if (r < nN) acc[r] += xs[(size_t)j * nN + r];
+#pragma unroll
+  for (int r = 0; r < kGsMaxNonlin; ++r) red[r][tid] = acc[r];
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off)
+#pragma unroll
+      for (int r = 0; r < kGsMaxNonlin; ++r) red[r][tid] += red[r][tid + off];
+    __syncthreads();
+  }
+  if (tid < nN) out[tid] = red[tid][0] / (double)M;
+}
+
+// logp of every pair, without log w: out [N x M] column-major (the probe's second output)
+template <int NR, bool ANG>
+__global__ void gs_logp_kernel(const GsArgs a, double* __restrict__ out) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (size_t)a.N * a.M) return;
+  const int i = (int)(q % a.N), j = (int)(q / a.N);
+  double h[NR + 1], x[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
+  h[NR] = 0.0;
+#pragma unroll
+  for (int k = 0; k < NR; ++k) x[k] = a.xs_next[(size_t)j * a.nN + a.rows[k]];
+  double l = 0.0;
+  gs_term<NR, ANG>(a.W, a.angle_mask, h, x, -INFINITY, l);
+  out[q] = l;
+}
+
+__global__ void gs_philox_kernel(unsigned long long seed, int T, int M, double* __restrict__ u) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (size_t)T * M) return;
+  double u0, u1;
+  philox_uniform2(seed, (uint32_t)(q % M), (uint32_t)(q / M), kGsPhiloxLane, 0u, u0, u1);
+  u[q] = u0;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+template <int NR, bool ANG>
+static hipError_t gs_launch_nr(const GsArgs& a, double* logp, hipStream_t s) {
+  if (logp) {
+    const size_t cnt = (size_t)a.N * a.M;
+    hipLaunchKernelGGL((gs_logp_kernel<NR, ANG>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, a, logp);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL((gs_pass_kernel<NR, ANG>), dim3((a.M + kGsTile - 1) / kGsTile, a.nchunks), dim3(kGsTile), 0, s, a);
+  hipLaunchKernelGGL((gs_locate_kernel<NR, ANG>), dim3((a.M + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+template <int NR>
+static hipError_t gs_launch_ang(const GsArgs& a, double* logp, hipStream_t s) {
+  return a.angle_mask ? gs_launch_nr<NR, true>(a, logp, s) : gs_launch_nr<NR, false>(a, logp, s);
+}
+
+// all-pairs pass + locate of one step (logp == null), or the logp kernel, in stream order
+static hipError_t gs_launch(int n_res, const GsArgs& a, double* logp, hipStream_t s) {
+  switch (n_res) {
+    case 1: return gs_launch_ang<1>(a, logp, s);
+    case 2: return gs_launch_ang<2>(a, logp, s);
+    case 3: return gs_launch_ang<3>(a, logp, s);
+    case 4: return gs_launch_ang<4>(a, logp, s);
+    case 5: return gs_launch_ang<5>(a, logp, s);
+    case 6: return gs_launch_ang<6>(a, logp, s);
+    case 7: return gs_launch_ang<7>(a, logp, s);
+    case 8: return gs_launch_ang<8>(a, logp, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// prologue + pass + locate of one step
+static hipError_t gs_launch_step(int n_res, const GsArgs& a, const double* mu, const double* w, double* Xhat, hipStream_t s) {
+  hipLaunchKernelGGL(gs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, n_res, mu, w, Xhat);
+  return gs_launch(n_res, a, nullptr, s);
+}
+
+static int gs_validate_rows(int n_nonlin, int n_res, const int32_t* rows, uint32_t angle_mask) {
+  if (n_nonlin < 1 || n_nonlin > kGsMaxNonlin) { set_error("n_nonlin must be in 1 .. 8"); return RBPF_ERR_INVALID_ARG; }
+  if (n_res < 1 || n_res > kGsMaxRes) { set_error("n_res (the rows that carry noise) must be in 1 .. 8"); return RBPF_ERR_INVALID_ARG; }
+  if (!rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  unsigned seen = 0;
+  for (int k = 0; k < n_res; ++k) {
+    if (rows[k] < 0 || rows[k] >= n_nonlin) { set_error("rows[" + std::to_string(k) + "] = " + std::to_string(rows[k]) + " is no row of the n_nonlin = " + std::to_string(n_nonlin) + " state"); return RBPF_ERR_INVALID_ARG; }
+    if (seen & (1u << rows[k])) { set_error("rows names row " + std::to_string(rows[k]) + " twice"); return RBPF_ERR_INVALID_ARG; }
+    seen |= 1u << rows[k];
+  }
+  if (angle_mask >> n_res) { set_error("angle_mask has a bit at or above n_res: an angle row must be one of rows"); return RBPF_ERR_INVALID_ARG; }
+  return RBPF_OK;
+}
+
+// cov [n x n] column-major (lower triangle read) -> W = inv(chol(cov, 'lower')), packed by rows
+static int gs_factor(const double* cov, int n, GsW& W, const std::string& where) {
+  double L[kGsMaxRes * kGsMaxRes];
+  for (int q = 0; q < n * n; ++q)
+    if (!std::isfinite(cov[q])) { set_error("cov" + where + " has a non-finite entry"); return RBPF_ERR_CHOL_FAILED; }
+  if (!chol_lower_host(cov, n, n, L, n)) {
+    set_error("cov" + where + " is not positive definite: the transition density does not exist");
+    return RBPF_ERR_CHOL_FAILED;
+  }
+  std::memset(&W, 0, sizeof(W));
+  for (int j = 0; j < n; ++j) {
+    W.w[j * (j + 1) / 2 + j] = 1.0 / L[j + n * j];
+    for (int i = j + 1; i < n; ++i) {
+      double s = 0.0;
+      for (int k = j; k < i; ++k) s += L[i + n * k] * W.w[k * (k + 1) / 2 + j];
+      W.w[i * (i + 1) / 2 + j] = -s / L[i + n * i];
+    }
+  }
+  return RBPF_OK;
+}
+
+static size_t gs_bytes(size_t nN, size_t NR, size_t N, size_t T, size_t M) {
+  const size_t C = (size_t)gs_chunk_size((int)N, (int)M), nch = (N + C - 1) / C;
+  return ((NR + 1) * N + 2 * nch * M + T * M + T * nN * M + nN * T) * sizeof(double) + T * M * sizeof(int);
+}
+
+static int gs_ctx_ok(const rbpf_ctx* c) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (!c->loc->generic) { set_error("not a generic localisation context (rbpf_loc_generic_create): the dense-mag map has rbpf_loc_backward_simulate"); return RBPF_ERR_INVALID_ARG; }
+  return RBPF_OK;
+}
+
+static void gs_release(rbpf_ctx* c) {
+  LocGenBackward& g = c->loc->gb;
+  for (void* p : {(void*)g.d_Xhat, (void*)g.d_pm, (void*)g.d_ps, (void*)g.d_u, (void*)g.d_xs, (void*)g.d_mean, (void*)g.d_idx}) c->pool.release(p);
+  g = LocGenBackward();
+}
+
+}  // namespace rbpf
+
+using namespace rbpf;
+
+extern "C" {
+
+int rbpf_loc_generic_backward_workspace_bytes(int32_t n_nonlin, int32_t n_res, int32_t N_P, int32_t N_T, int32_t n_traj, size_t* bytes) {
+  if (!bytes) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (n_nonlin < 1 || n_nonlin > kGsMaxNonlin || n_res < 1 || n_res > kGsMaxRes || n_res > n_nonlin) {
+    set_error("n_nonlin must be in 1 .. 8 and n_res in 1 .. n_nonlin");
+    return RBPF_ERR_INVALID_ARG;
+  }
+  if (N_P < 1 || N_T < 1 || n_traj < 1) { set_error("N_P, N_T and n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P > kMaxParticles) { set_error("N_P above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  *bytes = gs_bytes((size_t)n_nonlin, (size_t)n_res, (size_t)N_P, (size_t)N_T, (size_t)n_traj);
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_backward_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, int32_t n_res, const int32_t* rows,
+                                    uint32_t angle_mask) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  if (n_traj < 1) { set_error("n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(gs_validate_rows(L->nN, n_res, rows, angle_mask));
+  if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
+  if (!c->opt.keep_history || !c->opt.trace) {
+    set_error("backward simulation reads the stored particles and weights: create the context with keep_history = 1 and trace = 1");
+    return RBPF_ERR_STATE;
+  }
+  if (c->t < c->T) { set_error("rbpf_loc_generic_backward_begin: " + std::to_string(c->t) + " of " + std::to_string(c->T) + " steps are done"); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  const int N = c->N, T = c->T, M = n_traj, nN = L->nN;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  {
+    std::vector<double> lse((size_t)T);
+    HIPCHK(hipMemcpy(lse.data(), L->d_lse, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
+    for (int t = 0; t < T; ++t)
+      if (!(lse[t] > std::log(1e-12))) {
+        set_error("the forward run recorded a degenerate step (t = " + std::to_string(t) + "): its weights are no filtering distribution");
+        return RBPF_ERR_STATE;
+      }
+  }
+  LocGenBackward& g = L->gb;
+  g.M = M; g.n_res = n_res; g.angle_mask = angle_mask;
+  g.C = gs_chunk_size(N, M); g.nch = (N + g.C - 1) / g.C;
+  for (int k = 0; k < n_res; ++k) g.rows[k] = rows[k];
+  auto fail = [&](int s) { gs_release(c); return s; };
+  int s;
+  if ((s = c->pool.alloc(&g.d_Xhat, (size_t)(n_res + 1) * N)) != RBPF_OK) return fail(s);
+  if ((s = c->pool.alloc(&g.d_pm, (size_t)g.nch * M)) != RBPF_OK) return fail(s);
+  if ((s = c->pool.alloc(&g.d_ps, (size_t)g.nch * M)) != RBPF_OK) return fail(s);
+  if ((s = c->pool.alloc(&g.d_u, (size_t)T * M)) != RBPF_OK) return fail(s);
+  if ((s = c->pool.alloc(&g.d_xs, (size_t)T * nN * M)) != RBPF_OK) return fail(s);
+  if ((s = c->pool.alloc(&g.d_mean, (size_t)nN * T)) != RBPF_OK) return fail(s);
+  if ((s = c->pool.alloc(&g.d_idx, (size_t)T * M)) != RBPF_OK) return fail(s);
+  hipError_t e;
+  if (u) {
+    e = hipMemcpy(g.d_u, u, (size_t)T * M * sizeof(double), hipMemcpyHostToDevice);
+  } else {
+    const size_t cnt = (size_t)T * M;
+    hipLaunchKernelGGL(gs_philox_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, (unsigned long long)seed, T, M, g.d_u);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return fail(hip_fail(e, "uniforms of the backward pass", __FILE__, __LINE__));
+  g.t = T - 1;
+  g.open = true;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_backward_particles_device(rbpf_ctx* c, int32_t* t, const double** xn_dev) {
+  RB_TRY(gs_ctx_ok(c));
+  if (!t || !xn_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  const LocGenBackward& g = c->loc->gb;
+  if (!g.open) { set_error("no backward pass is open (rbpf_loc_generic_backward_begin first)"); return RBPF_ERR_STATE; }
+  if (g.t < 0) { set_error("every step of the backward pass is done (rbpf_loc_generic_backward_finish)"); return RBPF_ERR_STATE; }
+  *t = g.t;
+  *xn_dev = c->X + (size_t)g.t * c->loc->nN * c->N;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_backward_step_device(rbpf_ctx* c, const double* mu_dev, const double* cov) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenBackward& g = L->gb;
+  if (!g.open) { set_error("no backward pass is open (rbpf_loc_generic_backward_begin first)"); return RBPF_ERR_STATE; }
+  if (g.t < 0) { set_error("every step of the backward pass is done (rbpf_loc_generic_backward_finish)"); return RBPF_ERR_STATE; }
+  const int N = c->N, T = c->T, M = g.M, nN = L->nN, t = g.t;
+  GsArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.first = (t == T - 1);
+  if (!a.first) {
+    if (!mu_dev || !cov) { set_error("NULL argument (mu_dev and cov may be NULL at step N_T-1 only)"); return RBPF_ERR_INVALID_ARG; }
+    RB_TRY(gs_factor(cov, g.n_res, a.W, " of step " + std::to_string(t)));
+  }
+  HIPCHK(hipSetDevice(c->device));
+  a.N = N; a.M = M; a.C = g.C; a.nchunks = g.nch; a.nN = nN; a.angle_mask = g.angle_mask;
+  for (int k = 0; k < g.n_res; ++k) a.rows[k] = g.rows[k];
+  a.Xhat = g.d_Xhat; a.X = c->X + (size_t)t * nN * N;
+  a.xs_next = a.first ? nullptr : g.d_xs + (size_t)(t + 1) * nN * M;
+  a.u = g.d_u + (size_t)t * M; a.part_m = g.d_pm; a.part_s = g.d_ps;
+  a.index = g.d_idx + (size_t)t * M; a.xs = g.d_xs + (size_t)t * nN * M; a.clamped = c->d_flags + 1;
+  HIPCHK(gs_launch_step(g.n_res, a, a.first ? nullptr : mu_dev, c->w + (size_t)t * N, g.d_Xhat, c->stream));
+  hipLaunchKernelGGL(gs_mean_kernel, dim3(1), dim3(256), 0, c->stream, M, nN, a.xs, g.d_mean + (size_t)t * nN);
+  HIPCHK(hipGetLastError());
+  g.t = t - 1;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_backward_finish(rbpf_ctx* c, double* xs_traj, int32_t* index, double* traj_smooth_mean) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenBackward& g = L->gb;
+  if (!g.open) { set_error("no backward pass is open (rbpf_loc_generic_backward_begin first)"); return RBPF_ERR_STATE; }
+  const int T = c->T, M = g.M, nN = L->nN;
+  struct Close { rbpf_ctx* c; ~Close() { gs_release(c); } } close{c};    // the workspace goes back on every way out
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (g.t >= 0) {
+    if (!xs_traj && !index && !traj_smooth_mean) return RBPF_OK;         // the way out of a pass that was given up
+    set_error("rbpf_loc_generic_backward_finish: steps " + std::to_string(g.t) + " .. 0 of the backward pass were not run");
+    return RBPF_ERR_STATE;
+  }
+  RB_TRY(ctx_check_flags(c));
+  if (xs_traj) HIPCHK(hipMemcpy(xs_traj, g.d_xs, (size_t)nN * M * T * sizeof(double), hipMemcpyDeviceToHost));
+  if (index) HIPCHK(hipMemcpy(index, g.d_idx, (size_t)M * T * sizeof(int), hipMemcpyDeviceToHost));
+  if (traj_smooth_mean) HIPCHK(hipMemcpy(traj_smooth_mean, g.d_mean, (size_t)nN * T * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_backward_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_res, const int32_t* rows, uint32_t angle_mask,
+                                   const double* mu, const double* w, const double* xs_next, const double* cov, const double* u,
+                                   int32_t* index, double* logp, int32_t reps, double* ms) {
+  if (!mu || !w || !xs_next || !cov || !u || !index || !rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles) { set_error("N above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  RB_TRY(gs_validate_rows(n_nonlin, n_res, rows, angle_mask));
+  GsArgs a;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor(cov, n_res, a.W, ""));
+  if (!have_device()) { set_error("no HIP device: the backward pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  const int C = gs_chunk_size(N, M), nch = (N + C - 1) / C;
+  DevicePool tmp;
+  double *d_mu = nullptr, *d_w = nullptr, *d_xs = nullptr, *d_u = nullptr, *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_lp = nullptr;
+  int *d_idx = nullptr, *d_clamped = nullptr;
+  RB_TRY(tmp.upload(&d_mu, mu, (size_t)n_res * N));
+  RB_TRY(tmp.upload(&d_w, w, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xs_next, (size_t)n_nonlin * M));
+  RB_TRY(tmp.upload(&d_u, u, (size_t)M));
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)(n_res + 1) * N));
+  RB_TRY(tmp.alloc(&d_pm, (size_t)nch * M));
+  RB_TRY(tmp.alloc(&d_ps, (size_t)nch * M));
+  RB_TRY(tmp.alloc(&d_idx, (size_t)M));
+  RB_TRY(tmp.alloc(&d_clamped, (size_t)1));
+  HIPCHK(hipMemset(d_clamped, 0, sizeof(int)));
+  if (logp) RB_TRY(tmp.alloc(&d_lp, (size_t)N * M));
+  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.nN = n_nonlin; a.first = 0; a.angle_mask = angle_mask;
+  for (int k = 0; k < n_res; ++k) a.rows[k] = rows[k];
+  a.Xhat = d_Xhat; a.X = nullptr; a.xs_next = d_xs; a.u = d_u; a.part_m = d_pm; a.part_s = d_ps; a.index = d_idx; a.xs = nullptr;
+  a.clamped = d_clamped;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+  auto run = [&]() -> int {                       // (the events are destroyed whichever way it returns)
+    const int R = std::max(reps, 1);
+    for (int r = 0; r < R; ++r) {
+      hipEvent_t e0, e1;
+      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+      ev.emplace_back(e0, e1);
+      HIPCHK(hipEventRecord(e0, 0));
+      HIPCHK(gs_launch_step(n_res, a, d_mu, d_w, d_Xhat, 0));
+      HIPCHK(hipEventRecord(e1, 0));
+    }
+    if (logp) HIPCHK(gs_launch(n_res, a, d_lp, 0));
+    HIPCHK(hipDeviceSynchronize());
+    if (ms) {
+      std::vector<float> tt;
+      for (auto& p : ev) { float v = 0.f; HIPCHK(hipEventElapsedTime(&v, p.first, p.second)); tt.push_back(v); }
+      std::sort(tt.begin(), tt.end());
+      *ms = tt[tt.size() / 2];
+    }
+    HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+    if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
+    return RBPF_OK;
+  };
+  const int s = run();
+  for (auto& p : ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
+  return s;
+}
+
+}  // extern "C"

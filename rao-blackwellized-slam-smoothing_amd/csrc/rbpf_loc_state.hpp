@@ -6,6 +6,18 @@
 
 namespace rbpf {
 
+// An open backward-simulation pass over a generic map (rbpf_loc_generic_backward_begin .. _finish, rbpf_loc_generic_smooth.hip): the
+// workspace is taken from rbpf_ctx::pool at begin and handed back at finish (or with the context).
+struct LocGenBackward {
+  bool open = false;
+  int M = 0, n_res = 0, C = 0, nch = 0;
+  int t = -1;                      // the step the next rbpf_loc_generic_backward_step_device processes; -1: all done
+  int rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned angle_mask = 0;
+  double *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_u = nullptr, *d_xs = nullptr, *d_mean = nullptr;
+  int* d_idx = nullptr;
+};
+
 struct LocState {
   DevicePool pool;                 // owns the device buffers below; the context-level arrays of a localisation session are in rbpf_ctx::pool
   int n = 0;
@@ -20,6 +32,7 @@ struct LocState {
   int drawn_step = -1;             // step whose ancestors rbpf_loc_generic_ancestors_device has drawn
   double *d_R = nullptr;           // [n_y x n_y]
   double *d_H = nullptr;           // [N][n_y][ldx] rows packed from dy layout 0 (allocated on first use)
+  LocGenBackward gb;               // backward simulation with a Gaussian transition density
 };
 
 // of rbpf_options a localisation context reads keep_history, trace and on_step only

@@ -1827,6 +1827,9 @@ class _LocProblem:
 
 
 def _recognise_map(dynModel, measModel):
+    if isinstance(dynModel, DeviceTransition) or isinstance(measModel, DeviceTransition):
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "a DeviceTransition states the density of a DeviceMap's dynModel (DeviceMap(..., transition=...)): "
+                        "it is no handle, and the dense-mag map has its own transition density")
     mp = getattr(dynModel, "model", None)
     if not isinstance(mp, DenseMagMap) or getattr(measModel, "model", None) is not mp:
         raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleFilterLocalization runs the handles of a DenseMagMap, or a DeviceMap as dynModel; a host-callback "
@@ -1866,6 +1869,119 @@ def device_map_weights(dy, mean, V, R, y, dy_layout=2, ldx=None, pad=0.0, reps=1
     return yhat, S, logw, ms.value
 
 
+class DeviceTransition:
+    """The transition density of a DeviceHandles dynModel as it draws, for backward simulation in a DeviceMap: a drift plus Gaussian
+    noise on some rows of the state,
+
+        x'[rows] = mean(x) + L z,  L L' = cov:    r = wrap(x'[rows] - mean(x)),   z = L \\ r,   logp = -z'z / 2
+
+    (constants omitted, particleSmoother.m:181-182).
+    mean(xn (n_nonlin, N_P), dx, dt, Q) -> (n_res, N_P): torch float64 on the library's device and stream, the predicted rows; it
+        must be pure.  Called once per backward step t = N_T-2 .. 0 with the stored forward particles of step t (a view of library
+        memory: do not write to it) and odometry[t], dt[t], Q[:,:,t] -- the arguments the forward dynModel got when it made step
+        t+1.
+    rows: the indices of the n_nonlin state that carry noise (default: all), n_res = len(rows) in 1 .. 8, distinct.  Rows that are
+        not listed take NO part in the density, as in the reference's dense-radio dynResNorm (heading only): a trajectory is then
+        extended backwards whatever those rows of the candidate particles are.
+    angle_rows: a subset of rows whose residual is wrapped, r <- r - 2 pi rint(r / (2 pi)).
+    cov(dt, Q) -> (n_res, n_res): a host callable on numpy arrays (default: dt * Q, which needs n_w == n_res), evaluated once per
+        step page and factorised on the host; one that is not positive definite is refused before any kernel runs."""
+
+    def __init__(self, mean, cov=None, rows=None, angle_rows=()):
+        if not callable(mean) or (cov is not None and not callable(cov)):
+            raise TypeError("mean must be callable, cov callable or None")
+        self.mean, self.cov = mean, cov
+        self.rows = None if rows is None else tuple(int(r) for r in rows)
+        self.angle_rows = tuple(int(r) for r in angle_rows)
+
+    def resolve(self, n_nonlin):
+        """(rows, angle_mask) for a state of n_nonlin rows; bit k of the mask marks rows[k]."""
+        return _transition_rows(n_nonlin, self.rows, self.angle_rows)
+
+    def covariance(self, dt, Q, n_res):
+        """cov(dt, Q) as a Fortran-ordered [n_res x n_res] array, shape checked."""
+        Q = np.asarray(Q, dtype=np.float64)
+        if self.cov is None:
+            if Q.shape != (n_res, n_res):
+                raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"the default cov = dt * Q needs n_w == n_res: Q is {Q.shape[0]} x {Q.shape[1]} and "
+                                                           f"{n_res} rows carry noise (give DeviceTransition a cov(dt, Q))")
+            c = float(dt) * Q
+        else:
+            c = np.asarray(self.cov(float(dt), Q), dtype=np.float64)
+            c = c.reshape(1, 1) if c.ndim == 0 else c
+        if c.shape != (n_res, n_res):
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"cov(dt, Q) returned {c.shape}, expected {(n_res, n_res)}")
+        return np.asfortranarray(c)
+
+
+def _transition_rows(n_nonlin, rows, angle_rows):
+    rows = tuple(range(int(n_nonlin))) if rows is None else tuple(int(r) for r in rows)
+    if not 1 <= len(rows) <= 8:
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, "n_res (the rows that carry noise) must be in 1 .. 8")
+    if len(set(rows)) != len(rows) or min(rows) < 0 or max(rows) >= int(n_nonlin):
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"rows {rows} must be distinct rows of the n_nonlin = {int(n_nonlin)} state")
+    mask = 0
+    for r in angle_rows:
+        if int(r) not in rows:
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"angle row {int(r)} is not one of rows {rows}")
+        mask |= 1 << rows.index(int(r))
+    return rows, mask
+
+
+def device_map_backward_workspace_bytes(n_nonlin, n_res, N_P, N_T, n_traj):
+    """rbpf_loc_generic_backward_workspace_bytes (no device access)."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_generic_backward_workspace_bytes(int(n_nonlin), int(n_res), int(N_P), int(N_T), int(n_traj), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), want_logp=False, reps=1):
+    """rbpf_loc_generic_backward_step, the kernel-level probe: one backward step with a Gaussian transition on the caller's arrays.
+    mu [n_res x N] (the predicted rows of every particle), w [N], xs_next [n_nonlin x M], cov [n_res x n_res], u [M]; rows (default:
+    all n_nonlin = n_res rows) and angle_rows as in DeviceTransition -> (index [M], logp [N x M] or None, median ms of one step)."""
+    lib = load_library()
+    mu = np.asarray(mu, dtype=np.float64)
+    mu = np.ascontiguousarray(mu.reshape(1, -1) if mu.ndim == 1 else mu)
+    xs_next = np.asarray(xs_next, dtype=np.float64)
+    xs_next = np.asfortranarray(xs_next.reshape(1, -1) if xs_next.ndim == 1 else xs_next)
+    n_res, N = mu.shape
+    nN, M = xs_next.shape
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).ravel())
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).ravel())
+    cov = np.asarray(cov, dtype=np.float64)
+    cov = cov.reshape(1, 1) if cov.ndim == 0 else cov
+    if cov.shape != (n_res, n_res):
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"cov is {cov.shape}, expected {(n_res, n_res)}")
+    cov = np.asfortranarray(cov)
+    if w.size != N or u.size != M:
+        raise ValueError("w must be [N] and u [M]")
+    if rows is None:
+        rows_a, mask = np.arange(nN, dtype=np.int32), 0
+        for r in angle_rows:
+            if not 0 <= int(r) < nN:
+                raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"angle row {int(r)} is not one of rows")
+            mask |= 1 << int(r)
+        if nN != n_res:
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"mu has {n_res} rows and xs_next {nN}: name the rows that carry noise")
+    else:                                                         # (the library checks them: duplicates, range)
+        rows_a = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).ravel())
+        if rows_a.size != n_res:
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"mu has {n_res} rows and rows names {rows_a.size}")
+        mask = 0
+        for r in angle_rows:
+            pos = np.nonzero(rows_a == int(r))[0]
+            if pos.size == 0:
+                raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"angle row {int(r)} is not one of rows {tuple(rows_a.tolist())}")
+            mask |= 1 << int(pos[0])
+    index = np.zeros(M, dtype=np.int32)
+    logp = np.empty((N, M), order="F") if want_logp else None
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_generic_backward_step(N, M, nN, n_res, _ip(rows_a), mask, _dp(mu), _dp(w), _dp(xs_next), _dp(cov), _dp(u), _ip(index),
+                                             _dp(logp) if want_logp else None, int(reps), C.byref(ms)))
+    return index, logp, ms.value
+
+
 class DeviceMap:
     """A fixed map of an arbitrary model whose handles are device code: the posterior N(mean, V'V) over the nLin linear states, V
     lower (the DenseMagMap convention), as a SLAM filter or smoother run with the same DeviceHandles returns it (xl_max, P_max /
@@ -1878,10 +1994,15 @@ class DeviceMap:
     with H_i = dy(i,:,:) of handles.measModel(xn), called once per step with N_P columns; handles.dynModel draws its own random
     numbers, as for DeviceHandles.  The layout of every dy is read off its strides (MATLAB-order strides, C-contiguous, or the native
     view of a native_out handle, consumed in place); handles.dy_layout is not used.  n_y 1 .. 8, nLin 1 .. 1151, n_nonlin 1 .. 8; one
-    GPU.  Not built: backward simulation / particleSmootherLocalization (they need dynModel's transition density; a generic
-    dynModel is a sampler), host closures, sharding, sparse-feature maps."""
+    GPU.  transition: a DeviceTransition, the density of handles.dynModel as it draws (a drift plus Gaussian noise on some rows of
+    the state); with one, LocalizationSession.backward_simulate and particleSmootherLocalization draw smoothed trajectories in this
+    map.  Without one they refuse (they need dynModel's transition density; a generic dynModel is a sampler).  Not built: densities
+    that are not Gaussian in a wrapped difference, host closures, sharding, sparse-feature maps."""
 
-    def __init__(self, handles, mean, V, R):
+    def __init__(self, handles, mean, V, R, transition=None):
+        if transition is not None and not isinstance(transition, DeviceTransition):
+            raise TypeError("transition must be a DeviceTransition")
+        self.transition = transition
         if not isinstance(handles, DeviceHandles):
             raise TypeError("DeviceMap needs a DeviceHandles object")
         if isinstance(handles, DeviceSparseHandles):
@@ -1907,9 +2028,9 @@ class DeviceMap:
         return self.R.shape[0]
 
     @classmethod
-    def from_posterior(cls, handles, xl, P, R):
+    def from_posterior(cls, handles, xl, P, R, transition=None):
         """From a map posterior (mean xl, covariance P), factored as DenseMagMap.from_posterior factors it."""
-        return cls(handles, xl, _lower_factor(P), R)
+        return cls(handles, xl, _lower_factor(P), R, transition=transition)
 
     def predict(self, xn, reps=1):
         """The map's prediction at the states xn [n_nonlin x n_pred] (numpy or a device tensor), through the weight kernel on its
@@ -2201,8 +2322,9 @@ class LocalizationSession:
         """rbpf_loc_backward_simulate: n_traj trajectories drawn backwards through the stored particles (keep_history and trace,
         every step done).  rng: None / PhiloxRNG(seed): the device generator (PhiloxRNG.backward_uniforms(n_traj, N_T) are its
         draws); an array u [N_T x n_traj] of uniforms in (0, 1]: replay.  Returns a dict of the arrays named in `want`:
-        xs_traj [7 x n_traj x N_T], index [n_traj x N_T] (0-based), traj_smooth_mean [7 x N_T].  Not available in a DeviceMap."""
-        if self.driver is not None:
+        xs_traj [7 x n_traj x N_T], index [n_traj x N_T] (0-based), traj_smooth_mean [7 x N_T].  In a DeviceMap: n_nonlin rows in
+        place of 7, with the map's DeviceTransition (rbpf_loc_generic_backward_*); without one the call is refused."""
+        if self.driver is not None and self.map.transition is None:
             raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, _NO_BACKWARD_IN_DEVICE_MAP)
         M, T = int(n_traj), self.prob.N_T
         seed, u = 0, None
@@ -2220,16 +2342,72 @@ class LocalizationSession:
         Mb = max(M, 0)
         b = {}
         if "xs_traj" in want:
-            b["xs_traj"] = np.empty((7, Mb, T), order="F")
+            b["xs_traj"] = np.empty((self.nN, Mb, T), order="F")
         if "index" in want:
             b["index"] = np.zeros((Mb, T), dtype=np.int32, order="F")
         if "traj_smooth_mean" in want:
-            b["traj_smooth_mean"] = np.empty((7, T), order="F")
+            b["traj_smooth_mean"] = np.empty((self.nN, T), order="F")
+        if self.driver is not None:
+            self._backward_in_device_map(M, u, seed, b)
+            return b
         check(self.lib.rbpf_loc_backward_simulate(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed),
                                                   _dp(b["xs_traj"]) if "xs_traj" in b else None,
                                                   _ip(b["index"]) if "index" in b else None,
                                                   _dp(b["traj_smooth_mean"]) if "traj_smooth_mean" in b else None))
         return b
+
+    def _backward_in_device_map(self, M, u, seed, b):
+        """The backward pass with the map's DeviceTransition: the covariance pages on the host first, then begin, one
+        particles_device / mean handle / step_device per step in stream order, finish (also the way out of a failed handle)."""
+        lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
+        torch, T, N, nN = drv.torch, prob.N_T, prob.N_P, self.nN
+        rows, mask = tr.resolve(nN)
+        n_res = len(rows)
+        page = lambda a, t: t if a > 1 else 0                                                     # noqa: E731
+        covs = {}
+        for t in range(T - 1):                                    # one factorisation per distinct (dt, Q) page, checked before any kernel runs
+            key = (page(prob._dt.size, t), page(prob._Q.shape[2], t))
+            if key not in covs:
+                c = tr.covariance(prob._dt[key[0]], prob._Q[:, :, key[1]], n_res)
+                try:
+                    if not np.all(np.isfinite(c)):
+                        raise np.linalg.LinAlgError
+                    np.linalg.cholesky(c)
+                except np.linalg.LinAlgError:
+                    raise RBPFError(_ffi.RBPF_ERR_CHOL_FAILED, f"cov(dt, Q) of step {t} is not positive definite: the transition density "
+                                                               "does not exist") from None
+                covs[key] = c
+        rows_a = np.asarray(rows, dtype=np.int32)
+        check(lib.rbpf_loc_generic_backward_begin(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed), n_res, _ip(rows_a), mask))
+        try:
+            with torch.cuda.stream(drv.stream):
+                for _ in range(T):
+                    t, xn = C.c_int32(0), C.c_void_p()
+                    check(lib.rbpf_loc_generic_backward_particles_device(self.ctx, C.byref(t), C.byref(xn)))
+                    t = t.value
+                    if t == T - 1:                                # this draw reads log w only
+                        check(lib.rbpf_loc_generic_backward_step_device(self.ctx, None, None))
+                        continue
+                    X = drv._view(torch, xn, (nN, N), drv.device)
+                    Q = drv.Q[page(drv.Q.shape[0], t)]
+                    mu = tr.mean(X, drv.odo[t], float(drv.dt[page(drv.dt.size, t)]), Q)
+                    if not torch.is_tensor(mu) or tuple(mu.shape) != (n_res, N) or mu.dtype != torch.float64 or not mu.is_cuda:
+                        what = f"{tuple(mu.shape)} {mu.dtype} on {mu.device}" if torch.is_tensor(mu) else type(mu).__name__
+                        raise ValueError(f"mean returned {what}, expected a float64 device tensor of shape {(n_res, N)}")
+                    mu = mu.contiguous()
+                    self._keep_mu = mu                            # read in stream order by the step just enqueued
+                    check(lib.rbpf_loc_generic_backward_step_device(self.ctx, C.c_void_p(mu.data_ptr()),
+                                                                    _dp(covs[(page(prob._dt.size, t), page(prob._Q.shape[2], t))])))
+        except BaseException:
+            lib.rbpf_loc_generic_backward_finish(self.ctx, None, None, None)
+            self._keep_mu = None
+            raise
+        try:
+            check(lib.rbpf_loc_generic_backward_finish(self.ctx, _dp(b["xs_traj"]) if "xs_traj" in b else None,
+                                                       _ip(b["index"]) if "index" in b else None,
+                                                       _dp(b["traj_smooth_mean"]) if "traj_smooth_mean" in b else None))
+        finally:
+            self._keep_mu = None
 
     def close(self):
         if self.ctx:
@@ -2275,13 +2453,16 @@ def loc_backward_step(xn, w, xs_next, odo, dt, Q, u, want_logp=False, reps=1):
 def particleSmootherLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, N_S, dt, *, rng=None, extras=False):
     """Forward filter, backward simulation for localisation in a fixed map: particleFilterLocalization, then N_S trajectories drawn
     backwards through its particles -> (xs_traj [7 x N_S x N_T], traj_smooth_mean [7 x N_T][, extras]).  dynModel / measModel are
-    the handles of a DenseMagMap, R is accepted and not used, as there.  rng: PhiloxRNG (one seed keys the filter's and the
+    the handles of a DenseMagMap, R is accepted and not used, as there; or a DeviceMap with a DeviceTransition as dynModel (measModel
+    None): n_nonlin rows in place of 7.  rng: PhiloxRNG (one seed keys the filter's and the
     backward draws, on disjoint counters) or ReplayRNG(U, Z, Uback=u) with the backward uniforms u [N_T x N_S].
     extras: the filter's outputs (traj_max, traj_mean, first_degenerate_step, ...) and the drawn `index` [N_S x N_T]."""
     import warnings
-    if _device_map(dynModel, measModel) is not None:
+    mp = _device_map(dynModel, measModel)
+    if mp is not None and mp.transition is None:
         raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleSmootherLocalization: " + _NO_BACKWARD_IN_DEVICE_MAP)
-    mp = _recognise_map(dynModel, measModel)
+    if mp is None:
+        mp = _recognise_map(dynModel, measModel)
     if isinstance(rng, ReplayRNG):
         if rng.Uback is None:
             raise ValueError("a ReplayRNG needs Uback [N_T x N_S] to replay the backward draws")
