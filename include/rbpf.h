@@ -938,6 +938,49 @@ int rbpf_loc_generic_backward_step(int32_t N, int32_t M, int32_t n_nonlin, int32
                                    const double* mu, const double* w, const double* xs_next, const double* cov, const double* u,
                                    int32_t* index, double* logp, int32_t reps, double* ms);
 
+/* ---- localisation in the fixed landmark map of a generic device-code model ------------------------
+ * The frozen-map filter above for a model of the sparseFeatures branch (particleFilter.m:100-161 with :127-137): the map posterior
+ * N(mean, V'V), V lower, is shared by all particles and never updated, and the caller's measModel(xn, xl) returns the prediction
+ * yhat_i [n_y] (nonlinear in the map) next to H_i = dy(i,:,:) [n_y x n_lin].  Per step t, ind = ~isnan(y(t,:)), M = |ind|:
+ *     e_i = y_t(ind)' - yhat_i(ind),   S_i = H_i(ind,:) P H_i(ind,:)' + R(ind,ind),
+ *     logw_i = -sum log diag chol S_i - |chol(S_i) \ e_i|^2 / 2 - M log(2 pi) / 2                          (:129-136,145-150)
+ * mean is not read by the weight kernel.  Rows of yhat / dy that belong to outputs not observed at a step are never read; they may
+ * hold anything, NaN included.  M = 0: every log-weight is 0, the weights 1 / N_P.  The jitter retry of :145-148 is left out: S_i is
+ * a Gram matrix plus a principal submatrix of R, and an R that is not symmetric positive definite is RBPF_ERR_CHOL_FAILED at
+ * creation.  Everything after the weights is the generic localisation context's.  n_y 1 .. 32, n_lin 1 .. 96, n_nonlin 1 .. 8 (the
+ * limits of the SLAM branch; above: RBPF_ERR_UNSUPPORTED); one GPU, fp64.  NULL arguments and bad sizes are RBPF_ERR_INVALID_ARG
+ * before any device is touched; without a device: RBPF_ERR_NO_DEVICE.
+ *   rbpf_loc_landmark_create   arguments as rbpf_loc_generic_create; y [N_T x n_y] column-major, NaN = not observed.  The context is
+ *        a generic localisation context: rbpf_loc_finish, rbpf_loc_history, rbpf_filter_tell, rbpf_sync, rbpf_stream_get,
+ *        rbpf_destroy, rbpf_loc_generic_layout, rbpf_loc_generic_ancestors_device and all of rbpf_loc_generic_backward_* work on it
+ *        unchanged; rbpf_loc_advance is RBPF_ERR_STATE, rbpf_loc_backward_simulate RBPF_ERR_UNSUPPORTED, options other than
+ *        keep_history, trace, on_step RBPF_ERR_UNSUPPORTED, and rbpf_loc_generic_step_device RBPF_ERR_STATE (it has no yhat).
+ *   rbpf_loc_landmark_map_device   *xl_dev [N_P][ldx]: every row = mean, columns n_lin .. ldx-1 zero: the shape
+ *        rbpf_filter_sparse_gathered_device hands out, so a handle written for the SLAM filter runs unchanged.  Owned by the
+ *        context, constant for its life.
+ *   rbpf_loc_landmark_step_device   xn_new_dev as in rbpf_loc_generic_step_device; yhat / dy layouts as in
+ *        rbpf_filter_step_sparse_device: yhat 0 (yhat(i,k) at i + N_P*k) or 2 ([N_P][n_y]); dy 0 (MATLAB order, packed by a kernel
+ *        first), 1 ([N_P][n_y][ldx] rows; what stands in columns n_lin .. ldx-1 never enters a result) or 2 ([N_P][n_y][n_lin]).
+ *        RBPF_ERR_STATE at t >= 1 without rbpf_loc_generic_ancestors_device, and after the last step.  Returns without waiting
+ *        unless an on_step hook is set.
+ *   rbpf_loc_landmark_yhattraj   yhattraj [n_y x N_T] column-major: column t is the whole yhat of step t's maximum-weight particle
+ *        as the caller handed it in, NaN for steps not yet run.  Waits for the stream.
+ *   rbpf_loc_landmark_weights   the weight kernel on its own, host arrays: yhat and dy for n_p particles in their layouts (ldx: the
+ *        row stride of dy layout 1, otherwise ignored), y [n_y] with NaN = not observed -> S [M x M x n_p] column-major =
+ *        H_i(ind,:) P H_i(ind,:)' in ascending output order, before R is added, logw [n_p]; NULL outputs are skipped.  reps >= 1
+ *        repeats the launch; *ms (may be NULL) = median kernel time by device events.
+ * Not built: host closures, the MEX gateway, sharding, n_lin > 96, n_y > 32.                                                      */
+int rbpf_loc_landmark_create(int32_t n_nonlin, int32_t n_y, int32_t n_lin, const double* mean, const double* V, const double* R,
+                             int32_t N_P, int32_t N_T, const double* y, const double* x0_nonlin, int32_t x0_cols,
+                             const rbpf_rng* rng, const rbpf_options* opt, rbpf_ctx** ctx);
+int rbpf_loc_landmark_map_device(rbpf_ctx* ctx, const double** xl_dev, int32_t* ldx);
+int rbpf_loc_landmark_step_device(rbpf_ctx* ctx, const double* xn_new_dev, const double* yhat_dev, int32_t yhat_layout,
+                                  const double* dy_dev, int32_t dy_layout);
+int rbpf_loc_landmark_yhattraj(rbpf_ctx* ctx, double* yhattraj);
+int rbpf_loc_landmark_weights(int32_t n_y, int32_t n_lin, int32_t n_p, const double* yhat, int32_t yhat_layout, const double* dy,
+                              int32_t dy_layout, int32_t ldx, const double* V, const double* R, const double* y, double* S,
+                              double* logw, int32_t reps, double* ms);
+
 /* ---- the EKF comparison baseline of examples/slam-dense-mag, batched over data sets ---------------
  * ekf_dense.m:41-102 with the closures measModel_ekf / dynModel_ekf of run_dense3D_magfield.m:281-299,310-316, on the device:
  * one Gaussian state [position(3); orientation deviation(3); map(nLin = m_basis + 3)], n = 6 + nLin, per run.  The n_runs runs

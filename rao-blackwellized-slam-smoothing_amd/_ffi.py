@@ -168,6 +168,8 @@ EXPORTS = [
     "rbpf_loc_generic_weights",
     "rbpf_loc_generic_backward_begin", "rbpf_loc_generic_backward_particles_device", "rbpf_loc_generic_backward_step_device",
     "rbpf_loc_generic_backward_finish", "rbpf_loc_generic_backward_workspace_bytes", "rbpf_loc_generic_backward_step",
+    "rbpf_loc_landmark_create", "rbpf_loc_landmark_map_device", "rbpf_loc_landmark_step_device", "rbpf_loc_landmark_yhattraj",
+    "rbpf_loc_landmark_weights",
     "rbpf_ekf_dense", "rbpf_ekf_workspace_bytes",
 ]
 
@@ -316,6 +318,12 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_loc_generic_backward_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
     lib.rbpf_loc_generic_backward_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, c_double_p, c_double_p,
                                                    c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_landmark_create.argtypes = lib.rbpf_loc_generic_create.argtypes
+    lib.rbpf_loc_landmark_map_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p]
+    lib.rbpf_loc_landmark_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+    lib.rbpf_loc_landmark_yhattraj.argtypes = [C.c_void_p, c_double_p]
+    lib.rbpf_loc_landmark_weights.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int32, C.c_int32,
+                                              c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
     lib.rbpf_ekf_dense.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(rbpf_ekf_out)]
     lib.rbpf_ekf_workspace_bytes.argtypes = [C.POINTER(rbpf_ekf_problem), C.POINTER(rbpf_options), C.POINTER(C.c_size_t)]
     _lib = lib

@@ -317,15 +317,29 @@ int rbpf_loc_generic_create(int32_t n_nonlin, int32_t n_y, int32_t n_lin, const 
   *out = nullptr;
   if (!mean || !V || !R || !y || !x0_nonlin || !rng) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(lg_validate_sizes(n_nonlin, n_y, n_lin));
+  RB_TRY(loc_generic_validate_run(N_P, N_T, x0_cols, rng, opt));
+  RB_TRY(lg_validate_R(R, n_y));
+  if (!have_device()) { set_error("no HIP device: the localisation filter has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  return loc_generic_build(n_nonlin, n_y, n_lin, mean, V, R, N_P, N_T, y, x0_nonlin, x0_cols, rng, opt, out);
+}
+
+}  // extern "C"
+
+// what every generic localisation context checks of its run (rbpf_loc_generic_create, rbpf_loc_landmark_create)
+int rbpf::loc_generic_validate_run(int N_P, int N_T, int x0_cols, const rbpf_rng* rng, const rbpf_options* opt) {
   if (N_P < 1 || N_T < 1) { set_error("N_P and N_T must be >= 1"); return RBPF_ERR_INVALID_ARG; }
   if (N_P > kMaxParticles) { set_error("N_P above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
   if (x0_cols != 1 && x0_cols != N_P) { set_error("x0_nonlin must be n_nonlin x 1 or n_nonlin x N_P"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(loc_validate_options(opt));
   if (rng->mode != RBPF_RNG_REPLAY && rng->mode != RBPF_RNG_PHILOX) { set_error("unknown rng mode"); return RBPF_ERR_INVALID_ARG; }
   if (rng->mode == RBPF_RNG_REPLAY && N_T > 1 && !rng->U) { set_error("replay rng needs U (the handle draws its own normals: Z is not read)"); return RBPF_ERR_INVALID_ARG; }
-  RB_TRY(lg_validate_R(R, n_y));
-  if (!have_device()) { set_error("no HIP device: the localisation filter has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  return RBPF_OK;
+}
 
+// the context of validated arguments: the map, the measurements and the arrays of the filter's steps
+int rbpf::loc_generic_build(int n_nonlin, int n_y, int n_lin, const double* mean, const double* V, const double* R, int N_P, int N_T,
+                            const double* y, const double* x0_nonlin, int x0_cols, const rbpf_rng* rng, const rbpf_options* opt,
+                            rbpf_ctx** out) {
   const int N = N_P, T = N_T, n = n_lin, d = n_y, nN = n_nonlin;
   rbpf_ctx* c = new rbpf_ctx();
   LocState* L = new LocState();
@@ -369,6 +383,27 @@ int rbpf_loc_generic_create(int32_t n_nonlin, int32_t n_y, int32_t n_lin, const 
   return RBPF_OK;
 }
 
+// after the log-weights of step c->t: normalisation, the cdf for the next draw, traj_max / traj_mean, log(sum(w))
+int rbpf::loc_generic_normalise_step(rbpf_ctx* c, const double* X_new) {
+  LocState* L = c->loc;
+  const int t = c->t, N = c->N, nN = L->nN;
+  const size_t tr = c->opt.trace ? (size_t)t * N : 0;
+  NormArgs nm;
+  nm.N = N; nm.nN = nN; nm.t = t; nm.logw = c->logw + tr; nm.w = c->w + tr; nm.wc = c->wc; nm.xn = X_new;
+  nm.traj_max = c->traj_max + (size_t)t * nN; nm.traj_mean = c->traj_mean + (size_t)t * nN;
+  nm.iw_max = c->d_flags + 2; nm.lse_out = L->d_lse + t;
+  nm.parallel_scan = 1;
+  if (N > kSingleWgResampleMaxN) {
+    HIPCHK(launch_resample_pipeline(nm, nullptr, nullptr, nullptr, nullptr, c->d_rs, c->stream));
+    HIPCHK(launch_resample_lse(N, c->d_rs, L->d_lse + t, c->stream));
+  } else {
+    HIPCHK(launch_normalise_scan(nm, c->stream));
+  }
+  return RBPF_OK;
+}
+
+extern "C" {
+
 int rbpf_loc_generic_layout(const rbpf_ctx* c, int32_t* ldx) {
   if (!c || !ldx) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(lg_ctx_ok(c));
@@ -409,6 +444,7 @@ int rbpf_loc_generic_step_device(rbpf_ctx* c, const double* xn_new_dev, const do
   if (dy_layout < 0 || dy_layout > 2) { set_error("dy_layout must be 0 (MATLAB order), 1 (native) or 2 (C-contiguous)"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(lg_ctx_ok(c));
   LocState* L = c->loc;
+  if (L->landmark) { set_error("a landmark-map context takes its steps through rbpf_loc_landmark_step_device"); return RBPF_ERR_STATE; }
   const int t = c->t, N = c->N, nN = L->nN, n = L->n, d = L->d;
   if (t >= c->T) { set_error("advance past N_T"); return RBPF_ERR_STATE; }
   if (t > 0 && L->drawn_step != t) { set_error("no ancestors drawn for this step (rbpf_loc_generic_ancestors_device first)"); return RBPF_ERR_STATE; }
@@ -429,17 +465,7 @@ int rbpf_loc_generic_step_device(rbpf_ctx* c, const double* xn_new_dev, const do
   a.mean = L->d_mean; a.V = L->d_V; a.R = L->d_R; a.y = c->d_y + (size_t)t * d;
   a.yhat = nullptr; a.S = nullptr; a.logw = c->logw + tr;
   HIPCHK(launch_loc_generic_weights(d, a, c->stream));
-  NormArgs nm;
-  nm.N = N; nm.nN = nN; nm.t = t; nm.logw = c->logw + tr; nm.w = c->w + tr; nm.wc = c->wc; nm.xn = X_new;
-  nm.traj_max = c->traj_max + (size_t)t * nN; nm.traj_mean = c->traj_mean + (size_t)t * nN;
-  nm.iw_max = c->d_flags + 2; nm.lse_out = L->d_lse + t;
-  nm.parallel_scan = 1;
-  if (N > kSingleWgResampleMaxN) {
-    HIPCHK(launch_resample_pipeline(nm, nullptr, nullptr, nullptr, nullptr, c->d_rs, c->stream));
-    HIPCHK(launch_resample_lse(N, c->d_rs, L->d_lse + t, c->stream));
-  } else {
-    HIPCHK(launch_normalise_scan(nm, c->stream));
-  }
+  RB_TRY(loc_generic_normalise_step(c, X_new));
   c->t = t + 1;
   if (!c->opt.on_step) return RBPF_OK;
   HIPCHK(hipStreamSynchronize(c->stream));              // the hook sees a finished step

@@ -1,8 +1,11 @@
 // State of a localisation context (rbpf_ctx::loc), shared by the filter (rbpf_loc.hip), the backward-simulation smoother
-// (rbpf_loc_smooth.hip) and localisation in the map of a generic device-code model (rbpf_loc_generic.hip).
+// (rbpf_loc_smooth.hip) and localisation in the map of a generic device-code model (rbpf_loc_generic.hip), dense or of landmarks
+// (rbpf_loc_landmark.hip).
 #pragma once
 #include "../../include/rbpf.h"
 #include "rbpf_devmem.hpp"
+
+#include <vector>
 
 namespace rbpf {
 
@@ -33,9 +36,20 @@ struct LocState {
   double *d_R = nullptr;           // [n_y x n_y]
   double *d_H = nullptr;           // [N][n_y][ldx] rows packed from dy layout 0 (allocated on first use)
   LocGenBackward gb;               // backward simulation with a Gaussian transition density
+  // landmark map (rbpf_loc_landmark_create): the handle's yhat is the prediction and the outputs observed at a step are selected
+  bool landmark = false;
+  int *d_ind = nullptr;            // [N_T][32]: the observed outputs of every step, ascending
+  std::vector<int> n_obs;          // [N_T]: how many there are
+  double *d_xl = nullptr;          // [N_P][ldx]: every row the map's mean, what a sparse-feature measModel takes as xl
 };
 
 // of rbpf_options a localisation context reads keep_history, trace and on_step only
 int loc_validate_options(const rbpf_options* o);
+
+// pieces of rbpf_loc_generic_create / rbpf_loc_generic_step_device that a landmark-map context shares (rbpf_loc_generic.hip)
+int loc_generic_validate_run(int N_P, int N_T, int x0_cols, const rbpf_rng* rng, const rbpf_options* opt);
+int loc_generic_build(int n_nonlin, int n_y, int n_lin, const double* mean, const double* V, const double* R, int N_P, int N_T,
+                      const double* y, const double* x0_nonlin, int x0_cols, const rbpf_rng* rng, const rbpf_options* opt, rbpf_ctx** out);
+int loc_generic_normalise_step(rbpf_ctx* c, const double* X_new);
 
 }  // namespace rbpf

@@ -775,6 +775,23 @@ class _SparseDeviceDriver(_DeviceDriver):
                                  f"tensor of shape {shape}")
         return out
 
+    @staticmethod
+    def _layouts(yhat, dy):
+        """(yhat, yhat_layout, dy, dy_layout) of the C ABI read off the strides; anything else costs one contiguous()."""
+        if yhat.is_contiguous():
+            yl = 2
+        elif yhat.t().is_contiguous():
+            yl = 0
+        else:
+            yhat, yl = yhat.contiguous(), 2
+        if dy.is_contiguous():
+            dl = 2
+        elif dy.permute(2, 1, 0).is_contiguous():
+            dl = 0
+        else:
+            dy, dl = dy.contiguous(), 2
+        return yhat, yl, dy, dl
+
     def _step(self, t):
         torch, lib = self.torch, self.lib
         with torch.cuda.stream(self.stream):
@@ -788,19 +805,7 @@ class _SparseDeviceDriver(_DeviceDriver):
             xlp, ldx = C.c_void_p(), C.c_int32(0)
             check(lib.rbpf_filter_sparse_gathered_device(self.ctx, C.byref(xlp), C.byref(ldx)))
             xl = self._view(torch, xlp, (self.N, ldx.value), self.device)[:, :self.n]       # xl(:,ai), particleFilter.m:112
-            yhat, dy = self._meas_sparse(xn_cm.t(), xl)
-            if yhat.is_contiguous():
-                yl = 2
-            elif yhat.t().is_contiguous():
-                yl = 0
-            else:
-                yhat, yl = yhat.contiguous(), 2
-            if dy.is_contiguous():
-                dl = 2
-            elif dy.permute(2, 1, 0).is_contiguous():
-                dl = 0
-            else:
-                dy, dl = dy.contiguous(), 2
+            yhat, yl, dy, dl = self._layouts(*self._meas_sparse(xn_cm.t(), xl))
             self._keep = (xn_cm, yhat, dy)                                # read in stream order by the step just enqueued
             check(lib.rbpf_filter_step_sparse_device(self.ctx, C.c_void_p(xn_cm.data_ptr()), C.c_void_p(yhat.data_ptr()), yl,
                                                      C.c_void_p(dy.data_ptr()), dl))
@@ -1997,17 +2002,15 @@ class DeviceMap:
     GPU.  transition: a DeviceTransition, the density of handles.dynModel as it draws (a drift plus Gaussian noise on some rows of
     the state); with one, LocalizationSession.backward_simulate and particleSmootherLocalization draw smoothed trajectories in this
     map.  Without one they refuse (they need dynModel's transition density; a generic dynModel is a sampler).  Not built: densities
-    that are not Gaussian in a wrapped difference, host closures, sharding, sparse-feature maps."""
+    that are not Gaussian in a wrapped difference, host closures, sharding.  The map of a sparseFeatures model: DeviceLandmarkMap."""
+
+    _create = "rbpf_loc_generic_create"
 
     def __init__(self, handles, mean, V, R, transition=None):
         if transition is not None and not isinstance(transition, DeviceTransition):
             raise TypeError("transition must be a DeviceTransition")
         self.transition = transition
-        if not isinstance(handles, DeviceHandles):
-            raise TypeError("DeviceMap needs a DeviceHandles object")
-        if isinstance(handles, DeviceSparseHandles):
-            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceMap is built for dense models: a DeviceSparseHandles measModel "
-                                                       "linearises at every particle's own map, and a fixed map has none")
+        self._check_handles(handles)
         self.handles = handles
         self.mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).ravel())
         n = self.mean.size
@@ -2018,6 +2021,17 @@ class DeviceMap:
             raise ValueError("mean must be [nLin] and V [nLin x nLin]")
         if self.R.ndim != 2 or self.R.shape[0] != self.R.shape[1]:
             raise ValueError("R must be [n_y x n_y]")
+
+    @staticmethod
+    def _check_handles(handles):
+        if not isinstance(handles, DeviceHandles):
+            raise TypeError("DeviceMap needs a DeviceHandles object")
+        if isinstance(handles, DeviceSparseHandles):
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceMap is built for dense models: a DeviceSparseHandles measModel predicts "
+                                                       "from the map it is handed; DeviceLandmarkMap localises in a landmark map")
+
+    def _driver(self, lib, ctx, prob):
+        return _DeviceMapDriver(lib, ctx, self, prob)
 
     @property
     def nLin(self):
@@ -2083,6 +2097,17 @@ class _DeviceMapProblem:
             raise ValueError("odometry must have >= N_T-1 rows, Q and dt one or >= N_T-1 pages / entries")
 
 
+def _loc_generic_states(driver, t):
+    """The states of step t of a generic localisation context, [n_nonlin x N_P] column-major, on the driver's stream: the resampled
+    ancestors through dynModel (t = 0: the initial states)."""
+    ai, anc = C.c_void_p(), C.c_void_p()
+    check(driver.lib.rbpf_loc_generic_ancestors_device(driver.ctx, C.byref(ai), C.byref(anc)))
+    xn_cm = driver._view(driver.torch, anc, (driver.N, driver.nN), driver.device)
+    if t > 0:
+        xn_cm = driver._dyn(t - 1, xn_cm.t()).t().contiguous()
+    return xn_cm
+
+
 class _DeviceMapDriver(_DeviceDriver):
     """Runs the steps of a generic localisation context (rbpf_loc_generic_create) with the handles of a DeviceMap: the pair
     rbpf_loc_generic_ancestors_device / rbpf_loc_generic_step_device, the layout of every dy read off its strides."""
@@ -2094,15 +2119,128 @@ class _DeviceMapDriver(_DeviceDriver):
     def _step(self, t):
         torch, lib = self.torch, self.lib
         with torch.cuda.stream(self.stream):
-            ai, anc = C.c_void_p(), C.c_void_p()
-            check(lib.rbpf_loc_generic_ancestors_device(self.ctx, C.byref(ai), C.byref(anc)))
-            xn_cm = self._view(torch, anc, (self.N, self.nN), self.device)    # [n_nonlin x N_P] column-major; t = 0: the initial states
-            if t > 0:
-                xn_cm = self._dyn(t - 1, xn_cm.t()).t().contiguous()
+            xn_cm = _loc_generic_states(self, t)
             out = self._native_out()
             dy, layout = self._layout_of(self._meas(xn_cm.t(), out), out)
             self._keep = (xn_cm, dy)                                      # read in stream order by the step just enqueued
             check(lib.rbpf_loc_generic_step_device(self.ctx, C.c_void_p(xn_cm.data_ptr()), C.c_void_p(dy.data_ptr()), layout))
+
+
+class _LandmarkMapDriver(_SparseDeviceDriver):
+    """Runs the steps of a landmark-map localisation context (rbpf_loc_landmark_create) with the DeviceSparseHandles of a
+    DeviceLandmarkMap: measModel(xn, xl) with xl the context's rows of the map's mean."""
+
+    def __init__(self, lib, ctx, mp, prob):
+        self._setup(lib, ctx, mp.handles, (prob.nNonLin, mp.nLin, mp.ny, prob.N_P, prob.N_T), lib.rbpf_loc_generic_layout, prob)
+        xlp, ldx = C.c_void_p(), C.c_int32(0)
+        check(lib.rbpf_loc_landmark_map_device(ctx, C.byref(xlp), C.byref(ldx)))
+        self.xl = self._view(self.torch, xlp, (self.N, ldx.value), self.device)[:, :self.n]
+        self.torch.cuda.current_stream(self.device).synchronize()      # the constants, before the library's stream reads them
+
+    def _step(self, t):
+        torch, lib = self.torch, self.lib
+        with torch.cuda.stream(self.stream):
+            xn_cm = _loc_generic_states(self, t)
+            yhat, yl, dy, dl = self._layouts(*self._meas_sparse(xn_cm.t(), self.xl))
+            self._keep = (xn_cm, yhat, dy)                                # read in stream order by the step just enqueued
+            check(lib.rbpf_loc_landmark_step_device(self.ctx, C.c_void_p(xn_cm.data_ptr()), C.c_void_p(yhat.data_ptr()), yl,
+                                                    C.c_void_p(dy.data_ptr()), dl))
+
+    def yhattraj(self):
+        out = np.empty((self.d, self.T), order="F")
+        check(self.lib.rbpf_loc_landmark_yhattraj(self.ctx, _dp(out)))
+        return out
+
+
+def landmark_map_weights(yhat, dy, V, R, y, yhat_layout=2, dy_layout=2, ldx=None, pad=0.0, reps=1):
+    """rbpf_loc_landmark_weights, the kernel-level probe of localisation in a landmark map: yhat [N x n_y], dy [N x n_y x nLin] (the
+    handle's outputs for N particles), V [nLin x nLin] lower with V'V = P, R [n_y x n_y], y [n_y] with NaN = not observed ->
+    (S [N x M x M] = H_i(ind,:) P H_i(ind,:)' before R is added, logw [N], median kernel ms over `reps` launches), M the number of
+    observed outputs.  yhat_layout 0 / 2 and dy_layout 0 / 1 / 2: the memory layouts the arrays are handed over in; in dy layout 1
+    the columns behind nLin (row stride ldx, default the next multiple of 16) are filled with `pad`."""
+    lib = load_library()
+    dy = np.asarray(dy, dtype=np.float64)
+    if dy.ndim != 3:
+        raise ValueError("dy must be [N x n_y x nLin]")
+    N, d, n = dy.shape
+    yhat = np.asarray(yhat, dtype=np.float64)
+    if yhat.shape != (N, d):
+        raise ValueError("yhat must be [N x n_y]")
+    ybuf = np.asfortranarray(yhat) if yhat_layout == 0 else np.ascontiguousarray(yhat)
+    if dy_layout == 0:
+        buf = np.asfortranarray(dy)
+    elif dy_layout == 1:
+        ldx = (n + 15) // 16 * 16 if ldx is None else int(ldx)
+        buf = np.full((N, d, max(ldx, n)), float(pad))
+        buf[:, :, :n] = dy
+    else:
+        buf = np.ascontiguousarray(dy)
+    V = np.asfortranarray(np.asarray(V, dtype=np.float64))
+    R = np.asfortranarray(np.asarray(R, dtype=np.float64).reshape(d, d))
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
+    if V.shape != (n, n) or y.size != d:
+        raise ValueError("V must be [nLin x nLin] and y [n_y]")
+    M = int(np.count_nonzero(~np.isnan(y)))
+    S, logw = np.empty((N, M, M)), np.empty(N)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_landmark_weights(d, n, N, _dp(ybuf), int(yhat_layout), _dp(buf), int(dy_layout), int(ldx or 0), _dp(V), _dp(R),
+                                        _dp(y), _dp(S), _dp(logw), int(reps), C.byref(ms)))
+    return S, logw, ms.value
+
+
+class DeviceLandmarkMap(DeviceMap):
+    """A fixed landmark map of a sparseFeatures model whose handles are device code: the posterior N(mean, V'V) over the nLin
+    linear states, V lower, as the SLAM filter or smoother run with the same DeviceSparseHandles returns it (xl_max, P_max / XLK,
+    PK: from_posterior), and R [n_y x n_y], symmetric positive definite.  Accepted wherever a DeviceMap is
+    (particleFilterLocalization(landmark_map, None, ...), LocalizationSession, and with a DeviceTransition backward_simulate and
+    particleSmootherLocalization); the recursion is particleFilter.m:100-161 with the sparseFeatures branch of :127-137 and the map
+    frozen: per step, with ind the outputs whose y is not NaN and M their number,
+
+        e_i = y_t(ind)' - yhat_i(ind),   S_i = H_i(ind,:) P H_i(ind,:)' + R(ind,ind),
+        logw_i = -sum log diag chol S_i - |chol(S_i) \\ e_i|^2 / 2 - M log(2 pi) / 2
+
+    with (yhat, dy) = handles.measModel(xn, xl), called once per step with N_P columns and xl [N_P x nLin] the map's mean in every
+    row (the view the SLAM filter hands its handle, so the handle runs unchanged); rows of yhat / dy of outputs not observed may
+    hold anything.  Nothing observed: equal weights.  extras gains yhattraj [n_y x N_T], the handle's yhat of every step's
+    maximum-weight particle.  n_y 1 .. 32, nLin 1 .. 96, n_nonlin 1 .. 8; one GPU.  Not built: host closures, the MEX gateway,
+    sharding (n_devices is refused), nLin > 96, n_y > 32."""
+
+    _create = "rbpf_loc_landmark_create"
+
+    @staticmethod
+    def _check_handles(handles):
+        if not isinstance(handles, DeviceHandles):
+            raise TypeError("DeviceLandmarkMap needs a DeviceSparseHandles object")
+        if not isinstance(handles, DeviceSparseHandles):
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "DeviceLandmarkMap is built for sparseFeatures models (DeviceSparseHandles: "
+                                                       "measModel(xn, xl) -> (yhat, dy)); DeviceMap localises in the map of a dense model")
+
+    def _driver(self, lib, ctx, prob):
+        return _LandmarkMapDriver(lib, ctx, self, prob)
+
+    def predict(self, xn, reps=1):
+        """The map's prediction at the states xn [n_nonlin x n_pred] (numpy or a device tensor) with every output treated as
+        observed: (yhat [n_pred x n_y], the handle's, cov [n_pred x n_y x n_y] = H P H' without R, through the weight kernel on
+        its own).  measModel is called once, with n_pred columns."""
+        import torch
+        lib = load_library()
+        if lib.rbpf_device_count() < 1:
+            raise RBPFError(_ffi.RBPF_ERR_NO_DEVICE, "no HIP device: the localisation filter has no CPU fallback")
+        device = torch.device("cuda", torch.cuda.current_device())
+        xn = torch.as_tensor(xn, dtype=torch.float64, device=device)
+        xn = xn.reshape(-1, 1) if xn.dim() == 1 else xn
+        npred, d, n = xn.shape[1], self.ny, self.nLin
+        xl = torch.as_tensor(self.mean, device=device).repeat(npred, 1)
+        out = self.handles.measModel(xn, xl)
+        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(v) for v in out)):
+            raise ValueError("measModel must return (yhat, dy), two device tensors")
+        yhat, dy = out
+        if tuple(yhat.shape) != (npred, d) or tuple(dy.shape) != (npred, d, n) or yhat.dtype != torch.float64 or dy.dtype != torch.float64:
+            raise ValueError(f"measModel returned yhat {tuple(yhat.shape)} {yhat.dtype} and dy {tuple(dy.shape)} {dy.dtype}, expected "
+                             f"float64 tensors of shape {(npred, d)} and {(npred, d, n)}")
+        yhat = yhat.cpu().numpy()
+        S, _, _ = landmark_map_weights(yhat, dy.cpu().numpy(), self.V, self.R, np.zeros(d), reps=reps)
+        return yhat, S
 
 
 def _device_map(dynModel, measModel):
@@ -2120,12 +2258,12 @@ _NO_BACKWARD_IN_DEVICE_MAP = ("backward simulation needs the transition density 
 
 
 def _device_map_create(lib, mp, prob, rng, opt):
-    """rbpf_loc_generic_create -> (ctx, what must stay alive with it)."""
+    """rbpf_loc_generic_create (rbpf_loc_landmark_create for a landmark map) -> (ctx, what must stay alive with it)."""
     if isinstance(rng, ReplayRNG):                                # the handles draw their own normals: Z is not read
         rng = ReplayRNG(rng.U, np.zeros(rng.U.shape + (1,)))
     blk, keep = _rng_block(rng, prob.N_P, prob.N_T, 1, 1)
     ctx = C.c_void_p()
-    check(lib.rbpf_loc_generic_create(prob.nNonLin, mp.ny, mp.nLin, _dp(mp.mean), _dp(mp.V), _dp(mp.R), prob.N_P, prob.N_T, _dp(prob.y),
+    check(getattr(lib, mp._create)(prob.nNonLin, mp.ny, mp.nLin, _dp(mp.mean), _dp(mp.V), _dp(mp.R), prob.N_P, prob.N_T, _dp(prob.y),
                                       _dp(prob.x0), prob.x0.shape[1], C.byref(blk), C.byref(opt), C.byref(ctx)))
     return ctx, (blk, keep)
 
@@ -2151,7 +2289,8 @@ def particleFilterLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R
     xn_traj, traj_mean) is called after every step (:129-131).  A step whose weights sum to <= 1e-12 raises a RuntimeWarning
     with the reference's text (:113-115) and the run carries on.
     A DeviceMap as dynModel (measModel None) localises in the fixed map of an arbitrary device-code model (see DeviceMap): the same
-    outputs with n_nonlin rows in place of 7, yhattraj [n_y x N_T]; R is accepted and not used there either (the map's R counts)."""
+    outputs with n_nonlin rows in place of 7, yhattraj [n_y x N_T]; R is accepted and not used there either (the map's R counts).
+    A DeviceLandmarkMap likewise, for a sparseFeatures model (see there): makePlots gets the handle's yhattraj, extras gains it."""
     import warnings
     dmap = _device_map(dynModel, measModel)
     if dmap is not None:
@@ -2213,6 +2352,7 @@ def _device_map_localization(mp, odometry, y, x0_nonLin, Q, N_P, dt, makePlots, 
     lib = load_library()
     prob = _DeviceMapProblem(mp, odometry, y, x0_nonLin, Q, N_P, dt)
     N, T, nN = prob.N_P, prob.N_T, prob.nNonLin
+    landmark = isinstance(mp, DeviceLandmarkMap)                  # its driver keeps the handle's yhat of every step's best particle
     if lib.rbpf_device_count() < 1:
         raise RBPFError(_ffi.RBPF_ERR_NO_DEVICE, "no HIP device: the localisation filter has no CPU fallback")
     opt = _ffi.rbpf_options(keep_history=1, trace=1 if extras else 0, n_devices=int(n_devices), lazy_depth=int(lazy_depth))
@@ -2226,7 +2366,8 @@ def _device_map_localization(mp, odometry, y, x0_nonLin, Q, N_P, dt, makePlots, 
                 check(lib.rbpf_loc_finish(C.c_void_p(v.ctx), C.byref(o)))
                 xn_traj = np.zeros((nN, N, T))
                 xn_traj[:, :, :t + 1] = b["xn_traj"]
-                makePlots(b["final_xn"], b["traj_max"], np.full((prob.ny, T), np.nan), xn_traj, b["traj_mean"])
+                yhattraj = driver.yhattraj() if landmark else np.full((prob.ny, T), np.nan)
+                makePlots(b["final_xn"], b["traj_max"], yhattraj, xn_traj, b["traj_mean"])
                 return 0
             except Exception as exc:                                                      # noqa: BLE001
                 hook_error.append(exc)
@@ -2236,7 +2377,7 @@ def _device_map_localization(mp, odometry, y, x0_nonLin, Q, N_P, dt, makePlots, 
     ctx, _keep = _device_map_create(lib, mp, prob, rng, opt)      # (n_devices / lazy_depth: refused here, before anything is computed)
     try:
         try:
-            driver = _DeviceMapDriver(lib, ctx, mp, prob)          # (alive until the context is gone: it owns what the last step reads)
+            driver = mp._driver(lib, ctx, prob)                    # (alive until the context is gone: it owns what the last step reads)
             driver.advance(T)
         except RBPFError as exc:
             if exc.status == _ffi.RBPF_ERR_CALLBACK and hook_error:
@@ -2244,6 +2385,7 @@ def _device_map_localization(mp, odometry, y, x0_nonLin, Q, N_P, dt, makePlots, 
             raise
         o, b = _loc_out(N, T, T, extras, nN=nN)
         check(lib.rbpf_loc_finish(ctx, C.byref(o)))
+        yhattraj = driver.yhattraj() if landmark and extras else None
     finally:
         lib.rbpf_destroy(ctx)
     if o.first_degenerate_step >= 0:
@@ -2251,6 +2393,8 @@ def _device_map_localization(mp, odometry, y, x0_nonLin, Q, N_P, dt, makePlots, 
     if extras:
         ex = dict(logw=b["trace_logw"].T.copy(), w=b["trace_w"].T.copy(), ai=b["trace_ai"].T.copy(), xn=b["final_xn"],
                   xn_traj=b["xn_traj"], log_sum_w=b["log_sum_w"], first_degenerate_step=int(o.first_degenerate_step))
+        if landmark:
+            ex["yhattraj"] = yhattraj
         return b["traj_max"], b["traj_mean"], ex
     return b["traj_max"], b["traj_mean"]
 
@@ -2279,7 +2423,7 @@ class LocalizationSession:
             self.nN = self.prob.nNonLin
             self.ctx, self._rng = _device_map_create(self.lib, loc_map, self.prob, rng, self.opt)
             try:
-                self.driver = _DeviceMapDriver(self.lib, self.ctx, loc_map, self.prob)
+                self.driver = loc_map._driver(self.lib, self.ctx, self.prob)
             except Exception:
                 self.close()
                 raise
@@ -2309,6 +2453,8 @@ class LocalizationSession:
         o, b = _loc_out(self.prob.N_P, self.prob.N_T, self.tell(), extras, self.hist, bool(self.opt.trace), nN=self.nN)
         check(self.lib.rbpf_loc_finish(self.ctx, C.byref(o)))
         b["first_degenerate_step"] = int(o.first_degenerate_step)
+        if extras and isinstance(self.driver, _LandmarkMapDriver):
+            b["yhattraj"] = self.driver.yhattraj()
         return b
 
     def history(self):
