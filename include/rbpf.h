@@ -756,6 +756,10 @@ int rbpf_quat_helpers(int32_t op, int32_t n, const double* in, double* out);
  * folds + DPP row rotations) on its own, for the kernel-level test: in [4][64] (four values per lane of one wave64) -> out [4],
  * out[v] = sum over the 64 lanes of in[v][.] in the kernel's fixed association order.                                    */
 int rbpf_probe_wave_reduce(const double* in, double* out);
+/* The wave sums of the step kernel's body, four per register butterfly, beside the xor butterfly they replace: one wave64 sums
+ * nv (1 .. 36) vectors, in [nv][64] -> out_ref [nv] by the xor butterfly through LDS, out_packed [nv] by the packed form.  The two
+ * agree bit for bit (same lane pairs at every stage).                                                                   */
+int rbpf_probe_wave_sums_packed(int32_t nv, const double* in, double* out_ref, double* out_packed);
 
 /* ---- localisation in a fixed GP map (examples/mag-localization-mapping) --------------------------
  * particleFilterLocalization.m:84-132 with the closures of run_localization.m:241-281: a particle filter over the

@@ -153,7 +153,7 @@ EXPORTS = [
     "rbpf_filter_step_device", "rbpf_filter_set_device_callbacks",
     "rbpf_filter_sparse_gathered_device", "rbpf_filter_step_sparse_device", "rbpf_filter_sparse_yhattraj", "rbpf_particle_smoother_sparse_device", "rbpf_sparse_smoother_timing", "rbpf_sparse_ext_build_probe", "rbpf_timing_enable", "rbpf_timing_read", "rbpf_destroy",
     "rbpf_philox_fill", "rbpf_meas_model", "rbpf_dyn_model", "rbpf_dyn_res_norm", "rbpf_sample",
-    "rbpf_jacobian_phi3d", "rbpf_chol_weights", "rbpf_chol_sweep_probe", "rbpf_ext_pack_whiten_probe", "rbpf_quat_helpers", "rbpf_probe_wave_reduce",
+    "rbpf_jacobian_phi3d", "rbpf_chol_weights", "rbpf_chol_sweep_probe", "rbpf_ext_pack_whiten_probe", "rbpf_quat_helpers", "rbpf_probe_wave_reduce", "rbpf_probe_wave_sums_packed",
     "rbpf_shard_create", "rbpf_shard_views_get", "rbpf_shard_normalise_search", "rbpf_shard_pack", "rbpf_shard_step",
     "rbpf_shard_trajectories", "rbpf_shard_plan", "rbpf_shard_plan_read", "rbpf_shard_normalise_plan",
     "rbpf_stream_get", "rbpf_shard_set_async", "rbpf_shard_finish", "rbpf_shard_set_ancestors",

@@ -1765,6 +1765,18 @@ int rbpf_probe_wave_reduce(const double* in, double* out) {
   return RBPF_OK;
 }
 
+int rbpf_probe_wave_sums_packed(int32_t nv, const double* in, double* out_ref, double* out_packed) {
+  if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
+  if (nv < 1 || nv > 36 || !in || !out_ref || !out_packed) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }
+  DevicePool tmp; double *di = nullptr, *dref = nullptr, *dpk = nullptr;
+  RB_TRY(tmp.upload(&di, in, (size_t)nv * 64)); RB_TRY(tmp.alloc(&dref, (size_t)nv)); RB_TRY(tmp.alloc(&dpk, (size_t)nv));
+  HIPCHK(launch_probe_wave_sums_packed(nv, di, dref, dpk, 0));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out_ref, dref, (size_t)nv * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out_packed, dpk, (size_t)nv * 8, hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
 int rbpf_jacobian_phi3d(const rbpf_model* model, int32_t n_p, const double* x, const double* lower, const double* upper, double* J) {
   if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   if (!model || model->kind != RBPF_MODEL_DENSE_MAG_6D || !x || !lower || !upper || !J || n_p < 1) { set_error("bad argument"); return RBPF_ERR_INVALID_ARG; }

@@ -220,6 +220,8 @@ bool step_sym_shared_one_launch(const StepArgs& a);
 hipError_t launch_step_sym_shared(const StepArgs& a, hipStream_t s);
 // wave-level reduction primitives of the symmetric step kernel on their own (tests): in [4][64] -> out [4] lane sums
 hipError_t launch_probe_wave_reduce(const double* in, double* out, hipStream_t s);
+// nv = 1 .. 36 wave sums of one wave: in [nv][64] -> out_ref [nv] (wave_sum), out_packed [nv] (the step kernel's packed form)
+hipError_t launch_probe_wave_sums_packed(int nv, const double* in, double* out_ref, double* out_packed, hipStream_t s);
 
 // dynModel for all slots (must run before launch_step of the same StepArgs)
 hipError_t launch_propagate(const StepArgs& a, hipStream_t s);

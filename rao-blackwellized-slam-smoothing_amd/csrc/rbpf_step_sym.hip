@@ -171,16 +171,6 @@ __device__ __forceinline__ int sym_quad_row(int row, int lane) {
   const int rho = lane >> 4;
   return row * kSymChunk + 16 * ((rho & 1) * 2 + (rho >> 1)) + (lane & 15);
 }
-// wave_sum (rbpf_device.hpp) with the caller's lane index: the same butterfly, lane ^ 32, 16, .., 1, through ds_bpermute
-__device__ __forceinline__ double sym_wave_sum_lane(double v, int lane) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int at = (lane ^ off) << 2;
-    const int lo = __builtin_amdgcn_ds_bpermute(at, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(at, __double2hiint(v));
-    v += __hiloint2double(hi, lo);
-  }
-  return v;
-}
 // the value lane l holds (v_readlane on both halves: workgroup code that hands one lane's number to the wave)
 __device__ __forceinline__ double sym_lane_read(double v, int l) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
@@ -253,6 +243,30 @@ __device__ __forceinline__ double wave_sum4(double x0, double x1, double x2, dou
   return row16_sum(fold16(fold32(x0, x1), fold32(x2, x3)));
 }
 
+// The wave sums of NV per-lane values, four per butterfly (wave_sum4) and every butterfly in front of the first store: value 4 j + k
+// ends in row rho with (rho & 1) * 2 + (rho >> 1) == k, and lane 16 rho hands it to st(4 j + k, total) -- one predicated store per
+// group.  wave_sum4 pairs the lanes that wave_sum's xor butterfly pairs (32, 16, 8, 4, 2, 1; an add may see its operands swapped, and
+// after every stage all lanes of an xor class hold the same bits), so every total is wave_sum's, bit for bit.  A last group of one
+// to three values is filled up with its first value.
+template <int NV, typename St>
+__device__ __forceinline__ void wave_sums_packed(const double (&x)[NV], int lane, St&& st) {
+  constexpr int NGR = (NV + 3) / 4;
+  // (the lane index through an empty asm: the row, the store predicate and the slot addresses are then formed here and die here; taken
+  // from the lane id they are shared between the sums in front of the stream and those behind it and held across it -- the read-only
+  // kernels at eight tile rows with two, three, six and seven sets then spill a register, the mixed kernel with three sets two)
+  asm volatile("" : "+v"(lane));
+  double r[NGR];
+#pragma unroll
+  for (int j = 0; j < NGR; ++j)
+    r[j] = wave_sum4(x[4 * j], x[4 * j + 1 < NV ? 4 * j + 1 : 4 * j], x[4 * j + 2 < NV ? 4 * j + 2 : 4 * j], x[4 * j + 3 < NV ? 4 * j + 3 : 4 * j]);
+  const int rho = lane >> 4, k = (rho & 1) * 2 + (rho >> 1);
+  if ((lane & 15) == 0) {
+#pragma unroll
+    for (int j = 0; j < NGR; ++j)
+      if (4 * j + 3 < NV || 4 * j + k < NV) st(4 * j + k, r[j]);
+  }
+}
+
 __global__ void probe_wave_reduce_kernel(const double* __restrict__ in, double* __restrict__ out) {
   const int lane = threadIdx.x;
   const double r = wave_sum4(in[lane], in[64 + lane], in[128 + lane], in[192 + lane]);
@@ -262,6 +276,37 @@ __global__ void probe_wave_reduce_kernel(const double* __restrict__ in, double* 
 hipError_t launch_probe_wave_reduce(const double* in, double* out, hipStream_t s) {
   hipLaunchKernelGGL(probe_wave_reduce_kernel, dim3(1), dim3(64), 0, s, in, out);
   return hipGetLastError();
+}
+
+// one wave, NV values per lane (in[q * 64 + lane]): the NV totals by wave_sum (out_ref) and by wave_sums_packed (out_packed)
+template <int NV>
+__global__ void probe_wave_sums_packed_kernel(const double* __restrict__ in, double* __restrict__ out_ref, double* __restrict__ out_packed) {
+  const int lane = threadIdx.x;
+  double x[NV];
+#pragma unroll
+  for (int q = 0; q < NV; ++q) x[q] = in[q * 64 + lane];
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    const double s = wave_sum(x[q]);
+    if (lane == 0) out_ref[q] = s;
+  }
+  wave_sums_packed<NV>(x, lane, [&](int q, double s) { out_packed[q] = s; });
+}
+
+constexpr int kProbePackedMax = 36;
+template <int NV>
+static hipError_t launch_probe_packed_nv(int nv, const double* in, double* out_ref, double* out_packed, hipStream_t s) {
+  if (nv == NV) {
+    hipLaunchKernelGGL(probe_wave_sums_packed_kernel<NV>, dim3(1), dim3(64), 0, s, in, out_ref, out_packed);
+    return hipGetLastError();
+  }
+  if constexpr (NV < kProbePackedMax) return launch_probe_packed_nv<NV + 1>(nv, in, out_ref, out_packed, s);
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_probe_wave_sums_packed(int nv, const double* in, double* out_ref, double* out_packed, hipStream_t s) {
+  if (nv < 1 || nv > kProbePackedMax) return hipErrorInvalidValue;
+  return launch_probe_packed_nv<1>(nv, in, out_ref, out_packed, s);
 }
 
 // ---- one block column (64 columns = 32 pairs) of a wave's tiles ---------------------------------------------------------------

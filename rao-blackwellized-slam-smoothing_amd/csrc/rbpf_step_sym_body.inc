@@ -167,16 +167,8 @@
         for (int k = 0; k < D; ++k) kv[s * D + k] = Fs[s][(size_t)(D + k) * ldx + c];
       gcol(c, kv);
     }
-    // (the lane index through an empty asm: the six partner addresses of the butterfly are then formed here and die here; taken from
-    // the lane id they are shared with the wave sums behind the stream and held across it, six registers that the read-only kernels at
-    // eight tile rows do not have)
-    int lq = lane;
-    asm volatile("" : "+v"(lq));
-#pragma unroll
-    for (int q = 0; q < NG; ++q) {
-      const double s = sym_wave_sum_lane(g[q], lq);
-      if (lane == 0) red[wave * kSymRed + q] = s;
-    }
+    // (four sums per register butterfly, wave_sum's totals bit for bit: no LDS round trip, no partner address to keep out of the stream)
+    wave_sums_packed<NG>(g, lane, [&](int q, double s) { red[wave * kSymRed + q] = s; });
   }
 
   RBPF_SYM_KSTAMP(3);
@@ -371,10 +363,16 @@
       }
       if (WR) { dbl2s o; o.x = p[0]; o.y = p[1]; st_tile<TS>(dstb + c, o); }
     }
+    if constexpr (D > 1) {
+      wave_sums_packed<DE>(accb, lane, [&](int k, double s) { PHt[(size_t)k * ldx + b] = s; });
+    } else {
+      // dense-radio has no border rows (nb = 0 is a condition of its launch): this loop never runs there, and with the packed form in
+      // it the flushes with three and four sets took 134 and 149 registers instead of 122 and 120 (four -> three waves per SIMD)
 #pragma unroll
-    for (int k = 0; k < DE; ++k) {
-      const double s = wave_sum(accb[k]);
-      if (lane == 0) PHt[(size_t)k * ldx + b] = s;
+      for (int k = 0; k < DE; ++k) {
+        const double s = wave_sum(accb[k]);
+        if (lane == 0) PHt[(size_t)k * ldx + b] = s;
+      }
     }
   }
   if (NPH > 1 && cp > 0) {                                     // the other column phases: their row sums go through LDS
@@ -508,11 +506,7 @@
         part[D * D + D + 1] = fma(ivp, pivp, part[D * D + D + 1]);
       }
     }
-#pragma unroll
-    for (int q = 0; q < NRED; ++q) {
-      const double s = wave_sum(part[q]);
-      if (lane == 0) red[wave * kSymRed + q] = s;
-    }
+    wave_sums_packed<NRED>(part, lane, [&](int q, double s) { red[wave * kSymRed + q] = s; });
   }
   __syncthreads();
   if (wave == 0) {
@@ -618,11 +612,7 @@
     }
     if (E > 0) {
       __syncthreads();
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        const double s = wave_sum(uK[k]);
-        if (lane == 0) red[wave * kSymRed + k] = s;
-      }
+      wave_sums_packed<D>(uK, lane, [&](int k, double s) { red[wave * kSymRed + k] = s; });
       __syncthreads();
       if (tid == 0) {
         double u[D];
