@@ -930,8 +930,8 @@ int rbpf_loc_generic_weights(int32_t n_y, int32_t n_lin, int32_t n_p, const doub
  *        repeats the step's launches; *ms (may be NULL) = median time of one step by device events.
  * RBPF_ERR_STATE out of order (step without begin, begin twice, a step after the last); NULL arguments and bad sizes are
  * RBPF_ERR_INVALID_ARG before any device is touched; without a device RBPF_ERR_NO_DEVICE; the context stays usable after any
- * refusal.  rbpf_loc_backward_simulate keeps refusing a generic context.  Not built: densities that are not Gaussian in a wrapped
- * difference, n_res > 8, sharding.                                                                                              */
+ * refusal.  rbpf_loc_backward_simulate keeps refusing a generic context.  Not built: densities that are neither Gaussian in a wrapped
+ * difference nor the pose family below, n_res > 8, sharding.                                                                   */
 int rbpf_loc_generic_backward_begin(rbpf_ctx* ctx, int32_t n_traj, const double* u, uint64_t seed, int32_t n_res, const int32_t* rows,
                                     uint32_t angle_mask);
 int rbpf_loc_generic_backward_particles_device(rbpf_ctx* ctx, int32_t* t, const double** xn_dev);
@@ -941,6 +941,31 @@ int rbpf_loc_generic_backward_workspace_bytes(int32_t n_nonlin, int32_t n_res, i
 int rbpf_loc_generic_backward_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_res, const int32_t* rows, uint32_t angle_mask,
                                    const double* mu, const double* w, const double* xs_next, const double* cov, const double* u,
                                    int32_t* index, double* logp, int32_t reps, double* ms);
+
+/* ---- ... for pose states: a unit quaternion among the selected rows ----
+ * The same pass for a dynModel whose state holds a unit quaternion (q0, q1, q2, q3), scalar first (tools/q*.m), with the noise
+ * multiplied on the RIGHT of the predicted quaternion: x'_q = mu_q (x) expq(noise) (run_dense3D_magfield.m:202-203,
+ * run_localization.m:274-281).  rows [n_sel] names the selected state rows, the four of the block adjacent and in order at
+ * positions quat_pos .. quat_pos+3 of rows; the residual has n_res = n_sel - 1 entries, the block's place taken by three:
+ *     e = qInv(mu_q) (x) x'_q,   e <- -e if e0 < 0 (tools/logq.m:26-28),   phi = atan2(|e_v|, e0) e_v / |e_v|,  0 if |e_v| = 0
+ * (= logq(e) for a unit e), the other rows x'(rows[k]) - mu_k, wrapped where bit k of angle_mask is set: the bits index POSITIONS in
+ * rows.  mu_dev / mu is [n_sel][N_P]: its block rows are the predicted unit quaternion, composed with the odometry by the caller.
+ * cov [n_res x n_res] is in the caller's residual order (rows before the block, the block's three, rows behind it); the library
+ * evaluates the residual with the plain rows first and the block last and permutes cov symmetrically on the host to that order.
+ *   rbpf_loc_generic_backward_pose_begin   as _begin; then _particles_device, _step_device (mu_dev [n_sel][N_P]) and _finish as above.
+ *   rbpf_loc_generic_backward_pose_workspace_bytes   what it takes from the pool: Xhat has n_sel + 1 rows.
+ *   rbpf_loc_generic_backward_pose_step   the probe, mu [n_sel][N].
+ * With quat_pos = -1 the three are rbpf_loc_generic_backward_begin / _workspace_bytes / _step (n_sel = n_res), result for result.
+ * RBPF_ERR_INVALID_ARG, each with its message: a block that is not inside rows (quat_pos < -1 or >= n_sel), one that runs past
+ * n_sel, one that overlaps an angle bit, n_sel - 1 > 8.  One block, 0 .. 4 plain rows (n_sel 4 .. 8).  Not built: noise multiplied
+ * on the left, two blocks, noise through a non-square G.                                                                         */
+int rbpf_loc_generic_backward_pose_begin(rbpf_ctx* ctx, int32_t n_traj, const double* u, uint64_t seed, int32_t n_sel, const int32_t* rows,
+                                         uint32_t angle_mask, int32_t quat_pos);
+int rbpf_loc_generic_backward_pose_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T,
+                                                   int32_t n_traj, size_t* bytes);
+int rbpf_loc_generic_backward_pose_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                        int32_t quat_pos, const double* mu, const double* w, const double* xs_next, const double* cov,
+                                        const double* u, int32_t* index, double* logp, int32_t reps, double* ms);
 
 /* ---- localisation in the fixed landmark map of a generic device-code model ------------------------
  * The frozen-map filter above for a model of the sparseFeatures branch (particleFilter.m:100-161 with :127-137): the map posterior

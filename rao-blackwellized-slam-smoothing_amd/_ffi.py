@@ -168,6 +168,7 @@ EXPORTS = [
     "rbpf_loc_generic_weights",
     "rbpf_loc_generic_backward_begin", "rbpf_loc_generic_backward_particles_device", "rbpf_loc_generic_backward_step_device",
     "rbpf_loc_generic_backward_finish", "rbpf_loc_generic_backward_workspace_bytes", "rbpf_loc_generic_backward_step",
+    "rbpf_loc_generic_backward_pose_begin", "rbpf_loc_generic_backward_pose_workspace_bytes", "rbpf_loc_generic_backward_pose_step",
     "rbpf_loc_landmark_create", "rbpf_loc_landmark_map_device", "rbpf_loc_landmark_step_device", "rbpf_loc_landmark_yhattraj",
     "rbpf_loc_landmark_weights",
     "rbpf_ekf_dense", "rbpf_ekf_workspace_bytes",
@@ -318,6 +319,11 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_loc_generic_backward_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
     lib.rbpf_loc_generic_backward_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, c_double_p, c_double_p,
                                                    c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_generic_backward_pose_begin.argtypes = [C.c_void_p, C.c_int32, c_double_p, C.c_uint64, C.c_int32, c_int32_p, C.c_uint32, C.c_int32]
+    lib.rbpf_loc_generic_backward_pose_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                   C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_generic_backward_pose_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, C.c_int32, c_double_p,
+                                                        c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, C.c_int32, c_double_p]
     lib.rbpf_loc_landmark_create.argtypes = lib.rbpf_loc_generic_create.argtypes
     lib.rbpf_loc_landmark_map_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p]
     lib.rbpf_loc_landmark_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]

@@ -12,6 +12,7 @@
 //
 // Kernels of one step t (all in stream order), siblings of the bs_* kernels of rbpf_loc_smooth.hip:
 //   gs_prologue_kernel        Xhat[t] = (mu rows .., log w_i): n_res + 1 doubles per particle, SoA, shared by all M trajectories.
+//                             (gs_prologue_pose_kernel: the n_sel rows of mu in kernel order, see POSE STATES below.)
 //   gs_pass_kernel<NR, ANG>   all pairs.  Grid = (trajectory blocks of 256) x (particle chunks of C); a lane owns one trajectory,
 //                             keeps its selected rows in registers and a running (max, sum) pair; the particles come in tiles of 256
 //                             through LDS as [particle][NR + 1] and are read as broadcasts.  No cross-lane operation.  The partial
@@ -21,6 +22,17 @@
 //                             (gs_term, explicit fma throughout: no contraction is left to the compiler), gather all n_nonlin rows.
 //   gs_mean_kernel            traj_smooth_mean[:, t] = plain means over j of all n_nonlin rows.
 //   gs_logp_kernel<NR, ANG>   the probe's second output.
+//
+// POSE STATES (rbpf_loc_generic_backward_pose_*): four of the selected rows may be a unit quaternion (q0 .. q3, scalar first), whose
+// noise multiplies the predicted quaternion mu_q on the right (run_dense3D_magfield.m:202-203, run_localization.m:274-281).  In
+// the block's place the residual has the three entries
+//     e = qInv(mu_q) (x) x'_q,   e <- -e if e0 < 0,   phi = atan2(|e_v|, e0) e_v / |e_v|   (phi = 0 if |e_v| = 0)
+// = logq(e) of tools/logq.m for a unit e, in the form of rbpf_loc_smooth.hip.  n_sel = n_res + 1 rows are selected, Xhat and the
+// LDS tile hold n_sel + 1 doubles per particle.  KERNEL ORDER: the plain rows first, in the caller's order, the block last; the
+// host permutes rows, the angle bits, the rows of mu (in the prologue) and cov (symmetrically, before the factorisation) to it --
+// z'z does not depend on the order.  W is lower triangular, so the plain rows of z are final before the block is touched, and the
+// skip test sits there, after all NP plain rows and before the quaternion product and atan2 (NP = 0: no test).  The template
+// parameter QP of the kernels is NP with a block and -1 without one; with -1 every kernel is the code it was (gs_term).
 //
 // SUMMATION ORDER: that of rbpf_loc_smooth.hip's header, statement by statement -- chunk size from (N, M) only, ascending i inside
 // a chunk, chunk partials merged in ascending c, the walk and its carry-over, the clamped-draw counter, w_i = 0 never selected.
@@ -106,18 +118,89 @@ __device__ __forceinline__ bool gs_term(const GsW& W, unsigned amask, const doub
   return true;
 }
 
-template <int NR, bool ANG>
+struct GsSrc { int s[kGsMaxRes]; };        // kernel row k of Xhat is row s[k] of the caller's mu
+
+// the prologue of a transition with a quaternion block: NS = n_sel rows of mu, taken in kernel order
+__global__ void gs_prologue_pose_kernel(int N, int NS, GsSrc src, const double* __restrict__ mu, const double* __restrict__ w,
+                                        double* __restrict__ Xhat) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  for (int k = 0; k < NS; ++k) Xhat[(size_t)k * N + i] = mu ? mu[(size_t)src.s[k] * N + i] : 0.0;
+  const double wi = w[i];
+  Xhat[(size_t)NS * N + i] = wi > 0.0 ? log(wi) : -INFINITY;
+}
+
+// gs_term with a quaternion block behind NP plain rows: h = (NP predicted plain rows, the predicted unit quaternion, log w),
+// x = the trajectory's NP plain rows and its quaternion; NR = NP + 3 residuals.  false: the plain rows alone put the pair below
+// `bound` (NP >= 1 only).  Every product-sum is an explicit fma; e = qLeft(qInv(mu_q)) x_q (tools/qLeft.m:30-35, qInv.m:27-31)
+// is summed left to right, as bs_rot_term writes it.
+template <int NP, bool ANG>
+__device__ __forceinline__ bool gs_pose_term(const GsW& W, unsigned amask, const double* h, const double (&x)[NP + 4], double bound, double& l) {
+  constexpr int NR = NP + 3;
+  double r[NR];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    double d = x[k] - h[k];
+    if (ANG && ((amask >> k) & 1u)) d = fma(-kGsTwoPi, rint(d / kGsTwoPi), d);
+    r[k] = d;
+  }
+  double q = 0.0;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    double z = W.w[k * (k + 1) / 2] * r[0];
+#pragma unroll
+    for (int c = 1; c <= k; ++c) z = fma(W.w[k * (k + 1) / 2 + c], r[c], z);
+    q = fma(z, z, q);
+  }
+  if (NP >= 1 && fma(-0.5, q, l) < bound) return false;
+  const double a0 = h[NP], a1 = -h[NP + 1], a2 = -h[NP + 2], a3 = -h[NP + 3];
+  const double x0 = x[NP], x1 = x[NP + 1], x2 = x[NP + 2], x3 = x[NP + 3];
+  double e0 = fma(-a3, x3, fma(-a2, x2, fma(-a1, x1, a0 * x0)));
+  double e1 = fma(a2, x3, fma(-a3, x2, fma(a0, x1, a1 * x0)));
+  double e2 = fma(-a1, x3, fma(a0, x2, fma(a3, x1, a2 * x0)));
+  double e3 = fma(a0, x3, fma(a1, x2, fma(-a2, x1, a3 * x0)));
+  if (e0 < 0.0) { e0 = -e0; e1 = -e1; e2 = -e2; e3 = -e3; }                       // tools/logq.m:26-28
+  const double nv = sqrt(fma(e3, e3, fma(e2, e2, e1 * e1)));
+  const double f = (nv == 0.0) ? 1.0 : atan2(nv, e0) / nv;
+  r[NP] = f * e1; r[NP + 1] = f * e2; r[NP + 2] = f * e3;
+#pragma unroll
+  for (int k = NP; k < NR; ++k) {
+    double z = W.w[k * (k + 1) / 2] * r[0];
+#pragma unroll
+    for (int c = 1; c <= k; ++c) z = fma(W.w[k * (k + 1) / 2 + c], r[c], z);
+    q = fma(z, z, q);
+  }
+  l = fma(-0.5, q, l);
+  return true;
+}
+
+// QP < 0: NR selected rows and gs_term; QP = NP >= 0: a quaternion block behind NP plain rows (NR = NP + 3, NR + 1 selected rows)
+// kLocate: the launch bound of the locate kernel.  It is launched with 64 threads; stating that for the block's instantiations
+// lifts the 128-VGPR cap of the default bound (1024), under which NP = 4 spilled 12 bytes; without a block the default stays.
+template <int NR, int QP> struct GsSel {
+  static constexpr int NS = QP < 0 ? NR : NR + 1;
+  static constexpr int kLocate = QP < 0 ? 1024 : 64;
+};
+
+template <int NR, bool ANG, int QP>
+__device__ __forceinline__ bool gs_pair(const GsW& W, unsigned amask, const double* h, const double (&x)[GsSel<NR, QP>::NS], double bound, double& l) {
+  if constexpr (QP < 0) return gs_term<NR, ANG>(W, amask, h, x, bound, l);
+  else return gs_pose_term<QP, ANG>(W, amask, h, x, bound, l);
+}
+
+template <int NR, bool ANG, int QP = -1>
 __global__ __launch_bounds__(kGsTile) void gs_pass_kernel(const GsArgs a) {
-  constexpr int S = NR + 1;
-  __shared__ double tile[kGsTile * S];     // [particle][NR + 1]
+  constexpr int NS = GsSel<NR, QP>::NS;
+  constexpr int S = NS + 1;
+  __shared__ double tile[kGsTile * S];     // [particle][NS + 1]
   const int tid = threadIdx.x;
   const int j = blockIdx.x * kGsTile + tid;
   const int jl = min(j, a.M - 1);          // lanes past the end recompute the last trajectory; nothing of theirs is stored
   const int c = blockIdx.y;
   const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
-  double x[NR];
+  double x[NS];
 #pragma unroll
-  for (int k = 0; k < NR; ++k) x[k] = a.first ? 0.0 : a.xs_next[(size_t)jl * a.nN + a.rows[k]];
+  for (int k = 0; k < NS; ++k) x[k] = a.first ? 0.0 : a.xs_next[(size_t)jl * a.nN + a.rows[k]];
   double m = -INFINITY, s = 0.0;
   for (int base = i0; base < i1; base += kGsTile) {
     const int cnt = min(kGsTile, i1 - base);
@@ -129,9 +212,9 @@ __global__ __launch_bounds__(kGsTile) void gs_pass_kernel(const GsArgs a) {
     __syncthreads();
     for (int k = 0; k < cnt; ++k) {
       const double* h = tile + k * S;
-      double l = h[NR];
+      double l = h[NS];
       if (!a.first) {
-        if (!gs_term<NR, ANG>(a.W, a.angle_mask, h, x, m - kGsSkip, l)) continue;
+        if (!gs_pair<NR, ANG, QP>(a.W, a.angle_mask, h, x, m - kGsSkip, l)) continue;
       }
       if (l == -INFINITY) continue;
       const double d = l - m;
@@ -146,13 +229,14 @@ __global__ __launch_bounds__(kGsTile) void gs_pass_kernel(const GsArgs a) {
   }
 }
 
-template <int NR, bool ANG>
-__global__ void gs_locate_kernel(const GsArgs a) {
+template <int NR, bool ANG, int QP = -1>
+__global__ __launch_bounds__((GsSel<NR, QP>::kLocate)) void gs_locate_kernel(const GsArgs a) {
+  constexpr int NS = GsSel<NR, QP>::NS;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= a.M) return;
-  double x[NR];
+  double x[NS];
 #pragma unroll
-  for (int k = 0; k < NR; ++k) x[k] = a.first ? 0.0 : a.xs_next[(size_t)j * a.nN + a.rows[k]];
+  for (int k = 0; k < NS; ++k) x[k] = a.first ? 0.0 : a.xs_next[(size_t)j * a.nN + a.rows[k]];
   double Mx = -INFINITY;
   for (int c = 0; c < a.nchunks; ++c) Mx = fmax(Mx, a.part_m[(size_t)c * a.M + j]);
   int idx = -1;
@@ -177,14 +261,14 @@ __global__ void gs_locate_kernel(const GsArgs a) {
       if (!(a.part_s[(size_t)c * a.M + j] > 0.0)) continue;
       const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
       for (int i = i0; i < i1; ++i) {
-        double h[NR + 1];
-        h[NR] = a.Xhat[(size_t)NR * a.N + i];
-        if (h[NR] == -INFINITY) continue;
-        double l = h[NR];
+        double h[NS + 1];
+        h[NS] = a.Xhat[(size_t)NS * a.N + i];
+        if (h[NS] == -INFINITY) continue;
+        double l = h[NS];
         if (!a.first) {
 #pragma unroll
-          for (int r = 0; r < NR; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
-          if (!gs_term<NR, ANG>(a.W, a.angle_mask, h, x, Mx - kGsSkip, l)) continue;
+          for (int r = 0; r < NS; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
+          if (!gs_pair<NR, ANG, QP>(a.W, a.angle_mask, h, x, Mx - kGsSkip, l)) continue;
         }
         const double term = exp(l - Mx);
         if (!(term > 0.0)) continue;
@@ -200,7 +284,7 @@ __global__ void gs_locate_kernel(const GsArgs a) {
   }
   if (idx < 0) {                                   // no non-zero term at all: the last particle with a non-zero weight
     for (int i = a.N - 1; i >= 0 && idx < 0; --i)
-      if (a.Xhat[(size_t)NR * a.N + i] > -INFINITY) idx = i;
+      if (a.Xhat[(size_t)NS * a.N + i] > -INFINITY) idx = i;
     if (idx < 0) idx = a.N - 1;
   }
   a.index[j] = idx;
@@ -233,19 +317,20 @@ __global__ __launch_bounds__(256) void gs_mean_kernel(int M, int nN, const doubl
 }
 
 // logp of every pair, without log w: out [N x M] column-major (the probe's second output)
-template <int NR, bool ANG>
+template <int NR, bool ANG, int QP = -1>
 __global__ void gs_logp_kernel(const GsArgs a, double* __restrict__ out) {
+  constexpr int NS = GsSel<NR, QP>::NS;
   const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= (size_t)a.N * a.M) return;
   const int i = (int)(q % a.N), j = (int)(q / a.N);
-  double h[NR + 1], x[NR];
+  double h[NS + 1], x[NS];
 #pragma unroll
-  for (int r = 0; r < NR; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
-  h[NR] = 0.0;
+  for (int r = 0; r < NS; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
+  h[NS] = 0.0;
 #pragma unroll
-  for (int k = 0; k < NR; ++k) x[k] = a.xs_next[(size_t)j * a.nN + a.rows[k]];
+  for (int k = 0; k < NS; ++k) x[k] = a.xs_next[(size_t)j * a.nN + a.rows[k]];
   double l = 0.0;
-  gs_term<NR, ANG>(a.W, a.angle_mask, h, x, -INFINITY, l);
+  gs_pair<NR, ANG, QP>(a.W, a.angle_mask, h, x, -INFINITY, l);
   out[q] = l;
 }
 
@@ -258,15 +343,15 @@ __global__ void gs_philox_kernel(unsigned long long seed, int T, int M, double* 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-template <int NR, bool ANG>
+template <int NR, bool ANG, int QP = -1>
 static hipError_t gs_launch_nr(const GsArgs& a, double* logp, hipStream_t s) {
   if (logp) {
     const size_t cnt = (size_t)a.N * a.M;
-    hipLaunchKernelGGL((gs_logp_kernel<NR, ANG>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, a, logp);
+    hipLaunchKernelGGL((gs_logp_kernel<NR, ANG, QP>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, a, logp);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL((gs_pass_kernel<NR, ANG>), dim3((a.M + kGsTile - 1) / kGsTile, a.nchunks), dim3(kGsTile), 0, s, a);
-  hipLaunchKernelGGL((gs_locate_kernel<NR, ANG>), dim3((a.M + 63) / 64), dim3(64), 0, s, a);
+  hipLaunchKernelGGL((gs_pass_kernel<NR, ANG, QP>), dim3((a.M + kGsTile - 1) / kGsTile, a.nchunks), dim3(kGsTile), 0, s, a);
+  hipLaunchKernelGGL((gs_locate_kernel<NR, ANG, QP>), dim3((a.M + 63) / 64), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -275,9 +360,28 @@ static hipError_t gs_launch_ang(const GsArgs& a, double* logp, hipStream_t s) {
   return a.angle_mask ? gs_launch_nr<NR, true>(a, logp, s) : gs_launch_nr<NR, false>(a, logp, s);
 }
 
+// a quaternion block behind NP plain rows; an angle row is one of those
+template <int NP>
+static hipError_t gs_launch_pose(const GsArgs& a, double* logp, hipStream_t s) {
+  if constexpr (NP > 0) {
+    if (a.angle_mask) return gs_launch_nr<NP + 3, true, NP>(a, logp, s);
+  }
+  return gs_launch_nr<NP + 3, false, NP>(a, logp, s);
+}
+
 // all-pairs pass + locate of one step (logp == null), or the logp kernel, in stream order
-static hipError_t gs_launch(int n_res, const GsArgs& a, double* logp, hipStream_t s) {
-  switch (n_res) {
+static hipError_t gs_launch(const LocGenLayout& y, const GsArgs& a, double* logp, hipStream_t s) {
+  if (y.n_plain >= 0) {
+    switch (y.n_plain) {
+      case 0: return gs_launch_pose<0>(a, logp, s);
+      case 1: return gs_launch_pose<1>(a, logp, s);
+      case 2: return gs_launch_pose<2>(a, logp, s);
+      case 3: return gs_launch_pose<3>(a, logp, s);
+      case 4: return gs_launch_pose<4>(a, logp, s);
+      default: return hipErrorInvalidValue;
+    }
+  }
+  switch (y.n_res) {
     case 1: return gs_launch_ang<1>(a, logp, s);
     case 2: return gs_launch_ang<2>(a, logp, s);
     case 3: return gs_launch_ang<3>(a, logp, s);
@@ -291,9 +395,15 @@ static hipError_t gs_launch(int n_res, const GsArgs& a, double* logp, hipStream_
 }
 
 // prologue + pass + locate of one step
-static hipError_t gs_launch_step(int n_res, const GsArgs& a, const double* mu, const double* w, double* Xhat, hipStream_t s) {
-  hipLaunchKernelGGL(gs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, n_res, mu, w, Xhat);
-  return gs_launch(n_res, a, nullptr, s);
+static hipError_t gs_launch_step(const LocGenLayout& y, const GsArgs& a, const double* mu, const double* w, double* Xhat, hipStream_t s) {
+  if (y.n_plain >= 0) {
+    GsSrc src;
+    for (int k = 0; k < kGsMaxRes; ++k) src.s[k] = y.src[k];
+    hipLaunchKernelGGL(gs_prologue_pose_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, y.n_sel, src, mu, w, Xhat);
+  } else {
+    hipLaunchKernelGGL(gs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, y.n_res, mu, w, Xhat);
+  }
+  return gs_launch(y, a, nullptr, s);
 }
 
 static int gs_validate_rows(int n_nonlin, int n_res, const int32_t* rows, uint32_t angle_mask) {
@@ -307,6 +417,34 @@ static int gs_validate_rows(int n_nonlin, int n_res, const int32_t* rows, uint32
     seen |= 1u << rows[k];
   }
   if (angle_mask >> n_res) { set_error("angle_mask has a bit at or above n_res: an angle row must be one of rows"); return RBPF_ERR_INVALID_ARG; }
+  return RBPF_OK;
+}
+
+// validates (rows [n_sel], angle_mask over the positions in rows, quat_pos = the position of q0 in rows or -1) and lays them out
+// for the kernels
+static int gs_layout(int n_nonlin, int n_sel, const int32_t* rows, uint32_t angle_mask, int quat_pos, LocGenLayout& y) {
+  y = LocGenLayout();
+  if (quat_pos == -1) {
+    RB_TRY(gs_validate_rows(n_nonlin, n_sel, rows, angle_mask));
+    y.n_sel = y.n_res = n_sel; y.angle_mask = angle_mask;
+    for (int k = 0; k < n_sel; ++k) y.rows[k] = rows[k];
+    return RBPF_OK;
+  }
+  if (n_sel - 1 > kGsMaxRes) { set_error("n_res = n_sel - 1 = " + std::to_string(n_sel - 1) + " residuals: n_res must be in 1 .. 8"); return RBPF_ERR_INVALID_ARG; }
+  if (quat_pos < -1 || quat_pos >= n_sel) { set_error("quat_pos = " + std::to_string(quat_pos) + ": the quaternion block is not inside rows (positions 0 .. n_sel-1, or -1 for none)"); return RBPF_ERR_INVALID_ARG; }
+  if (quat_pos + 4 > n_sel) { set_error("the quaternion block (positions " + std::to_string(quat_pos) + " .. " + std::to_string(quat_pos + 3) + " of rows) runs past n_sel = " + std::to_string(n_sel)); return RBPF_ERR_INVALID_ARG; }
+  RB_TRY(gs_validate_rows(n_nonlin, n_sel, rows, angle_mask));        // (n_sel <= 8 from here on: the rows are distinct)
+  if (angle_mask & (0xFu << quat_pos)) { set_error("angle_mask marks a row of the quaternion block: its residual is logq, not a wrapped difference"); return RBPF_ERR_INVALID_ARG; }
+  y.n_sel = n_sel; y.n_res = n_sel - 1; y.n_plain = n_sel - 4;
+  int k = 0;
+  for (int p = 0; p < n_sel; ++p) {
+    if (p >= quat_pos && p < quat_pos + 4) continue;
+    y.rows[k] = rows[p]; y.src[k] = p; y.perm[k] = p < quat_pos ? p : p - 1;
+    if ((angle_mask >> p) & 1u) y.angle_mask |= 1u << k;
+    ++k;
+  }
+  for (int q = 0; q < 4; ++q) { y.rows[k + q] = rows[quat_pos + q]; y.src[k + q] = quat_pos + q; }
+  for (int q = 0; q < 3; ++q) y.perm[k + q] = quat_pos + q;
   return RBPF_OK;
 }
 
@@ -331,6 +469,20 @@ static int gs_factor(const double* cov, int n, GsW& W, const std::string& where)
   return RBPF_OK;
 }
 
+// gs_factor of cov in kernel order: cov_k(a, b) = cov(perm[a], perm[b]), the symmetric permutation (z'z is the same quadratic form)
+static int gs_factor_layout(const double* cov, const LocGenLayout& y, GsW& W, const std::string& where) {
+  if (y.n_plain < 0) return gs_factor(cov, y.n_res, W, where);
+  const int n = y.n_res;
+  double P[kGsMaxRes * kGsMaxRes];
+  for (int b = 0; b < n; ++b)
+    for (int a = b; a < n; ++a) {                  // the caller's lower triangle is the one read
+      const int i = std::max(y.perm[a], y.perm[b]), j = std::min(y.perm[a], y.perm[b]);
+      P[a + n * b] = P[b + n * a] = cov[i + n * j];
+    }
+  return gs_factor(P, n, W, where);
+}
+
+// NR: the rows of mu (n_res, or n_sel with a quaternion block); Xhat has one more
 static size_t gs_bytes(size_t nN, size_t NR, size_t N, size_t T, size_t M) {
   const size_t C = (size_t)gs_chunk_size((int)N, (int)M), nch = (N + C - 1) / C;
   return ((NR + 1) * N + 2 * nch * M + T * M + T * nN * M + nN * T) * sizeof(double) + T * M * sizeof(int);
@@ -366,12 +518,32 @@ int rbpf_loc_generic_backward_workspace_bytes(int32_t n_nonlin, int32_t n_res, i
   return RBPF_OK;
 }
 
+int rbpf_loc_generic_backward_pose_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T,
+                                                   int32_t n_traj, size_t* bytes) {
+  if (quat_pos == -1) return rbpf_loc_generic_backward_workspace_bytes(n_nonlin, n_sel, N_P, N_T, n_traj, bytes);
+  if (!bytes) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (n_nonlin < 4 || n_nonlin > kGsMaxNonlin || n_sel < 4 || n_sel > n_nonlin || quat_pos < 0 || quat_pos + 4 > n_sel) {
+    set_error("with a quaternion block n_nonlin must be in 4 .. 8, n_sel in 4 .. n_nonlin and the block inside the n_sel rows");
+    return RBPF_ERR_INVALID_ARG;
+  }
+  if (N_P < 1 || N_T < 1 || n_traj < 1) { set_error("N_P, N_T and n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P > kMaxParticles) { set_error("N_P above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  *bytes = gs_bytes((size_t)n_nonlin, (size_t)n_sel, (size_t)N_P, (size_t)N_T, (size_t)n_traj);
+  return RBPF_OK;
+}
+
 int rbpf_loc_generic_backward_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, int32_t n_res, const int32_t* rows,
                                     uint32_t angle_mask) {
+  return rbpf_loc_generic_backward_pose_begin(c, n_traj, u, seed, n_res, rows, angle_mask, -1);
+}
+
+int rbpf_loc_generic_backward_pose_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, int32_t n_sel, const int32_t* rows,
+                                         uint32_t angle_mask, int32_t quat_pos) {
   RB_TRY(gs_ctx_ok(c));
   LocState* L = c->loc;
   if (n_traj < 1) { set_error("n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
-  RB_TRY(gs_validate_rows(L->nN, n_res, rows, angle_mask));
+  LocGenLayout lay;
+  RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (!c->opt.keep_history || !c->opt.trace) {
     set_error("backward simulation reads the stored particles and weights: create the context with keep_history = 1 and trace = 1");
@@ -391,12 +563,11 @@ int rbpf_loc_generic_backward_begin(rbpf_ctx* c, int32_t n_traj, const double* u
       }
   }
   LocGenBackward& g = L->gb;
-  g.M = M; g.n_res = n_res; g.angle_mask = angle_mask;
+  g.M = M; g.lay = lay;
   g.C = gs_chunk_size(N, M); g.nch = (N + g.C - 1) / g.C;
-  for (int k = 0; k < n_res; ++k) g.rows[k] = rows[k];
   auto fail = [&](int s) { gs_release(c); return s; };
   int s;
-  if ((s = c->pool.alloc(&g.d_Xhat, (size_t)(n_res + 1) * N)) != RBPF_OK) return fail(s);
+  if ((s = c->pool.alloc(&g.d_Xhat, (size_t)(lay.n_sel + 1) * N)) != RBPF_OK) return fail(s);
   if ((s = c->pool.alloc(&g.d_pm, (size_t)g.nch * M)) != RBPF_OK) return fail(s);
   if ((s = c->pool.alloc(&g.d_ps, (size_t)g.nch * M)) != RBPF_OK) return fail(s);
   if ((s = c->pool.alloc(&g.d_u, (size_t)T * M)) != RBPF_OK) return fail(s);
@@ -440,16 +611,16 @@ int rbpf_loc_generic_backward_step_device(rbpf_ctx* c, const double* mu_dev, con
   a.first = (t == T - 1);
   if (!a.first) {
     if (!mu_dev || !cov) { set_error("NULL argument (mu_dev and cov may be NULL at step N_T-1 only)"); return RBPF_ERR_INVALID_ARG; }
-    RB_TRY(gs_factor(cov, g.n_res, a.W, " of step " + std::to_string(t)));
+    RB_TRY(gs_factor_layout(cov, g.lay, a.W, " of step " + std::to_string(t)));
   }
   HIPCHK(hipSetDevice(c->device));
-  a.N = N; a.M = M; a.C = g.C; a.nchunks = g.nch; a.nN = nN; a.angle_mask = g.angle_mask;
-  for (int k = 0; k < g.n_res; ++k) a.rows[k] = g.rows[k];
+  a.N = N; a.M = M; a.C = g.C; a.nchunks = g.nch; a.nN = nN; a.angle_mask = g.lay.angle_mask;
+  for (int k = 0; k < g.lay.n_sel; ++k) a.rows[k] = g.lay.rows[k];
   a.Xhat = g.d_Xhat; a.X = c->X + (size_t)t * nN * N;
   a.xs_next = a.first ? nullptr : g.d_xs + (size_t)(t + 1) * nN * M;
   a.u = g.d_u + (size_t)t * M; a.part_m = g.d_pm; a.part_s = g.d_ps;
   a.index = g.d_idx + (size_t)t * M; a.xs = g.d_xs + (size_t)t * nN * M; a.clamped = c->d_flags + 1;
-  HIPCHK(gs_launch_step(g.n_res, a, a.first ? nullptr : mu_dev, c->w + (size_t)t * N, g.d_Xhat, c->stream));
+  HIPCHK(gs_launch_step(g.lay, a, a.first ? nullptr : mu_dev, c->w + (size_t)t * N, g.d_Xhat, c->stream));
   hipLaunchKernelGGL(gs_mean_kernel, dim3(1), dim3(256), 0, c->stream, M, nN, a.xs, g.d_mean + (size_t)t * nN);
   HIPCHK(hipGetLastError());
   g.t = t - 1;
@@ -480,31 +651,38 @@ int rbpf_loc_generic_backward_finish(rbpf_ctx* c, double* xs_traj, int32_t* inde
 int rbpf_loc_generic_backward_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_res, const int32_t* rows, uint32_t angle_mask,
                                    const double* mu, const double* w, const double* xs_next, const double* cov, const double* u,
                                    int32_t* index, double* logp, int32_t reps, double* ms) {
+  return rbpf_loc_generic_backward_pose_step(N, M, n_nonlin, n_res, rows, angle_mask, -1, mu, w, xs_next, cov, u, index, logp, reps, ms);
+}
+
+int rbpf_loc_generic_backward_pose_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                        int32_t quat_pos, const double* mu, const double* w, const double* xs_next, const double* cov,
+                                        const double* u, int32_t* index, double* logp, int32_t reps, double* ms) {
   if (!mu || !w || !xs_next || !cov || !u || !index || !rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
   if (N > kMaxParticles) { set_error("N above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
-  RB_TRY(gs_validate_rows(n_nonlin, n_res, rows, angle_mask));
+  LocGenLayout lay;
+  RB_TRY(gs_layout(n_nonlin, n_sel, rows, angle_mask, quat_pos, lay));
   GsArgs a;
   std::memset(&a, 0, sizeof(a));
-  RB_TRY(gs_factor(cov, n_res, a.W, ""));
+  RB_TRY(gs_factor_layout(cov, lay, a.W, ""));
   if (!have_device()) { set_error("no HIP device: the backward pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
   const int C = gs_chunk_size(N, M), nch = (N + C - 1) / C;
   DevicePool tmp;
   double *d_mu = nullptr, *d_w = nullptr, *d_xs = nullptr, *d_u = nullptr, *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_lp = nullptr;
   int *d_idx = nullptr, *d_clamped = nullptr;
-  RB_TRY(tmp.upload(&d_mu, mu, (size_t)n_res * N));
+  RB_TRY(tmp.upload(&d_mu, mu, (size_t)lay.n_sel * N));
   RB_TRY(tmp.upload(&d_w, w, (size_t)N));
   RB_TRY(tmp.upload(&d_xs, xs_next, (size_t)n_nonlin * M));
   RB_TRY(tmp.upload(&d_u, u, (size_t)M));
-  RB_TRY(tmp.alloc(&d_Xhat, (size_t)(n_res + 1) * N));
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)(lay.n_sel + 1) * N));
   RB_TRY(tmp.alloc(&d_pm, (size_t)nch * M));
   RB_TRY(tmp.alloc(&d_ps, (size_t)nch * M));
   RB_TRY(tmp.alloc(&d_idx, (size_t)M));
   RB_TRY(tmp.alloc(&d_clamped, (size_t)1));
   HIPCHK(hipMemset(d_clamped, 0, sizeof(int)));
   if (logp) RB_TRY(tmp.alloc(&d_lp, (size_t)N * M));
-  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.nN = n_nonlin; a.first = 0; a.angle_mask = angle_mask;
-  for (int k = 0; k < n_res; ++k) a.rows[k] = rows[k];
+  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.nN = n_nonlin; a.first = 0; a.angle_mask = lay.angle_mask;
+  for (int k = 0; k < lay.n_sel; ++k) a.rows[k] = lay.rows[k];
   a.Xhat = d_Xhat; a.X = nullptr; a.xs_next = d_xs; a.u = d_u; a.part_m = d_pm; a.part_s = d_ps; a.index = d_idx; a.xs = nullptr;
   a.clamped = d_clamped;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -515,10 +693,10 @@ int rbpf_loc_generic_backward_step(int32_t N, int32_t M, int32_t n_nonlin, int32
       HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
       ev.emplace_back(e0, e1);
       HIPCHK(hipEventRecord(e0, 0));
-      HIPCHK(gs_launch_step(n_res, a, d_mu, d_w, d_Xhat, 0));
+      HIPCHK(gs_launch_step(lay, a, d_mu, d_w, d_Xhat, 0));
       HIPCHK(hipEventRecord(e1, 0));
     }
-    if (logp) HIPCHK(gs_launch(n_res, a, d_lp, 0));
+    if (logp) HIPCHK(gs_launch(lay, a, d_lp, 0));
     HIPCHK(hipDeviceSynchronize());
     if (ms) {
       std::vector<float> tt;

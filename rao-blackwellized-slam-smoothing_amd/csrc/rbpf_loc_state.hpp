@@ -11,12 +11,23 @@ namespace rbpf {
 
 // An open backward-simulation pass over a generic map (rbpf_loc_generic_backward_begin .. _finish, rbpf_loc_generic_smooth.hip): the
 // workspace is taken from rbpf_ctx::pool at begin and handed back at finish (or with the context).
+// How the selected rows of a transition reach the kernels.  With a quaternion block (rbpf_loc_generic_backward_pose_*) the KERNEL
+// ORDER is the plain rows in the caller's order, then q0 .. q3; without one it is the caller's order and both maps are the identity.
+struct LocGenLayout {
+  int n_sel = 0;                   // selected state rows = rows of mu; n_res + 1 with a block
+  int n_res = 0;                   // residuals = order of cov
+  int n_plain = -1;                // with a block: the plain rows before it in kernel order, 0 .. 4; -1: no block
+  int rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // state rows, kernel order
+  unsigned angle_mask = 0;         // bit k: kernel row k is an angle
+  int src[8] = {0, 1, 2, 3, 4, 5, 6, 7};    // kernel row k is row src[k] of the caller's mu
+  int perm[8] = {0, 1, 2, 3, 4, 5, 6, 7};   // kernel residual k is residual perm[k] of the caller's cov
+};
+
 struct LocGenBackward {
   bool open = false;
-  int M = 0, n_res = 0, C = 0, nch = 0;
+  int M = 0, C = 0, nch = 0;
   int t = -1;                      // the step the next rbpf_loc_generic_backward_step_device processes; -1: all done
-  int rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned angle_mask = 0;
+  LocGenLayout lay;
   double *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_u = nullptr, *d_xs = nullptr, *d_mean = nullptr;
   int* d_idx = nullptr;
 };

@@ -1890,18 +1890,39 @@ class DeviceTransition:
         extended backwards whatever those rows of the candidate particles are.
     angle_rows: a subset of rows whose residual is wrapped, r <- r - 2 pi rint(r / (2 pi)).
     cov(dt, Q) -> (n_res, n_res): a host callable on numpy arrays (default: dt * Q, which needs n_w == n_res), evaluated once per
-        step page and factorised on the host; one that is not positive definite is refused before any kernel runs."""
+        step page and factorised on the host; one that is not positive definite is refused before any kernel runs.
+    quat_rows: four state rows (q0, q1, q2, q3) that hold a unit quaternion, scalar first (the reference's tools/q*.m), for a pose
+        state whose rotation noise multiplies the predicted quaternion on the right, x'_q = mu_q (x) expq(noise)
+        (run_dense3D_magfield.m:202-203, run_localization.m:274-281).  All four must be in rows, adjacent there and in that order,
+        none in angle_rows; one block at most.  With n_sel = len(rows) in 4 .. 8, mean returns (n_sel, N_P): its four block rows are
+        the predicted UNIT quaternion, composed with the odometry by the handle (q (x) dq or dq (x) q).  The residual then has
+        n_res = n_sel - 1 entries: the plain rows' differences, and in the block's place the three of
 
-    def __init__(self, mean, cov=None, rows=None, angle_rows=()):
+            e = qInv(mu_q) (x) x'_q,   e <- -e if e0 < 0,   phi = atan2(|e_v|, e0) e_v / |e_v|   (0 if |e_v| = 0)
+
+        = logq(e) of tools/logq.m for a unit e.  cov(dt, Q) is (n_res, n_res) in that order.  Not built: noise multiplied on the
+        left, two blocks, noise through a non-square G."""
+
+    def __init__(self, mean, cov=None, rows=None, angle_rows=(), quat_rows=None):
         if not callable(mean) or (cov is not None and not callable(cov)):
             raise TypeError("mean must be callable, cov callable or None")
         self.mean, self.cov = mean, cov
         self.rows = None if rows is None else tuple(int(r) for r in rows)
         self.angle_rows = tuple(int(r) for r in angle_rows)
+        self.quat_rows = None if quat_rows is None else tuple(int(r) for r in quat_rows)
 
     def resolve(self, n_nonlin):
-        """(rows, angle_mask) for a state of n_nonlin rows; bit k of the mask marks rows[k]."""
-        return _transition_rows(n_nonlin, self.rows, self.angle_rows)
+        """(rows, angle_mask) for a state of n_nonlin rows, bit k of the mask marks rows[k]; with quat_rows
+        (rows, angle_mask, quat_pos), quat_pos the position of q0 in rows: what rbpf_loc_generic_backward_pose_begin takes."""
+        rows, mask = _transition_rows(n_nonlin, self.rows, self.angle_rows)
+        if self.quat_rows is None:
+            return rows, mask
+        return rows, mask, _quat_position(rows, self.angle_rows, self.quat_rows)
+
+    def layout(self, n_nonlin):
+        """(rows, angle_mask, quat_pos, n_res): quat_pos = -1 and n_res = len(rows) without a block, n_res = len(rows) - 1 with one."""
+        r = self.resolve(n_nonlin)
+        return (r[0], r[1], -1, len(r[0])) if len(r) == 2 else (r[0], r[1], r[2], len(r[0]) - 1)
 
     def covariance(self, dt, Q, n_res):
         """cov(dt, Q) as a Fortran-ordered [n_res x n_res] array, shape checked."""
@@ -1933,24 +1954,47 @@ def _transition_rows(n_nonlin, rows, angle_rows):
     return rows, mask
 
 
-def device_map_backward_workspace_bytes(n_nonlin, n_res, N_P, N_T, n_traj):
-    """rbpf_loc_generic_backward_workspace_bytes (no device access)."""
+def _quat_position(rows, angle_rows, quat_rows):
+    """The position of q0 in rows; the block must lie in rows, adjacent and in order, and hold no angle row."""
+    rows, quat_rows = tuple(int(r) for r in rows), tuple(int(r) for r in quat_rows)
+    if len(quat_rows) != 4 or len(set(quat_rows)) != 4:
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"quat_rows {quat_rows} must name four distinct rows (q0, q1, q2, q3): one block")
+    if any(q not in rows for q in quat_rows):
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"quat_rows {quat_rows} must all be among rows {rows}")
+    pos = rows.index(quat_rows[0])
+    if rows[pos:pos + 4] != quat_rows:
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"quat_rows {quat_rows} must be adjacent in rows {rows}, in the order q0, q1, q2, q3")
+    if any(int(a) in quat_rows for a in angle_rows):
+        raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"a row of the quaternion block {quat_rows} cannot be an angle row")
+    return pos
+
+
+def device_map_backward_workspace_bytes(n_nonlin, n_res, N_P, N_T, n_traj, quat_pos=-1):
+    """rbpf_loc_generic_backward_workspace_bytes (no device access).  quat_pos >= 0: a transition with a quaternion block at that
+    position of rows (rbpf_loc_generic_backward_pose_workspace_bytes); the second argument is then n_sel = len(rows) = n_res + 1."""
     lib = load_library()
     nbytes = C.c_size_t(0)
-    check(lib.rbpf_loc_generic_backward_workspace_bytes(int(n_nonlin), int(n_res), int(N_P), int(N_T), int(n_traj), C.byref(nbytes)))
+    if int(quat_pos) == -1:
+        check(lib.rbpf_loc_generic_backward_workspace_bytes(int(n_nonlin), int(n_res), int(N_P), int(N_T), int(n_traj), C.byref(nbytes)))
+    else:
+        check(lib.rbpf_loc_generic_backward_pose_workspace_bytes(int(n_nonlin), int(n_res), int(quat_pos), int(N_P), int(N_T), int(n_traj),
+                                                                 C.byref(nbytes)))
     return int(nbytes.value)
 
 
-def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), want_logp=False, reps=1):
+def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), want_logp=False, reps=1, quat_rows=None):
     """rbpf_loc_generic_backward_step, the kernel-level probe: one backward step with a Gaussian transition on the caller's arrays.
     mu [n_res x N] (the predicted rows of every particle), w [N], xs_next [n_nonlin x M], cov [n_res x n_res], u [M]; rows (default:
-    all n_nonlin = n_res rows) and angle_rows as in DeviceTransition -> (index [M], logp [N x M] or None, median ms of one step)."""
+    all n_nonlin = n_res rows) and angle_rows as in DeviceTransition -> (index [M], logp [N x M] or None, median ms of one step).
+    quat_rows as in DeviceTransition (rbpf_loc_generic_backward_pose_step): mu is then [n_sel x N], n_sel = len(rows) = n_res + 1, its
+    block rows the predicted unit quaternion."""
     lib = load_library()
     mu = np.asarray(mu, dtype=np.float64)
     mu = np.ascontiguousarray(mu.reshape(1, -1) if mu.ndim == 1 else mu)
     xs_next = np.asarray(xs_next, dtype=np.float64)
     xs_next = np.asfortranarray(xs_next.reshape(1, -1) if xs_next.ndim == 1 else xs_next)
-    n_res, N = mu.shape
+    n_sel, N = mu.shape
+    n_res = n_sel if quat_rows is None else n_sel - 1
     nN, M = xs_next.shape
     w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).ravel())
     u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).ravel())
@@ -1967,12 +2011,12 @@ def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), w
             if not 0 <= int(r) < nN:
                 raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"angle row {int(r)} is not one of rows")
             mask |= 1 << int(r)
-        if nN != n_res:
-            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"mu has {n_res} rows and xs_next {nN}: name the rows that carry noise")
+        if nN != n_sel:
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"mu has {n_sel} rows and xs_next {nN}: name the rows that carry noise")
     else:                                                         # (the library checks them: duplicates, range)
         rows_a = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).ravel())
-        if rows_a.size != n_res:
-            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"mu has {n_res} rows and rows names {rows_a.size}")
+        if rows_a.size != n_sel:
+            raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"mu has {n_sel} rows and rows names {rows_a.size}")
         mask = 0
         for r in angle_rows:
             pos = np.nonzero(rows_a == int(r))[0]
@@ -1982,8 +2026,13 @@ def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), w
     index = np.zeros(M, dtype=np.int32)
     logp = np.empty((N, M), order="F") if want_logp else None
     ms = C.c_double(0.0)
-    check(lib.rbpf_loc_generic_backward_step(N, M, nN, n_res, _ip(rows_a), mask, _dp(mu), _dp(w), _dp(xs_next), _dp(cov), _dp(u), _ip(index),
-                                             _dp(logp) if want_logp else None, int(reps), C.byref(ms)))
+    if quat_rows is None:
+        check(lib.rbpf_loc_generic_backward_step(N, M, nN, n_res, _ip(rows_a), mask, _dp(mu), _dp(w), _dp(xs_next), _dp(cov), _dp(u), _ip(index),
+                                                 _dp(logp) if want_logp else None, int(reps), C.byref(ms)))
+    else:
+        qpos = _quat_position(rows_a.tolist(), angle_rows, quat_rows)
+        check(lib.rbpf_loc_generic_backward_pose_step(N, M, nN, n_sel, _ip(rows_a), mask, qpos, _dp(mu), _dp(w), _dp(xs_next), _dp(cov), _dp(u),
+                                                      _ip(index), _dp(logp) if want_logp else None, int(reps), C.byref(ms)))
     return index, logp, ms.value
 
 
@@ -2001,8 +2050,10 @@ class DeviceMap:
     view of a native_out handle, consumed in place); handles.dy_layout is not used.  n_y 1 .. 8, nLin 1 .. 1151, n_nonlin 1 .. 8; one
     GPU.  transition: a DeviceTransition, the density of handles.dynModel as it draws (a drift plus Gaussian noise on some rows of
     the state); with one, LocalizationSession.backward_simulate and particleSmootherLocalization draw smoothed trajectories in this
-    map.  Without one they refuse (they need dynModel's transition density; a generic dynModel is a sampler).  Not built: densities
-    that are not Gaussian in a wrapped difference, host closures, sharding.  The map of a sparseFeatures model: DeviceLandmarkMap."""
+    map; a 3-D pose state (position + unit quaternion) states its rotation rows as the transition's quat_rows.  Without a transition
+    they refuse (they need dynModel's transition density; a generic dynModel is a sampler).  Not built: densities outside that family
+    (rotation noise multiplied on the left, two quaternion blocks, noise through a non-square G), host closures, sharding.  The map
+    of a sparseFeatures model: DeviceLandmarkMap."""
 
     _create = "rbpf_loc_generic_create"
 
@@ -2507,8 +2558,8 @@ class LocalizationSession:
         particles_device / mean handle / step_device per step in stream order, finish (also the way out of a failed handle)."""
         lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
         torch, T, N, nN = drv.torch, prob.N_T, prob.N_P, self.nN
-        rows, mask = tr.resolve(nN)
-        n_res = len(rows)
+        rows, mask, qpos, n_res = tr.layout(nN)
+        n_sel = len(rows)                                         # the rows of mu: n_res + 1 with a quaternion block
         page = lambda a, t: t if a > 1 else 0                                                     # noqa: E731
         covs = {}
         for t in range(T - 1):                                    # one factorisation per distinct (dt, Q) page, checked before any kernel runs
@@ -2524,7 +2575,8 @@ class LocalizationSession:
                                                                "does not exist") from None
                 covs[key] = c
         rows_a = np.asarray(rows, dtype=np.int32)
-        check(lib.rbpf_loc_generic_backward_begin(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed), n_res, _ip(rows_a), mask))
+        check(lib.rbpf_loc_generic_backward_pose_begin(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed), n_sel, _ip(rows_a), mask,
+                                                       qpos))
         try:
             with torch.cuda.stream(drv.stream):
                 for _ in range(T):
@@ -2537,9 +2589,9 @@ class LocalizationSession:
                     X = drv._view(torch, xn, (nN, N), drv.device)
                     Q = drv.Q[page(drv.Q.shape[0], t)]
                     mu = tr.mean(X, drv.odo[t], float(drv.dt[page(drv.dt.size, t)]), Q)
-                    if not torch.is_tensor(mu) or tuple(mu.shape) != (n_res, N) or mu.dtype != torch.float64 or not mu.is_cuda:
+                    if not torch.is_tensor(mu) or tuple(mu.shape) != (n_sel, N) or mu.dtype != torch.float64 or not mu.is_cuda:
                         what = f"{tuple(mu.shape)} {mu.dtype} on {mu.device}" if torch.is_tensor(mu) else type(mu).__name__
-                        raise ValueError(f"mean returned {what}, expected a float64 device tensor of shape {(n_res, N)}")
+                        raise ValueError(f"mean returned {what}, expected a float64 device tensor of shape {(n_sel, N)}")
                     mu = mu.contiguous()
                     self._keep_mu = mu                            # read in stream order by the step just enqueued
                     check(lib.rbpf_loc_generic_backward_step_device(self.ctx, C.c_void_p(mu.data_ptr()),

@@ -12,10 +12,17 @@ transitions), at N = M (particles = trajectories) in {8192, 65 536}, in ONE proc
   session   one full session: LocalizationSession on model A of tests/device_map_smoother_ref.py, backward_simulate(N) with the torch
             `mean` handle, host clock / N_T (the same kernels plus the handle, the Philox fill, the gathers, the means and the copies).
 
+  pose      (--leg pose, on its own) the probe rbpf_loc_generic_backward_pose_step, the density of a state with a unit quaternion, on
+            dense_mag_inputs(N, N) in model E's form -- mu = (p + dx_pos, qRight(q) dq), cov = blkdiag(dt Q(1:3,1:3), dt Q(4:6,4:6)), rows
+            all 7, quat_rows (3, 4, 5, 6): n_res = 6, 3 plain rows -- its windows alternated with rbpf_loc_backward_step on the same
+            inputs (the built-in kernel, the yardstick), and the quaternion alone (n_res = 3, no plain row) on the same clouds.  The
+            criterion: the pose step takes no longer than the built-in step plus slack, slack = the larger (spread x median) of the two.
+            Writes profiles/device_map_pose_backward_bench.json.
+
 The inputs of a generic shape: N particles scattered two standard deviations of the transition noise around a centre, the M next
 states drawn from random particles by the sampler, a full random SPD cov.  Writes profiles/device_map_backward_bench.json.
 
-Usage: device_map_backward_bench.py [--out FILE] [--sizes N ...] [--reps 3] [--windows 5] [--steps 6]"""
+Usage: device_map_backward_bench.py [--leg all|pose] [--out FILE] [--sizes N ...] [--reps 3] [--windows 5] [--steps 6]"""
 import argparse
 import importlib
 import json
@@ -143,16 +150,64 @@ def session_step(torch, dev, N, T):
     return dict(model="A (n_res = 3)", N_T=T, session_ms_per_step=ms, distinct_indices_at_t0=int(len(np.unique(out["index"][:, 0]))))
 
 
+def pose_leg(a, torch, dev):
+    doc = dict(tool="tools/device_map_backward_bench.py --leg pose", device=torch.cuda.get_device_name(dev),
+               timing=f"median of {a.windows} windows, a window = the median of {a.reps} event-timed repetitions of one step (prologue + "
+                      f"all-pairs pass + locate); the pose and the built-in windows alternate in one process, both warmed up first; spread = "
+                      f"(max - min) / median over the windows",
+               criterion="pose_ms <= built_in_ms + slack_ms, slack_ms = max(spread x median) of the two",
+               not_measured=["other N", "M != N", "a full session", "n_plain = 1, 2, 4 and angle rows", "hardware counters"], runs=[])
+    for N in a.sizes:
+        dm_in = dense_mag_inputs(N, N)
+        X, w, xs, dx, dt, Q, u = dm_in
+        dq, q = dx[3:7], X[3:7]                                            # qRight(q) dq = dq (x) q
+        mu_q = np.vstack((dq[0] * q[0] - dq[1] * q[1] - dq[2] * q[2] - dq[3] * q[3], dq[0] * q[1] + dq[1] * q[0] + dq[2] * q[3] - dq[3] * q[2],
+                          dq[0] * q[2] - dq[1] * q[3] + dq[2] * q[0] + dq[3] * q[1], dq[0] * q[3] + dq[1] * q[2] - dq[2] * q[1] + dq[3] * q[0]))
+        mu = np.vstack((X[0:3] + dx[0:3, None], mu_q))
+        cov = np.zeros((6, 6))
+        cov[0:3, 0:3], cov[3:6, 3:6] = dt * Q[0:3, 0:3], dt * Q[3:6, 3:6]
+        pose = lambda reps: rbpf.device_map_backward_step(mu, w, xs, cov, u, quat_rows=(3, 4, 5, 6), reps=reps)                # noqa: E731
+        quat = lambda reps: rbpf.device_map_backward_step(mu_q, w, xs[3:7], cov[3:6, 3:6], u, quat_rows=(0, 1, 2, 3), reps=reps)  # noqa: E731
+        built = lambda reps: rbpf.loc_backward_step(*dm_in, reps=reps)                                                        # noqa: E731
+        i_pose, i_built = pose(1)[0], built(1)[0]                          # warm-up
+        quat(1)
+        ms_pose, ms_built, ms_quat = [], [], []
+        for _ in range(a.windows):
+            ms_pose.append(pose(a.reps)[2])
+            ms_built.append(built(a.reps)[2])
+        for _ in range(a.windows):
+            ms_quat.append(quat(a.reps)[2])
+        rec = dict(N=N, M=N, pose=dict(n_res=6, n_plain=3, **stats(ms_pose, N, N)), built_in=stats(ms_built, N, N),
+                   quaternion_alone=dict(n_res=3, n_plain=0, **stats(ms_quat, N, N)),
+                   indices_equal_to_built_in=float(np.mean(i_pose == i_built)))
+        slack = max(rec["pose"]["spread"] * rec["pose"]["ms"], rec["built_in"]["spread"] * rec["built_in"]["ms"])
+        rec["pose_vs_built_in"] = dict(pose_ms=rec["pose"]["ms"], built_in_ms=rec["built_in"]["ms"], slack_ms=slack,
+                                       no_slower=bool(rec["pose"]["ms"] <= rec["built_in"]["ms"] + slack))
+        print(json.dumps(rec), flush=True)
+        doc["runs"].append(rec)
+    return doc
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "device_map_backward_bench.json"))
+    ap.add_argument("--leg", choices=("all", "pose"), default="all", help="all: generic, dense_mag, torch, session; pose: the pose leg alone")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", type=int, nargs="+", default=[8192, 65536])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--steps", type=int, default=6)
     a = ap.parse_args()
     dev = torch.device("cuda", torch.cuda.current_device())
+    if a.leg == "pose":
+        doc = pose_leg(a, torch, dev)
+        out = a.out or os.path.join(ROOT, "profiles", "device_map_pose_backward_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        return
+    a.out = a.out or os.path.join(ROOT, "profiles", "device_map_backward_bench.json")
     doc = dict(tool="tools/device_map_backward_bench.py", device=torch.cuda.get_device_name(dev),
                timing=f"probe: median of {a.windows} windows, a window = the median of {a.reps} event-timed repetitions of one step; torch: device "
                       f"events, median of {a.windows} windows; session: host clock, synchronised; spread = (max - min) / median over the windows",
