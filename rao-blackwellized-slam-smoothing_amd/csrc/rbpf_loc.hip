@@ -16,6 +16,7 @@
 #include "rbpf_device.hpp"
 #include "rbpf_ctx.hpp"
 #include "rbpf_loc_state.hpp"
+#include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -663,36 +664,15 @@ int rbpf_loc_predict(const rbpf_loc_map* map, int32_t n_pred, const double* xn, 
   if (map->V && var) RB_TRY(tmp.upload(&d_V, map->V, (size_t)n * n));
   RB_TRY(tmp.alloc(&d_E, (size_t)3 * n_pred));
   RB_TRY(tmp.alloc(&d_var, (size_t)3 * n_pred));
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  auto run = [&]() -> int {                       // (the events are destroyed whichever way it returns)
-    LocArgs a;
-    a.mdl = M; a.mdl.NN = d_nn; a.n = n; a.npart = n_pred;
-    a.xn = d_xn; a.xn_cs = 1; a.xn_ps = 7;
-    a.mean = d_mean; a.V = d_V; a.var_table = nullptr; a.sigma2 = map->sigma2; a.y = nullptr; a.logw = nullptr;
-    a.dEft = d_E; a.var = d_var;
-    const int R = std::max(reps, 1);
-    for (int r = 0; r < R; ++r) {
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-      ev.emplace_back(e0, e1);
-      HIPCHK(hipEventRecord(e0, 0));
-      HIPCHK(launch_loc_predict(a, 0));
-      HIPCHK(hipEventRecord(e1, 0));
-    }
-    HIPCHK(hipDeviceSynchronize());
-    if (ms) {
-      std::vector<float> tt;
-      for (auto& p : ev) { float v = 0.f; HIPCHK(hipEventElapsedTime(&v, p.first, p.second)); tt.push_back(v); }
-      std::sort(tt.begin(), tt.end());
-      *ms = tt[tt.size() / 2];
-    }
-    if (dEft) HIPCHK(hipMemcpy(dEft, d_E, (size_t)3 * n_pred * sizeof(double), hipMemcpyDeviceToHost));
-    if (var) HIPCHK(hipMemcpy(var, d_var, (size_t)3 * n_pred * sizeof(double), hipMemcpyDeviceToHost));
-    return RBPF_OK;
-  };
-  const int s = run();
-  for (auto& p : ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  return s;
+  LocArgs a;
+  a.mdl = M; a.mdl.NN = d_nn; a.n = n; a.npart = n_pred;
+  a.xn = d_xn; a.xn_cs = 1; a.xn_ps = 7;
+  a.mean = d_mean; a.V = d_V; a.var_table = nullptr; a.sigma2 = map->sigma2; a.y = nullptr; a.logw = nullptr;
+  a.dEft = d_E; a.var = d_var;
+  RB_TRY(timed_reps(reps, 0, [&] { return launch_loc_predict(a, 0); }, ms));
+  if (dEft) HIPCHK(hipMemcpy(dEft, d_E, (size_t)3 * n_pred * sizeof(double), hipMemcpyDeviceToHost));
+  if (var) HIPCHK(hipMemcpy(var, d_var, (size_t)3 * n_pred * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
 }
 
 int rbpf_loc_dyn_model(int32_t n_p, const double* xn, const double* odo, double dt, const double* Q, const double* z, double* xn_next) {

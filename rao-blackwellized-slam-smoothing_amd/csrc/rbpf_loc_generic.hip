@@ -21,6 +21,7 @@
 #include "rbpf_internal.hpp"
 #include "rbpf_ctx.hpp"
 #include "rbpf_loc_state.hpp"
+#include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -283,7 +284,7 @@ static hipError_t launch_loc_generic_weights(int ny, const LocGenArgs& a, hipStr
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-static int lg_ldx(int n) { return (n + 15) / 16 * 16; }   // row stride of the native layout: rows start on 128-byte lines
+int lg_ldx(int n) { return (n + 15) / 16 * 16; }   // row stride of the native layout: rows start on 128-byte lines
 
 static int lg_validate_sizes(int n_nonlin, int n_y, int n_lin) {
   if (n_nonlin < 1 || n_y < 1 || n_lin < 1) { set_error("n_nonlin, n_y and n_lin must be >= 1"); return RBPF_ERR_INVALID_ARG; }
@@ -293,9 +294,11 @@ static int lg_validate_sizes(int n_nonlin, int n_y, int n_lin) {
   return RBPF_OK;
 }
 
-static int lg_validate_R(const double* R, int d) {
-  double Lr[kLgMaxNy * kLgMaxNy];
-  if (!chol_lower_host(R, d, d, Lr, d)) { set_error("R must be positive definite"); return RBPF_ERR_CHOL_FAILED; }
+// (a principal submatrix of a positive definite matrix is positive definite: for a landmark map this one check covers every set
+// of observed outputs)
+int lg_validate_R(const double* R, int d) {
+  std::vector<double> Lr((size_t)d * d);            // sized by d: the landmark map's n_y goes past kLgMaxNy
+  if (!chol_lower_host(R, d, d, Lr.data(), d)) { set_error("R must be positive definite"); return RBPF_ERR_CHOL_FAILED; }
   return RBPF_OK;
 }
 
@@ -499,35 +502,14 @@ int rbpf_loc_generic_weights(int32_t n_y, int32_t n_lin, int32_t n_p, const doub
     RB_TRY(tmp.alloc(&d_H, (size_t)N * d * ld));
     HIPCHK(launch_ext_pack_dy(0, N, d, n, ld, d_dy, d_H, 0));
   }
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  auto run = [&]() -> int {                       // (the events are destroyed whichever way it returns)
-    LocGenArgs a;
-    a.n = n; a.npart = N; a.ld = ld; a.H = dy_layout == 0 ? d_H : d_dy;
-    a.mean = d_mean; a.V = d_V; a.R = d_R; a.y = d_y; a.yhat = d_yhat; a.S = d_S; a.logw = d_logw;
-    const int reps_ = std::max(reps, 1);
-    for (int r = 0; r < reps_; ++r) {
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-      ev.emplace_back(e0, e1);
-      HIPCHK(hipEventRecord(e0, 0));
-      HIPCHK(launch_loc_generic_weights(d, a, 0));
-      HIPCHK(hipEventRecord(e1, 0));
-    }
-    HIPCHK(hipDeviceSynchronize());
-    if (ms) {
-      std::vector<float> tt;
-      for (auto& p : ev) { float v = 0.f; HIPCHK(hipEventElapsedTime(&v, p.first, p.second)); tt.push_back(v); }
-      std::sort(tt.begin(), tt.end());
-      *ms = tt[tt.size() / 2];
-    }
-    if (yhat) HIPCHK(hipMemcpy(yhat, d_yhat, (size_t)N * d * sizeof(double), hipMemcpyDeviceToHost));
-    if (S) HIPCHK(hipMemcpy(S, d_S, (size_t)N * d * d * sizeof(double), hipMemcpyDeviceToHost));
-    if (logw) HIPCHK(hipMemcpy(logw, d_logw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-    return RBPF_OK;
-  };
-  const int s = run();
-  for (auto& p : ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  return s;
+  LocGenArgs a;
+  a.n = n; a.npart = N; a.ld = ld; a.H = dy_layout == 0 ? d_H : d_dy;
+  a.mean = d_mean; a.V = d_V; a.R = d_R; a.y = d_y; a.yhat = d_yhat; a.S = d_S; a.logw = d_logw;
+  RB_TRY(timed_reps(reps, 0, [&] { return launch_loc_generic_weights(d, a, 0); }, ms));
+  if (yhat) HIPCHK(hipMemcpy(yhat, d_yhat, (size_t)N * d * sizeof(double), hipMemcpyDeviceToHost));
+  if (S) HIPCHK(hipMemcpy(S, d_S, (size_t)N * d * d * sizeof(double), hipMemcpyDeviceToHost));
+  if (logw) HIPCHK(hipMemcpy(logw, d_logw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // Backward-simulation smoother in the fixed map of a generic device-code model (forward filter, backward simulation: Godsill,
 // Doucet & West 2004), for a dynModel that is a drift plus Gaussian noise on some rows of the state:
 //     x'[rows] = mean(x) + L z,   L L' = cov,   z ~ N(0, I)
-// The recursion is that of rbpf_loc_smooth.hip on the stored particles X [T][n_nonlin][N] and weights w [T][N] of a generic
+// The recursion is that of rbpf_loc_backward.hpp on the stored particles X [T][n_nonlin][N] and weights w [T][N] of a generic
 // localisation context (keep_history = 1, trace = 1):
 //     b[T-1][j] = sample(w[T-1], u[T-1][j]);   t = T-2 .. 0:  l_i = log w[t][i] + logp(xs[t+1][j] | X[t][:, i]),  b[t][j] = sample(p, u[t][j])
 // with the density, constants omitted (particleSmoother.m:181-182),
@@ -10,18 +10,15 @@
 // (begin / particles_device / step_device / finish), as the forward filter of such a context is.  W = inv(L) is lower triangular,
 // inverted on the host in fp64, and travels in the kernel arguments (n_res (n_res + 1) / 2 values, uniform: SGPRs).
 //
-// Kernels of one step t (all in stream order), siblings of the bs_* kernels of rbpf_loc_smooth.hip:
+// The recursion's kernels, the SUMMATION ORDER and the PHILOX COUNTERS are those of rbpf_loc_backward.hpp; this file brings a
+// Gaussian transition's part of a step:
 //   gs_prologue_kernel        Xhat[t] = (mu rows .., log w_i): n_res + 1 doubles per particle, SoA, shared by all M trajectories.
 //                             (gs_prologue_pose_kernel: the n_sel rows of mu in kernel order, see POSE STATES below.)
-//   gs_pass_kernel<NR, ANG>   all pairs.  Grid = (trajectory blocks of 256) x (particle chunks of C); a lane owns one trajectory,
-//                             keeps its selected rows in registers and a running (max, sum) pair; the particles come in tiles of 256
-//                             through LDS as [particle][NR + 1] and are read as broadcasts.  No cross-lane operation.  The partial
-//                             sums of z_k^2 only lower l, so after the first NR / 2 rows of W a pair more than 746 below the
-//                             running max skips the rest: its exp is exactly 0, wherever the test sits.
-//   gs_locate_kernel<NR, ANG> per j: merge the chunk partials, find the chunk that holds u * total, walk it with the SAME terms
-//                             (gs_term, explicit fma throughout: no contraction is left to the compiler), gather all n_nonlin rows.
-//   gs_mean_kernel            traj_smooth_mean[:, t] = plain means over j of all n_nonlin rows.
-//   gs_logp_kernel<NR, ANG>   the probe's second output.
+//   GsTerm<NR, ANG, QP>       logp of one pair (gs_term, gs_pose_term: explicit fma throughout, no contraction is left to the
+//                             compiler, so the pass and the locate walk see the SAME terms).  A lane keeps the trajectory's selected
+//                             rows only; the gather takes all n_nonlin rows.  The partial sums of z_k^2 only lower l, so after the
+//                             first NR / 2 rows of W a pair more than 746 below the running max skips the rest: its exp is exactly 0,
+//                             wherever the test sits.
 //
 // POSE STATES (rbpf_loc_generic_backward_pose_*): four of the selected rows may be a unit quaternion (q0 .. q3, scalar first), whose
 // noise multiplies the predicted quaternion mu_q on the right (run_dense3D_magfield.m:202-203, run_localization.m:274-281).  In
@@ -32,16 +29,14 @@
 // host permutes rows, the angle bits, the rows of mu (in the prologue) and cov (symmetrically, before the factorisation) to it --
 // z'z does not depend on the order.  W is lower triangular, so the plain rows of z are final before the block is touched, and the
 // skip test sits there, after all NP plain rows and before the quaternion product and atan2 (NP = 0: no test).  The template
-// parameter QP of the kernels is NP with a block and -1 without one; with -1 every kernel is the code it was (gs_term).
-//
-// SUMMATION ORDER: that of rbpf_loc_smooth.hip's header, statement by statement -- chunk size from (N, M) only, ascending i inside
-// a chunk, chunk partials merged in ascending c, the walk and its carry-over, the clamped-draw counter, w_i = 0 never selected.
-// PHILOX COUNTERS: u[t][j] = first uniform of philox_uniform2(seed, slot = j, step = t, lane = 0x42530000, iter = 0), as there.
+// parameter QP of the term is NP with a block and -1 without one; with -1 the pair is gs_term.
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
 #include "rbpf_ctx.hpp"
 #include "rbpf_loc_state.hpp"
+#include "rbpf_loc_backward.hpp"
+#include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -51,37 +46,20 @@
 
 namespace rbpf {
 
-constexpr int kGsTile = 256;               // particles per LDS tile = threads per workgroup
-constexpr int kGsMaxChunk = 2048;          // largest chunk (particles)
-constexpr int kGsMaxRes = 8, kGsMaxNonlin = 8;
-constexpr uint32_t kGsPhiloxLane = 0x42530000u;
-constexpr double kGsSkip = 746.0;          // exp(x) == 0 for x < -745.14
+constexpr int kGsMaxRes = 8, kGsMaxNonlin = kBackwardMaxRows;
 constexpr double kGsTwoPi = 6.283185307179586476925286766559;
-
-// chunk of the all-pairs pass: enough (trajectory block) x (chunk) workgroups to give every CU four, in whole tiles
-static int gs_chunk_size(int N, int M) {
-  const int bx = (M + kGsTile - 1) / kGsTile;
-  const int want = std::max(1, (1024 + bx - 1) / bx);
-  int C = ((N + want - 1) / want + kGsTile - 1) / kGsTile * kGsTile;
-  return std::min(std::max(C, kGsTile), kGsMaxChunk);
-}
 
 struct GsW { double w[kGsMaxRes * (kGsMaxRes + 1) / 2]; };   // W = inv(L), lower: W(k, c) at w[k (k + 1) / 2 + c], c <= k
 
-struct GsArgs {
-  int N, M, C, nchunks;
+// what every instantiation of the term carries (uniform: SGPRs): the integers that BackwardArgs keeps behind the sizes, and W
+struct GsHead {
   int nN;                          // rows of a state
   int first;                       // 1: the draw of step T-1, l_i = log w_i
   unsigned angle_mask;             // bit k: residual row k is an angle
   int rows[kGsMaxRes];             // the state rows that carry noise
-  const double* Xhat;              // [NR + 1][N]
-  const double* X;                 // [nN][N] particles of this step (gather)
-  const double* xs_next;           // [M][nN]
-  const double* u;                 // [M]
-  double* part_m; double* part_s;  // [nchunks][M]
-  int* index;                      // [M]
-  double* xs;                      // [M][nN] or null
-  int* clamped;                    // device counter
+};
+struct GsData {
+  typedef GsHead Head;
   GsW W;
 };
 
@@ -175,196 +153,42 @@ __device__ __forceinline__ bool gs_pose_term(const GsW& W, unsigned amask, const
 }
 
 // QP < 0: NR selected rows and gs_term; QP = NP >= 0: a quaternion block behind NP plain rows (NR = NP + 3, NR + 1 selected rows)
-// kLocate: the launch bound of the locate kernel.  It is launched with 64 threads; stating that for the block's instantiations
-// lifts the 128-VGPR cap of the default bound (1024), under which NP = 4 spilled 12 bytes; without a block the default stays.
-template <int NR, int QP> struct GsSel {
+// kLocateBound: the locate kernel is launched with 64 threads; stating that for the block's instantiations lifts the 128-VGPR cap
+// of the default bound (1024), under which NP = 4 spilled 12 bytes; without a block the default stays.
+template <int NR, bool ANG, int QP = -1>
+struct GsTerm : GsData {
   static constexpr int NS = QP < 0 ? NR : NR + 1;
-  static constexpr int kLocate = QP < 0 ? 1024 : 64;
+  static constexpr int kLocateBound = QP < 0 ? 1024 : 64;
+  __device__ __forceinline__ double load_x(const GsHead& y, const double* xs_next, int j, int k) const { return xs_next[(size_t)j * y.nN + y.rows[k]]; }
+  static constexpr bool kSplit = false;       // gs_term and gs_pose_term hold their own test
+  __device__ __forceinline__ bool pair(const GsHead& y, const double* h, const double (&x)[NS], double bound, double& l) const {
+    if constexpr (QP < 0) return gs_term<NR, ANG>(W, y.angle_mask, h, x, bound, l);
+    else return gs_pose_term<QP, ANG>(W, y.angle_mask, h, x, bound, l);
+  }
+  __device__ __forceinline__ void gather(const GsHead& y, const double* X, int N, int idx, double* xs, int j) const {
+    for (int r = 0; r < y.nN; ++r) xs[(size_t)j * y.nN + r] = X[(size_t)r * N + idx];
+  }
 };
 
-template <int NR, bool ANG, int QP>
-__device__ __forceinline__ bool gs_pair(const GsW& W, unsigned amask, const double* h, const double (&x)[GsSel<NR, QP>::NS], double bound, double& l) {
-  if constexpr (QP < 0) return gs_term<NR, ANG>(W, amask, h, x, bound, l);
-  else return gs_pose_term<QP, ANG>(W, amask, h, x, bound, l);
-}
-
-template <int NR, bool ANG, int QP = -1>
-__global__ __launch_bounds__(kGsTile) void gs_pass_kernel(const GsArgs a) {
-  constexpr int NS = GsSel<NR, QP>::NS;
-  constexpr int S = NS + 1;
-  __shared__ double tile[kGsTile * S];     // [particle][NS + 1]
-  const int tid = threadIdx.x;
-  const int j = blockIdx.x * kGsTile + tid;
-  const int jl = min(j, a.M - 1);          // lanes past the end recompute the last trajectory; nothing of theirs is stored
-  const int c = blockIdx.y;
-  const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
-  double x[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) x[k] = a.first ? 0.0 : a.xs_next[(size_t)jl * a.nN + a.rows[k]];
-  double m = -INFINITY, s = 0.0;
-  for (int base = i0; base < i1; base += kGsTile) {
-    const int cnt = min(kGsTile, i1 - base);
-    __syncthreads();
-    if (tid < cnt) {
-#pragma unroll
-      for (int r = 0; r < S; ++r) tile[tid * S + r] = a.Xhat[(size_t)r * a.N + base + tid];
-    }
-    __syncthreads();
-    for (int k = 0; k < cnt; ++k) {
-      const double* h = tile + k * S;
-      double l = h[NS];
-      if (!a.first) {
-        if (!gs_pair<NR, ANG, QP>(a.W, a.angle_mask, h, x, m - kGsSkip, l)) continue;
-      }
-      if (l == -INFINITY) continue;
-      const double d = l - m;
-      const double ex = exp(-fabs(d));
-      if (d > 0.0) { s = s * ex + 1.0; m = l; }
-      else s += ex;
-    }
-  }
-  if (j < a.M) {
-    a.part_m[(size_t)c * a.M + j] = m;
-    a.part_s[(size_t)c * a.M + j] = s;
-  }
-}
-
-template <int NR, bool ANG, int QP = -1>
-__global__ __launch_bounds__((GsSel<NR, QP>::kLocate)) void gs_locate_kernel(const GsArgs a) {
-  constexpr int NS = GsSel<NR, QP>::NS;
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= a.M) return;
-  double x[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) x[k] = a.first ? 0.0 : a.xs_next[(size_t)j * a.nN + a.rows[k]];
-  double Mx = -INFINITY;
-  for (int c = 0; c < a.nchunks; ++c) Mx = fmax(Mx, a.part_m[(size_t)c * a.M + j]);
-  int idx = -1;
-  if (Mx > -INFINITY) {
-    double total = 0.0;
-    for (int c = 0; c < a.nchunks; ++c) {
-      const double sc = a.part_s[(size_t)c * a.M + j];
-      if (sc > 0.0) total += sc * exp(a.part_m[(size_t)c * a.M + j] - Mx);
-    }
-    const double target = a.u[j] * total;
-    double acc = 0.0;
-    int c0 = 0;
-    for (; c0 < a.nchunks; ++c0) {
-      const double sc = a.part_s[(size_t)c0 * a.M + j];
-      if (!(sc > 0.0)) continue;
-      const double nxt = acc + sc * exp(a.part_m[(size_t)c0 * a.M + j] - Mx);
-      if (nxt >= target) break;
-      acc = nxt;
-    }
-    int last_nz = -1;
-    for (int c = c0; c < a.nchunks && idx < 0; ++c) {
-      if (!(a.part_s[(size_t)c * a.M + j] > 0.0)) continue;
-      const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
-      for (int i = i0; i < i1; ++i) {
-        double h[NS + 1];
-        h[NS] = a.Xhat[(size_t)NS * a.N + i];
-        if (h[NS] == -INFINITY) continue;
-        double l = h[NS];
-        if (!a.first) {
-#pragma unroll
-          for (int r = 0; r < NS; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
-          if (!gs_pair<NR, ANG, QP>(a.W, a.angle_mask, h, x, Mx - kGsSkip, l)) continue;
-        }
-        const double term = exp(l - Mx);
-        if (!(term > 0.0)) continue;
-        last_nz = i;
-        acc += term;
-        if (acc >= target) { idx = i; break; }
-      }
-    }
-    if (idx < 0) idx = last_nz;
-    if (idx < 0 || !(acc >= target)) atomicAdd(a.clamped, 1);
-  } else {
-    atomicAdd(a.clamped, 1);
-  }
-  if (idx < 0) {                                   // no non-zero term at all: the last particle with a non-zero weight
-    for (int i = a.N - 1; i >= 0 && idx < 0; --i)
-      if (a.Xhat[(size_t)NS * a.N + i] > -INFINITY) idx = i;
-    if (idx < 0) idx = a.N - 1;
-  }
-  a.index[j] = idx;
-  if (a.xs) {
-    for (int r = 0; r < a.nN; ++r) a.xs[(size_t)j * a.nN + r] = a.X[(size_t)r * a.N + idx];
-  }
-}
-
-// mean over the M trajectories of xs [M][nN] -> out [nN]: one workgroup, strided partial sums, then a fixed tree
-__global__ __launch_bounds__(256) void gs_mean_kernel(int M, int nN, const double* __restrict__ xs, double* __restrict__ out) {
-  __shared__ double red[kGsMaxNonlin][256];
-  const int tid = threadIdx.x;
-  double acc[kGsMaxNonlin];
-#pragma unroll
-  for (int r = 0; r < kGsMaxNonlin; ++r) acc[r] = 0.0;
-  for (int j = tid; j < M; j += 256)
-#pragma unroll
-    for (int r = 0; r < kGsMaxNonlin; ++r)
-      if (r < nN) acc[r] += xs[(size_t)j * nN + r];
-#pragma unroll
-  for (int r = 0; r < kGsMaxNonlin; ++r) red[r][tid] = acc[r];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off)
-#pragma unroll
-      for (int r = 0; r < kGsMaxNonlin; ++r) red[r][tid] += red[r][tid + off];
-    __syncthreads();
-  }
-  if (tid < nN) out[tid] = red[tid][0] / (double)M;
-}
-
-// logp of every pair, without log w: out [N x M] column-major (the probe's second output)
-template <int NR, bool ANG, int QP = -1>
-__global__ void gs_logp_kernel(const GsArgs a, double* __restrict__ out) {
-  constexpr int NS = GsSel<NR, QP>::NS;
-  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= (size_t)a.N * a.M) return;
-  const int i = (int)(q % a.N), j = (int)(q / a.N);
-  double h[NS + 1], x[NS];
-#pragma unroll
-  for (int r = 0; r < NS; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
-  h[NS] = 0.0;
-#pragma unroll
-  for (int k = 0; k < NS; ++k) x[k] = a.xs_next[(size_t)j * a.nN + a.rows[k]];
-  double l = 0.0;
-  gs_pair<NR, ANG, QP>(a.W, a.angle_mask, h, x, -INFINITY, l);
-  out[q] = l;
-}
-
-__global__ void gs_philox_kernel(unsigned long long seed, int T, int M, double* __restrict__ u) {
-  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= (size_t)T * M) return;
-  double u0, u1;
-  philox_uniform2(seed, (uint32_t)(q % M), (uint32_t)(q / M), kGsPhiloxLane, 0u, u0, u1);
-  u[q] = u0;
-}
+typedef BackwardArgs<GsData> GsArgs;
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 template <int NR, bool ANG, int QP = -1>
 static hipError_t gs_launch_nr(const GsArgs& a, double* logp, hipStream_t s) {
-  if (logp) {
-    const size_t cnt = (size_t)a.N * a.M;
-    hipLaunchKernelGGL((gs_logp_kernel<NR, ANG, QP>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, a, logp);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL((gs_pass_kernel<NR, ANG, QP>), dim3((a.M + kGsTile - 1) / kGsTile, a.nchunks), dim3(kGsTile), 0, s, a);
-  hipLaunchKernelGGL((gs_locate_kernel<NR, ANG, QP>), dim3((a.M + 63) / 64), dim3(64), 0, s, a);
-  return hipGetLastError();
+  const auto b = a.with(GsTerm<NR, ANG, QP>{a.term});
+  return logp ? backward_launch_logp(b, logp, s) : backward_launch_step(b, s);
 }
 
 template <int NR>
 static hipError_t gs_launch_ang(const GsArgs& a, double* logp, hipStream_t s) {
-  return a.angle_mask ? gs_launch_nr<NR, true>(a, logp, s) : gs_launch_nr<NR, false>(a, logp, s);
+  return a.head.angle_mask ? gs_launch_nr<NR, true>(a, logp, s) : gs_launch_nr<NR, false>(a, logp, s);
 }
 
 // a quaternion block behind NP plain rows; an angle row is one of those
 template <int NP>
 static hipError_t gs_launch_pose(const GsArgs& a, double* logp, hipStream_t s) {
   if constexpr (NP > 0) {
-    if (a.angle_mask) return gs_launch_nr<NP + 3, true, NP>(a, logp, s);
+    if (a.head.angle_mask) return gs_launch_nr<NP + 3, true, NP>(a, logp, s);
   }
   return gs_launch_nr<NP + 3, false, NP>(a, logp, s);
 }
@@ -484,7 +308,7 @@ static int gs_factor_layout(const double* cov, const LocGenLayout& y, GsW& W, co
 
 // NR: the rows of mu (n_res, or n_sel with a quaternion block); Xhat has one more
 static size_t gs_bytes(size_t nN, size_t NR, size_t N, size_t T, size_t M) {
-  const size_t C = (size_t)gs_chunk_size((int)N, (int)M), nch = (N + C - 1) / C;
+  const size_t C = (size_t)backward_chunk_size((int)N, (int)M), nch = (N + C - 1) / C;
   return ((NR + 1) * N + 2 * nch * M + T * M + T * nN * M + nN * T) * sizeof(double) + T * M * sizeof(int);
 }
 
@@ -495,9 +319,8 @@ static int gs_ctx_ok(const rbpf_ctx* c) {
 }
 
 static void gs_release(rbpf_ctx* c) {
-  LocGenBackward& g = c->loc->gb;
-  for (void* p : {(void*)g.d_Xhat, (void*)g.d_pm, (void*)g.d_ps, (void*)g.d_u, (void*)g.d_xs, (void*)g.d_mean, (void*)g.d_idx}) c->pool.release(p);
-  g = LocGenBackward();
+  c->loc->gb.ws.release();
+  c->loc->gb = LocGenBackward();
 }
 
 }  // namespace rbpf
@@ -545,44 +368,14 @@ int rbpf_loc_generic_backward_pose_begin(rbpf_ctx* c, int32_t n_traj, const doub
   LocGenLayout lay;
   RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
-  if (!c->opt.keep_history || !c->opt.trace) {
-    set_error("backward simulation reads the stored particles and weights: create the context with keep_history = 1 and trace = 1");
-    return RBPF_ERR_STATE;
-  }
-  if (c->t < c->T) { set_error("rbpf_loc_generic_backward_begin: " + std::to_string(c->t) + " of " + std::to_string(c->T) + " steps are done"); return RBPF_ERR_STATE; }
-  HIPCHK(hipSetDevice(c->device));
+  RB_TRY(backward_check_forward(c, "backward simulation", "rbpf_loc_generic_backward_begin"));
   const int N = c->N, T = c->T, M = n_traj, nN = L->nN;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  {
-    std::vector<double> lse((size_t)T);
-    HIPCHK(hipMemcpy(lse.data(), L->d_lse, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
-    for (int t = 0; t < T; ++t)
-      if (!(lse[t] > std::log(1e-12))) {
-        set_error("the forward run recorded a degenerate step (t = " + std::to_string(t) + "): its weights are no filtering distribution");
-        return RBPF_ERR_STATE;
-      }
-  }
   LocGenBackward& g = L->gb;
   g.M = M; g.lay = lay;
-  g.C = gs_chunk_size(N, M); g.nch = (N + g.C - 1) / g.C;
-  auto fail = [&](int s) { gs_release(c); return s; };
-  int s;
-  if ((s = c->pool.alloc(&g.d_Xhat, (size_t)(lay.n_sel + 1) * N)) != RBPF_OK) return fail(s);
-  if ((s = c->pool.alloc(&g.d_pm, (size_t)g.nch * M)) != RBPF_OK) return fail(s);
-  if ((s = c->pool.alloc(&g.d_ps, (size_t)g.nch * M)) != RBPF_OK) return fail(s);
-  if ((s = c->pool.alloc(&g.d_u, (size_t)T * M)) != RBPF_OK) return fail(s);
-  if ((s = c->pool.alloc(&g.d_xs, (size_t)T * nN * M)) != RBPF_OK) return fail(s);
-  if ((s = c->pool.alloc(&g.d_mean, (size_t)nN * T)) != RBPF_OK) return fail(s);
-  if ((s = c->pool.alloc(&g.d_idx, (size_t)T * M)) != RBPF_OK) return fail(s);
-  hipError_t e;
-  if (u) {
-    e = hipMemcpy(g.d_u, u, (size_t)T * M * sizeof(double), hipMemcpyHostToDevice);
-  } else {
-    const size_t cnt = (size_t)T * M;
-    hipLaunchKernelGGL(gs_philox_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, (unsigned long long)seed, T, M, g.d_u);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) return fail(hip_fail(e, "uniforms of the backward pass", __FILE__, __LINE__));
+  g.C = backward_chunk_size(N, M); g.nch = (N + g.C - 1) / g.C;
+  int s = g.ws.take(c->pool, (size_t)(lay.n_sel + 1) * N, (size_t)g.nch * M, (size_t)T * M, (size_t)T * nN * M, (size_t)nN * T);
+  if (s == RBPF_OK) s = backward_uniforms(u, seed, T, M, g.ws.u, c->stream);
+  if (s != RBPF_OK) { gs_release(c); return s; }
   g.t = T - 1;
   g.open = true;
   return RBPF_OK;
@@ -608,21 +401,20 @@ int rbpf_loc_generic_backward_step_device(rbpf_ctx* c, const double* mu_dev, con
   const int N = c->N, T = c->T, M = g.M, nN = L->nN, t = g.t;
   GsArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.first = (t == T - 1);
-  if (!a.first) {
+  a.head.first = (t == T - 1);
+  if (!a.head.first) {
     if (!mu_dev || !cov) { set_error("NULL argument (mu_dev and cov may be NULL at step N_T-1 only)"); return RBPF_ERR_INVALID_ARG; }
-    RB_TRY(gs_factor_layout(cov, g.lay, a.W, " of step " + std::to_string(t)));
+    RB_TRY(gs_factor_layout(cov, g.lay, a.term.W, " of step " + std::to_string(t)));
   }
   HIPCHK(hipSetDevice(c->device));
-  a.N = N; a.M = M; a.C = g.C; a.nchunks = g.nch; a.nN = nN; a.angle_mask = g.lay.angle_mask;
-  for (int k = 0; k < g.lay.n_sel; ++k) a.rows[k] = g.lay.rows[k];
-  a.Xhat = g.d_Xhat; a.X = c->X + (size_t)t * nN * N;
-  a.xs_next = a.first ? nullptr : g.d_xs + (size_t)(t + 1) * nN * M;
-  a.u = g.d_u + (size_t)t * M; a.part_m = g.d_pm; a.part_s = g.d_ps;
-  a.index = g.d_idx + (size_t)t * M; a.xs = g.d_xs + (size_t)t * nN * M; a.clamped = c->d_flags + 1;
-  HIPCHK(gs_launch_step(g.lay, a, a.first ? nullptr : mu_dev, c->w + (size_t)t * N, g.d_Xhat, c->stream));
-  hipLaunchKernelGGL(gs_mean_kernel, dim3(1), dim3(256), 0, c->stream, M, nN, a.xs, g.d_mean + (size_t)t * nN);
-  HIPCHK(hipGetLastError());
+  a.N = N; a.M = M; a.C = g.C; a.nchunks = g.nch; a.head.nN = nN; a.head.angle_mask = g.lay.angle_mask;
+  for (int k = 0; k < g.lay.n_sel; ++k) a.head.rows[k] = g.lay.rows[k];
+  a.Xhat = g.ws.Xhat; a.X = c->X + (size_t)t * nN * N;
+  a.xs_next = a.head.first ? nullptr : g.ws.xs + (size_t)(t + 1) * nN * M;
+  a.u = g.ws.u + (size_t)t * M; a.part_m = g.ws.pm; a.part_s = g.ws.ps;
+  a.index = g.ws.idx + (size_t)t * M; a.xs = g.ws.xs + (size_t)t * nN * M; a.clamped = c->d_flags + 1;
+  HIPCHK(gs_launch_step(g.lay, a, a.head.first ? nullptr : mu_dev, c->w + (size_t)t * N, g.ws.Xhat, c->stream));
+  HIPCHK(backward_launch_mean(M, nN, a.xs, g.ws.mean + (size_t)t * nN, c->stream));
   g.t = t - 1;
   return RBPF_OK;
 }
@@ -632,19 +424,21 @@ int rbpf_loc_generic_backward_finish(rbpf_ctx* c, double* xs_traj, int32_t* inde
   LocState* L = c->loc;
   LocGenBackward& g = L->gb;
   if (!g.open) { set_error("no backward pass is open (rbpf_loc_generic_backward_begin first)"); return RBPF_ERR_STATE; }
-  const int T = c->T, M = g.M, nN = L->nN;
-  struct Close { rbpf_ctx* c; ~Close() { gs_release(c); } } close{c};    // the workspace goes back on every way out
+  const int T = c->T, M = g.M, nN = L->nN, t_next = g.t;
+  BackwardWorkspace ws = g.ws;
+  g = LocGenBackward();                                                  // the pass is closed whichever way this returns,
+  BackwardWorkspaceGuard lease(ws);                                      // and its workspace goes back
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (g.t >= 0) {
+  if (t_next >= 0) {
     if (!xs_traj && !index && !traj_smooth_mean) return RBPF_OK;         // the way out of a pass that was given up
-    set_error("rbpf_loc_generic_backward_finish: steps " + std::to_string(g.t) + " .. 0 of the backward pass were not run");
+    set_error("rbpf_loc_generic_backward_finish: steps " + std::to_string(t_next) + " .. 0 of the backward pass were not run");
     return RBPF_ERR_STATE;
   }
   RB_TRY(ctx_check_flags(c));
-  if (xs_traj) HIPCHK(hipMemcpy(xs_traj, g.d_xs, (size_t)nN * M * T * sizeof(double), hipMemcpyDeviceToHost));
-  if (index) HIPCHK(hipMemcpy(index, g.d_idx, (size_t)M * T * sizeof(int), hipMemcpyDeviceToHost));
-  if (traj_smooth_mean) HIPCHK(hipMemcpy(traj_smooth_mean, g.d_mean, (size_t)nN * T * sizeof(double), hipMemcpyDeviceToHost));
+  if (xs_traj) HIPCHK(hipMemcpy(xs_traj, ws.xs, (size_t)nN * M * T * sizeof(double), hipMemcpyDeviceToHost));
+  if (index) HIPCHK(hipMemcpy(index, ws.idx, (size_t)M * T * sizeof(int), hipMemcpyDeviceToHost));
+  if (traj_smooth_mean) HIPCHK(hipMemcpy(traj_smooth_mean, ws.mean, (size_t)nN * T * sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
@@ -664,9 +458,9 @@ int rbpf_loc_generic_backward_pose_step(int32_t N, int32_t M, int32_t n_nonlin, 
   RB_TRY(gs_layout(n_nonlin, n_sel, rows, angle_mask, quat_pos, lay));
   GsArgs a;
   std::memset(&a, 0, sizeof(a));
-  RB_TRY(gs_factor_layout(cov, lay, a.W, ""));
+  RB_TRY(gs_factor_layout(cov, lay, a.term.W, ""));
   if (!have_device()) { set_error("no HIP device: the backward pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
-  const int C = gs_chunk_size(N, M), nch = (N + C - 1) / C;
+  const int C = backward_chunk_size(N, M), nch = (N + C - 1) / C;
   DevicePool tmp;
   double *d_mu = nullptr, *d_w = nullptr, *d_xs = nullptr, *d_u = nullptr, *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_lp = nullptr;
   int *d_idx = nullptr, *d_clamped = nullptr;
@@ -681,36 +475,15 @@ int rbpf_loc_generic_backward_pose_step(int32_t N, int32_t M, int32_t n_nonlin, 
   RB_TRY(tmp.alloc(&d_clamped, (size_t)1));
   HIPCHK(hipMemset(d_clamped, 0, sizeof(int)));
   if (logp) RB_TRY(tmp.alloc(&d_lp, (size_t)N * M));
-  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.nN = n_nonlin; a.first = 0; a.angle_mask = lay.angle_mask;
-  for (int k = 0; k < lay.n_sel; ++k) a.rows[k] = lay.rows[k];
+  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.head.nN = n_nonlin; a.head.first = 0; a.head.angle_mask = lay.angle_mask;
+  for (int k = 0; k < lay.n_sel; ++k) a.head.rows[k] = lay.rows[k];
   a.Xhat = d_Xhat; a.X = nullptr; a.xs_next = d_xs; a.u = d_u; a.part_m = d_pm; a.part_s = d_ps; a.index = d_idx; a.xs = nullptr;
   a.clamped = d_clamped;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  auto run = [&]() -> int {                       // (the events are destroyed whichever way it returns)
-    const int R = std::max(reps, 1);
-    for (int r = 0; r < R; ++r) {
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-      ev.emplace_back(e0, e1);
-      HIPCHK(hipEventRecord(e0, 0));
-      HIPCHK(gs_launch_step(lay, a, d_mu, d_w, d_Xhat, 0));
-      HIPCHK(hipEventRecord(e1, 0));
-    }
-    if (logp) HIPCHK(gs_launch(lay, a, d_lp, 0));
-    HIPCHK(hipDeviceSynchronize());
-    if (ms) {
-      std::vector<float> tt;
-      for (auto& p : ev) { float v = 0.f; HIPCHK(hipEventElapsedTime(&v, p.first, p.second)); tt.push_back(v); }
-      std::sort(tt.begin(), tt.end());
-      *ms = tt[tt.size() / 2];
-    }
-    HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
-    if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
-    return RBPF_OK;
-  };
-  const int s = run();
-  for (auto& p : ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  return s;
+  RB_TRY(timed_reps(reps, 0, [&] { return gs_launch_step(lay, a, d_mu, d_w, d_Xhat, 0); }, ms));
+  if (logp) HIPCHK(gs_launch(lay, a, d_lp, 0));
+  HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+  if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@
 #include "rbpf_internal.hpp"
 #include "rbpf_ctx.hpp"
 #include "rbpf_loc_state.hpp"
+#include "rbpf_timed_reps.hpp"
 #include "rbpf_sparse.hpp"
 
 #include <algorithm>
@@ -275,20 +276,11 @@ static hipError_t launch_loc_landmark_weights(const LocLmArgs& a, hipStream_t s)
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-static int lm_ldx(int n) { return (n + 15) / 16 * 16; }
-
 static int lm_validate_sizes(int n_nonlin, int n_y, int n_lin) {
   if (n_nonlin < 1 || n_y < 1 || n_lin < 1) { set_error("n_nonlin, n_y and n_lin must be >= 1"); return RBPF_ERR_INVALID_ARG; }
   if (n_y > kLmMaxNy) { set_error("localisation in a landmark map is built for n_y from 1 to 32"); return RBPF_ERR_UNSUPPORTED; }
   if (n_lin > kLmMaxN) { set_error("localisation in a landmark map is built for n_lin from 1 to 96"); return RBPF_ERR_UNSUPPORTED; }
   if (n_nonlin > kLmMaxNonlin) { set_error("localisation in a landmark map is built for n_nonlin from 1 to 8"); return RBPF_ERR_UNSUPPORTED; }
-  return RBPF_OK;
-}
-
-// (a principal submatrix of a positive definite matrix is positive definite: this one check covers every set of observed outputs)
-static int lm_validate_R(const double* R, int d) {
-  double Lr[kLmMaxNy * kLmMaxNy];
-  if (!chol_lower_host(R, d, d, Lr, d)) { set_error("R must be positive definite"); return RBPF_ERR_CHOL_FAILED; }
   return RBPF_OK;
 }
 
@@ -320,7 +312,7 @@ int rbpf_loc_landmark_create(int32_t n_nonlin, int32_t n_y, int32_t n_lin, const
   if (!mean || !V || !R || !y || !x0_nonlin || !rng) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   RB_TRY(lm_validate_sizes(n_nonlin, n_y, n_lin));
   RB_TRY(loc_generic_validate_run(N_P, N_T, x0_cols, rng, opt));
-  RB_TRY(lm_validate_R(R, n_y));
+  RB_TRY(lg_validate_R(R, n_y));
   if (!have_device()) { set_error("no HIP device: the localisation filter has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
   rbpf_ctx* c = nullptr;
   RB_TRY(loc_generic_build(n_nonlin, n_y, n_lin, mean, V, R, N_P, N_T, y, x0_nonlin, x0_cols, rng, opt, &c));
@@ -414,10 +406,10 @@ int rbpf_loc_landmark_weights(int32_t n_y, int32_t n_lin, int32_t n_p, const dou
   RB_TRY(lm_validate_sizes(1, n_y, n_lin));
   if (n_p < 1 || n_p > kMaxParticles) { set_error("n_p must be in 1 .. 1048576"); return RBPF_ERR_INVALID_ARG; }
   if (dy_layout == 1 && ldx < n_lin) { set_error("ldx must be >= n_lin"); return RBPF_ERR_INVALID_ARG; }
-  RB_TRY(lm_validate_R(R, n_y));
+  RB_TRY(lg_validate_R(R, n_y));
   if (!have_device()) { set_error("no HIP device"); return RBPF_ERR_NO_DEVICE; }
   const int n = n_lin, d = n_y, N = n_p;
-  const int ld = dy_layout == 1 ? ldx : (dy_layout == 0 ? lm_ldx(n) : n);
+  const int ld = dy_layout == 1 ? ldx : (dy_layout == 0 ? lg_ldx(n) : n);
   int ind[kLmMaxNy];
   const int M = lm_observed(y, 1, d, ind);
   DevicePool tmp;
@@ -435,35 +427,14 @@ int rbpf_loc_landmark_weights(int32_t n_y, int32_t n_lin, int32_t n_p, const dou
     RB_TRY(tmp.alloc(&d_H, (size_t)N * d * ld));
     HIPCHK(launch_ext_pack_dy(0, N, d, n, ld, d_dy, d_H, 0));
   }
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  auto run = [&]() -> int {                       // (the events are destroyed whichever way it returns)
-    LocLmArgs a;
-    a.n = n; a.npart = N; a.ld = ld; a.ny = d; a.M = M; a.H = dy_layout == 0 ? d_H : d_dy;
-    a.yhat = d_yhat; a.yhat_si = yhat_layout == 0 ? 1 : (size_t)d; a.yhat_sk = yhat_layout == 0 ? (size_t)N : 1;
-    a.V = d_V; a.R = d_R; a.y = d_y; a.ind = d_ind; a.S = d_S; a.logw = d_logw;
-    const int reps_ = std::max(reps, 1);
-    for (int r = 0; r < reps_; ++r) {
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-      ev.emplace_back(e0, e1);
-      HIPCHK(hipEventRecord(e0, 0));
-      HIPCHK(launch_loc_landmark_weights(a, 0));
-      HIPCHK(hipEventRecord(e1, 0));
-    }
-    HIPCHK(hipDeviceSynchronize());
-    if (ms) {
-      std::vector<float> tt;
-      for (auto& p : ev) { float v = 0.f; HIPCHK(hipEventElapsedTime(&v, p.first, p.second)); tt.push_back(v); }
-      std::sort(tt.begin(), tt.end());
-      *ms = tt[tt.size() / 2];
-    }
-    if (S && M > 0) HIPCHK(hipMemcpy(S, d_S, (size_t)N * M * M * sizeof(double), hipMemcpyDeviceToHost));
-    if (logw) HIPCHK(hipMemcpy(logw, d_logw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-    return RBPF_OK;
-  };
-  const int s = run();
-  for (auto& p : ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  return s;
+  LocLmArgs a;
+  a.n = n; a.npart = N; a.ld = ld; a.ny = d; a.M = M; a.H = dy_layout == 0 ? d_H : d_dy;
+  a.yhat = d_yhat; a.yhat_si = yhat_layout == 0 ? 1 : (size_t)d; a.yhat_sk = yhat_layout == 0 ? (size_t)N : 1;
+  a.V = d_V; a.R = d_R; a.y = d_y; a.ind = d_ind; a.S = d_S; a.logw = d_logw;
+  RB_TRY(timed_reps(reps, 0, [&] { return launch_loc_landmark_weights(a, 0); }, ms));
+  if (S && M > 0) HIPCHK(hipMemcpy(S, d_S, (size_t)N * M * M * sizeof(double), hipMemcpyDeviceToHost));
+  if (logw) HIPCHK(hipMemcpy(logw, d_logw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
 }
 
 }  // extern "C"

@@ -8,33 +8,18 @@
 // logq(e) = acos(e0) e_v / sin(acos(e0)) after the sign flip of tools/logq.m:26-28 is evaluated as atan2(|e_v|, e0) e_v / |e_v|: the
 // same value for a unit e, without the cancellation of acos near 1.
 //
-// Kernels of one step t (all in stream order):
+// The recursion, its kernels, the SUMMATION ORDER and the PHILOX COUNTERS are those of rbpf_loc_backward.hpp; this file brings the
+// dense-mag map's part of a step:
 //   bs_prologue_kernel   Xhat[t][:, i] = (p_i + dx(1:3), a_i, log w_i): 8 doubles per particle, SoA, shared by all M trajectories.
-//   bs_pass_kernel       all pairs.  Grid = (trajectory blocks of 256) x (particle chunks of C); a lane owns one trajectory, keeps
-//                        xs[t+1][j] in registers and a running (max, sum) pair; the particles come in tiles of 256 through LDS and
-//                        are read as broadcasts (all lanes one address).  No cross-lane operation.  Writes one (max, sum) per
-//                        (chunk, j).  A pair whose log w + position term alone lies more than 746 below the running max skips
-//                        its orientation term: its exp is exactly 0.
-//   bs_locate_kernel     per j: merge the chunk partials, find the chunk that holds u * total, walk it, gather xs[t][j].
-//   bs_mean_kernel       traj_smooth_mean[:, t] = mean over j (plain means of all 7 rows, particleFilterLocalization.m:123).
-//
-// SUMMATION ORDER (fixed; the indices depend on nothing else):
-//   * inside a chunk, particles in ascending i: (m, s) <- l_i: if l_i > m: s = s exp(m - l_i) + 1, m = l_i; else s += exp(l_i - m);
-//   * M_j = max over the chunks' m_c;  P_c = P_{c-1} + s_c exp(m_c - M_j) in ascending c, P_{-1} = 0; total = P_last;
-//   * c0 = first c with P_c >= u total;  walk: acc = P_{c0-1}; ascending i in chunk c0: acc += exp(l_i - M_j); the first i
-//     with a non-zero term and acc >= u total is b.  A walk that reaches the end of its chunk without crossing (the walk's sum and
-//     the chunk's rescaled partial differ by rounding) goes on, acc carried over, through the following chunks with s_c > 0; if
-//     none crosses, b = the last particle with a non-zero term (the clamp of a draw past the last cdf edge), counted in the
-//     context's clamped-draw flag like the filter's.  w_i = 0 gives l_i = -inf and a zero term: never selected.
-//   * C = chunk_size(N, M) below: a function of the two sizes only.
-//
-// PHILOX COUNTERS: u[t][j] = first uniform of philox_uniform2(seed, slot = j, step = t, lane = 0x42530000, iter = 0).  The filter's
-// draws use lanes 0 .. 3 (rbpf_device.hpp), so the two ranges are disjoint for the same seed.
+//   BsTerm               logp of one pair: the position term, then the orientation term.  A pair whose log w + position term alone
+//                        lies more than 746 below the running max skips its orientation term: its exp is exactly 0.
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
 #include "rbpf_ctx.hpp"
 #include "rbpf_loc_state.hpp"
+#include "rbpf_loc_backward.hpp"
+#include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -44,34 +29,7 @@
 
 namespace rbpf {
 
-constexpr int kBsTile = 256;               // particles per LDS tile = threads per workgroup
-constexpr int kBsMaxChunk = 2048;          // largest chunk (particles): the walk of the locate kernel is at most this long per chunk
-constexpr uint32_t kBsPhiloxLane = 0x42530000u;
-constexpr double kBsSkip = 746.0;          // exp(x) == 0 for x < -745.14
-
-// chunk of the all-pairs pass: enough (trajectory block) x (chunk) workgroups to give every CU four, in whole tiles
-static int bs_chunk_size(int N, int M) {
-  const int bx = (M + kBsTile - 1) / kBsTile;
-  const int want = std::max(1, (1024 + bx - 1) / bx);
-  int C = ((N + want - 1) / want + kBsTile - 1) / kBsTile * kBsTile;
-  return std::min(std::max(C, kBsTile), kBsMaxChunk);
-}
-
 struct BsNoise { double ip[9], ir[9]; };   // inv(S_pos), inv(S_rot), row-major
-
-struct BsArgs {
-  int N, M, C, nchunks;
-  int first;                       // 1: the draw of step T-1, l_i = log w_i
-  const double* Xhat;              // [8][N]
-  const double* X;                 // [7][N] particles of this step (gather)
-  const double* xs_next;           // [M][7]
-  const double* u;                 // [M]
-  double* part_m; double* part_s;  // [nchunks][M]
-  int* index;                      // [M]
-  double* xs;                      // [M][7] or null
-  int* clamped;                    // device counter
-  BsNoise nz;
-};
 
 __global__ void bs_prologue_kernel(int N, const double* __restrict__ xn, size_t cs, size_t ps, const double* __restrict__ w,
                                    const double* __restrict__ odo, double* __restrict__ Xhat) {
@@ -118,152 +76,21 @@ __device__ __forceinline__ double bs_rot_term(const BsNoise& nz, const double* h
   return -0.5 * (z0 * z0 + z1 * z1 + z2 * z2);
 }
 
-__global__ __launch_bounds__(kBsTile) void bs_pass_kernel(const BsArgs a) {
-  __shared__ double tile[kBsTile * 8];     // [particle][8]
-  const int tid = threadIdx.x;
-  const int j = blockIdx.x * kBsTile + tid;
-  const int jl = min(j, a.M - 1);          // lanes past the end recompute the last trajectory; nothing of theirs is stored
-  const int c = blockIdx.y;
-  const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
-  double x[7];
+// the dense-mag map's term: h = (predicted position, a, log w), x = the trajectory's state, all 7 rows
+struct BsTerm {
+  struct Head { int first; };                 // no integers of its own: all 7 rows, always
+  static constexpr int NS = 7;
+  static constexpr int kLocateBound = 1024;   // the default
+  BsNoise nz;
+  __device__ __forceinline__ double load_x(Head, const double* xs_next, int j, int k) const { return xs_next[(size_t)j * 7 + k]; }
+  static constexpr bool kSplit = true;        // the skip test sits between the two terms
+  __device__ __forceinline__ double pair_near(Head, const double* h, const double (&x)[7]) const { return bs_pos_term(nz, h, x); }
+  __device__ __forceinline__ double pair_far(Head, const double* h, const double (&x)[7]) const { return bs_rot_term(nz, h, x); }
+  __device__ __forceinline__ void gather(Head, const double* X, int N, int idx, double* xs, int j) const {
 #pragma unroll
-  for (int r = 0; r < 7; ++r) x[r] = a.first ? 0.0 : a.xs_next[(size_t)jl * 7 + r];
-  double m = -INFINITY, s = 0.0;
-  for (int base = i0; base < i1; base += kBsTile) {
-    const int cnt = min(kBsTile, i1 - base);
-    __syncthreads();
-    if (tid < cnt) {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) tile[tid * 8 + r] = a.Xhat[(size_t)r * a.N + base + tid];
-    }
-    __syncthreads();
-    for (int k = 0; k < cnt; ++k) {
-      const double* h = tile + k * 8;
-      double l = h[7];
-      if (!a.first) {
-        l += bs_pos_term(a.nz, h, x);
-        if (l < m - kBsSkip) continue;
-        l += bs_rot_term(a.nz, h, x);
-      }
-      if (l == -INFINITY) continue;
-      const double d = l - m;
-      const double ex = exp(-fabs(d));
-      if (d > 0.0) { s = s * ex + 1.0; m = l; }
-      else s += ex;
-    }
+    for (int r = 0; r < 7; ++r) xs[(size_t)j * 7 + r] = X[(size_t)r * N + idx];
   }
-  if (j < a.M) {
-    a.part_m[(size_t)c * a.M + j] = m;
-    a.part_s[(size_t)c * a.M + j] = s;
-  }
-}
-
-__global__ void bs_locate_kernel(const BsArgs a) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= a.M) return;
-  double x[7];
-#pragma unroll
-  for (int r = 0; r < 7; ++r) x[r] = a.first ? 0.0 : a.xs_next[(size_t)j * 7 + r];
-  double Mx = -INFINITY;
-  for (int c = 0; c < a.nchunks; ++c) Mx = fmax(Mx, a.part_m[(size_t)c * a.M + j]);
-  int idx = -1;
-  if (Mx > -INFINITY) {
-    double total = 0.0;
-    for (int c = 0; c < a.nchunks; ++c) {
-      const double sc = a.part_s[(size_t)c * a.M + j];
-      if (sc > 0.0) total += sc * exp(a.part_m[(size_t)c * a.M + j] - Mx);
-    }
-    const double target = a.u[j] * total;
-    double acc = 0.0;
-    int c0 = 0;
-    for (; c0 < a.nchunks; ++c0) {
-      const double sc = a.part_s[(size_t)c0 * a.M + j];
-      if (!(sc > 0.0)) continue;
-      const double nxt = acc + sc * exp(a.part_m[(size_t)c0 * a.M + j] - Mx);
-      if (nxt >= target) break;
-      acc = nxt;
-    }
-    int last_nz = -1;
-    for (int c = c0; c < a.nchunks && idx < 0; ++c) {
-      if (!(a.part_s[(size_t)c * a.M + j] > 0.0)) continue;
-      const int i0 = c * a.C, i1 = min(a.N, i0 + a.C);
-      for (int i = i0; i < i1; ++i) {
-        double h[8];
-        h[7] = a.Xhat[(size_t)7 * a.N + i];
-        if (h[7] == -INFINITY) continue;
-        double l = h[7];
-        if (!a.first) {
-#pragma unroll
-          for (int r = 0; r < 7; ++r) h[r] = a.Xhat[(size_t)r * a.N + i];
-          l += bs_pos_term(a.nz, h, x);
-          if (l < Mx - kBsSkip) continue;
-          l += bs_rot_term(a.nz, h, x);
-        }
-        const double term = exp(l - Mx);
-        if (!(term > 0.0)) continue;
-        last_nz = i;
-        acc += term;
-        if (acc >= target) { idx = i; break; }
-      }
-    }
-    if (idx < 0) idx = last_nz;
-    if (idx < 0 || !(acc >= target)) atomicAdd(a.clamped, 1);
-  } else {
-    atomicAdd(a.clamped, 1);
-  }
-  if (idx < 0) {                                   // no non-zero term at all: the last particle with a non-zero weight
-    for (int i = a.N - 1; i >= 0 && idx < 0; --i)
-      if (a.Xhat[(size_t)7 * a.N + i] > -INFINITY) idx = i;
-    if (idx < 0) idx = a.N - 1;
-  }
-  a.index[j] = idx;
-  if (a.xs) {
-#pragma unroll
-    for (int r = 0; r < 7; ++r) a.xs[(size_t)j * 7 + r] = a.X[(size_t)r * a.N + idx];
-  }
-}
-
-// mean over the M trajectories of xs [M][7] -> out [7]: one workgroup, strided partial sums, then a fixed tree
-__global__ __launch_bounds__(256) void bs_mean_kernel(int M, const double* __restrict__ xs, double* __restrict__ out) {
-  __shared__ double red[7][256];
-  const int tid = threadIdx.x;
-  double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int j = tid; j < M; j += 256)
-#pragma unroll
-    for (int r = 0; r < 7; ++r) acc[r] += xs[(size_t)j * 7 + r];
-#pragma unroll
-  for (int r = 0; r < 7; ++r) red[r][tid] = acc[r];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off)
-#pragma unroll
-      for (int r = 0; r < 7; ++r) red[r][tid] += red[r][tid + off];
-    __syncthreads();
-  }
-  if (tid < 7) out[tid] = red[tid][0] / (double)M;
-}
-
-// logp of every pair, without log w: out [N x M] column-major (the probe's second output)
-__global__ void bs_logp_kernel(int N, int M, const double* __restrict__ Xhat, const double* __restrict__ xs_next, BsNoise nz,
-                               double* __restrict__ out) {
-  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= (size_t)N * M) return;
-  const int i = (int)(q % N), j = (int)(q / N);
-  double h[8], x[7];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) h[r] = Xhat[(size_t)r * N + i];
-#pragma unroll
-  for (int r = 0; r < 7; ++r) x[r] = xs_next[(size_t)j * 7 + r];
-  out[q] = bs_pos_term(nz, h, x) + bs_rot_term(nz, h, x);
-}
-
-__global__ void bs_philox_kernel(unsigned long long seed, int T, int M, double* __restrict__ u) {
-  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= (size_t)T * M) return;
-  double u0, u1;
-  philox_uniform2(seed, (uint32_t)(q % M), (uint32_t)(q / M), kBsPhiloxLane, 0u, u0, u1);
-  u[q] = u0;
-}
+};
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 static bool bs_inv3(const double* S, int ld, double* inv) {   // S column-major with leading dimension ld -> inv row-major
@@ -288,17 +115,15 @@ static int bs_noise(const double* S, BsNoise& nz) {
 }
 
 static size_t bs_bytes(size_t N, size_t T, size_t M, bool full_xs) {
-  const size_t nch = (N + bs_chunk_size((int)N, (int)M) - 1) / bs_chunk_size((int)N, (int)M);
+  const size_t nch = (N + backward_chunk_size((int)N, (int)M) - 1) / backward_chunk_size((int)N, (int)M);
   return (8 * N + 2 * nch * M + T * M + (full_xs ? T : 2) * 7 * M + 7 * T) * sizeof(double) + T * M * sizeof(int);
 }
 
 // prologue + all-pairs pass + locate of one step, in stream order
-static hipError_t bs_launch_step(const BsArgs& a, const double* xn, size_t cs, size_t ps, const double* w, const double* odo,
+static hipError_t bs_launch_step(const BackwardArgs<BsTerm>& a, const double* xn, size_t cs, size_t ps, const double* w, const double* odo,
                                  double* Xhat, hipStream_t s) {
   hipLaunchKernelGGL(bs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, xn, cs, ps, w, odo, Xhat);
-  hipLaunchKernelGGL(bs_pass_kernel, dim3((a.M + kBsTile - 1) / kBsTile, a.nchunks), dim3(kBsTile), 0, s, a);
-  hipLaunchKernelGGL(bs_locate_kernel, dim3((a.M + 63) / 64), dim3(64), 0, s, a);
-  return hipGetLastError();
+  return backward_launch_step(a, s);
 }
 
 }  // namespace rbpf
@@ -339,76 +164,41 @@ int rbpf_loc_backward_simulate(rbpf_ctx* c, int32_t n_traj, const double* u, uin
     return RBPF_ERR_UNSUPPORTED;
   }
   if (n_traj < 1) { set_error("n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
-  if (!c->opt.keep_history || !c->opt.trace) {
-    set_error("rbpf_loc_backward_simulate reads the stored particles and weights: create the context with keep_history = 1 and trace = 1");
-    return RBPF_ERR_STATE;
-  }
-  if (c->t < c->T) { set_error("rbpf_loc_backward_simulate: " + std::to_string(c->t) + " of " + std::to_string(c->T) + " steps are done"); return RBPF_ERR_STATE; }
-  HIPCHK(hipSetDevice(c->device));
+  RB_TRY(backward_check_forward(c, "rbpf_loc_backward_simulate", "rbpf_loc_backward_simulate"));
   LocState* L = c->loc;
   const int N = c->N, T = c->T, M = n_traj;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  {
-    std::vector<double> lse((size_t)T);
-    HIPCHK(hipMemcpy(lse.data(), L->d_lse, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
-    for (int t = 0; t < T; ++t)
-      if (!(lse[t] > std::log(1e-12))) {
-        set_error("the forward run recorded a degenerate step (t = " + std::to_string(t) + "): its weights are no filtering distribution");
-        return RBPF_ERR_STATE;
-      }
-  }
   std::vector<BsNoise> nz((size_t)L->s_pages);
   {
     std::vector<double> S((size_t)L->s_pages * 36);
     HIPCHK(hipMemcpy(S.data(), L->d_S, S.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int p = 0; p < (T > 1 ? L->s_pages : 0); ++p) RB_TRY(bs_noise(S.data() + (size_t)p * 36, nz[p]));
   }
-  const int C = bs_chunk_size(N, M), nch = (N + C - 1) / C;
+  const int C = backward_chunk_size(N, M), nch = (N + C - 1) / C;
   const bool full_xs = xs_traj != nullptr;
   // workspace from the context's pool, handed back on every way out
-  struct Lease {
-    DevicePool& pool; std::vector<void*> ptrs;
-    ~Lease() { for (void* p : ptrs) pool.release(p); }
-  } lease{c->pool, {}};
-  double *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_u = nullptr, *d_xs = nullptr, *d_mean = nullptr;
-  int* d_idx = nullptr;
-  auto take = [&](auto** p, size_t count) -> int { const int s = c->pool.alloc(p, count); if (s == RBPF_OK) lease.ptrs.push_back(*p); return s; };
-  RB_TRY(take(&d_Xhat, (size_t)8 * N));
-  RB_TRY(take(&d_pm, (size_t)nch * M));
-  RB_TRY(take(&d_ps, (size_t)nch * M));
-  RB_TRY(take(&d_u, (size_t)T * M));
-  RB_TRY(take(&d_xs, (size_t)(full_xs ? T : 2) * 7 * M));
-  RB_TRY(take(&d_mean, (size_t)7 * T));
-  RB_TRY(take(&d_idx, (size_t)T * M));
-  if (u) {
-    HIPCHK(hipMemcpyAsync(d_u, u, (size_t)T * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  } else {
-    const size_t cnt = (size_t)T * M;
-    hipLaunchKernelGGL(bs_philox_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, (unsigned long long)seed, T, M, d_u);
-    HIPCHK(hipGetLastError());
-  }
-  auto slab = [&](int t) { return d_xs + (size_t)(full_xs ? t : (t & 1)) * 7 * M; };
+  BackwardWorkspace ws;
+  BackwardWorkspaceGuard lease(ws);
+  RB_TRY(ws.take(c->pool, (size_t)8 * N, (size_t)nch * M, (size_t)T * M, (size_t)(full_xs ? T : 2) * 7 * M, (size_t)7 * T));
+  RB_TRY(backward_uniforms(u, seed, T, M, ws.u, c->stream));
+  auto slab = [&](int t) { return ws.xs + (size_t)(full_xs ? t : (t & 1)) * 7 * M; };
   for (int t = T - 1; t >= 0; --t) {
-    BsArgs a;
-    a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.first = (t == T - 1);
-    a.Xhat = d_Xhat; a.X = c->X + (size_t)t * 7 * N;
-    a.xs_next = a.first ? nullptr : slab(t + 1);
-    a.u = d_u + (size_t)t * M; a.part_m = d_pm; a.part_s = d_ps;
-    a.index = d_idx + (size_t)t * M; a.xs = slab(t); a.clamped = c->d_flags + 1;
-    if (!a.first) a.nz = nz[L->s_pages > 1 ? t : 0];
-    else std::memset(&a.nz, 0, sizeof(a.nz));
-    const double* odo = c->d_odo + (size_t)(a.first ? 0 : t) * 7;          // the draw of step T-1 reads log w only
-    HIPCHK(bs_launch_step(a, a.X, (size_t)N, 1, c->w + (size_t)t * N, odo, d_Xhat, c->stream));
-    if (traj_smooth_mean) {
-      hipLaunchKernelGGL(bs_mean_kernel, dim3(1), dim3(256), 0, c->stream, M, slab(t), d_mean + (size_t)t * 7);
-      HIPCHK(hipGetLastError());
-    }
+    BackwardArgs<BsTerm> a;
+    a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.head.first = (t == T - 1);
+    a.Xhat = ws.Xhat; a.X = c->X + (size_t)t * 7 * N;
+    a.xs_next = a.head.first ? nullptr : slab(t + 1);
+    a.u = ws.u + (size_t)t * M; a.part_m = ws.pm; a.part_s = ws.ps;
+    a.index = ws.idx + (size_t)t * M; a.xs = slab(t); a.clamped = c->d_flags + 1;
+    if (!a.head.first) a.term.nz = nz[L->s_pages > 1 ? t : 0];
+    else std::memset(&a.term.nz, 0, sizeof(a.term.nz));
+    const double* odo = c->d_odo + (size_t)(a.head.first ? 0 : t) * 7;          // the draw of step T-1 reads log w only
+    HIPCHK(bs_launch_step(a, a.X, (size_t)N, 1, c->w + (size_t)t * N, odo, ws.Xhat, c->stream));
+    if (traj_smooth_mean) HIPCHK(backward_launch_mean(M, 7, slab(t), ws.mean + (size_t)t * 7, c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   RB_TRY(ctx_check_flags(c));
-  if (xs_traj) HIPCHK(hipMemcpy(xs_traj, d_xs, (size_t)7 * M * T * sizeof(double), hipMemcpyDeviceToHost));
-  if (index) HIPCHK(hipMemcpy(index, d_idx, (size_t)M * T * sizeof(int), hipMemcpyDeviceToHost));
-  if (traj_smooth_mean) HIPCHK(hipMemcpy(traj_smooth_mean, d_mean, (size_t)7 * T * sizeof(double), hipMemcpyDeviceToHost));
+  if (xs_traj) HIPCHK(hipMemcpy(xs_traj, ws.xs, (size_t)7 * M * T * sizeof(double), hipMemcpyDeviceToHost));
+  if (index) HIPCHK(hipMemcpy(index, ws.idx, (size_t)M * T * sizeof(int), hipMemcpyDeviceToHost));
+  if (traj_smooth_mean) HIPCHK(hipMemcpy(traj_smooth_mean, ws.mean, (size_t)7 * T * sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 
@@ -427,10 +217,10 @@ int rbpf_loc_backward_step(int32_t N, int32_t M, const double* xn, const double*
         if (!(v >= 0.0)) { set_error("dt * Q has a negative entry in a diagonal block: the element-wise sqrt of dynModel would be complex"); return RBPF_ERR_INVALID_ARG; }
         S[q] = std::sqrt(v);
       }
-  BsArgs a;
-  RB_TRY(bs_noise(S, a.nz));
+  BackwardArgs<BsTerm> a;
+  RB_TRY(bs_noise(S, a.term.nz));
   if (!have_device()) { set_error("no HIP device: the backward pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
-  const int C = bs_chunk_size(N, M), nch = (N + C - 1) / C;
+  const int C = backward_chunk_size(N, M), nch = (N + C - 1) / C;
   DevicePool tmp;
   double *d_xn = nullptr, *d_w = nullptr, *d_xs = nullptr, *d_odo = nullptr, *d_u = nullptr, *d_Xhat = nullptr, *d_pm = nullptr,
          *d_ps = nullptr, *d_lp = nullptr;
@@ -447,39 +237,14 @@ int rbpf_loc_backward_step(int32_t N, int32_t M, const double* xn, const double*
   RB_TRY(tmp.alloc(&d_clamped, (size_t)1));
   HIPCHK(hipMemset(d_clamped, 0, sizeof(int)));
   if (logp) RB_TRY(tmp.alloc(&d_lp, (size_t)N * M));
-  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.first = 0;
+  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.head.first = 0;
   a.Xhat = d_Xhat; a.X = nullptr; a.xs_next = d_xs; a.u = d_u; a.part_m = d_pm; a.part_s = d_ps; a.index = d_idx; a.xs = nullptr;
   a.clamped = d_clamped;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  auto run = [&]() -> int {                       // (the events are destroyed whichever way it returns)
-    const int R = std::max(reps, 1);
-    for (int r = 0; r < R; ++r) {
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-      ev.emplace_back(e0, e1);
-      HIPCHK(hipEventRecord(e0, 0));
-      HIPCHK(bs_launch_step(a, d_xn, 1, 7, d_w, d_odo, d_Xhat, 0));
-      HIPCHK(hipEventRecord(e1, 0));
-    }
-    if (logp) {
-      const size_t cnt = (size_t)N * M;
-      hipLaunchKernelGGL(bs_logp_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, 0, N, M, d_Xhat, d_xs, a.nz, d_lp);
-      HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipDeviceSynchronize());
-    if (ms) {
-      std::vector<float> tt;
-      for (auto& p : ev) { float v = 0.f; HIPCHK(hipEventElapsedTime(&v, p.first, p.second)); tt.push_back(v); }
-      std::sort(tt.begin(), tt.end());
-      *ms = tt[tt.size() / 2];
-    }
-    HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
-    if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
-    return RBPF_OK;
-  };
-  const int s = run();
-  for (auto& p : ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  return s;
+  RB_TRY(timed_reps(reps, 0, [&] { return bs_launch_step(a, d_xn, 1, 7, d_w, d_odo, d_Xhat, 0); }, ms));
+  if (logp) HIPCHK(backward_launch_logp(a, d_lp, 0));
+  HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+  if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
 }
 
 }  // extern "C"

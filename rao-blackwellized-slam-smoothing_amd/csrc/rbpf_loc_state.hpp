@@ -9,8 +9,6 @@
 
 namespace rbpf {
 
-// An open backward-simulation pass over a generic map (rbpf_loc_generic_backward_begin .. _finish, rbpf_loc_generic_smooth.hip): the
-// workspace is taken from rbpf_ctx::pool at begin and handed back at finish (or with the context).
 // How the selected rows of a transition reach the kernels.  With a quaternion block (rbpf_loc_generic_backward_pose_*) the KERNEL
 // ORDER is the plain rows in the caller's order, then q0 .. q3; without one it is the caller's order and both maps are the identity.
 struct LocGenLayout {
@@ -23,13 +21,52 @@ struct LocGenLayout {
   int perm[8] = {0, 1, 2, 3, 4, 5, 6, 7};   // kernel residual k is residual perm[k] of the caller's cov
 };
 
+// The device buffers of a backward-simulation pass (rbpf_loc_backward.hpp), leased from a pool (rbpf_ctx::pool) and handed back by
+// release().  It is plain data with no destructor (LocGenBackward keeps one across calls); a scope that must hand it back on every
+// way out holds a BackwardWorkspaceGuard on it.
+struct BackwardWorkspace {
+  DevicePool* pool = nullptr;
+  double *Xhat = nullptr;          // [rows + 1][N]
+  double *pm = nullptr, *ps = nullptr;   // [nchunks][M] each: n_part
+  double *u = nullptr;             // [T][M]: n_draws
+  double *xs = nullptr, *mean = nullptr;
+  int* idx = nullptr;              // [T][M]: n_draws
+  // all or nothing: a failed allocation hands back what was taken before it
+  int take(DevicePool& from, size_t n_Xhat, size_t n_part, size_t n_draws, size_t n_xs, size_t n_mean) {
+    pool = &from;
+    int s = from.alloc(&Xhat, n_Xhat);
+    if (s == RBPF_OK) s = from.alloc(&pm, n_part);
+    if (s == RBPF_OK) s = from.alloc(&ps, n_part);
+    if (s == RBPF_OK) s = from.alloc(&u, n_draws);
+    if (s == RBPF_OK) s = from.alloc(&xs, n_xs);
+    if (s == RBPF_OK) s = from.alloc(&mean, n_mean);
+    if (s == RBPF_OK) s = from.alloc(&idx, n_draws);
+    if (s != RBPF_OK) release();
+    return s;
+  }
+  void release() {
+    if (pool)
+      for (void* p : {(void*)Xhat, (void*)pm, (void*)ps, (void*)u, (void*)xs, (void*)mean, (void*)idx}) pool->release(p);
+    *this = BackwardWorkspace();
+  }
+};
+
+struct BackwardWorkspaceGuard {
+  BackwardWorkspace& ws;
+  explicit BackwardWorkspaceGuard(BackwardWorkspace& w) : ws(w) {}
+  BackwardWorkspaceGuard(const BackwardWorkspaceGuard&) = delete;
+  BackwardWorkspaceGuard& operator=(const BackwardWorkspaceGuard&) = delete;
+  ~BackwardWorkspaceGuard() { ws.release(); }
+};
+
+// An open backward-simulation pass over a generic map (rbpf_loc_generic_backward_begin .. _finish, rbpf_loc_generic_smooth.hip): the
+// workspace is taken from rbpf_ctx::pool at begin and handed back at finish (or with the context).
 struct LocGenBackward {
   bool open = false;
   int M = 0, C = 0, nch = 0;
   int t = -1;                      // the step the next rbpf_loc_generic_backward_step_device processes; -1: all done
   LocGenLayout lay;
-  double *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_u = nullptr, *d_xs = nullptr, *d_mean = nullptr;
-  int* d_idx = nullptr;
+  BackwardWorkspace ws;
 };
 
 struct LocState {
@@ -62,5 +99,7 @@ int loc_generic_validate_run(int N_P, int N_T, int x0_cols, const rbpf_rng* rng,
 int loc_generic_build(int n_nonlin, int n_y, int n_lin, const double* mean, const double* V, const double* R, int N_P, int N_T,
                       const double* y, const double* x0_nonlin, int x0_cols, const rbpf_rng* rng, const rbpf_options* opt, rbpf_ctx** out);
 int loc_generic_normalise_step(rbpf_ctx* c, const double* X_new);
+int lg_ldx(int n);                                 // row stride of the native dy layout: rows start on 128-byte lines
+int lg_validate_R(const double* R, int d);         // R [d x d] is positive definite (any d: the landmark map's goes up to 32)
 
 }  // namespace rbpf
