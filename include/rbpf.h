@@ -862,6 +862,31 @@ int rbpf_loc_backward_workspace_bytes(int32_t N_P, int32_t N_T, int32_t n_traj, 
 int rbpf_loc_backward_step(int32_t N, int32_t M, const double* xn, const double* w, const double* xs_next, const double* odo,
                            double dt, const double* Q, const double* u, int32_t* index, double* logp, int32_t reps, double* ms);
 
+/* ---- the MAP trajectory of a localisation run ------------------------------------------------------
+ * MAP sequence estimation over the stored particles (Godsill, Doucet & West 2001): the one path through the forward particles
+ * X [7 x N_P x N_T] (as propagated) of a context created with keep_history = 1 and trace = 1, all N_T steps done, that maximises
+ * the joint of states and measurements.  A Viterbi recursion whose states at step t are the N_P particles:
+ *     delta(j, 1)   = log(w(j, 1))
+ *     delta(j, t+1) = log(w(j, t+1)) + max_i [ delta(i, t) + logp(X(:, j, t+1) | X(:, i, t)) ],   psi(j, t+1) = the arg max
+ *     i(N_T) = arg max_j delta(j, N_T),   i(t) = psi(i(t+1), t+1),   x_map(:, t) = X(:, i(t), t),   score = delta(i(N_T), N_T)
+ * with logp the density of rbpf_loc_backward_simulate and odometry row t, dt(t), Q(:,:,t).  Among equal candidates the lowest
+ * index wins, at every max.  log(w) stands in for the measurement likelihood: the filter resamples at every step, so the normalised
+ * weights are the likelihoods up to one constant per step; score is the log joint up to constants that do not depend on the path
+ * (those, and the normaliser of the transition density).  A particle with w = 0, or one no predecessor reaches, has delta = -inf
+ * and psi = 0.  In a fixed map the state is Markov, so the recursion is exact over particle paths.
+ * Outputs (NULL pointers are skipped): x_map [7 x N_T], index [N_T] 0-based, *score.  The workspace (psi as int32 [N_T][N_P], two
+ * rows of delta, the chunk partials, the predicted particles) comes from the context's pool and is returned before the call
+ * returns.  Refusals as rbpf_loc_backward_simulate: RBPF_ERR_STATE for steps missing, no keep_history / trace or a degenerate
+ * forward step, RBPF_ERR_UNSUPPORTED for a generic context (rbpf_loc_generic_map_* below).  The context stays usable.            */
+int rbpf_loc_map_trajectory(rbpf_ctx* ctx, double* x_map, int32_t* index, double* score);
+/* Bytes of device memory rbpf_loc_map_trajectory takes from the pool while it runs (no device access).                          */
+int rbpf_loc_map_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes);
+/* One step of the recursion on the caller's arrays, the kernel-level probe: xn [7 x N], delta [N] (-inf allowed), xs_next [7 x M]
+ * (the successors), odo [7], Q [6 x 6] -> best [M] = max_i [delta(i) + logp(xs_next(:, j) | xn(:, i))] and arg [M] its lowest arg
+ * max, 0 where best = -inf.  reps >= 1 repeats the step's launches; *ms (may be NULL) = median time of one step.                */
+int rbpf_loc_map_step(int32_t N, int32_t M, const double* xn, const double* delta, const double* xs_next, const double* odo, double dt,
+                      const double* Q, double* best, int32_t* arg, int32_t reps, double* ms);
+
 /* ---- localisation in the fixed map of a generic device-code model --------------------------------
  * particleFilter.m:100-161 with the map frozen: xl = mean and P = V'V (V lower n_lin x n_lin, column-major, lower triangle read:
  * the rbpf_loc_map convention) are the same for every particle and never updated (:163-204 are left out).  The model is the
@@ -966,6 +991,37 @@ int rbpf_loc_generic_backward_pose_workspace_bytes(int32_t n_nonlin, int32_t n_s
 int rbpf_loc_generic_backward_pose_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
                                         int32_t quat_pos, const double* mu, const double* w, const double* xs_next, const double* cov,
                                         const double* u, int32_t* index, double* logp, int32_t reps, double* ms);
+
+/* ---- the MAP trajectory in the fixed map of a generic device-code model ----
+ * The recursion of rbpf_loc_map_trajectory on a context of rbpf_loc_generic_create or rbpf_loc_landmark_create (the pass never reads
+ * the map), with the transition density of rbpf_loc_generic_backward_pose_begin: n_sel, rows, angle_mask, quat_pos as there,
+ * quat_pos = -1 for a density without a quaternion block (n_sel = n_res).  It runs FORWARDS in time, t = 0 .. N_T-2:
+ *   rbpf_loc_generic_map_begin   takes the workspace from the context's pool and enqueues delta of step 0.  The argument checks
+ *        of _pose_begin; RBPF_ERR_STATE: a MAP pass or a backward pass is open (the two cannot be open at once; _backward_begin
+ *        refuses likewise while a MAP pass is open), steps missing, no keep_history / trace, a degenerate forward step.
+ *   rbpf_loc_generic_map_particles_device   *t = the step the next step call processes, *xn_dev = its stored particles
+ *        [n_nonlin][N_P], library memory, read only.
+ *   rbpf_loc_generic_map_step_device   mu_dev [n_sel][N_P] = mean of the particles of step t on rbpf_stream_get(ctx), cov
+ *        [n_res x n_res] on the host, with odometry row t, dt(t), Q(:,:,t): what the backward pass gets for the same t.  A cov that
+ *        is not positive definite: RBPF_ERR_CHOL_FAILED, the step named, before anything is launched.  Enqueues prologue, all-pairs
+ *        pass and merge (delta and psi of step t+1) without waiting.
+ *   rbpf_loc_generic_map_finish   backtracks, synchronises, copies out (NULL outputs are skipped) x_map [n_nonlin x N_T], index
+ *        [N_T] 0-based, *score, and returns the workspace.  With steps left undone it returns the workspace all the same: RBPF_OK
+ *        when every output is NULL (the way out after a failed handle), RBPF_ERR_STATE otherwise.  rbpf_destroy releases an open
+ *        pass too.
+ *   rbpf_loc_generic_map_workspace_bytes   what begin takes from the pool (no device access): Xhat has n_sel + 1 rows.
+ *   rbpf_loc_generic_map_step   one step on host arrays, the kernel-level probe: mu [n_sel][N], delta [N], xs_next [n_nonlin x M]
+ *        column-major, cov [n_res x n_res] -> best [M], arg [M] as rbpf_loc_map_step.
+ * RBPF_ERR_STATE out of order (step without begin, begin twice, a step after the last); the context stays usable after any
+ * refusal.  Not built: sharding, host closures, N-best paths, other successors than the N_P particles outside the probe.           */
+int rbpf_loc_generic_map_begin(rbpf_ctx* ctx, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos);
+int rbpf_loc_generic_map_particles_device(rbpf_ctx* ctx, int32_t* t, const double** xn_dev);
+int rbpf_loc_generic_map_step_device(rbpf_ctx* ctx, const double* mu_dev, const double* cov);
+int rbpf_loc_generic_map_finish(rbpf_ctx* ctx, double* x_map, int32_t* index, double* score);
+int rbpf_loc_generic_map_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, size_t* bytes);
+int rbpf_loc_generic_map_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                              int32_t quat_pos, const double* mu, const double* delta, const double* xs_next, const double* cov,
+                              double* best, int32_t* arg, int32_t reps, double* ms);
 
 /* ---- localisation in the fixed landmark map of a generic device-code model ------------------------
  * The frozen-map filter above for a model of the sparseFeatures branch (particleFilter.m:100-161 with :127-137): the map posterior

@@ -15,7 +15,8 @@ from .host import (particleFilter, particleSmoother, particleSmootherInformation
                    domain_cartesian_dx, eigenval, PhiloxRNG, ReplayRNG, FilterSession, sample, chol_weights, chol_sweep_probe, pack_whiten_probe, sparse_ext_build_probe, sparse_smoother_timing, quat_helper,
                    GenericDenseModel, GenericSparseModel, DeviceHandles, DeviceSmootherHandles, DeviceSparseHandles, DeviceSparseSmootherHandles, particle_filter_external, chol_refresh_in_use,
                    DenseMagMap, DeviceMap, DeviceLandmarkMap, DeviceTransition, device_map_weights, landmark_map_weights, device_map_backward_step, device_map_backward_workspace_bytes, particleFilterLocalization, LocalizationSession, loc_workspace_bytes,
-                   particleSmootherLocalization, loc_backward_step, loc_backward_workspace_bytes)
+                   particleSmootherLocalization, loc_backward_step, loc_backward_workspace_bytes,
+                   particleMapLocalization, loc_map_step, loc_map_workspace_bytes, device_map_map_step, device_map_map_workspace_bytes)
 
 
 def device_count() -> int:

@@ -30,12 +30,16 @@
 // z'z does not depend on the order.  W is lower triangular, so the plain rows of z are final before the block is touched, and the
 // skip test sits there, after all NP plain rows and before the quaternion product and atan2 (NP = 0: no test).  The template
 // parameter QP of the term is NP with a block and -1 without one; with -1 the pair is gs_term.
+//
+// THE MAP TRAJECTORY (rbpf_loc_generic_map_*): the Viterbi recursion of rbpf_loc_viterbi.hpp on the same prologues, terms, layout and
+// factorisation, driven forwards in time (begin / particles_device / step_device for t = 0 .. N_T-2 / finish).
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
 #include "rbpf_ctx.hpp"
 #include "rbpf_loc_state.hpp"
 #include "rbpf_loc_backward.hpp"
+#include "rbpf_loc_viterbi.hpp"
 #include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
@@ -160,6 +164,7 @@ struct GsTerm : GsData {
   static constexpr int NS = QP < 0 ? NR : NR + 1;
   static constexpr int kLocateBound = QP < 0 ? 1024 : 64;
   __device__ __forceinline__ double load_x(const GsHead& y, const double* xs_next, int j, int k) const { return xs_next[(size_t)j * y.nN + y.rows[k]]; }
+  __device__ __forceinline__ double load_next(const GsHead& y, const double* xn, int ld, int j, int k) const { return xn[(size_t)y.rows[k] * ld + j]; }   // particles [nN][ld]
   static constexpr bool kSplit = false;       // gs_term and gs_pose_term hold their own test
   __device__ __forceinline__ bool pair(const GsHead& y, const double* h, const double (&x)[NS], double bound, double& l) const {
     if constexpr (QP < 0) return gs_term<NR, ANG>(W, y.angle_mask, h, x, bound, l);
@@ -173,61 +178,85 @@ struct GsTerm : GsData {
 typedef BackwardArgs<GsData> GsArgs;
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-template <int NR, bool ANG, int QP = -1>
-static hipError_t gs_launch_nr(const GsArgs& a, double* logp, hipStream_t s) {
-  const auto b = a.with(GsTerm<NR, ANG, QP>{a.term});
-  return logp ? backward_launch_logp(b, logp, s) : backward_launch_step(b, s);
-}
+// The term type of a layout is chosen at run time: gs_pick calls f(GsTag<GsTerm<NR, ANG, QP>>()) for it, f a generic lambda
+// that builds the kernel arguments with that term and launches.
+template <class T>
+struct GsTag { typedef T Term; };
 
-template <int NR>
-static hipError_t gs_launch_ang(const GsArgs& a, double* logp, hipStream_t s) {
-  return a.head.angle_mask ? gs_launch_nr<NR, true>(a, logp, s) : gs_launch_nr<NR, false>(a, logp, s);
+template <int NR, class F>
+static hipError_t gs_pick_ang(unsigned angle_mask, F&& f) {
+  return angle_mask ? f(GsTag<GsTerm<NR, true>>()) : f(GsTag<GsTerm<NR, false>>());
 }
 
 // a quaternion block behind NP plain rows; an angle row is one of those
-template <int NP>
-static hipError_t gs_launch_pose(const GsArgs& a, double* logp, hipStream_t s) {
+template <int NP, class F>
+static hipError_t gs_pick_pose(unsigned angle_mask, F&& f) {
   if constexpr (NP > 0) {
-    if (a.head.angle_mask) return gs_launch_nr<NP + 3, true, NP>(a, logp, s);
+    if (angle_mask) return f(GsTag<GsTerm<NP + 3, true, NP>>());
   }
-  return gs_launch_nr<NP + 3, false, NP>(a, logp, s);
+  return f(GsTag<GsTerm<NP + 3, false, NP>>());
 }
 
-// all-pairs pass + locate of one step (logp == null), or the logp kernel, in stream order
-static hipError_t gs_launch(const LocGenLayout& y, const GsArgs& a, double* logp, hipStream_t s) {
+template <class F>
+static hipError_t gs_pick(const LocGenLayout& y, unsigned angle_mask, F&& f) {
   if (y.n_plain >= 0) {
     switch (y.n_plain) {
-      case 0: return gs_launch_pose<0>(a, logp, s);
-      case 1: return gs_launch_pose<1>(a, logp, s);
-      case 2: return gs_launch_pose<2>(a, logp, s);
-      case 3: return gs_launch_pose<3>(a, logp, s);
-      case 4: return gs_launch_pose<4>(a, logp, s);
+      case 0: return gs_pick_pose<0>(angle_mask, f);
+      case 1: return gs_pick_pose<1>(angle_mask, f);
+      case 2: return gs_pick_pose<2>(angle_mask, f);
+      case 3: return gs_pick_pose<3>(angle_mask, f);
+      case 4: return gs_pick_pose<4>(angle_mask, f);
       default: return hipErrorInvalidValue;
     }
   }
   switch (y.n_res) {
-    case 1: return gs_launch_ang<1>(a, logp, s);
-    case 2: return gs_launch_ang<2>(a, logp, s);
-    case 3: return gs_launch_ang<3>(a, logp, s);
-    case 4: return gs_launch_ang<4>(a, logp, s);
-    case 5: return gs_launch_ang<5>(a, logp, s);
-    case 6: return gs_launch_ang<6>(a, logp, s);
-    case 7: return gs_launch_ang<7>(a, logp, s);
-    case 8: return gs_launch_ang<8>(a, logp, s);
+    case 1: return gs_pick_ang<1>(angle_mask, f);
+    case 2: return gs_pick_ang<2>(angle_mask, f);
+    case 3: return gs_pick_ang<3>(angle_mask, f);
+    case 4: return gs_pick_ang<4>(angle_mask, f);
+    case 5: return gs_pick_ang<5>(angle_mask, f);
+    case 6: return gs_pick_ang<6>(angle_mask, f);
+    case 7: return gs_pick_ang<7>(angle_mask, f);
+    case 8: return gs_pick_ang<8>(angle_mask, f);
     default: return hipErrorInvalidValue;
+  }
+}
+
+// all-pairs pass + locate of one step (logp == null), or the logp kernel, in stream order
+static hipError_t gs_launch(const LocGenLayout& y, const GsArgs& a, double* logp, hipStream_t s) {
+  return gs_pick(y, a.head.angle_mask, [&](auto tag) {
+    const auto b = a.with(typename decltype(tag)::Term{a.term});
+    return logp ? backward_launch_logp(b, logp, s) : backward_launch_step(b, s);
+  });
+}
+
+static void gs_launch_prologue(const LocGenLayout& y, int N, const double* mu, const double* w, double* Xhat, hipStream_t s) {
+  if (y.n_plain >= 0) {
+    GsSrc src;
+    for (int k = 0; k < kGsMaxRes; ++k) src.s[k] = y.src[k];
+    hipLaunchKernelGGL(gs_prologue_pose_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, y.n_sel, src, mu, w, Xhat);
+  } else {
+    hipLaunchKernelGGL(gs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, y.n_res, mu, w, Xhat);
   }
 }
 
 // prologue + pass + locate of one step
 static hipError_t gs_launch_step(const LocGenLayout& y, const GsArgs& a, const double* mu, const double* w, double* Xhat, hipStream_t s) {
-  if (y.n_plain >= 0) {
-    GsSrc src;
-    for (int k = 0; k < kGsMaxRes; ++k) src.s[k] = y.src[k];
-    hipLaunchKernelGGL(gs_prologue_pose_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, y.n_sel, src, mu, w, Xhat);
-  } else {
-    hipLaunchKernelGGL(gs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, y.n_res, mu, w, Xhat);
-  }
+  gs_launch_prologue(y, a.N, mu, w, Xhat, s);
   return gs_launch(y, a, nullptr, s);
+}
+
+typedef ViterbiArgs<GsData> GvArgs;
+
+// prologue + delta over its log w + max-plus pass + merge of one MAP step (rbpf_loc_viterbi.hpp)
+static hipError_t gs_launch_map_step(const LocGenLayout& y, const GvArgs& a, const double* mu, const double* w, const double* delta, double* Xhat,
+                                     const double* w_next, double* delta_next, int* psi_next, hipStream_t s) {
+  gs_launch_prologue(y, a.N, mu, w, Xhat, s);
+  const hipError_t e = gs_pick(y, a.head.angle_mask, [&](auto tag) {
+    return viterbi_launch_pass(a.with(typename decltype(tag)::Term{a.term}), delta, Xhat, s);
+  });
+  if (e != hipSuccess) return e;
+  return viterbi_launch_merge(a.M, a.nchunks, a.part_best, a.part_arg, w_next, delta_next, psi_next, s);
 }
 
 static int gs_validate_rows(int n_nonlin, int n_res, const int32_t* rows, uint32_t angle_mask) {
@@ -368,6 +397,7 @@ int rbpf_loc_generic_backward_pose_begin(rbpf_ctx* c, int32_t n_traj, const doub
   LocGenLayout lay;
   RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "backward simulation", "rbpf_loc_generic_backward_begin"));
   const int N = c->N, T = c->T, M = n_traj, nN = L->nN;
   LocGenBackward& g = L->gb;
@@ -483,6 +513,141 @@ int rbpf_loc_generic_backward_pose_step(int32_t N, int32_t M, int32_t n_nonlin, 
   if (logp) HIPCHK(gs_launch(lay, a, d_lp, 0));
   HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
   if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+// ---- the MAP trajectory ---------------------------------------------------------------------------------------------------
+int rbpf_loc_generic_map_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, size_t* bytes) {
+  if (!bytes) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (quat_pos == -1) {
+    if (n_nonlin < 1 || n_nonlin > kGsMaxNonlin || n_sel < 1 || n_sel > kGsMaxRes || n_sel > n_nonlin) {
+      set_error("n_nonlin must be in 1 .. 8 and n_res in 1 .. n_nonlin");
+      return RBPF_ERR_INVALID_ARG;
+    }
+  } else if (n_nonlin < 4 || n_nonlin > kGsMaxNonlin || n_sel < 4 || n_sel > n_nonlin || quat_pos < 0 || quat_pos + 4 > n_sel) {
+    set_error("with a quaternion block n_nonlin must be in 4 .. 8, n_sel in 4 .. n_nonlin and the block inside the n_sel rows");
+    return RBPF_ERR_INVALID_ARG;
+  }
+  if (N_P < 1 || N_T < 1) { set_error("N_P and N_T must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P > kMaxParticles) { set_error("N_P above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  *bytes = viterbi_bytes((size_t)n_nonlin, (size_t)n_sel, (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_map_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenLayout lay;
+  RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
+  if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
+  RB_TRY(backward_check_forward(c, "the MAP trajectory", "rbpf_loc_generic_map_begin"));
+  const int N = c->N, T = c->T;
+  LocGenBackward& g = L->gv;
+  g.M = N; g.lay = lay;
+  g.C = backward_chunk_size(N, N); g.nch = (N + g.C - 1) / g.C;
+  int s = viterbi_take(g.ws, c->pool, L->nN, lay.n_sel, N, T);
+  if (s == RBPF_OK) {
+    const hipError_t e = viterbi_launch_init(N, c->w, g.ws.u, c->stream);
+    if (e != hipSuccess) s = hip_fail(e, "delta of step 0", __FILE__, __LINE__);
+  }
+  if (s != RBPF_OK) { g.ws.release(); g = LocGenBackward(); return s; }
+  g.t = 0;
+  g.open = true;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_map_particles_device(rbpf_ctx* c, int32_t* t, const double** xn_dev) {
+  RB_TRY(gs_ctx_ok(c));
+  if (!t || !xn_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  const LocGenBackward& g = c->loc->gv;
+  if (!g.open) { set_error("no MAP pass is open (rbpf_loc_generic_map_begin first)"); return RBPF_ERR_STATE; }
+  if (g.t + 1 >= c->T) { set_error("every step of the MAP pass is done (rbpf_loc_generic_map_finish)"); return RBPF_ERR_STATE; }
+  *t = g.t;
+  *xn_dev = c->X + (size_t)g.t * c->loc->nN * c->N;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_map_step_device(rbpf_ctx* c, const double* mu_dev, const double* cov) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenBackward& g = L->gv;
+  if (!g.open) { set_error("no MAP pass is open (rbpf_loc_generic_map_begin first)"); return RBPF_ERR_STATE; }
+  if (g.t + 1 >= c->T) { set_error("every step of the MAP pass is done (rbpf_loc_generic_map_finish)"); return RBPF_ERR_STATE; }
+  if (!mu_dev || !cov) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  const int N = c->N, nN = L->nN, t = g.t;
+  GvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, g.lay, a.term.W, " of step " + std::to_string(t)));
+  HIPCHK(hipSetDevice(c->device));
+  a.N = N; a.M = N; a.C = g.C; a.nchunks = g.nch; a.head.nN = nN; a.head.angle_mask = g.lay.angle_mask;
+  for (int k = 0; k < g.lay.n_sel; ++k) a.head.rows[k] = g.lay.rows[k];
+  a.Xhat = g.ws.Xhat; a.xn_next = c->X + (size_t)(t + 1) * nN * N; a.part_best = g.ws.pm; a.part_arg = g.ws.arg;
+  HIPCHK(gs_launch_map_step(g.lay, a, mu_dev, c->w + (size_t)t * N, g.ws.u + (size_t)(t & 1) * N, g.ws.Xhat, c->w + (size_t)(t + 1) * N,
+                            g.ws.u + (size_t)((t + 1) & 1) * N, g.ws.idx + (size_t)(t + 1) * N, c->stream));
+  g.t = t + 1;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_map_finish(rbpf_ctx* c, double* x_map, int32_t* index, double* score) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenBackward& g = L->gv;
+  if (!g.open) { set_error("no MAP pass is open (rbpf_loc_generic_map_begin first)"); return RBPF_ERR_STATE; }
+  const int N = c->N, T = c->T, nN = L->nN, t_next = g.t;
+  BackwardWorkspace ws = g.ws;
+  g = LocGenBackward();                                                  // the pass is closed whichever way this returns,
+  BackwardWorkspaceGuard lease(ws);                                      // and its workspace goes back
+  HIPCHK(hipSetDevice(c->device));
+  if (t_next + 1 < T) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (!x_map && !index && !score) return RBPF_OK;                      // the way out of a pass that was given up
+    set_error("rbpf_loc_generic_map_finish: steps " + std::to_string(t_next) + " .. " + std::to_string(T - 2) + " of the MAP pass were not run");
+    return RBPF_ERR_STATE;
+  }
+  const hipError_t e = viterbi_launch_backtrack(N, T, nN, c->X, ws.idx, ws.u + (size_t)((T - 1) & 1) * N, ws.mean, ws.idx + (size_t)T * N,
+                                                ws.mean + (size_t)nN * T, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);                 // (waited for whichever way this returns: the workspace goes back)
+  HIPCHK(e);
+  HIPCHK(e2);
+  RB_TRY(ctx_check_flags(c));
+  return viterbi_copy_out(ws, nN, N, T, x_map, index, score);
+}
+
+int rbpf_loc_generic_map_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos,
+                              const double* mu, const double* delta, const double* xs_next, const double* cov, double* best, int32_t* arg,
+                              int32_t reps, double* ms) {
+  if (!mu || !delta || !xs_next || !cov || !best || !arg || !rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles || M > kMaxParticles) { set_error("N or M above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  LocGenLayout lay;
+  RB_TRY(gs_layout(n_nonlin, n_sel, rows, angle_mask, quat_pos, lay));
+  GvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, lay, a.term.W, ""));
+  if (!have_device()) { set_error("no HIP device: the MAP pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  const int C = backward_chunk_size(N, M), nch = (N + C - 1) / C;
+  std::vector<double> xt((size_t)n_nonlin * M);                           // the successors as the history holds them: [n_nonlin][M]
+  for (int j = 0; j < M; ++j)
+    for (int r = 0; r < n_nonlin; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * n_nonlin + r];
+  DevicePool tmp;
+  double *d_mu = nullptr, *d_delta = nullptr, *d_xs = nullptr, *d_Xhat = nullptr, *d_pb = nullptr, *d_best = nullptr;
+  int *d_pa = nullptr, *d_arg = nullptr;
+  RB_TRY(tmp.upload(&d_mu, mu, (size_t)lay.n_sel * N));
+  RB_TRY(tmp.upload(&d_delta, delta, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)n_nonlin * M));
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)(lay.n_sel + 1) * N));
+  RB_TRY(tmp.alloc(&d_pb, (size_t)nch * M));
+  RB_TRY(tmp.alloc(&d_pa, (size_t)nch * M));
+  RB_TRY(tmp.alloc(&d_best, (size_t)M));
+  RB_TRY(tmp.alloc(&d_arg, (size_t)M));
+  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.head.nN = n_nonlin; a.head.first = 0; a.head.angle_mask = lay.angle_mask;
+  for (int k = 0; k < lay.n_sel; ++k) a.head.rows[k] = lay.rows[k];
+  a.Xhat = d_Xhat; a.xn_next = d_xs; a.part_best = d_pb; a.part_arg = d_pa;
+  // (the prologue's last row is overwritten with delta: what it reads as w does not matter)
+  RB_TRY(timed_reps(reps, 0, [&] { return gs_launch_map_step(lay, a, d_mu, d_delta, d_delta, d_Xhat, nullptr, d_best, d_arg, 0); }, ms));
+  HIPCHK(hipMemcpy(best, d_best, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(arg, d_arg, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 

@@ -13,12 +13,14 @@
 //   bs_prologue_kernel   Xhat[t][:, i] = (p_i + dx(1:3), a_i, log w_i): 8 doubles per particle, SoA, shared by all M trajectories.
 //   BsTerm               logp of one pair: the position term, then the orientation term.  A pair whose log w + position term alone
 //                        lies more than 746 below the running max skips its orientation term: its exp is exactly 0.
+// The MAP trajectory (rbpf_loc_map_trajectory, the recursion and kernels of rbpf_loc_viterbi.hpp) runs on the same prologue and term.
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
 #include "rbpf_ctx.hpp"
 #include "rbpf_loc_state.hpp"
 #include "rbpf_loc_backward.hpp"
+#include "rbpf_loc_viterbi.hpp"
 #include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
@@ -83,6 +85,7 @@ struct BsTerm {
   static constexpr int kLocateBound = 1024;   // the default
   BsNoise nz;
   __device__ __forceinline__ double load_x(Head, const double* xs_next, int j, int k) const { return xs_next[(size_t)j * 7 + k]; }
+  __device__ __forceinline__ double load_next(Head, const double* xn, int ld, int j, int k) const { return xn[(size_t)k * ld + j]; }   // particles [7][ld]
   static constexpr bool kSplit = true;        // the skip test sits between the two terms
   __device__ __forceinline__ double pair_near(Head, const double* h, const double (&x)[7]) const { return bs_pos_term(nz, h, x); }
   __device__ __forceinline__ double pair_far(Head, const double* h, const double (&x)[7]) const { return bs_rot_term(nz, h, x); }
@@ -124,6 +127,15 @@ static hipError_t bs_launch_step(const BackwardArgs<BsTerm>& a, const double* xn
                                  double* Xhat, hipStream_t s) {
   hipLaunchKernelGGL(bs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, xn, cs, ps, w, odo, Xhat);
   return backward_launch_step(a, s);
+}
+
+// prologue + delta over its log w + max-plus pass + merge of one MAP step: (best, arg) of every successor into delta_next / psi_next
+static hipError_t bs_launch_map_step(const ViterbiArgs<BsTerm>& a, const double* xn, size_t cs, size_t ps, const double* w, const double* odo,
+                                     const double* delta, double* Xhat, const double* w_next, double* delta_next, int* psi_next, hipStream_t s) {
+  hipLaunchKernelGGL(bs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, xn, cs, ps, w, odo, Xhat);
+  const hipError_t e = viterbi_launch_pass(a, delta, Xhat, s);
+  if (e != hipSuccess) return e;
+  return viterbi_launch_merge(a.M, a.nchunks, a.part_best, a.part_arg, w_next, delta_next, psi_next, s);
 }
 
 }  // namespace rbpf
@@ -244,6 +256,93 @@ int rbpf_loc_backward_step(int32_t N, int32_t M, const double* xn, const double*
   if (logp) HIPCHK(backward_launch_logp(a, d_lp, 0));
   HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
   if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+int rbpf_loc_map_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes) {
+  if (!bytes) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P < 1 || N_T < 1) { set_error("N_P and N_T must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P > kMaxParticles) { set_error("N_P above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  *bytes = viterbi_bytes(7, 7, (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_map_trajectory(rbpf_ctx* c, double* x_map, int32_t* index, double* score) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (c->loc->generic) {
+    set_error("the MAP trajectory needs the transition density of dynModel: a generic map's dynModel is a sampler (its handles carry no density)");
+    return RBPF_ERR_UNSUPPORTED;
+  }
+  RB_TRY(backward_check_forward(c, "rbpf_loc_map_trajectory", "rbpf_loc_map_trajectory"));
+  LocState* L = c->loc;
+  const int N = c->N, T = c->T;
+  std::vector<BsNoise> nz((size_t)L->s_pages);
+  {
+    std::vector<double> S((size_t)L->s_pages * 36);
+    HIPCHK(hipMemcpy(S.data(), L->d_S, S.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < (T > 1 ? L->s_pages : 0); ++p) RB_TRY(bs_noise(S.data() + (size_t)p * 36, nz[p]));
+  }
+  const int C = backward_chunk_size(N, N), nch = (N + C - 1) / C;
+  BackwardWorkspace ws;
+  BackwardWorkspaceGuard lease(ws);
+  RB_TRY(viterbi_take(ws, c->pool, 7, 7, N, T));
+  HIPCHK(viterbi_launch_init(N, c->w, ws.u, c->stream));
+  for (int t = 0; t + 1 < T; ++t) {
+    ViterbiArgs<BsTerm> a;
+    a.N = N; a.M = N; a.C = C; a.nchunks = nch; a.head.first = 0;
+    a.Xhat = ws.Xhat; a.xn_next = c->X + (size_t)(t + 1) * 7 * N; a.part_best = ws.pm; a.part_arg = ws.arg;
+    a.term.nz = nz[L->s_pages > 1 ? t : 0];
+    HIPCHK(bs_launch_map_step(a, c->X + (size_t)t * 7 * N, (size_t)N, 1, c->w + (size_t)t * N, c->d_odo + (size_t)t * 7,
+                              ws.u + (size_t)(t & 1) * N, ws.Xhat, c->w + (size_t)(t + 1) * N, ws.u + (size_t)((t + 1) & 1) * N,
+                              ws.idx + (size_t)(t + 1) * N, c->stream));
+  }
+  HIPCHK(viterbi_launch_backtrack(N, T, 7, c->X, ws.idx, ws.u + (size_t)((T - 1) & 1) * N, ws.mean, ws.idx + (size_t)T * N,
+                                  ws.mean + (size_t)7 * T, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  RB_TRY(ctx_check_flags(c));
+  return viterbi_copy_out(ws, 7, N, T, x_map, index, score);
+}
+
+int rbpf_loc_map_step(int32_t N, int32_t M, const double* xn, const double* delta, const double* xs_next, const double* odo, double dt,
+                      const double* Q, double* best, int32_t* arg, int32_t reps, double* ms) {
+  if (!xn || !delta || !xs_next || !odo || !Q || !best || !arg) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles || M > kMaxParticles) { set_error("N or M above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  double S[36];
+  for (int q = 0; q < 36; ++q) S[q] = 0.0;
+  for (int b = 0; b < 2; ++b)
+    for (int cc = 0; cc < 3; ++cc)
+      for (int r = 0; r < 3; ++r) {
+        const int q = (3 * b + r) + 6 * (3 * b + cc);
+        const double v = dt * Q[q];
+        if (!(v >= 0.0)) { set_error("dt * Q has a negative entry in a diagonal block: the element-wise sqrt of dynModel would be complex"); return RBPF_ERR_INVALID_ARG; }
+        S[q] = std::sqrt(v);
+      }
+  ViterbiArgs<BsTerm> a;
+  RB_TRY(bs_noise(S, a.term.nz));
+  if (!have_device()) { set_error("no HIP device: the MAP pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  const int C = backward_chunk_size(N, M), nch = (N + C - 1) / C;
+  std::vector<double> xt((size_t)7 * M);                                  // the successors as the history holds them: [7][M]
+  for (int j = 0; j < M; ++j)
+    for (int r = 0; r < 7; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * 7 + r];
+  DevicePool tmp;
+  double *d_xn = nullptr, *d_delta = nullptr, *d_xs = nullptr, *d_odo = nullptr, *d_Xhat = nullptr, *d_pb = nullptr, *d_best = nullptr;
+  int *d_pa = nullptr, *d_arg = nullptr;
+  RB_TRY(tmp.upload(&d_xn, xn, (size_t)7 * N));
+  RB_TRY(tmp.upload(&d_delta, delta, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)7 * M));
+  RB_TRY(tmp.upload(&d_odo, odo, (size_t)7));
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)8 * N));
+  RB_TRY(tmp.alloc(&d_pb, (size_t)nch * M));
+  RB_TRY(tmp.alloc(&d_pa, (size_t)nch * M));
+  RB_TRY(tmp.alloc(&d_best, (size_t)M));
+  RB_TRY(tmp.alloc(&d_arg, (size_t)M));
+  a.N = N; a.M = M; a.C = C; a.nchunks = nch; a.head.first = 0;
+  a.Xhat = d_Xhat; a.xn_next = d_xs; a.part_best = d_pb; a.part_arg = d_pa;
+  // (the prologue's last row is overwritten with delta: what it reads as w does not matter)
+  RB_TRY(timed_reps(reps, 0, [&] { return bs_launch_map_step(a, d_xn, 1, 7, d_delta, d_odo, d_delta, d_Xhat, nullptr, d_best, d_arg, 0); }, ms));
+  HIPCHK(hipMemcpy(best, d_best, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(arg, d_arg, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 

@@ -31,6 +31,7 @@ struct BackwardWorkspace {
   double *u = nullptr;             // [T][M]: n_draws
   double *xs = nullptr, *mean = nullptr;
   int* idx = nullptr;              // [T][M]: n_draws
+  int* arg = nullptr;              // a MAP pass only (take_map)
   // all or nothing: a failed allocation hands back what was taken before it
   int take(DevicePool& from, size_t n_Xhat, size_t n_part, size_t n_draws, size_t n_xs, size_t n_mean) {
     pool = &from;
@@ -44,9 +45,22 @@ struct BackwardWorkspace {
     if (s != RBPF_OK) release();
     return s;
   }
+  // the buffers of a MAP pass (rbpf_loc_viterbi.hpp) in the same fields: pm and arg [n_part] the chunk partials (best, arg max),
+  // u [n_delta] two rows of delta, idx [n_psi] psi and the path's index, mean [n_xmap] x_map and the score; ps and xs stay null
+  int take_map(DevicePool& from, size_t n_Xhat, size_t n_part, size_t n_delta, size_t n_psi, size_t n_xmap) {
+    pool = &from;
+    int s = from.alloc(&Xhat, n_Xhat);
+    if (s == RBPF_OK) s = from.alloc(&pm, n_part);
+    if (s == RBPF_OK) s = from.alloc(&arg, n_part);
+    if (s == RBPF_OK) s = from.alloc(&u, n_delta);
+    if (s == RBPF_OK) s = from.alloc(&idx, n_psi);
+    if (s == RBPF_OK) s = from.alloc(&mean, n_xmap);
+    if (s != RBPF_OK) release();
+    return s;
+  }
   void release() {
     if (pool)
-      for (void* p : {(void*)Xhat, (void*)pm, (void*)ps, (void*)u, (void*)xs, (void*)mean, (void*)idx}) pool->release(p);
+      for (void* p : {(void*)Xhat, (void*)pm, (void*)ps, (void*)u, (void*)xs, (void*)mean, (void*)idx, (void*)arg}) pool->release(p);
     *this = BackwardWorkspace();
   }
 };
@@ -60,7 +74,8 @@ struct BackwardWorkspaceGuard {
 };
 
 // An open backward-simulation pass over a generic map (rbpf_loc_generic_backward_begin .. _finish, rbpf_loc_generic_smooth.hip): the
-// workspace is taken from rbpf_ctx::pool at begin and handed back at finish (or with the context).
+// workspace is taken from rbpf_ctx::pool at begin and handed back at finish (or with the context).  An open MAP pass
+// (rbpf_loc_generic_map_begin .. _finish) is kept in the same form.
 struct LocGenBackward {
   bool open = false;
   int M = 0, C = 0, nch = 0;
@@ -84,6 +99,7 @@ struct LocState {
   double *d_R = nullptr;           // [n_y x n_y]
   double *d_H = nullptr;           // [N][n_y][ldx] rows packed from dy layout 0 (allocated on first use)
   LocGenBackward gb;               // backward simulation with a Gaussian transition density
+  LocGenBackward gv;               // the MAP trajectory with one (rbpf_loc_generic_map_begin .. _finish): t counts up, M = N_P; never open with gb
   // landmark map (rbpf_loc_landmark_create): the handle's yhat is the prediction and the outputs observed at a step are selected
   bool landmark = false;
   int *d_ind = nullptr;            // [N_T][32]: the observed outputs of every step, ascending

@@ -1982,29 +1982,21 @@ def device_map_backward_workspace_bytes(n_nonlin, n_res, N_P, N_T, n_traj, quat_
     return int(nbytes.value)
 
 
-def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), want_logp=False, reps=1, quat_rows=None):
-    """rbpf_loc_generic_backward_step, the kernel-level probe: one backward step with a Gaussian transition on the caller's arrays.
-    mu [n_res x N] (the predicted rows of every particle), w [N], xs_next [n_nonlin x M], cov [n_res x n_res], u [M]; rows (default:
-    all n_nonlin = n_res rows) and angle_rows as in DeviceTransition -> (index [M], logp [N x M] or None, median ms of one step).
-    quat_rows as in DeviceTransition (rbpf_loc_generic_backward_pose_step): mu is then [n_sel x N], n_sel = len(rows) = n_res + 1, its
-    block rows the predicted unit quaternion."""
-    lib = load_library()
+def _transition_probe_args(mu, xs_next, cov, rows, angle_rows, quat_rows):
+    """The arrays and integers the one-step probes of a Gaussian transition share: (mu [n_sel x N] C-contiguous, xs_next
+    [n_nonlin x M] Fortran-ordered, cov [n_res x n_res], rows (int32), angle_mask, quat_pos or -1)."""
     mu = np.asarray(mu, dtype=np.float64)
     mu = np.ascontiguousarray(mu.reshape(1, -1) if mu.ndim == 1 else mu)
     xs_next = np.asarray(xs_next, dtype=np.float64)
     xs_next = np.asfortranarray(xs_next.reshape(1, -1) if xs_next.ndim == 1 else xs_next)
-    n_sel, N = mu.shape
+    n_sel = mu.shape[0]
     n_res = n_sel if quat_rows is None else n_sel - 1
-    nN, M = xs_next.shape
-    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).ravel())
-    u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).ravel())
+    nN = xs_next.shape[0]
     cov = np.asarray(cov, dtype=np.float64)
     cov = cov.reshape(1, 1) if cov.ndim == 0 else cov
     if cov.shape != (n_res, n_res):
         raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"cov is {cov.shape}, expected {(n_res, n_res)}")
     cov = np.asfortranarray(cov)
-    if w.size != N or u.size != M:
-        raise ValueError("w must be [N] and u [M]")
     if rows is None:
         rows_a, mask = np.arange(nN, dtype=np.int32), 0
         for r in angle_rows:
@@ -2023,17 +2015,60 @@ def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), w
             if pos.size == 0:
                 raise RBPFError(_ffi.RBPF_ERR_INVALID_ARG, f"angle row {int(r)} is not one of rows {tuple(rows_a.tolist())}")
             mask |= 1 << int(pos[0])
+    qpos = -1 if quat_rows is None else _quat_position(rows_a.tolist(), angle_rows, quat_rows)
+    return mu, xs_next, cov, rows_a, mask, qpos
+
+
+def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), want_logp=False, reps=1, quat_rows=None):
+    """rbpf_loc_generic_backward_step, the kernel-level probe: one backward step with a Gaussian transition on the caller's arrays.
+    mu [n_res x N] (the predicted rows of every particle), w [N], xs_next [n_nonlin x M], cov [n_res x n_res], u [M]; rows (default:
+    all n_nonlin = n_res rows) and angle_rows as in DeviceTransition -> (index [M], logp [N x M] or None, median ms of one step).
+    quat_rows as in DeviceTransition (rbpf_loc_generic_backward_pose_step): mu is then [n_sel x N], n_sel = len(rows) = n_res + 1, its
+    block rows the predicted unit quaternion."""
+    lib = load_library()
+    mu, xs_next, cov, rows_a, mask, qpos = _transition_probe_args(mu, xs_next, cov, rows, angle_rows, quat_rows)
+    (n_sel, N), (nN, M) = mu.shape, xs_next.shape
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).ravel())
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).ravel())
+    if w.size != N or u.size != M:
+        raise ValueError("w must be [N] and u [M]")
     index = np.zeros(M, dtype=np.int32)
     logp = np.empty((N, M), order="F") if want_logp else None
     ms = C.c_double(0.0)
     if quat_rows is None:
-        check(lib.rbpf_loc_generic_backward_step(N, M, nN, n_res, _ip(rows_a), mask, _dp(mu), _dp(w), _dp(xs_next), _dp(cov), _dp(u), _ip(index),
+        check(lib.rbpf_loc_generic_backward_step(N, M, nN, n_sel, _ip(rows_a), mask, _dp(mu), _dp(w), _dp(xs_next), _dp(cov), _dp(u), _ip(index),
                                                  _dp(logp) if want_logp else None, int(reps), C.byref(ms)))
     else:
-        qpos = _quat_position(rows_a.tolist(), angle_rows, quat_rows)
         check(lib.rbpf_loc_generic_backward_pose_step(N, M, nN, n_sel, _ip(rows_a), mask, qpos, _dp(mu), _dp(w), _dp(xs_next), _dp(cov), _dp(u),
                                                       _ip(index), _dp(logp) if want_logp else None, int(reps), C.byref(ms)))
     return index, logp, ms.value
+
+
+def device_map_map_step(mu, delta, xs_next, cov, rows=None, angle_rows=(), reps=1, quat_rows=None):
+    """rbpf_loc_generic_map_step, the kernel-level probe: one step of the MAP recursion with a Gaussian transition on the caller's
+    arrays.  mu [n_sel x N], delta [N] (-inf allowed), xs_next [n_nonlin x M] (the successors), cov [n_res x n_res]; rows, angle_rows
+    and quat_rows as in device_map_backward_step -> (best [M] = max_i [delta_i + logp(xs_next[:, j] | i)], arg [M] the lowest arg max,
+    0 where best is -inf, median ms of one step)."""
+    lib = load_library()
+    mu, xs_next, cov, rows_a, mask, qpos = _transition_probe_args(mu, xs_next, cov, rows, angle_rows, quat_rows)
+    (n_sel, N), (nN, M) = mu.shape, xs_next.shape
+    delta = np.ascontiguousarray(np.asarray(delta, dtype=np.float64).ravel())
+    if delta.size != N:
+        raise ValueError("delta must be [N]")
+    best, arg = np.empty(M), np.zeros(M, dtype=np.int32)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_generic_map_step(N, M, nN, n_sel, _ip(rows_a), mask, qpos, _dp(mu), _dp(delta), _dp(xs_next), _dp(cov), _dp(best),
+                                        _ip(arg), int(reps), C.byref(ms)))
+    return best, arg, ms.value
+
+
+def device_map_map_workspace_bytes(n_nonlin, n_sel, N_P, N_T, quat_pos=-1):
+    """rbpf_loc_generic_map_workspace_bytes (no device access): n_sel = len(rows), quat_pos the position of a quaternion block in
+    rows or -1."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_generic_map_workspace_bytes(int(n_nonlin), int(n_sel), int(quat_pos), int(N_P), int(N_T), C.byref(nbytes)))
+    return int(nbytes.value)
 
 
 class DeviceMap:
@@ -2553,16 +2588,15 @@ class LocalizationSession:
                                                   _dp(b["traj_smooth_mean"]) if "traj_smooth_mean" in b else None))
         return b
 
-    def _backward_in_device_map(self, M, u, seed, b):
-        """The backward pass with the map's DeviceTransition: the covariance pages on the host first, then begin, one
-        particles_device / mean handle / step_device per step in stream order, finish (also the way out of a failed handle)."""
-        lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
-        torch, T, N, nN = drv.torch, prob.N_T, prob.N_P, self.nN
-        rows, mask, qpos, n_res = tr.layout(nN)
-        n_sel = len(rows)                                         # the rows of mu: n_res + 1 with a quaternion block
+    def _transition_pages(self):
+        """What a pass with the map's DeviceTransition needs before it begins: (rows, angle_mask, quat_pos, n_sel = the rows of mu
+        (n_res + 1 with a quaternion block), covs, page).  covs[(page of dt, page of Q)] = cov(dt, Q), one per distinct page of steps
+        0 .. N_T-2, each checked here, before any kernel runs."""
+        tr, prob = self.map.transition, self.prob
+        rows, mask, qpos, n_res = tr.layout(self.nN)
         page = lambda a, t: t if a > 1 else 0                                                     # noqa: E731
         covs = {}
-        for t in range(T - 1):                                    # one factorisation per distinct (dt, Q) page, checked before any kernel runs
+        for t in range(prob.N_T - 1):
             key = (page(prob._dt.size, t), page(prob._Q.shape[2], t))
             if key not in covs:
                 c = tr.covariance(prob._dt[key[0]], prob._Q[:, :, key[1]], n_res)
@@ -2574,7 +2608,14 @@ class LocalizationSession:
                     raise RBPFError(_ffi.RBPF_ERR_CHOL_FAILED, f"cov(dt, Q) of step {t} is not positive definite: the transition density "
                                                                "does not exist") from None
                 covs[key] = c
-        rows_a = np.asarray(rows, dtype=np.int32)
+        return np.asarray(rows, dtype=np.int32), mask, qpos, len(rows), covs, page
+
+    def _backward_in_device_map(self, M, u, seed, b):
+        """The backward pass with the map's DeviceTransition: the covariance pages on the host first, then begin, one
+        particles_device / mean handle / step_device per step in stream order, finish (also the way out of a failed handle)."""
+        lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
+        torch, T, N, nN = drv.torch, prob.N_T, prob.N_P, self.nN
+        rows_a, mask, qpos, n_sel, covs, page = self._transition_pages()
         check(lib.rbpf_loc_generic_backward_pose_begin(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed), n_sel, _ip(rows_a), mask,
                                                        qpos))
         try:
@@ -2607,6 +2648,69 @@ class LocalizationSession:
         finally:
             self._keep_mu = None
 
+    def map_trajectory(self, want=("x_map", "index", "score")):
+        """rbpf_loc_map_trajectory: the MAP trajectory over the stored particles (keep_history and trace, every step done), a Viterbi
+        recursion whose states at step t are the N_P particles (Godsill, Doucet & West 2001).  Returns a dict of what `want` names:
+        x_map [7 x N_T] (one stored particle per step), index [N_T] (0-based, which one) and score = delta_{T-1}(i_{T-1}), the log
+        joint of the path and the measurements up to constants that do not depend on the path.  Among equal candidates the lowest
+        index wins.  In a DeviceMap: n_nonlin rows in place of 7, with the map's DeviceTransition (rbpf_loc_generic_map_*); without
+        one the call is refused."""
+        if self.driver is not None and self.map.transition is None:
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, _NO_BACKWARD_IN_DEVICE_MAP)
+        unknown = set(want) - {"x_map", "index", "score"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        T = self.prob.N_T
+        x_map = np.empty((self.nN, T), order="F") if "x_map" in want else None
+        index = np.zeros(T, dtype=np.int32) if "index" in want else None
+        score = C.c_double(0.0)
+        outs = (_dp(x_map) if x_map is not None else None, _ip(index) if index is not None else None,
+                C.byref(score) if "score" in want else None)
+        if self.driver is not None:
+            self._map_in_device_map(outs)
+        else:
+            check(self.lib.rbpf_loc_map_trajectory(self.ctx, *outs))
+        b = {}
+        if x_map is not None:
+            b["x_map"] = x_map
+        if index is not None:
+            b["index"] = index
+        if "score" in want:
+            b["score"] = float(score.value)
+        return b
+
+    def _map_in_device_map(self, outs):
+        """The MAP pass with the map's DeviceTransition: the covariance pages on the host first, then begin, one particles_device /
+        mean handle / step_device per step t = 0 .. N_T-2 in stream order, finish (also the way out of a failed handle)."""
+        lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
+        torch, T, N, nN = drv.torch, prob.N_T, prob.N_P, self.nN
+        rows_a, mask, qpos, n_sel, covs, page = self._transition_pages()
+        check(lib.rbpf_loc_generic_map_begin(self.ctx, n_sel, _ip(rows_a), mask, qpos))
+        try:
+            with torch.cuda.stream(drv.stream):
+                for _ in range(T - 1):
+                    t, xn = C.c_int32(0), C.c_void_p()
+                    check(lib.rbpf_loc_generic_map_particles_device(self.ctx, C.byref(t), C.byref(xn)))
+                    t = t.value
+                    X = drv._view(torch, xn, (nN, N), drv.device)
+                    Q = drv.Q[page(drv.Q.shape[0], t)]
+                    mu = tr.mean(X, drv.odo[t], float(drv.dt[page(drv.dt.size, t)]), Q)
+                    if not torch.is_tensor(mu) or tuple(mu.shape) != (n_sel, N) or mu.dtype != torch.float64 or not mu.is_cuda:
+                        what = f"{tuple(mu.shape)} {mu.dtype} on {mu.device}" if torch.is_tensor(mu) else type(mu).__name__
+                        raise ValueError(f"mean returned {what}, expected a float64 device tensor of shape {(n_sel, N)}")
+                    mu = mu.contiguous()
+                    self._keep_mu = mu                            # read in stream order by the step just enqueued
+                    check(lib.rbpf_loc_generic_map_step_device(self.ctx, C.c_void_p(mu.data_ptr()),
+                                                               _dp(covs[(page(prob._dt.size, t), page(prob._Q.shape[2], t))])))
+        except BaseException:
+            lib.rbpf_loc_generic_map_finish(self.ctx, None, None, None)
+            self._keep_mu = None
+            raise
+        try:
+            check(lib.rbpf_loc_generic_map_finish(self.ctx, *outs))
+        finally:
+            self._keep_mu = None
+
     def close(self):
         if self.ctx:
             self.lib.rbpf_destroy(self.ctx)
@@ -2617,6 +2721,56 @@ class LocalizationSession:
 
     def __exit__(self, *a):
         self.close()
+
+
+def loc_map_workspace_bytes(N_P, N_T):
+    """rbpf_loc_map_workspace_bytes (no device access)."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_map_workspace_bytes(int(N_P), int(N_T), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def loc_map_step(xn, delta, xs_next, odo, dt, Q, reps=1):
+    """rbpf_loc_map_step, the kernel-level probe: one step of the MAP recursion on the caller's arrays.  xn [7 x N], delta [N],
+    xs_next [7 x M] (the successors), odo [7], Q [6 x 6] -> (best [M], arg [M], median ms of one step)."""
+    lib = load_library()
+    xn = np.asfortranarray(np.asarray(xn, dtype=np.float64).reshape(7, -1))
+    xs_next = np.asfortranarray(np.asarray(xs_next, dtype=np.float64).reshape(7, -1))
+    N, M = xn.shape[1], xs_next.shape[1]
+    delta = np.ascontiguousarray(np.asarray(delta, dtype=np.float64).ravel())
+    odo = np.ascontiguousarray(np.asarray(odo, dtype=np.float64).ravel())
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(6, 6))
+    if delta.size != N or odo.size != 7:
+        raise ValueError("delta must be [N] and odo [7]")
+    best, arg = np.empty(M), np.zeros(M, dtype=np.int32)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_map_step(N, M, _dp(xn), _dp(delta), _dp(xs_next), _dp(odo), float(dt), _dp(Q), _dp(best), _ip(arg), int(reps), C.byref(ms)))
+    return best, arg, ms.value
+
+
+def particleMapLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, dt, *, rng=None, extras=False):
+    """The MAP trajectory of localisation in a fixed map: particleFilterLocalization, then MAP sequence estimation over its stored
+    particles (LocalizationSession.map_trajectory) -> (x_map [7 x N_T], score[, extras]).  dynModel / measModel, R and rng as
+    particleSmootherLocalization takes them: the handles of a DenseMagMap, or a DeviceMap with a DeviceTransition as dynModel
+    (measModel None), n_nonlin rows in place of 7.  extras: the filter's outputs (traj_max, traj_mean, first_degenerate_step, ...)
+    and `index` [N_T], the particle of every step."""
+    import warnings
+    mp = _device_map(dynModel, measModel)
+    if mp is not None and mp.transition is None:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleMapLocalization: " + _NO_BACKWARD_IN_DEVICE_MAP)
+    if mp is None:
+        mp = _recognise_map(dynModel, measModel)
+    with LocalizationSession(mp, odometry, y, x0_nonLin, Q, N_P, dt, rng=rng, keep_history=True, trace=True) as s:
+        s.advance(s.prob.N_T)
+        fwd = s.finish(extras=extras)
+        if fwd["first_degenerate_step"] >= 0:
+            warnings.warn(f"Weights filter close to zero at t={fwd['first_degenerate_step'] + 1} !!!", RuntimeWarning, stacklevel=2)
+        out = s.map_trajectory()
+    if extras:
+        fwd["index"] = out["index"]
+        return out["x_map"], out["score"], fwd
+    return out["x_map"], out["score"]
 
 
 def loc_backward_workspace_bytes(N_P, N_T, n_traj):
