@@ -887,6 +887,32 @@ int rbpf_loc_map_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes);
 int rbpf_loc_map_step(int32_t N, int32_t M, const double* xn, const double* delta, const double* xs_next, const double* odo, double dt,
                       const double* Q, double* best, int32_t* arg, int32_t reps, double* ms);
 
+/* ---- the marginal smoothing weights of a localisation run -------------------------------------------
+ * Forward filtering, backward smoothing (FFBSm, Doucet, Godsill & Andrieu 2000) over the forward particles X [7 x N_P x N_T] (as
+ * propagated) and weights w of a context created with keep_history = 1 and trace = 1, all N_T steps done: the smoothed weight
+ * of EVERY stored particle,
+ *     ws(i, N_T) = w(i, N_T)
+ *     D(j, t)    = sum_l w(l, t) p(X(:, j, t+1) | X(:, l, t))
+ *     ws(i, t)   = w(i, t) sum_j ws(j, t+1) p(X(:, j, t+1) | X(:, i, t)) / D(j, t)              t = N_T-1 .. 1
+ * with p the density of rbpf_loc_backward_simulate and odometry row t, dt(t), Q(:,:,t).  Deterministic: no uniforms, no n_traj.
+ * All sums run in the log domain in fp64, in a fixed order that depends on N_P only; every step is normalised by its
+ * mass(t) = sum_i ws(i, t) before normalisation, 1 in exact arithmetic and returned as a diagnostic (mass(N_T) = 1).  A particle
+ * with w = 0 has ws = 0 exactly and passes nothing back; a successor that no predecessor reaches passes nothing back either (its
+ * share shows as mass < 1).  ws(:, N_T) is w(:, N_T) bit for bit.
+ * Outputs (NULL pointers are skipped): w_smooth [N_P x N_T], mean [7 x N_T] = sum_i ws(i, t) X(:, i, t), cov [7 x 7 x N_T] the
+ * weighted second central moment about that mean, ess [N_T] = 1 / sum_i ws(i, t)^2, mass [N_T].  The means are PLAIN weighted
+ * means of all 7 rows, the way the filter's traj_mean treats them: the quaternion rows get no special handling.  The workspace
+ * comes from the context's pool and is returned before the call returns.  Refusals as rbpf_loc_map_trajectory.                   */
+int rbpf_loc_marginal_smooth(rbpf_ctx* ctx, double* w_smooth, double* mean, double* cov, double* ess, double* mass);
+/* Bytes of device memory rbpf_loc_marginal_smooth takes from the pool while it runs (no device access).                          */
+int rbpf_loc_marginal_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes);
+/* One step of the recursion on the caller's arrays, the kernel-level probe: xn [7 x N], logw [N] = log w(:, t), xs_next [7 x M]
+ * (the successors), logws_next [M] = log ws(:, t+1) (-inf allowed in both), odo [7], Q [6 x 6] -> D [M] = log sum_l exp(logw(l) +
+ * logp(xs_next(:, j) | xn(:, l))) and lws [N] = log of the un-normalised ws(:, t); -inf where nothing contributes.  reps >= 1
+ * repeats the step's launches; *ms (may be NULL) = median time of one step.                                                     */
+int rbpf_loc_marginal_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* logws_next,
+                           const double* odo, double dt, const double* Q, double* D, double* lws, int32_t reps, double* ms);
+
 /* ---- localisation in the fixed map of a generic device-code model --------------------------------
  * particleFilter.m:100-161 with the map frozen: xl = mean and P = V'V (V lower n_lin x n_lin, column-major, lower triangle read:
  * the rbpf_loc_map convention) are the same for every particle and never updated (:163-204 are left out).  The model is the
@@ -1022,6 +1048,39 @@ int rbpf_loc_generic_map_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_
 int rbpf_loc_generic_map_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
                               int32_t quat_pos, const double* mu, const double* delta, const double* xs_next, const double* cov,
                               double* best, int32_t* arg, int32_t reps, double* ms);
+
+/* ---- the marginal smoothing weights in the fixed map of a generic device-code model ----
+ * The recursion of rbpf_loc_marginal_smooth on a context of rbpf_loc_generic_create or rbpf_loc_landmark_create (the pass never
+ * reads the map), with the transition density of rbpf_loc_generic_backward_pose_begin: n_sel, rows, angle_mask, quat_pos as there,
+ * quat_pos = -1 for a density without a quaternion block.  It runs BACKWARDS in time, t = N_T-2 .. 0, as the backward pass does:
+ *   rbpf_loc_generic_marginal_begin   takes the workspace from the context's pool and enqueues step N_T-1 (ws = w, its moments).
+ *        The argument checks of _pose_begin; RBPF_ERR_STATE: a marginal, MAP or backward pass is open (only one of the three can
+ *        be open at once; _backward_begin and _map_begin refuse likewise while a marginal pass is open), steps missing, no
+ *        keep_history / trace, a degenerate forward step.
+ *   rbpf_loc_generic_marginal_particles_device   *t = the step the next step call processes, *xn_dev = its stored particles
+ *        [n_nonlin][N_P], library memory, read only.
+ *   rbpf_loc_generic_marginal_step_device   mu_dev [n_sel][N_P] = mean of the particles of step t on rbpf_stream_get(ctx), cov
+ *        [n_res x n_res] on the host, with odometry row t, dt(t), Q(:,:,t).  A cov that is not positive definite:
+ *        RBPF_ERR_CHOL_FAILED, the step named, before anything is launched.  Enqueues prologue, the two all-pairs passes, their
+ *        merges, the normalisation and the moments of step t without waiting.
+ *   rbpf_loc_generic_marginal_finish   synchronises, copies out (NULL outputs are skipped) w_smooth [N_P x N_T], mean [n_nonlin x
+ *        N_T], cov [n_nonlin x n_nonlin x N_T], ess [N_T], mass [N_T], and returns the workspace.  With steps left undone it
+ *        returns the workspace all the same: RBPF_OK when every output is NULL (the way out after a failed handle), RBPF_ERR_STATE
+ *        otherwise.  rbpf_destroy releases an open pass too.  mean and cov are plain weighted moments of all n_nonlin rows: angle
+ *        and quaternion rows get no special handling.
+ *   rbpf_loc_generic_marginal_workspace_bytes   what begin takes from the pool (no device access): Xhat has n_sel + 1 rows.
+ *   rbpf_loc_generic_marginal_step   one step on host arrays, the kernel-level probe: mu [n_sel][N], logw [N], xs_next [n_nonlin x
+ *        M] column-major, logws_next [M], cov [n_res x n_res] -> D [M], lws [N] as rbpf_loc_marginal_step.
+ * RBPF_ERR_STATE out of order; the context stays usable after any refusal.  Not built: sharding, host closures, two-slice
+ * (pairwise) marginals, other successors than the N_P particles outside the probe, sub-quadratic approximations.                  */
+int rbpf_loc_generic_marginal_begin(rbpf_ctx* ctx, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos);
+int rbpf_loc_generic_marginal_particles_device(rbpf_ctx* ctx, int32_t* t, const double** xn_dev);
+int rbpf_loc_generic_marginal_step_device(rbpf_ctx* ctx, const double* mu_dev, const double* cov);
+int rbpf_loc_generic_marginal_finish(rbpf_ctx* ctx, double* w_smooth, double* mean, double* cov, double* ess, double* mass);
+int rbpf_loc_generic_marginal_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, size_t* bytes);
+int rbpf_loc_generic_marginal_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                   int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
+                                   const double* cov, double* D, double* lws, int32_t reps, double* ms);
 
 /* ---- localisation in the fixed landmark map of a generic device-code model ------------------------
  * The frozen-map filter above for a model of the sparseFeatures branch (particleFilter.m:100-161 with :127-137): the map posterior

@@ -16,7 +16,9 @@ from .host import (particleFilter, particleSmoother, particleSmootherInformation
                    GenericDenseModel, GenericSparseModel, DeviceHandles, DeviceSmootherHandles, DeviceSparseHandles, DeviceSparseSmootherHandles, particle_filter_external, chol_refresh_in_use,
                    DenseMagMap, DeviceMap, DeviceLandmarkMap, DeviceTransition, device_map_weights, landmark_map_weights, device_map_backward_step, device_map_backward_workspace_bytes, particleFilterLocalization, LocalizationSession, loc_workspace_bytes,
                    particleSmootherLocalization, loc_backward_step, loc_backward_workspace_bytes,
-                   particleMapLocalization, loc_map_step, loc_map_workspace_bytes, device_map_map_step, device_map_map_workspace_bytes)
+                   particleMapLocalization, loc_map_step, loc_map_workspace_bytes, device_map_map_step, device_map_map_workspace_bytes,
+                   particleMarginalSmootherLocalization, loc_marginal_step, loc_marginal_workspace_bytes, device_map_marginal_step,
+                   device_map_marginal_workspace_bytes)
 
 
 def device_count() -> int:

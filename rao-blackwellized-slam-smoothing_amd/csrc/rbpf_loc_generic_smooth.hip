@@ -33,6 +33,9 @@
 //
 // THE MAP TRAJECTORY (rbpf_loc_generic_map_*): the Viterbi recursion of rbpf_loc_viterbi.hpp on the same prologues, terms, layout and
 // factorisation, driven forwards in time (begin / particles_device / step_device for t = 0 .. N_T-2 / finish).
+//
+// THE MARGINAL SMOOTHING WEIGHTS (rbpf_loc_generic_marginal_*): the recursion of rbpf_loc_marginal.hpp on the same prologues, terms,
+// layout and factorisation, driven backwards in time (begin / particles_device / step_device for t = N_T-2 .. 0 / finish).
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
@@ -40,6 +43,7 @@
 #include "rbpf_loc_state.hpp"
 #include "rbpf_loc_backward.hpp"
 #include "rbpf_loc_viterbi.hpp"
+#include "rbpf_loc_marginal.hpp"
 #include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
@@ -259,6 +263,22 @@ static hipError_t gs_launch_map_step(const LocGenLayout& y, const GvArgs& a, con
   return viterbi_launch_merge(a.M, a.nchunks, a.part_best, a.part_arg, w_next, delta_next, psi_next, s);
 }
 
+typedef MarginalArgs<GsData> GmArgs;
+
+// prologue (logw: the caller's log w over its last row, the probes) + the two all-pairs passes and their merges of one
+// marginal-smoothing step (rbpf_loc_marginal.hpp)
+static hipError_t gs_launch_marginal_step(const LocGenLayout& y, const GmArgs& a, const double* mu, const double* w, const double* logw, double* Xhat,
+                                          const double* logws_next, double* D, double* cj, double* lws, hipStream_t s) {
+  gs_launch_prologue(y, a.N, mu, w, Xhat, s);
+  if (logw) {
+    const hipError_t e = hipMemcpyAsync(Xhat + (size_t)y.n_sel * a.N, logw, (size_t)a.N * sizeof(double), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return e;
+  }
+  return gs_pick(y, a.head.angle_mask, [&](auto tag) {
+    return marginal_launch_step(a.with(typename decltype(tag)::Term{a.term}), logws_next, D, cj, lws, s);
+  });
+}
+
 static int gs_validate_rows(int n_nonlin, int n_res, const int32_t* rows, uint32_t angle_mask) {
   if (n_nonlin < 1 || n_nonlin > kGsMaxNonlin) { set_error("n_nonlin must be in 1 .. 8"); return RBPF_ERR_INVALID_ARG; }
   if (n_res < 1 || n_res > kGsMaxRes) { set_error("n_res (the rows that carry noise) must be in 1 .. 8"); return RBPF_ERR_INVALID_ARG; }
@@ -398,6 +418,7 @@ int rbpf_loc_generic_backward_pose_begin(rbpf_ctx* c, int32_t n_traj, const doub
   RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "backward simulation", "rbpf_loc_generic_backward_begin"));
   const int N = c->N, T = c->T, M = n_traj, nN = L->nN;
   LocGenBackward& g = L->gb;
@@ -541,6 +562,7 @@ int rbpf_loc_generic_map_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, 
   RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "the MAP trajectory", "rbpf_loc_generic_map_begin"));
   const int N = c->N, T = c->T;
   LocGenBackward& g = L->gv;
@@ -648,6 +670,132 @@ int rbpf_loc_generic_map_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_
   RB_TRY(timed_reps(reps, 0, [&] { return gs_launch_map_step(lay, a, d_mu, d_delta, d_delta, d_Xhat, nullptr, d_best, d_arg, 0); }, ms));
   HIPCHK(hipMemcpy(best, d_best, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(arg, d_arg, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+// ---- the marginal smoothing weights ------------------------------------------------------------------------------------------
+int rbpf_loc_generic_marginal_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, size_t* bytes) {
+  if (!bytes) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  size_t unused = 0;
+  RB_TRY(rbpf_loc_generic_map_workspace_bytes(n_nonlin, n_sel, quat_pos, N_P, N_T, &unused));   // the argument checks of the MAP pass
+  *bytes = marginal_bytes((size_t)n_nonlin, (size_t)n_sel, (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_marginal_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenLayout lay;
+  RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
+  if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
+  RB_TRY(backward_check_forward(c, "marginal smoothing", "rbpf_loc_generic_marginal_begin"));
+  const int N = c->N, T = c->T;
+  LocGenBackward& g = L->gm;
+  g.M = N; g.lay = lay;                                                  // (the chunking of both passes: marginal_set_sizes, per step)
+  int s = marginal_take(g.ws, c->pool, L->nN, lay.n_sel, N, T);
+  if (s == RBPF_OK) {
+    const hipError_t e = marginal_launch_last(g.ws, L->nN, N, T, c->X, c->w, c->stream);
+    if (e != hipSuccess) s = hip_fail(e, "the last step of the marginal pass", __FILE__, __LINE__);
+  }
+  if (s != RBPF_OK) { g.ws.release(); g = LocGenBackward(); return s; }
+  g.t = T - 2;
+  g.open = true;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_marginal_particles_device(rbpf_ctx* c, int32_t* t, const double** xn_dev) {
+  RB_TRY(gs_ctx_ok(c));
+  if (!t || !xn_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  const LocGenBackward& g = c->loc->gm;
+  if (!g.open) { set_error("no marginal pass is open (rbpf_loc_generic_marginal_begin first)"); return RBPF_ERR_STATE; }
+  if (g.t < 0) { set_error("every step of the marginal pass is done (rbpf_loc_generic_marginal_finish)"); return RBPF_ERR_STATE; }
+  *t = g.t;
+  *xn_dev = c->X + (size_t)g.t * c->loc->nN * c->N;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_marginal_step_device(rbpf_ctx* c, const double* mu_dev, const double* cov) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenBackward& g = L->gm;
+  if (!g.open) { set_error("no marginal pass is open (rbpf_loc_generic_marginal_begin first)"); return RBPF_ERR_STATE; }
+  if (g.t < 0) { set_error("every step of the marginal pass is done (rbpf_loc_generic_marginal_finish)"); return RBPF_ERR_STATE; }
+  if (!mu_dev || !cov) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  const int N = c->N, T = c->T, nN = L->nN, t = g.t;
+  GmArgs a;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, g.lay, a.term.W, " of step " + std::to_string(t)));
+  HIPCHK(hipSetDevice(c->device));
+  marginal_set_sizes(a, N, N);
+  a.head.nN = nN; a.head.angle_mask = g.lay.angle_mask;
+  for (int k = 0; k < g.lay.n_sel; ++k) a.head.rows[k] = g.lay.rows[k];
+  a.Xhat = g.ws.Xhat; a.xn_next = c->X + (size_t)(t + 1) * nN * N; a.cj = g.ws.u + (size_t)2 * N; a.part_m = g.ws.pm; a.part_s = g.ws.ps;
+  HIPCHK(gs_launch_marginal_step(g.lay, a, mu_dev, c->w + (size_t)t * N, nullptr, g.ws.Xhat, g.ws.u + (size_t)((t + 1) & 1) * N, nullptr,
+                                 g.ws.u + (size_t)2 * N, g.ws.u + (size_t)(t & 1) * N, c->stream));
+  HIPCHK(marginal_launch_close_step(g.ws, nN, N, T, t, c->X, c->stream));
+  g.t = t - 1;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_marginal_finish(rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenBackward& g = L->gm;
+  if (!g.open) { set_error("no marginal pass is open (rbpf_loc_generic_marginal_begin first)"); return RBPF_ERR_STATE; }
+  const int N = c->N, T = c->T, nN = L->nN, t_next = g.t;
+  BackwardWorkspace ws = g.ws;
+  g = LocGenBackward();                                                  // the pass is closed whichever way this returns,
+  BackwardWorkspaceGuard lease(ws);                                      // and its workspace goes back
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (t_next >= 0) {
+    if (!w_smooth && !mean && !cov && !ess && !mass) return RBPF_OK;     // the way out of a pass that was given up
+    set_error("rbpf_loc_generic_marginal_finish: steps " + std::to_string(t_next) + " .. 0 of the marginal pass were not run");
+    return RBPF_ERR_STATE;
+  }
+  RB_TRY(ctx_check_flags(c));
+  return marginal_copy_out(ws, nN, N, T, w_smooth, mean, cov, ess, mass);
+}
+
+int rbpf_loc_generic_marginal_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                   int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
+                                   const double* cov, double* D, double* lws, int32_t reps, double* ms) {
+  if (!mu || !logw || !xs_next || !logws_next || !cov || !D || !lws || !rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles || M > kMaxParticles) { set_error("N or M above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  LocGenLayout lay;
+  RB_TRY(gs_layout(n_nonlin, n_sel, rows, angle_mask, quat_pos, lay));
+  GmArgs a;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, lay, a.term.W, ""));
+  if (!have_device()) { set_error("no HIP device: the marginal pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  marginal_set_sizes(a, N, M);
+  std::vector<double> xt((size_t)n_nonlin * M);                           // the successors as the history holds them: [n_nonlin][M]
+  for (int j = 0; j < M; ++j)
+    for (int r = 0; r < n_nonlin; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * n_nonlin + r];
+  const size_t np = marginal_part_count((size_t)N, (size_t)M);
+  DevicePool tmp;
+  double *d_mu = nullptr, *d_lw = nullptr, *d_xs = nullptr, *d_lwn = nullptr, *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_D = nullptr,
+         *d_c = nullptr, *d_lws = nullptr;
+  RB_TRY(tmp.upload(&d_mu, mu, (size_t)lay.n_sel * N));
+  RB_TRY(tmp.upload(&d_lw, logw, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)n_nonlin * M));
+  RB_TRY(tmp.upload(&d_lwn, logws_next, (size_t)M));
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)(lay.n_sel + 1) * N));
+  RB_TRY(tmp.alloc(&d_pm, np));
+  RB_TRY(tmp.alloc(&d_ps, np));
+  RB_TRY(tmp.alloc(&d_D, (size_t)M));
+  RB_TRY(tmp.alloc(&d_c, (size_t)M));
+  RB_TRY(tmp.alloc(&d_lws, (size_t)N));
+  a.head.nN = n_nonlin; a.head.first = 0; a.head.angle_mask = lay.angle_mask;
+  for (int k = 0; k < lay.n_sel; ++k) a.head.rows[k] = lay.rows[k];
+  a.Xhat = d_Xhat; a.xn_next = d_xs; a.cj = d_c; a.part_m = d_pm; a.part_s = d_ps;
+  // (the prologue's last row is overwritten with the caller's log w: what it reads as w does not matter)
+  RB_TRY(timed_reps(reps, 0, [&] { return gs_launch_marginal_step(lay, a, d_mu, d_lw, d_lw, d_Xhat, d_lwn, d_D, d_c, d_lws, 0); }, ms));
+  HIPCHK(hipMemcpy(D, d_D, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(lws, d_lws, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 

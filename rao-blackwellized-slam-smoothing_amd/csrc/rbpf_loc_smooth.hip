@@ -13,7 +13,8 @@
 //   bs_prologue_kernel   Xhat[t][:, i] = (p_i + dx(1:3), a_i, log w_i): 8 doubles per particle, SoA, shared by all M trajectories.
 //   BsTerm               logp of one pair: the position term, then the orientation term.  A pair whose log w + position term alone
 //                        lies more than 746 below the running max skips its orientation term: its exp is exactly 0.
-// The MAP trajectory (rbpf_loc_map_trajectory, the recursion and kernels of rbpf_loc_viterbi.hpp) runs on the same prologue and term.
+// The MAP trajectory (rbpf_loc_map_trajectory, the recursion and kernels of rbpf_loc_viterbi.hpp) runs on the same prologue and term,
+// and so do the marginal smoothing weights (rbpf_loc_marginal_smooth, rbpf_loc_marginal.hpp).
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
@@ -21,6 +22,7 @@
 #include "rbpf_loc_state.hpp"
 #include "rbpf_loc_backward.hpp"
 #include "rbpf_loc_viterbi.hpp"
+#include "rbpf_loc_marginal.hpp"
 #include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
@@ -136,6 +138,14 @@ static hipError_t bs_launch_map_step(const ViterbiArgs<BsTerm>& a, const double*
   const hipError_t e = viterbi_launch_pass(a, delta, Xhat, s);
   if (e != hipSuccess) return e;
   return viterbi_launch_merge(a.M, a.nchunks, a.part_best, a.part_arg, w_next, delta_next, psi_next, s);
+}
+
+// prologue + the two all-pairs passes and their merges of one marginal-smoothing step (rbpf_loc_marginal.hpp): c(j), D where wanted,
+// and the un-normalised lws
+static hipError_t bs_launch_marginal_step(const MarginalArgs<BsTerm>& a, const double* xn, size_t cs, size_t ps, const double* w, const double* odo,
+                                          double* Xhat, const double* logws_next, double* D, double* cj, double* lws, hipStream_t s) {
+  hipLaunchKernelGGL(bs_prologue_kernel, dim3((a.N + 255) / 256), dim3(256), 0, s, a.N, xn, cs, ps, w, odo, Xhat);
+  return marginal_launch_step(a, logws_next, D, cj, lws, s);
 }
 
 }  // namespace rbpf
@@ -343,6 +353,99 @@ int rbpf_loc_map_step(int32_t N, int32_t M, const double* xn, const double* delt
   RB_TRY(timed_reps(reps, 0, [&] { return bs_launch_map_step(a, d_xn, 1, 7, d_delta, d_odo, d_delta, d_Xhat, nullptr, d_best, d_arg, 0); }, ms));
   HIPCHK(hipMemcpy(best, d_best, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(arg, d_arg, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+int rbpf_loc_marginal_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes) {
+  if (!bytes) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P < 1 || N_T < 1) { set_error("N_P and N_T must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N_P > kMaxParticles) { set_error("N_P above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  *bytes = marginal_bytes(7, 7, (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_marginal_smooth(rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (c->loc->generic) {
+    set_error("marginal smoothing needs the transition density of dynModel: a generic map's dynModel is a sampler (its handles carry no density)");
+    return RBPF_ERR_UNSUPPORTED;
+  }
+  RB_TRY(backward_check_forward(c, "rbpf_loc_marginal_smooth", "rbpf_loc_marginal_smooth"));
+  LocState* L = c->loc;
+  const int N = c->N, T = c->T;
+  std::vector<BsNoise> nz((size_t)L->s_pages);
+  {
+    std::vector<double> S((size_t)L->s_pages * 36);
+    HIPCHK(hipMemcpy(S.data(), L->d_S, S.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < (T > 1 ? L->s_pages : 0); ++p) RB_TRY(bs_noise(S.data() + (size_t)p * 36, nz[p]));
+  }
+  BackwardWorkspace ws;
+  BackwardWorkspaceGuard lease(ws);
+  RB_TRY(marginal_take(ws, c->pool, 7, 7, N, T));
+  HIPCHK(marginal_launch_last(ws, 7, N, T, c->X, c->w, c->stream));
+  for (int t = T - 2; t >= 0; --t) {
+    MarginalArgs<BsTerm> a;
+    marginal_set_sizes(a, N, N);
+    a.head.first = 0;
+    a.Xhat = ws.Xhat; a.xn_next = c->X + (size_t)(t + 1) * 7 * N; a.cj = ws.u + (size_t)2 * N; a.part_m = ws.pm; a.part_s = ws.ps;
+    a.term.nz = nz[L->s_pages > 1 ? t : 0];
+    HIPCHK(bs_launch_marginal_step(a, c->X + (size_t)t * 7 * N, (size_t)N, 1, c->w + (size_t)t * N, c->d_odo + (size_t)t * 7, ws.Xhat,
+                                   ws.u + (size_t)((t + 1) & 1) * N, nullptr, ws.u + (size_t)2 * N, ws.u + (size_t)(t & 1) * N, c->stream));
+    HIPCHK(marginal_launch_close_step(ws, 7, N, T, t, c->X, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  RB_TRY(ctx_check_flags(c));
+  return marginal_copy_out(ws, 7, N, T, w_smooth, mean, cov, ess, mass);
+}
+
+int rbpf_loc_marginal_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* logws_next,
+                           const double* odo, double dt, const double* Q, double* D, double* lws, int32_t reps, double* ms) {
+  if (!xn || !logw || !xs_next || !logws_next || !odo || !Q || !D || !lws) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles || M > kMaxParticles) { set_error("N or M above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  double S[36];
+  for (int q = 0; q < 36; ++q) S[q] = 0.0;
+  for (int b = 0; b < 2; ++b)
+    for (int cc = 0; cc < 3; ++cc)
+      for (int r = 0; r < 3; ++r) {
+        const int q = (3 * b + r) + 6 * (3 * b + cc);
+        const double v = dt * Q[q];
+        if (!(v >= 0.0)) { set_error("dt * Q has a negative entry in a diagonal block: the element-wise sqrt of dynModel would be complex"); return RBPF_ERR_INVALID_ARG; }
+        S[q] = std::sqrt(v);
+      }
+  MarginalArgs<BsTerm> a;
+  RB_TRY(bs_noise(S, a.term.nz));
+  if (!have_device()) { set_error("no HIP device: the marginal pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  marginal_set_sizes(a, N, M);
+  std::vector<double> xt((size_t)7 * M);                                  // the successors as the history holds them: [7][M]
+  for (int j = 0; j < M; ++j)
+    for (int r = 0; r < 7; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * 7 + r];
+  DevicePool tmp;
+  double *d_xn = nullptr, *d_lw = nullptr, *d_xs = nullptr, *d_lwn = nullptr, *d_odo = nullptr, *d_Xhat = nullptr, *d_pm = nullptr,
+         *d_ps = nullptr, *d_D = nullptr, *d_c = nullptr, *d_lws = nullptr;
+  const size_t np = marginal_part_count((size_t)N, (size_t)M);
+  RB_TRY(tmp.upload(&d_xn, xn, (size_t)7 * N));
+  RB_TRY(tmp.upload(&d_lw, logw, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)7 * M));
+  RB_TRY(tmp.upload(&d_lwn, logws_next, (size_t)M));
+  RB_TRY(tmp.upload(&d_odo, odo, (size_t)7));
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)8 * N));
+  RB_TRY(tmp.alloc(&d_pm, np));
+  RB_TRY(tmp.alloc(&d_ps, np));
+  RB_TRY(tmp.alloc(&d_D, (size_t)M));
+  RB_TRY(tmp.alloc(&d_c, (size_t)M));
+  RB_TRY(tmp.alloc(&d_lws, (size_t)N));
+  a.head.first = 0;
+  a.Xhat = d_Xhat; a.xn_next = d_xs; a.cj = d_c; a.part_m = d_pm; a.part_s = d_ps;
+  RB_TRY(timed_reps(reps, 0, [&] {
+    hipLaunchKernelGGL(bs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, 0, N, d_xn, (size_t)1, (size_t)7, d_lw, d_odo, d_Xhat);
+    // the caller's log w over the prologue's last row (what it read as w does not matter)
+    const hipError_t e = hipMemcpyAsync(d_Xhat + (size_t)7 * N, d_lw, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0);
+    if (e != hipSuccess) return e;
+    return marginal_launch_step(a, d_lwn, d_D, d_c, d_lws, 0);
+  }, ms));
+  HIPCHK(hipMemcpy(D, d_D, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(lws, d_lws, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 

@@ -58,6 +58,20 @@ struct BackwardWorkspace {
     if (s != RBPF_OK) release();
     return s;
   }
+  // the buffers of a marginal-smoothing pass (rbpf_loc_marginal.hpp) in the same fields: pm and ps [n_part] the chunk partials of both
+  // passes, u [n_lw] two rows of log w_{.|T} and c, xs [n_w] w_smooth, mean [n_out] mean, cov, ess and mass of every step; idx and
+  // arg stay null
+  int take_marginal(DevicePool& from, size_t n_Xhat, size_t n_part, size_t n_lw, size_t n_w, size_t n_out) {
+    pool = &from;
+    int s = from.alloc(&Xhat, n_Xhat);
+    if (s == RBPF_OK) s = from.alloc(&pm, n_part);
+    if (s == RBPF_OK) s = from.alloc(&ps, n_part);
+    if (s == RBPF_OK) s = from.alloc(&u, n_lw);
+    if (s == RBPF_OK) s = from.alloc(&xs, n_w);
+    if (s == RBPF_OK) s = from.alloc(&mean, n_out);
+    if (s != RBPF_OK) release();
+    return s;
+  }
   void release() {
     if (pool)
       for (void* p : {(void*)Xhat, (void*)pm, (void*)ps, (void*)u, (void*)xs, (void*)mean, (void*)idx, (void*)arg}) pool->release(p);
@@ -75,7 +89,8 @@ struct BackwardWorkspaceGuard {
 
 // An open backward-simulation pass over a generic map (rbpf_loc_generic_backward_begin .. _finish, rbpf_loc_generic_smooth.hip): the
 // workspace is taken from rbpf_ctx::pool at begin and handed back at finish (or with the context).  An open MAP pass
-// (rbpf_loc_generic_map_begin .. _finish) is kept in the same form.
+// (rbpf_loc_generic_map_begin .. _finish) and an open marginal-smoothing pass (rbpf_loc_generic_marginal_begin .. _finish) are kept
+// in the same form.
 struct LocGenBackward {
   bool open = false;
   int M = 0, C = 0, nch = 0;
@@ -100,6 +115,7 @@ struct LocState {
   double *d_H = nullptr;           // [N][n_y][ldx] rows packed from dy layout 0 (allocated on first use)
   LocGenBackward gb;               // backward simulation with a Gaussian transition density
   LocGenBackward gv;               // the MAP trajectory with one (rbpf_loc_generic_map_begin .. _finish): t counts up, M = N_P; never open with gb
+  LocGenBackward gm;               // marginal smoothing with one (rbpf_loc_generic_marginal_begin .. _finish): t counts down from N_T-2, M = N_P; never open with gb or gv
   // landmark map (rbpf_loc_landmark_create): the handle's yhat is the prediction and the outputs observed at a step are selected
   bool landmark = false;
   int *d_ind = nullptr;            // [N_T][32]: the observed outputs of every step, ascending

@@ -2071,6 +2071,34 @@ def device_map_map_workspace_bytes(n_nonlin, n_sel, N_P, N_T, quat_pos=-1):
     return int(nbytes.value)
 
 
+def device_map_marginal_step(mu, logw, xs_next, logws_next, cov, rows=None, angle_rows=(), quat_rows=None, reps=1):
+    """rbpf_loc_generic_marginal_step, the kernel-level probe: one step of the marginal-smoothing recursion with a Gaussian transition
+    on the caller's arrays.  mu [n_sel x N], logw [N] = log w_t, xs_next [n_nonlin x M] (the successors), logws_next [M] =
+    log w_{t+1|T} (-inf allowed in both), cov [n_res x n_res]; rows, angle_rows and quat_rows as in device_map_backward_step ->
+    (D [M], lws [N] un-normalised, median ms of one step)."""
+    lib = load_library()
+    mu, xs_next, cov, rows_a, mask, qpos = _transition_probe_args(mu, xs_next, cov, rows, angle_rows, quat_rows)
+    (n_sel, N), (nN, M) = mu.shape, xs_next.shape
+    logw = np.ascontiguousarray(np.asarray(logw, dtype=np.float64).ravel())
+    logws_next = np.ascontiguousarray(np.asarray(logws_next, dtype=np.float64).ravel())
+    if logw.size != N or logws_next.size != M:
+        raise ValueError("logw must be [N] and logws_next [M]")
+    D, lws = np.empty(M), np.empty(N)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_generic_marginal_step(N, M, nN, n_sel, _ip(rows_a), mask, qpos, _dp(mu), _dp(logw), _dp(xs_next), _dp(logws_next),
+                                             _dp(cov), _dp(D), _dp(lws), int(reps), C.byref(ms)))
+    return D, lws, ms.value
+
+
+def device_map_marginal_workspace_bytes(n_nonlin, n_sel, N_P, N_T, quat_pos=-1):
+    """rbpf_loc_generic_marginal_workspace_bytes (no device access): n_sel = len(rows), quat_pos the position of a quaternion block
+    in rows or -1."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_generic_marginal_workspace_bytes(int(n_nonlin), int(n_sel), int(quat_pos), int(N_P), int(N_T), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
 class DeviceMap:
     """A fixed map of an arbitrary model whose handles are device code: the posterior N(mean, V'V) over the nLin linear states, V
     lower (the DenseMagMap convention), as a SLAM filter or smoother run with the same DeviceHandles returns it (xl_max, P_max /
@@ -2682,15 +2710,22 @@ class LocalizationSession:
     def _map_in_device_map(self, outs):
         """The MAP pass with the map's DeviceTransition: the covariance pages on the host first, then begin, one particles_device /
         mean handle / step_device per step t = 0 .. N_T-2 in stream order, finish (also the way out of a failed handle)."""
+        self._stepped_pass_in_device_map("map", outs)
+
+    def _stepped_pass_in_device_map(self, family, outs):
+        """A pass of rbpf_loc_generic_<family>_* (map: t = 0 .. N_T-2; marginal: t = N_T-2 .. 0) whose every step takes the `mean`
+        handle's mu and cov(dt, Q); the library names the step."""
         lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
         torch, T, N, nN = drv.torch, prob.N_T, prob.N_P, self.nN
+        begin, particles, step, finish = (getattr(lib, f"rbpf_loc_generic_{family}_{f}")
+                                          for f in ("begin", "particles_device", "step_device", "finish"))
         rows_a, mask, qpos, n_sel, covs, page = self._transition_pages()
-        check(lib.rbpf_loc_generic_map_begin(self.ctx, n_sel, _ip(rows_a), mask, qpos))
+        check(begin(self.ctx, n_sel, _ip(rows_a), mask, qpos))
         try:
             with torch.cuda.stream(drv.stream):
                 for _ in range(T - 1):
                     t, xn = C.c_int32(0), C.c_void_p()
-                    check(lib.rbpf_loc_generic_map_particles_device(self.ctx, C.byref(t), C.byref(xn)))
+                    check(particles(self.ctx, C.byref(t), C.byref(xn)))
                     t = t.value
                     X = drv._view(torch, xn, (nN, N), drv.device)
                     Q = drv.Q[page(drv.Q.shape[0], t)]
@@ -2700,16 +2735,38 @@ class LocalizationSession:
                         raise ValueError(f"mean returned {what}, expected a float64 device tensor of shape {(n_sel, N)}")
                     mu = mu.contiguous()
                     self._keep_mu = mu                            # read in stream order by the step just enqueued
-                    check(lib.rbpf_loc_generic_map_step_device(self.ctx, C.c_void_p(mu.data_ptr()),
-                                                               _dp(covs[(page(prob._dt.size, t), page(prob._Q.shape[2], t))])))
+                    check(step(self.ctx, C.c_void_p(mu.data_ptr()), _dp(covs[(page(prob._dt.size, t), page(prob._Q.shape[2], t))])))
         except BaseException:
-            lib.rbpf_loc_generic_map_finish(self.ctx, None, None, None)
+            finish(self.ctx, *([None] * len(outs)))
             self._keep_mu = None
             raise
         try:
-            check(lib.rbpf_loc_generic_map_finish(self.ctx, *outs))
+            check(finish(self.ctx, *outs))
         finally:
             self._keep_mu = None
+
+    def smoothed_marginals(self, want=("w_smooth", "mean", "ess")):
+        """rbpf_loc_marginal_smooth: the marginal smoothing weights of EVERY stored particle (keep_history and trace, every step done),
+        forward filtering backward smoothing (Doucet, Godsill & Andrieu 2000): deterministic, no uniforms, no n_traj.  Returns a dict
+        of what `want` names: w_smooth [N_P x N_T] (column N_T-1 is the filter's last weights bit for bit), mean [7 x N_T] and cov
+        [7 x 7 x N_T] (plain weighted moments of all rows: quaternion and angle rows get no special handling), ess [N_T] =
+        1 / sum w_smooth^2 and mass [N_T], the sum of a step's weights before its normalisation (1 in exact arithmetic).  In a
+        DeviceMap: n_nonlin rows in place of 7, with the map's DeviceTransition (rbpf_loc_generic_marginal_*); without one the call
+        is refused."""
+        if self.driver is not None and self.map.transition is None:
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, _NO_BACKWARD_IN_DEVICE_MAP)
+        unknown = set(want) - {"w_smooth", "mean", "cov", "ess", "mass"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        T, N, nN = self.prob.N_T, self.prob.N_P, self.nN
+        shapes = dict(w_smooth=(N, T), mean=(nN, T), cov=(nN, nN, T), ess=(T,), mass=(T,))
+        b = {k: np.empty(shapes[k], order="F") for k in ("w_smooth", "mean", "cov", "ess", "mass") if k in want}
+        outs = tuple(_dp(b[k]) if k in b else None for k in ("w_smooth", "mean", "cov", "ess", "mass"))
+        if self.driver is not None:
+            self._stepped_pass_in_device_map("marginal", outs)
+        else:
+            check(self.lib.rbpf_loc_marginal_smooth(self.ctx, *outs))
+        return b
 
     def close(self):
         if self.ctx:
@@ -2771,6 +2828,59 @@ def particleMapLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N
         fwd["index"] = out["index"]
         return out["x_map"], out["score"], fwd
     return out["x_map"], out["score"]
+
+
+def loc_marginal_workspace_bytes(N_P, N_T):
+    """rbpf_loc_marginal_workspace_bytes (no device access)."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_marginal_workspace_bytes(int(N_P), int(N_T), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def loc_marginal_step(xn, logw, xs_next, logws_next, odo, dt, Q, reps=1):
+    """rbpf_loc_marginal_step, the kernel-level probe: one step of the marginal-smoothing recursion on the caller's arrays.  xn
+    [7 x N], logw [N] = log w_t, xs_next [7 x M] (the successors), logws_next [M] = log w_{t+1|T} (-inf allowed in both), odo [7],
+    Q [6 x 6] -> (D [M] = log sum_l w_t(l) p(j | l), lws [N] = log of the un-normalised w_{t|T}, median ms of one step)."""
+    lib = load_library()
+    xn = np.asfortranarray(np.asarray(xn, dtype=np.float64).reshape(7, -1))
+    xs_next = np.asfortranarray(np.asarray(xs_next, dtype=np.float64).reshape(7, -1))
+    N, M = xn.shape[1], xs_next.shape[1]
+    logw = np.ascontiguousarray(np.asarray(logw, dtype=np.float64).ravel())
+    logws_next = np.ascontiguousarray(np.asarray(logws_next, dtype=np.float64).ravel())
+    odo = np.ascontiguousarray(np.asarray(odo, dtype=np.float64).ravel())
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(6, 6))
+    if logw.size != N or logws_next.size != M or odo.size != 7:
+        raise ValueError("logw must be [N], logws_next [M] and odo [7]")
+    D, lws = np.empty(M), np.empty(N)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_marginal_step(N, M, _dp(xn), _dp(logw), _dp(xs_next), _dp(logws_next), _dp(odo), float(dt), _dp(Q), _dp(D), _dp(lws),
+                                     int(reps), C.byref(ms)))
+    return D, lws, ms.value
+
+
+def particleMarginalSmootherLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, dt, *, rng=None, extras=False):
+    """The marginal smoother of localisation in a fixed map: particleFilterLocalization, then the marginal smoothing weights of its
+    stored particles (LocalizationSession.smoothed_marginals) -> (traj_marginal_mean [7 x N_T], w_smooth [N_P x N_T][, extras]).
+    dynModel / measModel, R and rng as particleMapLocalization takes them: the handles of a DenseMagMap, or a DeviceMap with a
+    DeviceTransition as dynModel (measModel None), n_nonlin rows in place of 7.  extras: the filter's outputs (traj_max, traj_mean,
+    first_degenerate_step, ...) and `cov`, `ess`, `mass` of every step."""
+    import warnings
+    mp = _device_map(dynModel, measModel)
+    if mp is not None and mp.transition is None:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleMarginalSmootherLocalization: " + _NO_BACKWARD_IN_DEVICE_MAP)
+    if mp is None:
+        mp = _recognise_map(dynModel, measModel)
+    with LocalizationSession(mp, odometry, y, x0_nonLin, Q, N_P, dt, rng=rng, keep_history=True, trace=True) as s:
+        s.advance(s.prob.N_T)
+        fwd = s.finish(extras=extras)
+        if fwd["first_degenerate_step"] >= 0:
+            warnings.warn(f"Weights filter close to zero at t={fwd['first_degenerate_step'] + 1} !!!", RuntimeWarning, stacklevel=2)
+        out = s.smoothed_marginals(want=("w_smooth", "mean", "cov", "ess", "mass") if extras else ("w_smooth", "mean"))
+    if extras:
+        fwd.update(cov=out["cov"], ess=out["ess"], mass=out["mass"])
+        return out["mean"], out["w_smooth"], fwd
+    return out["mean"], out["w_smooth"]
 
 
 def loc_backward_workspace_bytes(N_P, N_T, n_traj):
