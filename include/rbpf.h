@@ -1082,6 +1082,47 @@ int rbpf_loc_generic_marginal_step(int32_t N, int32_t M, int32_t n_nonlin, int32
                                    int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
                                    const double* cov, double* D, double* lws, int32_t reps, double* ms);
 
+/* ---- backward simulation by rejection sampling, in every fixed map -----------------------------------
+ * The law of rbpf_loc_backward_simulate / rbpf_loc_generic_backward_*, drawn without the all-pairs pass where a proposal is
+ * accepted (Douc, Garivier, Moulines & Olsson 2011): every transition density here has logp = -z'z / 2 <= 0.  Step N_T-1 is the
+ * draw of the all-pairs calls.  For t = N_T-2 .. 0 and trajectory j, tries r = 0 .. max_tries-1:
+ *     (u0, u1) = Philox(seed; slot = j, step = t, lane = 0x42530001, iter = r),  i = #{k : cdf_k < u0 cdf_{N-1}} (cdf: the inclusive
+ *     prefix sums of w[t], fp64, in an order fixed by N_P),  accept iff logp(xs[t+1][j] | X[t][:, i]) >= log u1  (no log w_i: the
+ *     weights are the proposal);  the first accepted i is index[t][j].
+ * Trajectories without an acceptance are drawn by the all-pairs pass with their uniform of the all-pairs calls (lane 0x42530000),
+ * compacted in ascending j into M' rows, with the chunk size and summation order of (N_P, M'); M' comes to the host once per step.
+ * The law of every index is the backward kernel's for every max_tries; max_tries = 0 gives the arrays of the all-pairs calls with
+ * the same seed bit for bit.  The device generator only: the probes take uniforms.  Refusals as the all-pairs calls, and
+ * max_tries outside 0 .. 4194304 is RBPF_ERR_INVALID_ARG.
+ *   rbpf_loc_backward_simulate_reject   the dense-mag map; outputs as rbpf_loc_backward_simulate, and (either may be NULL)
+ *        n_fallback [N_T] = M' of every step and n_tries [N_T] = the tries of every step summed over the trajectories (both 0 at
+ *        step N_T-1).
+ *   rbpf_loc_generic_backward_reject_begin   opens the pass on a generic or landmark-map context; rbpf_loc_generic_backward_
+ *        particles_device / _step_device / _finish drive it as they drive rbpf_loc_generic_backward_pose_begin's (each _step_device
+ *        below N_T-1 waits for the stream once).  rbpf_loc_generic_backward_reject_stats: the two counters of the last pass that
+ *        _finish closed with every step done (RBPF_ERR_STATE if there is none).
+ *   *_reject_workspace_bytes   device bytes of a pass (no device access).
+ *   rbpf_loc_backward_reject_step, rbpf_loc_generic_backward_reject_step   one step on host arrays, the kernel-level probes: the
+ *        arguments of rbpf_loc_backward_step / rbpf_loc_generic_backward_pose_step without logp, and u_try [R][M][2] (try r of
+ *        trajectory j: u0 at [r][j][0], u1 at [r][j][1]; NULL: the device generator's draws of seed 0 at step 0, for timing runs
+ *        whose R x M uniforms would not fit a host array), u [M] the fallback's uniforms, R = max_tries ->
+ *        index [M], accepted_at [M] (the try that was accepted, -1: fallback; may be NULL); ms: median over reps of the whole step. */
+int rbpf_loc_backward_simulate_reject(rbpf_ctx* ctx, int32_t n_traj, uint64_t seed, int32_t max_tries, double* xs_traj, int32_t* index,
+                                      double* traj_smooth_mean, int32_t* n_fallback, int64_t* n_tries);
+int rbpf_loc_backward_reject_workspace_bytes(int32_t N_P, int32_t N_T, int32_t n_traj, size_t* bytes);
+int rbpf_loc_backward_reject_step(int32_t N, int32_t M, const double* xn, const double* w, const double* xs_next, const double* odo, double dt,
+                                  const double* Q, const double* u_try, const double* u, int32_t R, int32_t* index, int32_t* accepted_at,
+                                  int32_t reps, double* ms);
+int rbpf_loc_generic_backward_reject_begin(rbpf_ctx* ctx, int32_t n_traj, uint64_t seed, int32_t max_tries, int32_t n_sel, const int32_t* rows,
+                                           uint32_t angle_mask, int32_t quat_pos);
+int rbpf_loc_generic_backward_reject_stats(rbpf_ctx* ctx, int32_t* n_fallback, int64_t* n_tries);
+int rbpf_loc_generic_backward_reject_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, int32_t n_traj,
+                                                     size_t* bytes);
+int rbpf_loc_generic_backward_reject_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                          int32_t quat_pos, const double* mu, const double* w, const double* xs_next, const double* cov,
+                                          const double* u_try, const double* u, int32_t R, int32_t* index, int32_t* accepted_at, int32_t reps,
+                                          double* ms);
+
 /* ---- localisation in the fixed landmark map of a generic device-code model ------------------------
  * The frozen-map filter above for a model of the sparseFeatures branch (particleFilter.m:100-161 with :127-137): the map posterior
  * N(mean, V'V), V lower, is shared by all particles and never updated, and the caller's measModel(xn, xl) returns the prediction

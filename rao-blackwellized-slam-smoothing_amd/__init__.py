@@ -18,7 +18,8 @@ from .host import (particleFilter, particleSmoother, particleSmootherInformation
                    particleSmootherLocalization, loc_backward_step, loc_backward_workspace_bytes,
                    particleMapLocalization, loc_map_step, loc_map_workspace_bytes, device_map_map_step, device_map_map_workspace_bytes,
                    particleMarginalSmootherLocalization, loc_marginal_step, loc_marginal_workspace_bytes, device_map_marginal_step,
-                   device_map_marginal_workspace_bytes)
+                   device_map_marginal_workspace_bytes,
+                   loc_backward_reject_step, loc_backward_reject_workspace_bytes, device_map_backward_reject_step, reject_default_max_tries)
 
 
 def device_count() -> int:

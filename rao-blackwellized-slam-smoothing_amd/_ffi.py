@@ -175,6 +175,9 @@ EXPORTS = [
     "rbpf_loc_marginal_smooth", "rbpf_loc_marginal_workspace_bytes", "rbpf_loc_marginal_step",
     "rbpf_loc_generic_marginal_begin", "rbpf_loc_generic_marginal_particles_device", "rbpf_loc_generic_marginal_step_device",
     "rbpf_loc_generic_marginal_finish", "rbpf_loc_generic_marginal_workspace_bytes", "rbpf_loc_generic_marginal_step",
+    "rbpf_loc_backward_simulate_reject", "rbpf_loc_backward_reject_workspace_bytes", "rbpf_loc_backward_reject_step",
+    "rbpf_loc_generic_backward_reject_begin", "rbpf_loc_generic_backward_reject_stats", "rbpf_loc_generic_backward_reject_workspace_bytes",
+    "rbpf_loc_generic_backward_reject_step",
     "rbpf_loc_landmark_create", "rbpf_loc_landmark_map_device", "rbpf_loc_landmark_step_device", "rbpf_loc_landmark_yhattraj",
     "rbpf_loc_landmark_weights",
     "rbpf_ekf_dense", "rbpf_ekf_workspace_bytes",
@@ -352,6 +355,19 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_loc_generic_marginal_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
     lib.rbpf_loc_generic_marginal_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, C.c_int32, c_double_p,
                                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
+    c_int64_p = C.POINTER(C.c_int64)
+    lib.rbpf_loc_backward_simulate_reject.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, c_double_p, c_int32_p, c_double_p, c_int32_p,
+                                                      c_int64_p]
+    lib.rbpf_loc_backward_reject_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_backward_reject_step.argtypes = [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p,
+                                                  c_double_p, c_double_p, C.c_int32, c_int32_p, c_int32_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_generic_backward_reject_begin.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, C.c_int32]
+    lib.rbpf_loc_generic_backward_reject_stats.argtypes = [C.c_void_p, c_int32_p, c_int64_p]
+    lib.rbpf_loc_generic_backward_reject_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                     C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_generic_backward_reject_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, C.c_int32, c_double_p,
+                                                          c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_int32_p, c_int32_p,
+                                                          C.c_int32, c_double_p]
     lib.rbpf_loc_landmark_create.argtypes = lib.rbpf_loc_generic_create.argtypes
     lib.rbpf_loc_landmark_map_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p]
     lib.rbpf_loc_landmark_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]

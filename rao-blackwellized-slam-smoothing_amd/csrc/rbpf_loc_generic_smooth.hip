@@ -36,6 +36,9 @@
 //
 // THE MARGINAL SMOOTHING WEIGHTS (rbpf_loc_generic_marginal_*): the recursion of rbpf_loc_marginal.hpp on the same prologues, terms,
 // layout and factorisation, driven backwards in time (begin / particles_device / step_device for t = N_T-2 .. 0 / finish).
+//
+// REJECTION SAMPLING (rbpf_loc_generic_backward_reject_begin): the pass that rbpf_loc_reject.hpp puts in front of the all-pairs pass
+// at steps N_T-2 .. 0, on the same prologues and terms, driven by the same particles_device / step_device / finish.
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
@@ -44,6 +47,7 @@
 #include "rbpf_loc_backward.hpp"
 #include "rbpf_loc_viterbi.hpp"
 #include "rbpf_loc_marginal.hpp"
+#include "rbpf_loc_reject.hpp"
 #include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
@@ -367,7 +371,18 @@ static int gs_ctx_ok(const rbpf_ctx* c) {
   return RBPF_OK;
 }
 
+// prologue + the rejection step of rbpf_loc_reject.hpp (waits for the stream once)
+static hipError_t gs_launch_reject_step(const LocGenLayout& y, const GsArgs& a, const RejectWorkspace& rw, const double* mu, const double* w,
+                                        double* Xhat, int max_tries, const double* u_try, unsigned long long seed, int step, int* n_fb,
+                                        long long* n_tries, hipStream_t s) {
+  gs_launch_prologue(y, a.N, mu, w, Xhat, s);
+  return gs_pick(y, a.head.angle_mask, [&](auto tag) {
+    return reject_launch_step(a.with(typename decltype(tag)::Term{a.term}), rw, w, a.head.nN, max_tries, u_try, seed, step, n_fb, n_tries, s);
+  });
+}
+
 static void gs_release(rbpf_ctx* c) {
+  c->loc->gb.rw.release();
   c->loc->gb.ws.release();
   c->loc->gb = LocGenBackward();
 }
@@ -409,8 +424,9 @@ int rbpf_loc_generic_backward_begin(rbpf_ctx* c, int32_t n_traj, const double* u
   return rbpf_loc_generic_backward_pose_begin(c, n_traj, u, seed, n_res, rows, angle_mask, -1);
 }
 
-int rbpf_loc_generic_backward_pose_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, int32_t n_sel, const int32_t* rows,
-                                         uint32_t angle_mask, int32_t quat_pos) {
+// rbpf_loc_generic_backward_pose_begin (max_tries = -1) and rbpf_loc_generic_backward_reject_begin (max_tries >= 0)
+static int gs_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, int max_tries, int32_t n_sel, const int32_t* rows,
+                    uint32_t angle_mask, int32_t quat_pos, const char* who) {
   RB_TRY(gs_ctx_ok(c));
   LocState* L = c->loc;
   if (n_traj < 1) { set_error("n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
@@ -419,16 +435,59 @@ int rbpf_loc_generic_backward_pose_begin(rbpf_ctx* c, int32_t n_traj, const doub
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
-  RB_TRY(backward_check_forward(c, "backward simulation", "rbpf_loc_generic_backward_begin"));
+  RB_TRY(backward_check_forward(c, "backward simulation", who));
   const int N = c->N, T = c->T, M = n_traj, nN = L->nN;
   LocGenBackward& g = L->gb;
   g.M = M; g.lay = lay;
   g.C = backward_chunk_size(N, M); g.nch = (N + g.C - 1) / g.C;
-  int s = g.ws.take(c->pool, (size_t)(lay.n_sel + 1) * N, (size_t)g.nch * M, (size_t)T * M, (size_t)T * nN * M, (size_t)nN * T);
+  g.reject = max_tries >= 0; g.max_tries = std::max(max_tries, 0); g.seed = seed;
+  int s = g.ws.take(c->pool, (size_t)(lay.n_sel + 1) * N, g.reject ? reject_part_count(N, M) : (size_t)g.nch * M, (size_t)T * M, (size_t)T * nN * M,
+                    (size_t)nN * T);
+  if (s == RBPF_OK && g.reject) {
+    L->reject_n_fb.clear();
+    L->reject_n_tries.clear();
+    s = g.rw.take(c->pool, (size_t)N, reject_cdf_blocks(N), (size_t)M, (size_t)nN, (size_t)T);
+    if (s == RBPF_OK) {
+      hipError_t e = hipMemsetAsync(g.rw.n_fb, 0, (size_t)T * sizeof(int), c->stream);
+      if (e == hipSuccess) e = hipMemsetAsync(g.rw.n_tries, 0, (size_t)T * sizeof(long long), c->stream);
+      if (e != hipSuccess) s = hip_fail(e, "counters of the rejection pass", __FILE__, __LINE__);
+    }
+  }
   if (s == RBPF_OK) s = backward_uniforms(u, seed, T, M, g.ws.u, c->stream);
   if (s != RBPF_OK) { gs_release(c); return s; }
   g.t = T - 1;
   g.open = true;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_backward_pose_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, int32_t n_sel, const int32_t* rows,
+                                         uint32_t angle_mask, int32_t quat_pos) {
+  return gs_begin(c, n_traj, u, seed, -1, n_sel, rows, angle_mask, quat_pos, "rbpf_loc_generic_backward_begin");
+}
+
+int rbpf_loc_generic_backward_reject_begin(rbpf_ctx* c, int32_t n_traj, uint64_t seed, int32_t max_tries, int32_t n_sel, const int32_t* rows,
+                                           uint32_t angle_mask, int32_t quat_pos) {
+  if (max_tries < 0 || max_tries > kRejectMaxTries) { set_error("max_tries must be in 0 .. 4194304"); return RBPF_ERR_INVALID_ARG; }
+  return gs_begin(c, n_traj, nullptr, seed, max_tries, n_sel, rows, angle_mask, quat_pos, "rbpf_loc_generic_backward_reject_begin");
+}
+
+int rbpf_loc_generic_backward_reject_stats(rbpf_ctx* c, int32_t* n_fallback, int64_t* n_tries) {
+  RB_TRY(gs_ctx_ok(c));
+  const LocState* L = c->loc;
+  if (L->reject_n_fb.empty()) { set_error("no rejection pass has finished on this context (rbpf_loc_generic_backward_reject_begin .. _finish first)"); return RBPF_ERR_STATE; }
+  for (size_t t = 0; t < L->reject_n_fb.size(); ++t) {
+    if (n_fallback) n_fallback[t] = L->reject_n_fb[t];
+    if (n_tries) n_tries[t] = L->reject_n_tries[t];
+  }
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_backward_reject_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, int32_t n_traj,
+                                                     size_t* bytes) {
+  RB_TRY(rbpf_loc_generic_backward_pose_workspace_bytes(n_nonlin, n_sel, quat_pos, N_P, N_T, n_traj, bytes));
+  const size_t nch = ((size_t)N_P + backward_chunk_size(N_P, n_traj) - 1) / backward_chunk_size(N_P, n_traj);
+  *bytes += 2 * (reject_part_count(N_P, n_traj) - nch * (size_t)n_traj) * sizeof(double) +
+            reject_bytes((size_t)N_P, (size_t)n_traj, (size_t)n_nonlin, (size_t)N_T);
   return RBPF_OK;
 }
 
@@ -464,7 +523,11 @@ int rbpf_loc_generic_backward_step_device(rbpf_ctx* c, const double* mu_dev, con
   a.xs_next = a.head.first ? nullptr : g.ws.xs + (size_t)(t + 1) * nN * M;
   a.u = g.ws.u + (size_t)t * M; a.part_m = g.ws.pm; a.part_s = g.ws.ps;
   a.index = g.ws.idx + (size_t)t * M; a.xs = g.ws.xs + (size_t)t * nN * M; a.clamped = c->d_flags + 1;
-  HIPCHK(gs_launch_step(g.lay, a, a.head.first ? nullptr : mu_dev, c->w + (size_t)t * N, g.ws.Xhat, c->stream));
+  if (g.reject && !a.head.first)
+    HIPCHK(gs_launch_reject_step(g.lay, a, g.rw, mu_dev, c->w + (size_t)t * N, g.ws.Xhat, g.max_tries, nullptr, g.seed, t, g.rw.n_fb + t,
+                                 g.rw.n_tries + t, c->stream));
+  else
+    HIPCHK(gs_launch_step(g.lay, a, a.head.first ? nullptr : mu_dev, c->w + (size_t)t * N, g.ws.Xhat, c->stream));
   HIPCHK(backward_launch_mean(M, nN, a.xs, g.ws.mean + (size_t)t * nN, c->stream));
   g.t = t - 1;
   return RBPF_OK;
@@ -476,9 +539,12 @@ int rbpf_loc_generic_backward_finish(rbpf_ctx* c, double* xs_traj, int32_t* inde
   LocGenBackward& g = L->gb;
   if (!g.open) { set_error("no backward pass is open (rbpf_loc_generic_backward_begin first)"); return RBPF_ERR_STATE; }
   const int T = c->T, M = g.M, nN = L->nN, t_next = g.t;
+  const bool reject = g.reject;
   BackwardWorkspace ws = g.ws;
+  RejectWorkspace rw = g.rw;
   g = LocGenBackward();                                                  // the pass is closed whichever way this returns,
   BackwardWorkspaceGuard lease(ws);                                      // and its workspace goes back
+  RejectWorkspaceGuard reject_lease(rw);
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (t_next >= 0) {
@@ -487,6 +553,14 @@ int rbpf_loc_generic_backward_finish(rbpf_ctx* c, double* xs_traj, int32_t* inde
     return RBPF_ERR_STATE;
   }
   RB_TRY(ctx_check_flags(c));
+  if (reject) {
+    std::vector<int> nf((size_t)T);
+    std::vector<long long> nt((size_t)T);
+    HIPCHK(hipMemcpy(nf.data(), rw.n_fb, (size_t)T * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(nt.data(), rw.n_tries, (size_t)T * sizeof(long long), hipMemcpyDeviceToHost));
+    L->reject_n_fb.swap(nf);
+    L->reject_n_tries.swap(nt);
+  }
   if (xs_traj) HIPCHK(hipMemcpy(xs_traj, ws.xs, (size_t)nN * M * T * sizeof(double), hipMemcpyDeviceToHost));
   if (index) HIPCHK(hipMemcpy(index, ws.idx, (size_t)M * T * sizeof(int), hipMemcpyDeviceToHost));
   if (traj_smooth_mean) HIPCHK(hipMemcpy(traj_smooth_mean, ws.mean, (size_t)nN * T * sizeof(double), hipMemcpyDeviceToHost));
@@ -534,6 +608,54 @@ int rbpf_loc_generic_backward_pose_step(int32_t N, int32_t M, int32_t n_nonlin, 
   if (logp) HIPCHK(gs_launch(lay, a, d_lp, 0));
   HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
   if (logp) HIPCHK(hipMemcpy(logp, d_lp, (size_t)N * M * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_backward_reject_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                          int32_t quat_pos, const double* mu, const double* w, const double* xs_next, const double* cov,
+                                          const double* u_try, const double* u, int32_t R, int32_t* index, int32_t* accepted_at, int32_t reps,
+                                          double* ms) {
+  if (!mu || !w || !xs_next || !cov || !u || !index || !rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (R < 0 || R > kRejectMaxTries) { set_error("max_tries must be in 0 .. 4194304"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles) { set_error("N above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  LocGenLayout lay;
+  RB_TRY(gs_layout(n_nonlin, n_sel, rows, angle_mask, quat_pos, lay));
+  GsArgs a;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, lay, a.term.W, ""));
+  if (!have_device()) { set_error("no HIP device: the backward pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  DevicePool tmp;
+  RejectWorkspace rw;
+  RejectWorkspaceGuard lease(rw);
+  double *d_mu = nullptr, *d_w = nullptr, *d_xs = nullptr, *d_u = nullptr, *d_ut = nullptr, *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr;
+  int *d_idx = nullptr, *d_clamped = nullptr;
+  const size_t np = reject_part_count(N, M);
+  RB_TRY(tmp.upload(&d_mu, mu, (size_t)lay.n_sel * N));
+  RB_TRY(tmp.upload(&d_w, w, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xs_next, (size_t)n_nonlin * M));
+  RB_TRY(tmp.upload(&d_u, u, (size_t)M));
+  if (R > 0 && u_try) RB_TRY(tmp.upload(&d_ut, u_try, (size_t)2 * M * R));   // (null: the device generator, seed 0, step 0)
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)(lay.n_sel + 1) * N));
+  RB_TRY(tmp.alloc(&d_pm, np));
+  RB_TRY(tmp.alloc(&d_ps, np));
+  RB_TRY(tmp.alloc(&d_idx, (size_t)M));
+  RB_TRY(tmp.alloc(&d_clamped, (size_t)1));
+  RB_TRY(rw.take(tmp, (size_t)N, reject_cdf_blocks(N), (size_t)M, (size_t)n_nonlin, 1));
+  HIPCHK(hipMemset(d_clamped, 0, sizeof(int)));
+  a.N = N; a.M = M; a.C = backward_chunk_size(N, M); a.nchunks = (N + a.C - 1) / a.C;
+  a.head.nN = n_nonlin; a.head.first = 0; a.head.angle_mask = lay.angle_mask;
+  for (int k = 0; k < lay.n_sel; ++k) a.head.rows[k] = lay.rows[k];
+  a.Xhat = d_Xhat; a.X = nullptr; a.xs_next = d_xs; a.u = d_u; a.part_m = d_pm; a.part_s = d_ps; a.index = d_idx; a.xs = nullptr;
+  a.clamped = d_clamped;
+  RB_TRY(timed_reps(reps, 0, [&] { return gs_launch_reject_step(lay, a, rw, d_mu, d_w, d_Xhat, R, d_ut, 0ull, 0, rw.n_fb, rw.n_tries, 0); }, ms));
+  HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+  if (accepted_at) {
+    std::vector<int> acc((size_t)M), tr((size_t)M);
+    HIPCHK(hipMemcpy(acc.data(), rw.acc, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tr.data(), rw.tries, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+    for (int j = 0; j < M; ++j) accepted_at[j] = acc[j] >= 0 ? tr[j] - 1 : -1;
+  }
   return RBPF_OK;
 }
 

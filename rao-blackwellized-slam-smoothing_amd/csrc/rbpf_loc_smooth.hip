@@ -14,7 +14,8 @@
 //   BsTerm               logp of one pair: the position term, then the orientation term.  A pair whose log w + position term alone
 //                        lies more than 746 below the running max skips its orientation term: its exp is exactly 0.
 // The MAP trajectory (rbpf_loc_map_trajectory, the recursion and kernels of rbpf_loc_viterbi.hpp) runs on the same prologue and term,
-// and so do the marginal smoothing weights (rbpf_loc_marginal_smooth, rbpf_loc_marginal.hpp).
+// and so do the marginal smoothing weights (rbpf_loc_marginal_smooth, rbpf_loc_marginal.hpp) and backward simulation by rejection
+// sampling (rbpf_loc_backward_simulate_reject, rbpf_loc_reject.hpp).
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
@@ -23,6 +24,7 @@
 #include "rbpf_loc_backward.hpp"
 #include "rbpf_loc_viterbi.hpp"
 #include "rbpf_loc_marginal.hpp"
+#include "rbpf_loc_reject.hpp"
 #include "rbpf_timed_reps.hpp"
 
 #include <algorithm>
@@ -178,17 +180,20 @@ int rbpf_loc_history(rbpf_ctx* c, double* xn_fwd) {
   return RBPF_OK;
 }
 
-int rbpf_loc_backward_simulate(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, double* xs_traj, int32_t* index,
-                               double* traj_smooth_mean) {
+// rbpf_loc_backward_simulate (max_tries = -1: every step is the all-pairs pass) and rbpf_loc_backward_simulate_reject (max_tries >= 0:
+// steps N_T-2 .. 0 by rbpf_loc_reject.hpp); `who` is how the entry point names itself in its refusals
+static int bs_simulate(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, int max_tries, double* xs_traj, int32_t* index,
+                       double* traj_smooth_mean, int32_t* n_fallback, int64_t* n_tries, const char* who) {
   if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
   if (c->loc->generic) {
     set_error("backward simulation needs the transition density of dynModel: a generic map's dynModel is a sampler (its handles carry no density)");
     return RBPF_ERR_UNSUPPORTED;
   }
   if (n_traj < 1) { set_error("n_traj must be >= 1"); return RBPF_ERR_INVALID_ARG; }
-  RB_TRY(backward_check_forward(c, "rbpf_loc_backward_simulate", "rbpf_loc_backward_simulate"));
+  RB_TRY(backward_check_forward(c, who, who));
   LocState* L = c->loc;
   const int N = c->N, T = c->T, M = n_traj;
+  const bool reject = max_tries >= 0;
   std::vector<BsNoise> nz((size_t)L->s_pages);
   {
     std::vector<double> S((size_t)L->s_pages * 36);
@@ -200,7 +205,15 @@ int rbpf_loc_backward_simulate(rbpf_ctx* c, int32_t n_traj, const double* u, uin
   // workspace from the context's pool, handed back on every way out
   BackwardWorkspace ws;
   BackwardWorkspaceGuard lease(ws);
-  RB_TRY(ws.take(c->pool, (size_t)8 * N, (size_t)nch * M, (size_t)T * M, (size_t)(full_xs ? T : 2) * 7 * M, (size_t)7 * T));
+  RB_TRY(ws.take(c->pool, (size_t)8 * N, reject ? reject_part_count(N, M) : (size_t)nch * M, (size_t)T * M, (size_t)(full_xs ? T : 2) * 7 * M,
+                 (size_t)7 * T));
+  RejectWorkspace rw;
+  RejectWorkspaceGuard reject_lease(rw);
+  if (reject) {
+    RB_TRY(rw.take(c->pool, (size_t)N, reject_cdf_blocks(N), (size_t)M, 7, (size_t)T));
+    HIPCHK(hipMemsetAsync(rw.n_fb, 0, (size_t)T * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(rw.n_tries, 0, (size_t)T * sizeof(long long), c->stream));
+  }
   RB_TRY(backward_uniforms(u, seed, T, M, ws.u, c->stream));
   auto slab = [&](int t) { return ws.xs + (size_t)(full_xs ? t : (t & 1)) * 7 * M; };
   for (int t = T - 1; t >= 0; --t) {
@@ -213,14 +226,96 @@ int rbpf_loc_backward_simulate(rbpf_ctx* c, int32_t n_traj, const double* u, uin
     if (!a.head.first) a.term.nz = nz[L->s_pages > 1 ? t : 0];
     else std::memset(&a.term.nz, 0, sizeof(a.term.nz));
     const double* odo = c->d_odo + (size_t)(a.head.first ? 0 : t) * 7;          // the draw of step T-1 reads log w only
-    HIPCHK(bs_launch_step(a, a.X, (size_t)N, 1, c->w + (size_t)t * N, odo, ws.Xhat, c->stream));
+    if (reject && !a.head.first) {
+      hipLaunchKernelGGL(bs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, c->stream, N, a.X, (size_t)N, (size_t)1, c->w + (size_t)t * N, odo, ws.Xhat);
+      HIPCHK(reject_launch_step(a, rw, c->w + (size_t)t * N, 7, max_tries, nullptr, seed, t, rw.n_fb + t, rw.n_tries + t, c->stream));
+    } else {
+      HIPCHK(bs_launch_step(a, a.X, (size_t)N, 1, c->w + (size_t)t * N, odo, ws.Xhat, c->stream));
+    }
     if (traj_smooth_mean) HIPCHK(backward_launch_mean(M, 7, slab(t), ws.mean + (size_t)t * 7, c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   RB_TRY(ctx_check_flags(c));
+  if (reject && n_fallback) HIPCHK(hipMemcpy(n_fallback, rw.n_fb, (size_t)T * sizeof(int), hipMemcpyDeviceToHost));
+  if (reject && n_tries) HIPCHK(hipMemcpy(n_tries, rw.n_tries, (size_t)T * sizeof(long long), hipMemcpyDeviceToHost));
   if (xs_traj) HIPCHK(hipMemcpy(xs_traj, ws.xs, (size_t)7 * M * T * sizeof(double), hipMemcpyDeviceToHost));
   if (index) HIPCHK(hipMemcpy(index, ws.idx, (size_t)M * T * sizeof(int), hipMemcpyDeviceToHost));
   if (traj_smooth_mean) HIPCHK(hipMemcpy(traj_smooth_mean, ws.mean, (size_t)7 * T * sizeof(double), hipMemcpyDeviceToHost));
+  return RBPF_OK;
+}
+
+int rbpf_loc_backward_simulate(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed, double* xs_traj, int32_t* index,
+                               double* traj_smooth_mean) {
+  return bs_simulate(c, n_traj, u, seed, -1, xs_traj, index, traj_smooth_mean, nullptr, nullptr, "rbpf_loc_backward_simulate");
+}
+
+int rbpf_loc_backward_reject_workspace_bytes(int32_t N_P, int32_t N_T, int32_t n_traj, size_t* bytes) {
+  RB_TRY(rbpf_loc_backward_workspace_bytes(N_P, N_T, n_traj, bytes));
+  const size_t nch = ((size_t)N_P + backward_chunk_size(N_P, n_traj) - 1) / backward_chunk_size(N_P, n_traj);
+  *bytes += 2 * (reject_part_count(N_P, n_traj) - nch * (size_t)n_traj) * sizeof(double) + reject_bytes((size_t)N_P, (size_t)n_traj, 7, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_backward_simulate_reject(rbpf_ctx* c, int32_t n_traj, uint64_t seed, int32_t max_tries, double* xs_traj, int32_t* index,
+                                      double* traj_smooth_mean, int32_t* n_fallback, int64_t* n_tries) {
+  if (max_tries < 0 || max_tries > kRejectMaxTries) { set_error("max_tries must be in 0 .. 4194304"); return RBPF_ERR_INVALID_ARG; }
+  return bs_simulate(c, n_traj, nullptr, seed, max_tries, xs_traj, index, traj_smooth_mean, n_fallback, n_tries, "rbpf_loc_backward_simulate_reject");
+}
+
+int rbpf_loc_backward_reject_step(int32_t N, int32_t M, const double* xn, const double* w, const double* xs_next, const double* odo, double dt,
+                                  const double* Q, const double* u_try, const double* u, int32_t R, int32_t* index, int32_t* accepted_at,
+                                  int32_t reps, double* ms) {
+  if (!xn || !w || !xs_next || !odo || !Q || !u || !index) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (R < 0 || R > kRejectMaxTries) { set_error("max_tries must be in 0 .. 4194304"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles) { set_error("N above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  double S[36];
+  for (int q = 0; q < 36; ++q) S[q] = 0.0;
+  for (int b = 0; b < 2; ++b)
+    for (int cc = 0; cc < 3; ++cc)
+      for (int r = 0; r < 3; ++r) {
+        const int q = (3 * b + r) + 6 * (3 * b + cc);
+        const double v = dt * Q[q];
+        if (!(v >= 0.0)) { set_error("dt * Q has a negative entry in a diagonal block: the element-wise sqrt of dynModel would be complex"); return RBPF_ERR_INVALID_ARG; }
+        S[q] = std::sqrt(v);
+      }
+  BackwardArgs<BsTerm> a;
+  RB_TRY(bs_noise(S, a.term.nz));
+  if (!have_device()) { set_error("no HIP device: the backward pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  DevicePool tmp;
+  RejectWorkspace rw;
+  RejectWorkspaceGuard lease(rw);
+  double *d_xn = nullptr, *d_w = nullptr, *d_xs = nullptr, *d_odo = nullptr, *d_u = nullptr, *d_ut = nullptr, *d_Xhat = nullptr, *d_pm = nullptr,
+         *d_ps = nullptr;
+  int *d_idx = nullptr, *d_clamped = nullptr;
+  const size_t np = reject_part_count(N, M);
+  RB_TRY(tmp.upload(&d_xn, xn, (size_t)7 * N));
+  RB_TRY(tmp.upload(&d_w, w, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xs_next, (size_t)7 * M));
+  RB_TRY(tmp.upload(&d_odo, odo, (size_t)7));
+  RB_TRY(tmp.upload(&d_u, u, (size_t)M));
+  if (R > 0 && u_try) RB_TRY(tmp.upload(&d_ut, u_try, (size_t)2 * M * R));   // (null: the device generator, seed 0, step 0)
+  RB_TRY(tmp.alloc(&d_Xhat, (size_t)8 * N));
+  RB_TRY(tmp.alloc(&d_pm, np));
+  RB_TRY(tmp.alloc(&d_ps, np));
+  RB_TRY(tmp.alloc(&d_idx, (size_t)M));
+  RB_TRY(tmp.alloc(&d_clamped, (size_t)1));
+  RB_TRY(rw.take(tmp, (size_t)N, reject_cdf_blocks(N), (size_t)M, 7, 1));
+  HIPCHK(hipMemset(d_clamped, 0, sizeof(int)));
+  a.N = N; a.M = M; a.C = backward_chunk_size(N, M); a.nchunks = (N + a.C - 1) / a.C; a.head.first = 0;
+  a.Xhat = d_Xhat; a.X = nullptr; a.xs_next = d_xs; a.u = d_u; a.part_m = d_pm; a.part_s = d_ps; a.index = d_idx; a.xs = nullptr;
+  a.clamped = d_clamped;
+  RB_TRY(timed_reps(reps, 0, [&] {
+    hipLaunchKernelGGL(bs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, 0, N, d_xn, (size_t)1, (size_t)7, d_w, d_odo, d_Xhat);
+    return reject_launch_step(a, rw, d_w, 7, R, d_ut, 0ull, 0, rw.n_fb, rw.n_tries, 0);
+  }, ms));
+  HIPCHK(hipMemcpy(index, d_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+  if (accepted_at) {
+    std::vector<int> acc((size_t)M), tr((size_t)M);
+    HIPCHK(hipMemcpy(acc.data(), rw.acc, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tr.data(), rw.tries, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+    for (int j = 0; j < M; ++j) accepted_at[j] = acc[j] >= 0 ? tr[j] - 1 : -1;
+  }
   return RBPF_OK;
 }
 

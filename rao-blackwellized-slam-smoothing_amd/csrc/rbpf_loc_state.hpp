@@ -87,6 +87,52 @@ struct BackwardWorkspaceGuard {
   ~BackwardWorkspaceGuard() { ws.release(); }
 };
 
+// What rejection-sampling backward simulation (rbpf_loc_reject.hpp) keeps next to a BackwardWorkspace, leased and handed back the
+// same way: the cdf of a step's weights, what the tries left per trajectory, and the compacted rows of the trajectories that fall
+// back to the all-pairs pass.  (The chunk partials of that pass are the BackwardWorkspace's pm / ps, sized by reject_part_count.)
+struct RejectWorkspace {
+  DevicePool* pool = nullptr;
+  double *cdf = nullptr, *btot = nullptr;   // [N] inclusive prefix sums of w[t]; [blocks] the totals of their first level
+  double *xs_c = nullptr, *u_c = nullptr;   // [M][rows], [M]: successors and uniforms of the trajectories that fall back, ascending j
+  int *acc = nullptr, *tries = nullptr;     // [M]: the accepted particle or -1; tries made
+  int *pos = nullptr, *fb = nullptr;        // [M]: row of trajectory j among the compacted ones or -1; the fallback's index per row
+  int* bcnt = nullptr;                      // [ceil(M / 256)]: trajectories without an acceptance per block of 256, then their offsets
+  long long* btries = nullptr;              // [ceil(M / 256)]: tries per block
+  int *n_fb = nullptr;                      // [T]: M' of every step (step T-1: 0)
+  long long* n_tries = nullptr;             // [T]: tries of every step, summed over the trajectories
+  int take(DevicePool& from, size_t N, size_t n_blocks, size_t M, size_t rows, size_t T) {
+    pool = &from;
+    int s = from.alloc(&cdf, N);
+    if (s == RBPF_OK) s = from.alloc(&btot, n_blocks);
+    if (s == RBPF_OK) s = from.alloc(&xs_c, M * rows);
+    if (s == RBPF_OK) s = from.alloc(&u_c, M);
+    if (s == RBPF_OK) s = from.alloc(&acc, M);
+    if (s == RBPF_OK) s = from.alloc(&tries, M);
+    if (s == RBPF_OK) s = from.alloc(&pos, M);
+    if (s == RBPF_OK) s = from.alloc(&fb, M);
+    if (s == RBPF_OK) s = from.alloc(&bcnt, (M + 255) / 256);
+    if (s == RBPF_OK) s = from.alloc(&btries, (M + 255) / 256);
+    if (s == RBPF_OK) s = from.alloc(&n_fb, T);
+    if (s == RBPF_OK) s = from.alloc(&n_tries, T);
+    if (s != RBPF_OK) release();
+    return s;
+  }
+  void release() {
+    if (pool)
+      for (void* p : {(void*)cdf, (void*)btot, (void*)xs_c, (void*)u_c, (void*)acc, (void*)tries, (void*)pos, (void*)fb, (void*)bcnt, (void*)btries, (void*)n_fb, (void*)n_tries})
+        pool->release(p);
+    *this = RejectWorkspace();
+  }
+};
+
+struct RejectWorkspaceGuard {
+  RejectWorkspace& ws;
+  explicit RejectWorkspaceGuard(RejectWorkspace& w) : ws(w) {}
+  RejectWorkspaceGuard(const RejectWorkspaceGuard&) = delete;
+  RejectWorkspaceGuard& operator=(const RejectWorkspaceGuard&) = delete;
+  ~RejectWorkspaceGuard() { ws.release(); }
+};
+
 // An open backward-simulation pass over a generic map (rbpf_loc_generic_backward_begin .. _finish, rbpf_loc_generic_smooth.hip): the
 // workspace is taken from rbpf_ctx::pool at begin and handed back at finish (or with the context).  An open MAP pass
 // (rbpf_loc_generic_map_begin .. _finish) and an open marginal-smoothing pass (rbpf_loc_generic_marginal_begin .. _finish) are kept
@@ -97,6 +143,11 @@ struct LocGenBackward {
   int t = -1;                      // the step the next rbpf_loc_generic_backward_step_device processes; -1: all done
   LocGenLayout lay;
   BackwardWorkspace ws;
+  // rbpf_loc_generic_backward_reject_begin: steps N_T-2 .. 0 try max_tries proposals per trajectory before the all-pairs pass
+  bool reject = false;
+  int max_tries = 0;
+  unsigned long long seed = 0;
+  RejectWorkspace rw;
 };
 
 struct LocState {
@@ -114,6 +165,8 @@ struct LocState {
   double *d_R = nullptr;           // [n_y x n_y]
   double *d_H = nullptr;           // [N][n_y][ldx] rows packed from dy layout 0 (allocated on first use)
   LocGenBackward gb;               // backward simulation with a Gaussian transition density
+  std::vector<int> reject_n_fb;    // [N_T] of the last finished rejection pass (rbpf_loc_generic_backward_reject_stats); empty: none
+  std::vector<long long> reject_n_tries;
   LocGenBackward gv;               // the MAP trajectory with one (rbpf_loc_generic_map_begin .. _finish): t counts up, M = N_P; never open with gb
   LocGenBackward gm;               // marginal smoothing with one (rbpf_loc_generic_marginal_begin .. _finish): t counts down from N_T-2, M = N_P; never open with gb or gv
   // landmark map (rbpf_loc_landmark_create): the handle's yhat is the prediction and the outputs observed at a step are selected

@@ -2044,6 +2044,27 @@ def device_map_backward_step(mu, w, xs_next, cov, u, rows=None, angle_rows=(), w
     return index, logp, ms.value
 
 
+def device_map_backward_reject_step(mu, w, xs_next, cov, u_try, u, rows=None, angle_rows=(), reps=1, quat_rows=None):
+    """rbpf_loc_generic_backward_reject_step, the kernel-level probe: one step of backward simulation by rejection sampling with a
+    Gaussian transition on the caller's arrays.  mu, w, xs_next, cov, rows, angle_rows and quat_rows as device_map_backward_step;
+    u_try [R x M x 2]: the uniforms (u0, u1) of try r of trajectory j, R = max_tries (R = 0: an empty array); u [M]: the fallback's
+    uniforms -> (index [M], accepted_at [M]: the try that was accepted or -1 for a trajectory the all-pairs pass drew, median ms)."""
+    lib = load_library()
+    mu, xs_next, cov, rows_a, mask, qpos = _transition_probe_args(mu, xs_next, cov, rows, angle_rows, quat_rows)
+    (n_sel, N), (nN, M) = mu.shape, xs_next.shape
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).ravel())
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).ravel())
+    if w.size != N or u.size != M:
+        raise ValueError("w must be [N] and u [M]")
+    u_try, R = _reject_uniforms(u_try, M)
+    index, acc = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_generic_backward_reject_step(N, M, nN, n_sel, _ip(rows_a), mask, -1 if quat_rows is None else qpos, _dp(mu), _dp(w),
+                                                    _dp(xs_next), _dp(cov), _dp(u_try) if u_try is not None else None, _dp(u), R, _ip(index), _ip(acc), int(reps),
+                                                    C.byref(ms)))
+    return index, acc, ms.value
+
+
 def device_map_map_step(mu, delta, xs_next, cov, rows=None, angle_rows=(), reps=1, quat_rows=None):
     """rbpf_loc_generic_map_step, the kernel-level probe: one step of the MAP recursion with a Gaussian transition on the caller's
     arrays.  mu [n_sel x N], delta [N] (-inf allowed), xs_next [n_nonlin x M] (the successors), cov [n_res x n_res]; rows, angle_rows
@@ -2578,12 +2599,22 @@ class LocalizationSession:
         check(self.lib.rbpf_loc_history(self.ctx, _dp(X)))
         return X
 
-    def backward_simulate(self, n_traj, rng=None, want=("xs_traj", "index", "traj_smooth_mean")):
+    def backward_simulate(self, n_traj, rng=None, want=("xs_traj", "index", "traj_smooth_mean"), method="all_pairs", max_tries=None):
         """rbpf_loc_backward_simulate: n_traj trajectories drawn backwards through the stored particles (keep_history and trace,
         every step done).  rng: None / PhiloxRNG(seed): the device generator (PhiloxRNG.backward_uniforms(n_traj, N_T) are its
         draws); an array u [N_T x n_traj] of uniforms in (0, 1]: replay.  Returns a dict of the arrays named in `want`:
         xs_traj [7 x n_traj x N_T], index [n_traj x N_T] (0-based), traj_smooth_mean [7 x N_T].  In a DeviceMap: n_nonlin rows in
-        place of 7, with the map's DeviceTransition (rbpf_loc_generic_backward_*); without one the call is refused."""
+        place of 7, with the map's DeviceTransition (rbpf_loc_generic_backward_*); without one the call is refused.
+        method="rejection" (rbpf_loc_backward_simulate_reject, rbpf_loc_generic_backward_reject_begin): the same law, steps N_T-2 .. 0
+        by up to max_tries proposals from the weights per trajectory, accepted against the transition density, before the all-pairs
+        pass draws the trajectories that are left; rng is None or a PhiloxRNG, and `want` may name n_fallback [N_T] (trajectories
+        left to the all-pairs pass at every step) and n_tries [N_T] (int64, tries summed over the trajectories).  max_tries = 0 gives
+        the arrays of method="all_pairs" with the same seed bit for bit.  max_tries=None is reject_default_max_tries(N_P, n_traj)."""
+        if method not in ("all_pairs", "rejection"):
+            raise ValueError(f"unknown method {method!r}: 'all_pairs' or 'rejection'")
+        reject = method == "rejection"
+        if not reject and max_tries is not None:
+            raise ValueError("max_tries belongs to method='rejection'")
         if self.driver is not None and self.map.transition is None:
             raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, _NO_BACKWARD_IN_DEVICE_MAP)
         M, T = int(n_traj), self.prob.N_T
@@ -2592,11 +2623,18 @@ class LocalizationSession:
             rng = PhiloxRNG(1)
         if isinstance(rng, PhiloxRNG):
             seed = int(rng.seed)
+        elif reject:
+            raise ValueError("method='rejection' draws its tries on the device: rng must be None or a PhiloxRNG; uniforms are replayed by the "
+                             "probes loc_backward_reject_step and device_map_backward_reject_step")
         else:
             u = np.ascontiguousarray(np.asarray(rng, dtype=np.float64))
             if M >= 1 and u.shape != (T, M):
                 raise ValueError(f"u must be [{T} x {M}] (row t = step t)")
-        unknown = set(want) - {"xs_traj", "index", "traj_smooth_mean"}
+        if reject:
+            max_tries = reject_default_max_tries(self.prob.N_P, M) if max_tries is None else int(max_tries)
+            if max_tries < 0:
+                raise ValueError("max_tries must be >= 0")
+        unknown = set(want) - ({"xs_traj", "index", "traj_smooth_mean"} | ({"n_fallback", "n_tries"} if reject else set()))
         if unknown:
             raise ValueError(f"unknown outputs {sorted(unknown)}")
         Mb = max(M, 0)
@@ -2607,8 +2645,20 @@ class LocalizationSession:
             b["index"] = np.zeros((Mb, T), dtype=np.int32, order="F")
         if "traj_smooth_mean" in want:
             b["traj_smooth_mean"] = np.empty((self.nN, T), order="F")
+        if "n_fallback" in want:
+            b["n_fallback"] = np.zeros(T, dtype=np.int32)
+        if "n_tries" in want:
+            b["n_tries"] = np.zeros(T, dtype=np.int64)
         if self.driver is not None:
-            self._backward_in_device_map(M, u, seed, b)
+            self._backward_in_device_map(M, u, seed, b, max_tries if reject else None)
+            return b
+        if reject:
+            check(self.lib.rbpf_loc_backward_simulate_reject(self.ctx, M, C.c_uint64(seed), max_tries,
+                                                             _dp(b["xs_traj"]) if "xs_traj" in b else None,
+                                                             _ip(b["index"]) if "index" in b else None,
+                                                             _dp(b["traj_smooth_mean"]) if "traj_smooth_mean" in b else None,
+                                                             _ip(b["n_fallback"]) if "n_fallback" in b else None,
+                                                             b["n_tries"].ctypes.data_as(C.POINTER(C.c_int64)) if "n_tries" in b else None))
             return b
         check(self.lib.rbpf_loc_backward_simulate(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed),
                                                   _dp(b["xs_traj"]) if "xs_traj" in b else None,
@@ -2638,14 +2688,18 @@ class LocalizationSession:
                 covs[key] = c
         return np.asarray(rows, dtype=np.int32), mask, qpos, len(rows), covs, page
 
-    def _backward_in_device_map(self, M, u, seed, b):
+    def _backward_in_device_map(self, M, u, seed, b, max_tries=None):
         """The backward pass with the map's DeviceTransition: the covariance pages on the host first, then begin, one
-        particles_device / mean handle / step_device per step in stream order, finish (also the way out of a failed handle)."""
+        particles_device / mean handle / step_device per step in stream order, finish (also the way out of a failed handle).
+        max_tries: None, or the tries of method="rejection" (rbpf_loc_generic_backward_reject_begin; the same steps drive it)."""
         lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
         torch, T, N, nN = drv.torch, prob.N_T, prob.N_P, self.nN
         rows_a, mask, qpos, n_sel, covs, page = self._transition_pages()
-        check(lib.rbpf_loc_generic_backward_pose_begin(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed), n_sel, _ip(rows_a), mask,
-                                                       qpos))
+        if max_tries is None:
+            check(lib.rbpf_loc_generic_backward_pose_begin(self.ctx, M, _dp(u) if u is not None else None, C.c_uint64(seed), n_sel, _ip(rows_a),
+                                                           mask, qpos))
+        else:
+            check(lib.rbpf_loc_generic_backward_reject_begin(self.ctx, M, C.c_uint64(seed), int(max_tries), n_sel, _ip(rows_a), mask, qpos))
         try:
             with torch.cuda.stream(drv.stream):
                 for _ in range(T):
@@ -2673,6 +2727,9 @@ class LocalizationSession:
             check(lib.rbpf_loc_generic_backward_finish(self.ctx, _dp(b["xs_traj"]) if "xs_traj" in b else None,
                                                        _ip(b["index"]) if "index" in b else None,
                                                        _dp(b["traj_smooth_mean"]) if "traj_smooth_mean" in b else None))
+            if "n_fallback" in b or "n_tries" in b:
+                check(lib.rbpf_loc_generic_backward_reject_stats(self.ctx, _ip(b["n_fallback"]) if "n_fallback" in b else None,
+                                                                 b["n_tries"].ctypes.data_as(C.POINTER(C.c_int64)) if "n_tries" in b else None))
         finally:
             self._keep_mu = None
 
@@ -2912,14 +2969,89 @@ def loc_backward_step(xn, w, xs_next, odo, dt, Q, u, want_logp=False, reps=1):
     return index, logp, ms.value
 
 
-def particleSmootherLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, N_S, dt, *, rng=None, extras=False):
+# What tools/loc_reject_bench.py measured on an MI355X at N = M = 65 536 in the dense-mag map (profiles/loc_reject_bench.json): the
+# all-pairs step over one round of tries of a run whose every try is rejected.  None: not measured, max_tries is then mandatory.
+REJECT_R_STAR = 5183.0                         # t_pass = 20.65 ms over t_try = 3.98 us
+REJECT_R_STAR_SIZE = 65536
+
+
+def reject_default_max_tries(N_P, n_traj, r_star=None):
+    """max_tries of method="rejection" where the caller gives none.  A trajectory should never spend more on tries than its fallback
+    costs: at N_P = n_traj = 65 536 that is R* = t_pass / t_try tries, and the default there is the largest power of two not above
+    R*.  A round of tries is paced by the latency of its dependent loads and costs the same at every size, while the all-pairs step
+    grows with N_P x n_traj, so below that size the bound is scaled by N_P n_traj / 65 536^2 (0: every trajectory goes to the
+    all-pairs pass); above it the measured value stands."""
+    r_star = REJECT_R_STAR if r_star is None else r_star
+    if r_star is None:
+        raise ValueError("method='rejection' has no measured default for max_tries on this build (tools/loc_reject_bench.py has not run): "
+                         "pass max_tries explicitly")
+    r = float(r_star) * min(1.0, float(N_P) * float(n_traj) / float(REJECT_R_STAR_SIZE) ** 2)
+    return 0 if r < 1.0 else int(2 ** int(np.floor(np.log2(r))))
+
+
+def loc_backward_reject_workspace_bytes(N_P, N_T, n_traj):
+    """rbpf_loc_backward_reject_workspace_bytes (no device access)."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_backward_reject_workspace_bytes(int(N_P), int(N_T), int(n_traj), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def _reject_uniforms(u_try, M):
+    """u_try [R x M x 2] (C order: try, trajectory, (u0, u1)) -> (the contiguous array, R); an int R: (None, R), the device
+    generator's draws of seed 0 at step 0 (timing runs)."""
+    if isinstance(u_try, (int, np.integer)):
+        if u_try < 0:
+            raise ValueError("max_tries must be >= 0")
+        return None, int(u_try)
+    u_try = np.ascontiguousarray(np.asarray(u_try, dtype=np.float64))
+    if u_try.size == 0:
+        return None, 0
+    if u_try.ndim != 3 or u_try.shape[1:] != (M, 2):
+        raise ValueError(f"u_try must be [R x {M} x 2]")
+    return u_try, u_try.shape[0]
+
+
+def loc_backward_reject_step(xn, w, xs_next, odo, dt, Q, u_try, u, reps=1):
+    """rbpf_loc_backward_reject_step, the kernel-level probe: one step of backward simulation by rejection sampling on the caller's
+    arrays.  xn [7 x N], w [N], xs_next [7 x M], odo [7], Q [6 x 6] as loc_backward_step; u_try [R x M x 2]: the uniforms (u0, u1) of
+    try r of trajectory j, R = max_tries (R = 0: an empty array; an int R: the device generator's draws, for timing); u [M]: the
+    fallback's uniforms -> (index [M], accepted_at [M]: the try that was accepted or -1 for a trajectory the all-pairs pass drew,
+    median ms of one step)."""
+    lib = load_library()
+    xn = np.asfortranarray(np.asarray(xn, dtype=np.float64).reshape(7, -1))
+    xs_next = np.asfortranarray(np.asarray(xs_next, dtype=np.float64).reshape(7, -1))
+    N, M = xn.shape[1], xs_next.shape[1]
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).ravel())
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).ravel())
+    odo = np.ascontiguousarray(np.asarray(odo, dtype=np.float64).ravel())
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(6, 6))
+    if w.size != N or u.size != M or odo.size != 7:
+        raise ValueError("w must be [N], u [M] and odo [7]")
+    u_try, R = _reject_uniforms(u_try, M)
+    index, acc = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_backward_reject_step(N, M, _dp(xn), _dp(w), _dp(xs_next), _dp(odo), float(dt), _dp(Q), _dp(u_try) if u_try is not None else None, _dp(u),
+                                            R, _ip(index), _ip(acc), int(reps), C.byref(ms)))
+    return index, acc, ms.value
+
+
+def particleSmootherLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, N_S, dt, *, rng=None, extras=False, method="all_pairs",
+                                 max_tries=None):
     """Forward filter, backward simulation for localisation in a fixed map: particleFilterLocalization, then N_S trajectories drawn
     backwards through its particles -> (xs_traj [7 x N_S x N_T], traj_smooth_mean [7 x N_T][, extras]).  dynModel / measModel are
     the handles of a DenseMagMap, R is accepted and not used, as there; or a DeviceMap with a DeviceTransition as dynModel (measModel
     None): n_nonlin rows in place of 7.  rng: PhiloxRNG (one seed keys the filter's and the
     backward draws, on disjoint counters) or ReplayRNG(U, Z, Uback=u) with the backward uniforms u [N_T x N_S].
-    extras: the filter's outputs (traj_max, traj_mean, first_degenerate_step, ...) and the drawn `index` [N_S x N_T]."""
+    extras: the filter's outputs (traj_max, traj_mean, first_degenerate_step, ...) and the drawn `index` [N_S x N_T].
+    method, max_tries: as LocalizationSession.backward_simulate; method="rejection" takes a PhiloxRNG or None, and extras then hold
+    n_fallback and n_tries [N_T] too."""
     import warnings
+    if method not in ("all_pairs", "rejection"):
+        raise ValueError(f"unknown method {method!r}: 'all_pairs' or 'rejection'")
+    if method == "rejection" and isinstance(rng, ReplayRNG):
+        raise ValueError("method='rejection' draws its tries on the device: rng must be None or a PhiloxRNG; uniforms are replayed by the "
+                         "probes loc_backward_reject_step and device_map_backward_reject_step")
     mp = _device_map(dynModel, measModel)
     if mp is not None and mp.transition is None:
         raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleSmootherLocalization: " + _NO_BACKWARD_IN_DEVICE_MAP)
@@ -2936,8 +3068,14 @@ def particleSmootherLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q,
         fwd = s.finish(extras=extras)
         if fwd["first_degenerate_step"] >= 0:
             warnings.warn(f"Weights filter close to zero at t={fwd['first_degenerate_step'] + 1} !!!", RuntimeWarning, stacklevel=2)
-        out = s.backward_simulate(N_S, rng=back)
+        if method == "rejection":
+            out = s.backward_simulate(N_S, rng=back, want=("xs_traj", "index", "traj_smooth_mean", "n_fallback", "n_tries"), method=method,
+                                      max_tries=max_tries)
+        else:
+            out = s.backward_simulate(N_S, rng=back, max_tries=max_tries)
     if extras:
+        if method == "rejection":
+            fwd["n_fallback"], fwd["n_tries"] = out["n_fallback"], out["n_tries"]
         fwd["index"] = out["index"]
         return out["xs_traj"], out["traj_smooth_mean"], fwd
     return out["xs_traj"], out["traj_smooth_mean"]
