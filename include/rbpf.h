@@ -913,6 +913,29 @@ int rbpf_loc_marginal_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes);
 int rbpf_loc_marginal_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* logws_next,
                            const double* odo, double dt, const double* Q, double* D, double* lws, int32_t reps, double* ms);
 
+/* ---- the two-slice statistics of the transition residual of a localisation run ----------------------
+ * rbpf_loc_marginal_smooth, and with its weights the pairwise (two-slice) smoothed moments of the transition residual: with
+ *     xi(i, j, t) = w(i, t) p(X(:, j, t+1) | X(:, i, t)) ws(j, t+1) / D(j, t)                  (sums to 1 over all pairs)
+ * and r(i, j) = [p~ - (p_i + dx(1:3)); phi] the UN-WHITENED residual of rbpf_loc_backward_simulate's density (before S_pos and
+ * S_rot divide it),
+ *     S(:, :, t) = sum_ij xi r r',     m(:, t) = sum_ij xi r,     pair_mass(t) = sum_ij xi                       t = 1 .. N_T-1
+ * page t belongs to the pair of steps (t, t+1).  S is the E-step of EM for the transition noise (its mean over t, divided by
+ * dt(t), estimates the covariance per unit time), m the smoothed odometry bias, pair_mass 1 in exact arithmetic.  xi is never
+ * stored: one more all-pairs pass per step reduces every pair on the fly, in fp64, in a summation order fixed by N_P; a pair whose
+ * log xi lies below -746 contributes exactly 0.
+ * Outputs (NULL pointers are skipped): the five of rbpf_loc_marginal_smooth, bit for bit what it returns, then S [6 x 6 x (N_T-1)],
+ * m [6 x (N_T-1)], pair_mass [N_T-1].  Refusals as rbpf_loc_marginal_smooth.                                                     */
+int rbpf_loc_pair_stats_smooth(rbpf_ctx* ctx, double* w_smooth, double* mean, double* cov, double* ess, double* mass, double* S, double* m,
+                               double* pair_mass);
+/* Bytes of device memory rbpf_loc_pair_stats_smooth takes from the pool while it runs (no device access).                        */
+int rbpf_loc_pair_stats_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes);
+/* One step on the caller's arrays, the kernel-level probe: the arguments and the outputs D, lws of rbpf_loc_marginal_step, then
+ * S [6 x 6], m [6], pair_mass [1] of that step (computed with the step's own mass = sum_i exp(lws(i))).  *ms = median time of
+ * the marginal step, the normalisation and the statistics pass together.                                                       */
+int rbpf_loc_pair_stats_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* logws_next,
+                             const double* odo, double dt, const double* Q, double* D, double* lws, double* S, double* m, double* pair_mass,
+                             int32_t reps, double* ms);
+
 /* ---- localisation in the fixed map of a generic device-code model --------------------------------
  * particleFilter.m:100-161 with the map frozen: xl = mean and P = V'V (V lower n_lin x n_lin, column-major, lower triangle read:
  * the rbpf_loc_map convention) are the same for every particle and never updated (:163-204 are left out).  The model is the
@@ -1071,8 +1094,9 @@ int rbpf_loc_generic_map_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_
  *   rbpf_loc_generic_marginal_workspace_bytes   what begin takes from the pool (no device access): Xhat has n_sel + 1 rows.
  *   rbpf_loc_generic_marginal_step   one step on host arrays, the kernel-level probe: mu [n_sel][N], logw [N], xs_next [n_nonlin x
  *        M] column-major, logws_next [M], cov [n_res x n_res] -> D [M], lws [N] as rbpf_loc_marginal_step.
- * RBPF_ERR_STATE out of order; the context stays usable after any refusal.  Not built: sharding, host closures, two-slice
- * (pairwise) marginals, other successors than the N_P particles outside the probe, sub-quadratic approximations.                  */
+ * RBPF_ERR_STATE out of order; the context stays usable after any refusal.  Not built: sharding, host closures, other
+ * successors than the N_P particles outside the probe, sub-quadratic approximations.  (The two-slice moments of the transition
+ * residual: rbpf_loc_generic_pair_stats_* below.)                                                                                 */
 int rbpf_loc_generic_marginal_begin(rbpf_ctx* ctx, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos);
 int rbpf_loc_generic_marginal_particles_device(rbpf_ctx* ctx, int32_t* t, const double** xn_dev);
 int rbpf_loc_generic_marginal_step_device(rbpf_ctx* ctx, const double* mu_dev, const double* cov);
@@ -1081,6 +1105,25 @@ int rbpf_loc_generic_marginal_workspace_bytes(int32_t n_nonlin, int32_t n_sel, i
 int rbpf_loc_generic_marginal_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
                                    int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
                                    const double* cov, double* D, double* lws, int32_t reps, double* ms);
+
+/* ---- the two-slice statistics of the transition residual in the fixed map of a generic device-code model ----
+ * The statistics of rbpf_loc_pair_stats_smooth on a context of rbpf_loc_generic_create or rbpf_loc_landmark_create, driven exactly
+ * as the rbpf_loc_generic_marginal_* family is (same arguments, checks and refusals; a statistics pass counts as a fourth kind of
+ * pass, and only one of the four can be open at once).  r is the un-whitened residual of rbpf_loc_generic_backward_pose_begin's
+ * density: a wrapped difference on plain and angle rows, logq of the quaternion error in a block.  _finish returns the five outputs
+ * of _marginal_finish and S [n_res x n_res x (N_T-1)], m [n_res x (N_T-1)], pair_mass [N_T-1] in the CALLER's residual order (the
+ * order of cov).  _step is the probe: the arguments of rbpf_loc_generic_marginal_step, then S [n_res x n_res], m [n_res],
+ * pair_mass [1].                                                                                                                */
+int rbpf_loc_generic_pair_stats_begin(rbpf_ctx* ctx, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos);
+int rbpf_loc_generic_pair_stats_particles_device(rbpf_ctx* ctx, int32_t* t, const double** xn_dev);
+int rbpf_loc_generic_pair_stats_step_device(rbpf_ctx* ctx, const double* mu_dev, const double* cov);
+int rbpf_loc_generic_pair_stats_finish(rbpf_ctx* ctx, double* w_smooth, double* mean, double* cov, double* ess, double* mass, double* S,
+                                       double* m, double* pair_mass);
+int rbpf_loc_generic_pair_stats_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, size_t* bytes);
+int rbpf_loc_generic_pair_stats_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                     int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
+                                     const double* cov, double* D, double* lws, double* S, double* m, double* pair_mass, int32_t reps,
+                                     double* ms);
 
 /* ---- backward simulation by rejection sampling, in every fixed map -----------------------------------
  * The law of rbpf_loc_backward_simulate / rbpf_loc_generic_backward_*, drawn without the all-pairs pass where a proposal is

@@ -19,6 +19,8 @@ from .host import (particleFilter, particleSmoother, particleSmootherInformation
                    particleMapLocalization, loc_map_step, loc_map_workspace_bytes, device_map_map_step, device_map_map_workspace_bytes,
                    particleMarginalSmootherLocalization, loc_marginal_step, loc_marginal_workspace_bytes, device_map_marginal_step,
                    device_map_marginal_workspace_bytes,
+                   particleTransitionStatisticsLocalization, loc_pair_stats_step, loc_pair_stats_workspace_bytes, device_map_pair_stats_step,
+                   device_map_pair_stats_workspace_bytes, transition_noise_estimate,
                    loc_backward_reject_step, loc_backward_reject_workspace_bytes, device_map_backward_reject_step, reject_default_max_tries)
 
 

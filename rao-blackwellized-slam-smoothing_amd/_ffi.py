@@ -175,6 +175,9 @@ EXPORTS = [
     "rbpf_loc_marginal_smooth", "rbpf_loc_marginal_workspace_bytes", "rbpf_loc_marginal_step",
     "rbpf_loc_generic_marginal_begin", "rbpf_loc_generic_marginal_particles_device", "rbpf_loc_generic_marginal_step_device",
     "rbpf_loc_generic_marginal_finish", "rbpf_loc_generic_marginal_workspace_bytes", "rbpf_loc_generic_marginal_step",
+    "rbpf_loc_pair_stats_smooth", "rbpf_loc_pair_stats_workspace_bytes", "rbpf_loc_pair_stats_step",
+    "rbpf_loc_generic_pair_stats_begin", "rbpf_loc_generic_pair_stats_particles_device", "rbpf_loc_generic_pair_stats_step_device",
+    "rbpf_loc_generic_pair_stats_finish", "rbpf_loc_generic_pair_stats_workspace_bytes", "rbpf_loc_generic_pair_stats_step",
     "rbpf_loc_backward_simulate_reject", "rbpf_loc_backward_reject_workspace_bytes", "rbpf_loc_backward_reject_step",
     "rbpf_loc_generic_backward_reject_begin", "rbpf_loc_generic_backward_reject_stats", "rbpf_loc_generic_backward_reject_workspace_bytes",
     "rbpf_loc_generic_backward_reject_step",
@@ -368,6 +371,18 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_loc_generic_backward_reject_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, C.c_int32, c_double_p,
                                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_int32_p, c_int32_p,
                                                           C.c_int32, c_double_p]
+    lib.rbpf_loc_pair_stats_smooth.argtypes = [C.c_void_p] + [c_double_p] * 8
+    lib.rbpf_loc_pair_stats_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_pair_stats_step.argtypes = [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p,
+                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_generic_pair_stats_begin.argtypes = [C.c_void_p, C.c_int32, c_int32_p, C.c_uint32, C.c_int32]
+    lib.rbpf_loc_generic_pair_stats_particles_device.argtypes = [C.c_void_p, c_int32_p, C.POINTER(C.c_void_p)]
+    lib.rbpf_loc_generic_pair_stats_step_device.argtypes = [C.c_void_p, C.c_void_p, c_double_p]
+    lib.rbpf_loc_generic_pair_stats_finish.argtypes = [C.c_void_p] + [c_double_p] * 8
+    lib.rbpf_loc_generic_pair_stats_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_generic_pair_stats_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, C.c_int32, c_double_p,
+                                                     c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                     c_double_p, C.c_int32, c_double_p]
     lib.rbpf_loc_landmark_create.argtypes = lib.rbpf_loc_generic_create.argtypes
     lib.rbpf_loc_landmark_map_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p]
     lib.rbpf_loc_landmark_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]

@@ -37,6 +37,10 @@
 // THE MARGINAL SMOOTHING WEIGHTS (rbpf_loc_generic_marginal_*): the recursion of rbpf_loc_marginal.hpp on the same prologues, terms,
 // layout and factorisation, driven backwards in time (begin / particles_device / step_device for t = N_T-2 .. 0 / finish).
 //
+// THE TWO-SLICE STATISTICS (rbpf_loc_generic_pair_stats_*): the marginal pass, and behind every step's normalisation the pass of
+// rbpf_loc_pairstats.hpp on the same Xhat, c and mass; GsTerm::pair_res hands out the un-whitened residual in kernel order, and the
+// host puts S and m back into the caller's order (LocGenLayout::perm) when it copies out.
+//
 // REJECTION SAMPLING (rbpf_loc_generic_backward_reject_begin): the pass that rbpf_loc_reject.hpp puts in front of the all-pairs pass
 // at steps N_T-2 .. 0, on the same prologues and terms, driven by the same particles_device / step_device / finish.
 #include "../../include/rbpf.h"
@@ -47,6 +51,7 @@
 #include "rbpf_loc_backward.hpp"
 #include "rbpf_loc_viterbi.hpp"
 #include "rbpf_loc_marginal.hpp"
+#include "rbpf_loc_pairstats.hpp"
 #include "rbpf_loc_reject.hpp"
 #include "rbpf_timed_reps.hpp"
 
@@ -85,8 +90,10 @@ __global__ void gs_prologue_kernel(int N, int NR, const double* __restrict__ mu,
 
 // l <- l - z'z / 2 of one pair; h: the particle's NR + 1 doubles (predicted rows, log w), x: the trajectory's selected rows.
 // false: after NR / 2 rows the pair already lies below `bound` (l is then not final).  Every product-sum is an explicit fma.
+// rout (may be null): where a pair that is not skipped leaves its un-whitened residual r, NR doubles (pair_res).
 template <int NR, bool ANG>
-__device__ __forceinline__ bool gs_term(const GsW& W, unsigned amask, const double* h, const double (&x)[NR], double bound, double& l) {
+__device__ __forceinline__ bool gs_term(const GsW& W, unsigned amask, const double* h, const double (&x)[NR], double bound, double& l,
+                                        double* rout = nullptr) {
   constexpr int KT = NR / 2;
   double r[NR];
 #pragma unroll
@@ -105,6 +112,10 @@ __device__ __forceinline__ bool gs_term(const GsW& W, unsigned amask, const doub
     if (k + 1 == KT && fma(-0.5, q, l) < bound) return false;
   }
   l = fma(-0.5, q, l);
+  if (rout) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) rout[k] = r[k];
+  }
   return true;
 }
 
@@ -124,8 +135,10 @@ __global__ void gs_prologue_pose_kernel(int N, int NS, GsSrc src, const double* 
 // x = the trajectory's NP plain rows and its quaternion; NR = NP + 3 residuals.  false: the plain rows alone put the pair below
 // `bound` (NP >= 1 only).  Every product-sum is an explicit fma; e = qLeft(qInv(mu_q)) x_q (tools/qLeft.m:30-35, qInv.m:27-31)
 // is summed left to right, as bs_rot_term writes it.
+// rout (may be null): where a pair that is not skipped leaves its un-whitened residual in kernel order, the block's phi last.
 template <int NP, bool ANG>
-__device__ __forceinline__ bool gs_pose_term(const GsW& W, unsigned amask, const double* h, const double (&x)[NP + 4], double bound, double& l) {
+__device__ __forceinline__ bool gs_pose_term(const GsW& W, unsigned amask, const double* h, const double (&x)[NP + 4], double bound, double& l,
+                                             double* rout = nullptr) {
   constexpr int NR = NP + 3;
   double r[NR];
 #pragma unroll
@@ -161,14 +174,19 @@ __device__ __forceinline__ bool gs_pose_term(const GsW& W, unsigned amask, const
     q = fma(z, z, q);
   }
   l = fma(-0.5, q, l);
+  if (rout) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) rout[k] = r[k];
+  }
   return true;
 }
 
 // QP < 0: NR selected rows and gs_term; QP = NP >= 0: a quaternion block behind NP plain rows (NR = NP + 3, NR + 1 selected rows)
 // kLocateBound: the locate kernel is launched with 64 threads; stating that for the block's instantiations lifts the 128-VGPR cap
 // of the default bound (1024), under which NP = 4 spilled 12 bytes; without a block the default stays.
-template <int NR, bool ANG, int QP = -1>
+template <int NRES, bool ANG, int QP = -1>
 struct GsTerm : GsData {
+  static constexpr int NR = NRES;             // residuals
   static constexpr int NS = QP < 0 ? NR : NR + 1;
   static constexpr int kLocateBound = QP < 0 ? 1024 : 64;
   __device__ __forceinline__ double load_x(const GsHead& y, const double* xs_next, int j, int k) const { return xs_next[(size_t)j * y.nN + y.rows[k]]; }
@@ -177,6 +195,11 @@ struct GsTerm : GsData {
   __device__ __forceinline__ bool pair(const GsHead& y, const double* h, const double (&x)[NS], double bound, double& l) const {
     if constexpr (QP < 0) return gs_term<NR, ANG>(W, y.angle_mask, h, x, bound, l);
     else return gs_pose_term<QP, ANG>(W, y.angle_mask, h, x, bound, l);
+  }
+  // pair, and the un-whitened residual in kernel order (rbpf_loc_pairstats.hpp)
+  __device__ __forceinline__ bool pair_res(const GsHead& y, const double* h, const double (&x)[NS], double bound, double& l, double (&r)[NR]) const {
+    if constexpr (QP < 0) return gs_term<NR, ANG>(W, y.angle_mask, h, x, bound, l, r);
+    else return gs_pose_term<QP, ANG>(W, y.angle_mask, h, x, bound, l, r);
   }
   __device__ __forceinline__ void gather(const GsHead& y, const double* X, int N, int idx, double* xs, int j) const {
     for (int r = 0; r < y.nN; ++r) xs[(size_t)j * y.nN + r] = X[(size_t)r * N + idx];
@@ -280,6 +303,24 @@ static hipError_t gs_launch_marginal_step(const LocGenLayout& y, const GmArgs& a
   }
   return gs_pick(y, a.head.angle_mask, [&](auto tag) {
     return marginal_launch_step(a.with(typename decltype(tag)::Term{a.term}), logws_next, D, cj, lws, s);
+  });
+}
+
+typedef PairStatsArgs<GsData> GpArgs;
+
+// the statistics pass's arguments on what a marginal step's hold (rbpf_loc_pairstats.hpp)
+static GpArgs gs_pair_stats_args(const GmArgs& a, const double* mass, double* part) {
+  GpArgs b;
+  std::memset(&b, 0, sizeof(b));
+  pair_stats_set_sizes(b, a.N, a.M);
+  b.head = a.head; b.Xhat = a.Xhat; b.xn_next = a.xn_next; b.cj = a.cj; b.mass = mass; b.part = part; b.term = a.term;
+  return b;
+}
+
+// statistics pass + reduce of one step, after the marginal step's normalisation
+static hipError_t gs_launch_pair_stats(const LocGenLayout& y, const GpArgs& a, double* page, hipStream_t s) {
+  return gs_pick(y, a.head.angle_mask, [&](auto tag) {
+    return pair_stats_launch_step(a.with(typename decltype(tag)::Term{a.term}), page, s);
   });
 }
 
@@ -435,6 +476,7 @@ static int gs_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed,
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "backward simulation", who));
   const int N = c->N, T = c->T, M = n_traj, nN = L->nN;
   LocGenBackward& g = L->gb;
@@ -685,6 +727,7 @@ int rbpf_loc_generic_map_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, 
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "the MAP trajectory", "rbpf_loc_generic_map_begin"));
   const int N = c->N, T = c->T;
   LocGenBackward& g = L->gv;
@@ -804,19 +847,42 @@ int rbpf_loc_generic_marginal_workspace_bytes(int32_t n_nonlin, int32_t n_sel, i
   return RBPF_OK;
 }
 
-int rbpf_loc_generic_marginal_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos) {
+// The marginal pass (rbpf_loc_generic_marginal_*) and the statistics pass (rbpf_loc_generic_pair_stats_*: the same steps, and after
+// every step's normalisation the pass of rbpf_loc_pairstats.hpp) share their entry points' bodies; a kind says which slot of LocState
+// holds the open pass and how the family names itself.
+struct GmKind {
+  LocGenBackward LocState::*slot;
+  bool stats;
+  const char* noun;                // "a <noun> pass is open"
+  const char* fam;                 // the entry points' common prefix
+  const char* reader;              // how backward_check_forward names the reader
+};
+static const GmKind kGmMarginal = {&LocState::gm, false, "marginal", "rbpf_loc_generic_marginal", "marginal smoothing"};
+static const GmKind kGmStats = {&LocState::gp, true, "statistics", "rbpf_loc_generic_pair_stats", "the transition statistics"};
+
+static int gm_not_open(const GmKind& k) {
+  set_error(std::string("no ") + k.noun + " pass is open (" + k.fam + "_begin first)");
+  return RBPF_ERR_STATE;
+}
+static int gm_all_done(const GmKind& k) {
+  set_error(std::string("every step of the ") + k.noun + " pass is done (" + k.fam + "_finish)");
+  return RBPF_ERR_STATE;
+}
+
+static int gm_begin(const GmKind& k, rbpf_ctx* c, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos) {
   RB_TRY(gs_ctx_ok(c));
   LocState* L = c->loc;
   LocGenLayout lay;
   RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
-  RB_TRY(backward_check_forward(c, "marginal smoothing", "rbpf_loc_generic_marginal_begin"));
+  RB_TRY(backward_check_forward(c, k.reader, (std::string(k.fam) + "_begin").c_str()));
   const int N = c->N, T = c->T;
-  LocGenBackward& g = L->gm;
+  LocGenBackward& g = L->*k.slot;
   g.M = N; g.lay = lay;                                                  // (the chunking of both passes: marginal_set_sizes, per step)
-  int s = marginal_take(g.ws, c->pool, L->nN, lay.n_sel, N, T);
+  int s = k.stats ? pair_stats_take(g.ws, c->pool, L->nN, lay.n_sel, lay.n_res, N, T) : marginal_take(g.ws, c->pool, L->nN, lay.n_sel, N, T);
   if (s == RBPF_OK) {
     const hipError_t e = marginal_launch_last(g.ws, L->nN, N, T, c->X, c->w, c->stream);
     if (e != hipSuccess) s = hip_fail(e, "the last step of the marginal pass", __FILE__, __LINE__);
@@ -827,23 +893,23 @@ int rbpf_loc_generic_marginal_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* r
   return RBPF_OK;
 }
 
-int rbpf_loc_generic_marginal_particles_device(rbpf_ctx* c, int32_t* t, const double** xn_dev) {
+static int gm_particles_device(const GmKind& k, rbpf_ctx* c, int32_t* t, const double** xn_dev) {
   RB_TRY(gs_ctx_ok(c));
   if (!t || !xn_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
-  const LocGenBackward& g = c->loc->gm;
-  if (!g.open) { set_error("no marginal pass is open (rbpf_loc_generic_marginal_begin first)"); return RBPF_ERR_STATE; }
-  if (g.t < 0) { set_error("every step of the marginal pass is done (rbpf_loc_generic_marginal_finish)"); return RBPF_ERR_STATE; }
+  const LocGenBackward& g = c->loc->*k.slot;
+  if (!g.open) return gm_not_open(k);
+  if (g.t < 0) return gm_all_done(k);
   *t = g.t;
   *xn_dev = c->X + (size_t)g.t * c->loc->nN * c->N;
   return RBPF_OK;
 }
 
-int rbpf_loc_generic_marginal_step_device(rbpf_ctx* c, const double* mu_dev, const double* cov) {
+static int gm_step_device(const GmKind& k, rbpf_ctx* c, const double* mu_dev, const double* cov) {
   RB_TRY(gs_ctx_ok(c));
   LocState* L = c->loc;
-  LocGenBackward& g = L->gm;
-  if (!g.open) { set_error("no marginal pass is open (rbpf_loc_generic_marginal_begin first)"); return RBPF_ERR_STATE; }
-  if (g.t < 0) { set_error("every step of the marginal pass is done (rbpf_loc_generic_marginal_finish)"); return RBPF_ERR_STATE; }
+  LocGenBackward& g = L->*k.slot;
+  if (!g.open) return gm_not_open(k);
+  if (g.t < 0) return gm_all_done(k);
   if (!mu_dev || !cov) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   const int N = c->N, T = c->T, nN = L->nN, t = g.t;
   GmArgs a;
@@ -852,39 +918,47 @@ int rbpf_loc_generic_marginal_step_device(rbpf_ctx* c, const double* mu_dev, con
   HIPCHK(hipSetDevice(c->device));
   marginal_set_sizes(a, N, N);
   a.head.nN = nN; a.head.angle_mask = g.lay.angle_mask;
-  for (int k = 0; k < g.lay.n_sel; ++k) a.head.rows[k] = g.lay.rows[k];
+  for (int q = 0; q < g.lay.n_sel; ++q) a.head.rows[q] = g.lay.rows[q];
   a.Xhat = g.ws.Xhat; a.xn_next = c->X + (size_t)(t + 1) * nN * N; a.cj = g.ws.u + (size_t)2 * N; a.part_m = g.ws.pm; a.part_s = g.ws.ps;
   HIPCHK(gs_launch_marginal_step(g.lay, a, mu_dev, c->w + (size_t)t * N, nullptr, g.ws.Xhat, g.ws.u + (size_t)((t + 1) & 1) * N, nullptr,
                                  g.ws.u + (size_t)2 * N, g.ws.u + (size_t)(t & 1) * N, c->stream));
   HIPCHK(marginal_launch_close_step(g.ws, nN, N, T, t, c->X, c->stream));
+  if (k.stats)
+    HIPCHK(gs_launch_pair_stats(g.lay, gs_pair_stats_args(a, marginal_out(g.ws, nN, T).mass + t, g.ws.pstat),
+                                g.ws.stat + (size_t)t * pair_stats_page(g.lay.n_res), c->stream));
   g.t = t - 1;
   return RBPF_OK;
 }
 
-int rbpf_loc_generic_marginal_finish(rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass) {
+static int gm_finish(const GmKind& k, rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass, double* S, double* m,
+                     double* pair_mass) {
   RB_TRY(gs_ctx_ok(c));
   LocState* L = c->loc;
-  LocGenBackward& g = L->gm;
-  if (!g.open) { set_error("no marginal pass is open (rbpf_loc_generic_marginal_begin first)"); return RBPF_ERR_STATE; }
+  LocGenBackward& g = L->*k.slot;
+  if (!g.open) return gm_not_open(k);
   const int N = c->N, T = c->T, nN = L->nN, t_next = g.t;
+  const LocGenLayout lay = g.lay;
   BackwardWorkspace ws = g.ws;
   g = LocGenBackward();                                                  // the pass is closed whichever way this returns,
   BackwardWorkspaceGuard lease(ws);                                      // and its workspace goes back
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (t_next >= 0) {
-    if (!w_smooth && !mean && !cov && !ess && !mass) return RBPF_OK;     // the way out of a pass that was given up
-    set_error("rbpf_loc_generic_marginal_finish: steps " + std::to_string(t_next) + " .. 0 of the marginal pass were not run");
+    if (!w_smooth && !mean && !cov && !ess && !mass && !S && !m && !pair_mass) return RBPF_OK;     // the way out of a pass that was given up
+    set_error(std::string(k.fam) + "_finish: steps " + std::to_string(t_next) + " .. 0 of the " + k.noun + " pass were not run");
     return RBPF_ERR_STATE;
   }
   RB_TRY(ctx_check_flags(c));
-  return marginal_copy_out(ws, nN, N, T, w_smooth, mean, cov, ess, mass);
+  RB_TRY(marginal_copy_out(ws, nN, N, T, w_smooth, mean, cov, ess, mass));
+  return k.stats ? pair_stats_copy_out(ws, lay.n_res, T, lay.perm, S, m, pair_mass) : RBPF_OK;
 }
 
-int rbpf_loc_generic_marginal_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
-                                   int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
-                                   const double* cov, double* D, double* lws, int32_t reps, double* ms) {
+// rbpf_loc_generic_marginal_step (S, m, pair_mass null) and rbpf_loc_generic_pair_stats_step
+static int gm_probe(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos,
+                    const double* mu, const double* logw, const double* xs_next, const double* logws_next, const double* cov, double* D,
+                    double* lws, bool stats, double* S, double* m, double* pair_mass, int32_t reps, double* ms) {
   if (!mu || !logw || !xs_next || !logws_next || !cov || !D || !lws || !rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (stats && (!S || !m || !pair_mass)) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
   if (N > kMaxParticles || M > kMaxParticles) { set_error("N or M above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
   LocGenLayout lay;
@@ -900,7 +974,7 @@ int rbpf_loc_generic_marginal_step(int32_t N, int32_t M, int32_t n_nonlin, int32
   const size_t np = marginal_part_count((size_t)N, (size_t)M);
   DevicePool tmp;
   double *d_mu = nullptr, *d_lw = nullptr, *d_xs = nullptr, *d_lwn = nullptr, *d_Xhat = nullptr, *d_pm = nullptr, *d_ps = nullptr, *d_D = nullptr,
-         *d_c = nullptr, *d_lws = nullptr;
+         *d_c = nullptr, *d_lws = nullptr, *d_nrm = nullptr, *d_part = nullptr, *d_page = nullptr;
   RB_TRY(tmp.upload(&d_mu, mu, (size_t)lay.n_sel * N));
   RB_TRY(tmp.upload(&d_lw, logw, (size_t)N));
   RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)n_nonlin * M));
@@ -911,14 +985,78 @@ int rbpf_loc_generic_marginal_step(int32_t N, int32_t M, int32_t n_nonlin, int32
   RB_TRY(tmp.alloc(&d_D, (size_t)M));
   RB_TRY(tmp.alloc(&d_c, (size_t)M));
   RB_TRY(tmp.alloc(&d_lws, (size_t)N));
+  if (stats) {
+    RB_TRY(tmp.alloc(&d_nrm, (size_t)2 * N + 1));                        // the normalised copy of lws, its weights, the mass
+    RB_TRY(tmp.alloc(&d_part, (size_t)pair_stats_count(lay.n_res) * pair_stats_groups((size_t)N, (size_t)M)));
+    RB_TRY(tmp.alloc(&d_page, (size_t)pair_stats_page(lay.n_res)));
+  }
   a.head.nN = n_nonlin; a.head.first = 0; a.head.angle_mask = lay.angle_mask;
   for (int k = 0; k < lay.n_sel; ++k) a.head.rows[k] = lay.rows[k];
   a.Xhat = d_Xhat; a.xn_next = d_xs; a.cj = d_c; a.part_m = d_pm; a.part_s = d_ps;
   // (the prologue's last row is overwritten with the caller's log w: what it reads as w does not matter)
-  RB_TRY(timed_reps(reps, 0, [&] { return gs_launch_marginal_step(lay, a, d_mu, d_lw, d_lw, d_Xhat, d_lwn, d_D, d_c, d_lws, 0); }, ms));
+  RB_TRY(timed_reps(reps, 0, [&] {
+    hipError_t e = gs_launch_marginal_step(lay, a, d_mu, d_lw, d_lw, d_Xhat, d_lwn, d_D, d_c, d_lws, 0);
+    if (e != hipSuccess || !stats) return e;
+    e = hipMemcpyAsync(d_nrm, d_lws, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0);
+    if (e != hipSuccess) return e;
+    e = marginal_launch_normalise(N, d_nrm, d_nrm + N, d_nrm + (size_t)2 * N, 0);
+    if (e != hipSuccess) return e;
+    return gs_launch_pair_stats(lay, gs_pair_stats_args(a, d_nrm + (size_t)2 * N, d_part), d_page, 0);
+  }, ms));
   HIPCHK(hipMemcpy(D, d_D, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(lws, d_lws, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  if (stats) {
+    BackwardWorkspace view;
+    view.stat = d_page;
+    RB_TRY(pair_stats_copy_out(view, lay.n_res, 2, lay.perm, S, m, pair_mass));
+  }
   return RBPF_OK;
+}
+
+int rbpf_loc_generic_marginal_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos) {
+  return gm_begin(kGmMarginal, c, n_sel, rows, angle_mask, quat_pos);
+}
+
+int rbpf_loc_generic_marginal_particles_device(rbpf_ctx* c, int32_t* t, const double** xn_dev) { return gm_particles_device(kGmMarginal, c, t, xn_dev); }
+
+int rbpf_loc_generic_marginal_step_device(rbpf_ctx* c, const double* mu_dev, const double* cov) { return gm_step_device(kGmMarginal, c, mu_dev, cov); }
+
+int rbpf_loc_generic_marginal_finish(rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass) {
+  return gm_finish(kGmMarginal, c, w_smooth, mean, cov, ess, mass, nullptr, nullptr, nullptr);
+}
+
+int rbpf_loc_generic_marginal_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                   int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
+                                   const double* cov, double* D, double* lws, int32_t reps, double* ms) {
+  return gm_probe(N, M, n_nonlin, n_sel, rows, angle_mask, quat_pos, mu, logw, xs_next, logws_next, cov, D, lws, false, nullptr, nullptr, nullptr,
+                  reps, ms);
+}
+
+// ---- the two-slice statistics of the transition residual ---------------------------------------------------------------------
+int rbpf_loc_generic_pair_stats_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, size_t* bytes) {
+  RB_TRY(rbpf_loc_generic_marginal_workspace_bytes(n_nonlin, n_sel, quat_pos, N_P, N_T, bytes));   // its argument checks
+  *bytes = pair_stats_bytes((size_t)n_nonlin, (size_t)n_sel, (size_t)(quat_pos == -1 ? n_sel : n_sel - 1), (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_pair_stats_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos) {
+  return gm_begin(kGmStats, c, n_sel, rows, angle_mask, quat_pos);
+}
+
+int rbpf_loc_generic_pair_stats_particles_device(rbpf_ctx* c, int32_t* t, const double** xn_dev) { return gm_particles_device(kGmStats, c, t, xn_dev); }
+
+int rbpf_loc_generic_pair_stats_step_device(rbpf_ctx* c, const double* mu_dev, const double* cov) { return gm_step_device(kGmStats, c, mu_dev, cov); }
+
+int rbpf_loc_generic_pair_stats_finish(rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass, double* S, double* m,
+                                       double* pair_mass) {
+  return gm_finish(kGmStats, c, w_smooth, mean, cov, ess, mass, S, m, pair_mass);
+}
+
+int rbpf_loc_generic_pair_stats_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                     int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
+                                     const double* cov, double* D, double* lws, double* S, double* m, double* pair_mass, int32_t reps,
+                                     double* ms) {
+  return gm_probe(N, M, n_nonlin, n_sel, rows, angle_mask, quat_pos, mu, logw, xs_next, logws_next, cov, D, lws, true, S, m, pair_mass, reps, ms);
 }
 
 }  // extern "C"

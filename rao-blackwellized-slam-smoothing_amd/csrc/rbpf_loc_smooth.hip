@@ -14,8 +14,9 @@
 //   BsTerm               logp of one pair: the position term, then the orientation term.  A pair whose log w + position term alone
 //                        lies more than 746 below the running max skips its orientation term: its exp is exactly 0.
 // The MAP trajectory (rbpf_loc_map_trajectory, the recursion and kernels of rbpf_loc_viterbi.hpp) runs on the same prologue and term,
-// and so do the marginal smoothing weights (rbpf_loc_marginal_smooth, rbpf_loc_marginal.hpp) and backward simulation by rejection
-// sampling (rbpf_loc_backward_simulate_reject, rbpf_loc_reject.hpp).
+// and so do the marginal smoothing weights (rbpf_loc_marginal_smooth, rbpf_loc_marginal.hpp), backward simulation by rejection
+// sampling (rbpf_loc_backward_simulate_reject, rbpf_loc_reject.hpp) and the two-slice statistics of the transition residual
+// (rbpf_loc_pair_stats_smooth, rbpf_loc_pairstats.hpp: BsTerm::pair_res hands out r = [p~ - (p_i + dx); phi]).
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
@@ -24,6 +25,7 @@
 #include "rbpf_loc_backward.hpp"
 #include "rbpf_loc_viterbi.hpp"
 #include "rbpf_loc_marginal.hpp"
+#include "rbpf_loc_pairstats.hpp"
 #include "rbpf_loc_reject.hpp"
 #include "rbpf_timed_reps.hpp"
 
@@ -56,16 +58,19 @@ __global__ void bs_prologue_kernel(int N, const double* __restrict__ xn, size_t 
   Xhat[(size_t)7 * N + i] = wi > 0.0 ? log(wi) : -INFINITY;
 }
 
-// -z_pos'z_pos / 2 of one pair; h: the particle's 8 doubles (predicted position, a, log w), x: the trajectory's state
-__device__ __forceinline__ double bs_pos_term(const BsNoise& nz, const double* h, const double x[7]) {
+// -z_pos'z_pos / 2 of one pair; h: the particle's 8 doubles (predicted position, a, log w), x: the trajectory's state; r (may be
+// null): the un-whitened residual p~ - (p_i + dx), 3 doubles
+__device__ __forceinline__ double bs_pos_term(const BsNoise& nz, const double* h, const double x[7], double* r = nullptr) {
   const double r0 = x[0] - h[0], r1 = x[1] - h[1], r2 = x[2] - h[2];
+  if (r) { r[0] = r0; r[1] = r1; r[2] = r2; }
   const double z0 = nz.ip[0] * r0 + nz.ip[1] * r1 + nz.ip[2] * r2;
   const double z1 = nz.ip[3] * r0 + nz.ip[4] * r1 + nz.ip[5] * r2;
   const double z2 = nz.ip[6] * r0 + nz.ip[7] * r1 + nz.ip[8] * r2;
   return -0.5 * (z0 * z0 + z1 * z1 + z2 * z2);
 }
 
-__device__ __forceinline__ double bs_rot_term(const BsNoise& nz, const double* h, const double x[7]) {
+// r (may be null): the un-whitened residual phi, 3 doubles
+__device__ __forceinline__ double bs_rot_term(const BsNoise& nz, const double* h, const double x[7], double* r = nullptr) {
   // e = qLeft(qInv(a)) q~ (tools/qLeft.m:30-35, qInv.m:27-31)
   const double a0 = h[3], a1 = -h[4], a2 = -h[5], a3 = -h[6];
   double e0 = a0 * x[3] + (-a1) * x[4] + (-a2) * x[5] + (-a3) * x[6];
@@ -76,6 +81,7 @@ __device__ __forceinline__ double bs_rot_term(const BsNoise& nz, const double* h
   const double nv = sqrt(e1 * e1 + e2 * e2 + e3 * e3);
   const double f = (nv == 0.0) ? 1.0 : atan2(nv, e0) / nv;
   const double p0 = f * e1, p1 = f * e2, p2 = f * e3;
+  if (r) { r[0] = p0; r[1] = p1; r[2] = p2; }
   const double z0 = nz.ir[0] * p0 + nz.ir[1] * p1 + nz.ir[2] * p2;
   const double z1 = nz.ir[3] * p0 + nz.ir[4] * p1 + nz.ir[5] * p2;
   const double z2 = nz.ir[6] * p0 + nz.ir[7] * p1 + nz.ir[8] * p2;
@@ -86,6 +92,7 @@ __device__ __forceinline__ double bs_rot_term(const BsNoise& nz, const double* h
 struct BsTerm {
   struct Head { int first; };                 // no integers of its own: all 7 rows, always
   static constexpr int NS = 7;
+  static constexpr int NR = 6;                // residuals: [p~ - (p_i + dx); phi]
   static constexpr int kLocateBound = 1024;   // the default
   BsNoise nz;
   __device__ __forceinline__ double load_x(Head, const double* xs_next, int j, int k) const { return xs_next[(size_t)j * 7 + k]; }
@@ -93,6 +100,13 @@ struct BsTerm {
   static constexpr bool kSplit = true;        // the skip test sits between the two terms
   __device__ __forceinline__ double pair_near(Head, const double* h, const double (&x)[7]) const { return bs_pos_term(nz, h, x); }
   __device__ __forceinline__ double pair_far(Head, const double* h, const double (&x)[7]) const { return bs_rot_term(nz, h, x); }
+  // pair_near, the test, pair_far; r: the un-whitened residual (rbpf_loc_pairstats.hpp)
+  __device__ __forceinline__ bool pair_res(Head, const double* h, const double (&x)[7], double bound, double& l, double (&r)[6]) const {
+    l += bs_pos_term(nz, h, x, r);
+    if (l < bound) return false;
+    l += bs_rot_term(nz, h, x, r + 3);
+    return true;
+  }
   __device__ __forceinline__ void gather(Head, const double* X, int N, int idx, double* xs, int j) const {
 #pragma unroll
     for (int r = 0; r < 7; ++r) xs[(size_t)j * 7 + r] = X[(size_t)r * N + idx];
@@ -459,24 +473,27 @@ int rbpf_loc_marginal_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes) {
   return RBPF_OK;
 }
 
-int rbpf_loc_marginal_smooth(rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass) {
+// rbpf_loc_marginal_smooth (stats = false) and rbpf_loc_pair_stats_smooth (stats = true: after every step's normalisation the
+// statistics pass of rbpf_loc_pairstats.hpp on the same Xhat, c and mass); `who` and `what` are how the entry point names itself
+static int bs_marginal(rbpf_ctx* c, bool stats, double* w_smooth, double* mean, double* cov, double* ess, double* mass, double* S, double* m,
+                       double* pair_mass, const char* who, const char* what) {
   if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
   if (c->loc->generic) {
-    set_error("marginal smoothing needs the transition density of dynModel: a generic map's dynModel is a sampler (its handles carry no density)");
+    set_error(std::string(what) + " the transition density of dynModel: a generic map's dynModel is a sampler (its handles carry no density)");
     return RBPF_ERR_UNSUPPORTED;
   }
-  RB_TRY(backward_check_forward(c, "rbpf_loc_marginal_smooth", "rbpf_loc_marginal_smooth"));
+  RB_TRY(backward_check_forward(c, who, who));
   LocState* L = c->loc;
   const int N = c->N, T = c->T;
   std::vector<BsNoise> nz((size_t)L->s_pages);
   {
-    std::vector<double> S((size_t)L->s_pages * 36);
-    HIPCHK(hipMemcpy(S.data(), L->d_S, S.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int p = 0; p < (T > 1 ? L->s_pages : 0); ++p) RB_TRY(bs_noise(S.data() + (size_t)p * 36, nz[p]));
+    std::vector<double> Sq((size_t)L->s_pages * 36);
+    HIPCHK(hipMemcpy(Sq.data(), L->d_S, Sq.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < (T > 1 ? L->s_pages : 0); ++p) RB_TRY(bs_noise(Sq.data() + (size_t)p * 36, nz[p]));
   }
   BackwardWorkspace ws;
   BackwardWorkspaceGuard lease(ws);
-  RB_TRY(marginal_take(ws, c->pool, 7, 7, N, T));
+  RB_TRY(stats ? pair_stats_take(ws, c->pool, 7, 7, BsTerm::NR, N, T) : marginal_take(ws, c->pool, 7, 7, N, T));
   HIPCHK(marginal_launch_last(ws, 7, N, T, c->X, c->w, c->stream));
   for (int t = T - 2; t >= 0; --t) {
     MarginalArgs<BsTerm> a;
@@ -487,29 +504,56 @@ int rbpf_loc_marginal_smooth(rbpf_ctx* c, double* w_smooth, double* mean, double
     HIPCHK(bs_launch_marginal_step(a, c->X + (size_t)t * 7 * N, (size_t)N, 1, c->w + (size_t)t * N, c->d_odo + (size_t)t * 7, ws.Xhat,
                                    ws.u + (size_t)((t + 1) & 1) * N, nullptr, ws.u + (size_t)2 * N, ws.u + (size_t)(t & 1) * N, c->stream));
     HIPCHK(marginal_launch_close_step(ws, 7, N, T, t, c->X, c->stream));
+    if (stats) {
+      PairStatsArgs<BsTerm> b;
+      pair_stats_set_sizes(b, N, N);
+      b.head = a.head; b.Xhat = a.Xhat; b.xn_next = a.xn_next; b.cj = a.cj; b.mass = marginal_out(ws, 7, T).mass + t; b.part = ws.pstat;
+      b.term = a.term;
+      HIPCHK(pair_stats_launch_step(b, ws.stat + (size_t)t * pair_stats_page(BsTerm::NR), c->stream));
+    }
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   RB_TRY(ctx_check_flags(c));
-  return marginal_copy_out(ws, 7, N, T, w_smooth, mean, cov, ess, mass);
+  RB_TRY(marginal_copy_out(ws, 7, N, T, w_smooth, mean, cov, ess, mass));
+  return stats ? pair_stats_copy_out(ws, BsTerm::NR, T, nullptr, S, m, pair_mass) : RBPF_OK;
 }
 
-int rbpf_loc_marginal_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* logws_next,
-                           const double* odo, double dt, const double* Q, double* D, double* lws, int32_t reps, double* ms) {
+int rbpf_loc_marginal_smooth(rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass) {
+  return bs_marginal(c, false, w_smooth, mean, cov, ess, mass, nullptr, nullptr, nullptr, "rbpf_loc_marginal_smooth", "marginal smoothing needs");
+}
+
+int rbpf_loc_pair_stats_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes) {
+  RB_TRY(rbpf_loc_marginal_workspace_bytes(N_P, N_T, bytes));
+  *bytes = pair_stats_bytes(7, 7, BsTerm::NR, (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_pair_stats_smooth(rbpf_ctx* c, double* w_smooth, double* mean, double* cov, double* ess, double* mass, double* S, double* m,
+                               double* pair_mass) {
+  return bs_marginal(c, true, w_smooth, mean, cov, ess, mass, S, m, pair_mass, "rbpf_loc_pair_stats_smooth", "the transition statistics need");
+}
+
+// rbpf_loc_marginal_step (S, m and pair_mass null) and rbpf_loc_pair_stats_step: the marginal step, and behind it the normalisation
+// of a copy of lws (the probes return lws un-normalised) and the statistics pass
+static int bs_marginal_probe(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* logws_next,
+                             const double* odo, double dt, const double* Q, double* D, double* lws, bool stats, double* S, double* m,
+                             double* pair_mass, int32_t reps, double* ms) {
   if (!xn || !logw || !xs_next || !logws_next || !odo || !Q || !D || !lws) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (stats && (!S || !m || !pair_mass)) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
   if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
   if (N > kMaxParticles || M > kMaxParticles) { set_error("N or M above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
-  double S[36];
-  for (int q = 0; q < 36; ++q) S[q] = 0.0;
+  double Sq[36];
+  for (int q = 0; q < 36; ++q) Sq[q] = 0.0;
   for (int b = 0; b < 2; ++b)
     for (int cc = 0; cc < 3; ++cc)
       for (int r = 0; r < 3; ++r) {
         const int q = (3 * b + r) + 6 * (3 * b + cc);
         const double v = dt * Q[q];
         if (!(v >= 0.0)) { set_error("dt * Q has a negative entry in a diagonal block: the element-wise sqrt of dynModel would be complex"); return RBPF_ERR_INVALID_ARG; }
-        S[q] = std::sqrt(v);
+        Sq[q] = std::sqrt(v);
       }
   MarginalArgs<BsTerm> a;
-  RB_TRY(bs_noise(S, a.term.nz));
+  RB_TRY(bs_noise(Sq, a.term.nz));
   if (!have_device()) { set_error("no HIP device: the marginal pass has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
   marginal_set_sizes(a, N, M);
   std::vector<double> xt((size_t)7 * M);                                  // the successors as the history holds them: [7][M]
@@ -517,7 +561,7 @@ int rbpf_loc_marginal_step(int32_t N, int32_t M, const double* xn, const double*
     for (int r = 0; r < 7; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * 7 + r];
   DevicePool tmp;
   double *d_xn = nullptr, *d_lw = nullptr, *d_xs = nullptr, *d_lwn = nullptr, *d_odo = nullptr, *d_Xhat = nullptr, *d_pm = nullptr,
-         *d_ps = nullptr, *d_D = nullptr, *d_c = nullptr, *d_lws = nullptr;
+         *d_ps = nullptr, *d_D = nullptr, *d_c = nullptr, *d_lws = nullptr, *d_nrm = nullptr, *d_part = nullptr, *d_page = nullptr;
   const size_t np = marginal_part_count((size_t)N, (size_t)M);
   RB_TRY(tmp.upload(&d_xn, xn, (size_t)7 * N));
   RB_TRY(tmp.upload(&d_lw, logw, (size_t)N));
@@ -532,16 +576,46 @@ int rbpf_loc_marginal_step(int32_t N, int32_t M, const double* xn, const double*
   RB_TRY(tmp.alloc(&d_lws, (size_t)N));
   a.head.first = 0;
   a.Xhat = d_Xhat; a.xn_next = d_xs; a.cj = d_c; a.part_m = d_pm; a.part_s = d_ps;
+  PairStatsArgs<BsTerm> b;
+  if (stats) {
+    RB_TRY(tmp.alloc(&d_nrm, (size_t)2 * N + 1));                        // the normalised copy of lws, its weights, the mass
+    RB_TRY(tmp.alloc(&d_part, (size_t)pair_stats_count(BsTerm::NR) * pair_stats_groups((size_t)N, (size_t)M)));
+    RB_TRY(tmp.alloc(&d_page, (size_t)pair_stats_page(BsTerm::NR)));
+    pair_stats_set_sizes(b, N, M);
+    b.head = a.head; b.Xhat = d_Xhat; b.xn_next = d_xs; b.cj = d_c; b.mass = d_nrm + (size_t)2 * N; b.part = d_part; b.term = a.term;
+  }
   RB_TRY(timed_reps(reps, 0, [&] {
     hipLaunchKernelGGL(bs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, 0, N, d_xn, (size_t)1, (size_t)7, d_lw, d_odo, d_Xhat);
     // the caller's log w over the prologue's last row (what it read as w does not matter)
-    const hipError_t e = hipMemcpyAsync(d_Xhat + (size_t)7 * N, d_lw, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0);
+    hipError_t e = hipMemcpyAsync(d_Xhat + (size_t)7 * N, d_lw, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0);
     if (e != hipSuccess) return e;
-    return marginal_launch_step(a, d_lwn, d_D, d_c, d_lws, 0);
+    e = marginal_launch_step(a, d_lwn, d_D, d_c, d_lws, 0);
+    if (e != hipSuccess || !stats) return e;
+    e = hipMemcpyAsync(d_nrm, d_lws, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0);
+    if (e != hipSuccess) return e;
+    e = marginal_launch_normalise(N, d_nrm, d_nrm + N, d_nrm + (size_t)2 * N, 0);
+    if (e != hipSuccess) return e;
+    return pair_stats_launch_step(b, d_page, 0);
   }, ms));
   HIPCHK(hipMemcpy(D, d_D, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(lws, d_lws, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  if (stats) {
+    BackwardWorkspace view;
+    view.stat = d_page;
+    RB_TRY(pair_stats_copy_out(view, BsTerm::NR, 2, nullptr, S, m, pair_mass));
+  }
   return RBPF_OK;
+}
+
+int rbpf_loc_marginal_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* logws_next,
+                           const double* odo, double dt, const double* Q, double* D, double* lws, int32_t reps, double* ms) {
+  return bs_marginal_probe(N, M, xn, logw, xs_next, logws_next, odo, dt, Q, D, lws, false, nullptr, nullptr, nullptr, reps, ms);
+}
+
+int rbpf_loc_pair_stats_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* logws_next,
+                             const double* odo, double dt, const double* Q, double* D, double* lws, double* S, double* m, double* pair_mass,
+                             int32_t reps, double* ms) {
+  return bs_marginal_probe(N, M, xn, logw, xs_next, logws_next, odo, dt, Q, D, lws, true, S, m, pair_mass, reps, ms);
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@ struct BackwardWorkspace {
   double *xs = nullptr, *mean = nullptr;
   int* idx = nullptr;              // [T][M]: n_draws
   int* arg = nullptr;              // a MAP pass only (take_map)
+  double *pstat = nullptr, *stat = nullptr;   // a statistics pass only (take_pair_stats)
   // all or nothing: a failed allocation hands back what was taken before it
   int take(DevicePool& from, size_t n_Xhat, size_t n_part, size_t n_draws, size_t n_xs, size_t n_mean) {
     pool = &from;
@@ -72,9 +73,19 @@ struct BackwardWorkspace {
     if (s != RBPF_OK) release();
     return s;
   }
+  // the buffers of a two-slice statistics pass (rbpf_loc_pairstats.hpp): those of a marginal pass, pstat [n_pstat] the workgroups'
+  // vectors of the statistics pass and stat [n_stat] its pages (S, m and the pair mass of every pair of steps)
+  int take_pair_stats(DevicePool& from, size_t n_Xhat, size_t n_part, size_t n_lw, size_t n_w, size_t n_out, size_t n_pstat, size_t n_stat) {
+    int s = take_marginal(from, n_Xhat, n_part, n_lw, n_w, n_out);
+    if (s == RBPF_OK) s = from.alloc(&pstat, n_pstat);
+    if (s == RBPF_OK) s = from.alloc(&stat, n_stat);
+    if (s != RBPF_OK) release();
+    return s;
+  }
   void release() {
     if (pool)
-      for (void* p : {(void*)Xhat, (void*)pm, (void*)ps, (void*)u, (void*)xs, (void*)mean, (void*)idx, (void*)arg}) pool->release(p);
+      for (void* p : {(void*)Xhat, (void*)pm, (void*)ps, (void*)u, (void*)xs, (void*)mean, (void*)idx, (void*)arg, (void*)pstat, (void*)stat})
+        pool->release(p);
     *this = BackwardWorkspace();
   }
 };
@@ -169,6 +180,7 @@ struct LocState {
   std::vector<long long> reject_n_tries;
   LocGenBackward gv;               // the MAP trajectory with one (rbpf_loc_generic_map_begin .. _finish): t counts up, M = N_P; never open with gb
   LocGenBackward gm;               // marginal smoothing with one (rbpf_loc_generic_marginal_begin .. _finish): t counts down from N_T-2, M = N_P; never open with gb or gv
+  LocGenBackward gp;               // two-slice statistics with one (rbpf_loc_generic_pair_stats_begin .. _finish): as gm; never open with gb, gv or gm
   // landmark map (rbpf_loc_landmark_create): the handle's yhat is the prediction and the outputs observed at a step are selected
   bool landmark = false;
   int *d_ind = nullptr;            // [N_T][32]: the observed outputs of every step, ascending

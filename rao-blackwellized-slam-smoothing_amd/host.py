@@ -2120,6 +2120,34 @@ def device_map_marginal_workspace_bytes(n_nonlin, n_sel, N_P, N_T, quat_pos=-1):
     return int(nbytes.value)
 
 
+def device_map_pair_stats_step(mu, logw, xs_next, logws_next, cov, rows=None, angle_rows=(), quat_rows=None, reps=1):
+    """rbpf_loc_generic_pair_stats_step, the kernel-level probe: device_map_marginal_step, and behind it the two-slice statistics of
+    that step with its own mass -> (D [M], lws [N] un-normalised, S [n_res x n_res], m [n_res], pair_mass, median ms of the marginal
+    step, the normalisation and the statistics pass together).  S and m are in the order of cov."""
+    lib = load_library()
+    mu, xs_next, cov, rows_a, mask, qpos = _transition_probe_args(mu, xs_next, cov, rows, angle_rows, quat_rows)
+    (n_sel, N), (nN, M) = mu.shape, xs_next.shape
+    n = cov.shape[0]
+    logw = np.ascontiguousarray(np.asarray(logw, dtype=np.float64).ravel())
+    logws_next = np.ascontiguousarray(np.asarray(logws_next, dtype=np.float64).ravel())
+    if logw.size != N or logws_next.size != M:
+        raise ValueError("logw must be [N] and logws_next [M]")
+    D, lws, S, m, pm = np.empty(M), np.empty(N), np.empty((n, n), order="F"), np.empty(n), np.empty(1)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_generic_pair_stats_step(N, M, nN, n_sel, _ip(rows_a), mask, qpos, _dp(mu), _dp(logw), _dp(xs_next), _dp(logws_next),
+                                               _dp(cov), _dp(D), _dp(lws), _dp(S), _dp(m), _dp(pm), int(reps), C.byref(ms)))
+    return D, lws, S, m, float(pm[0]), ms.value
+
+
+def device_map_pair_stats_workspace_bytes(n_nonlin, n_sel, N_P, N_T, quat_pos=-1):
+    """rbpf_loc_generic_pair_stats_workspace_bytes (no device access): n_sel = len(rows), quat_pos the position of a quaternion block
+    in rows or -1."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_generic_pair_stats_workspace_bytes(int(n_nonlin), int(n_sel), int(quat_pos), int(N_P), int(N_T), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
 class DeviceMap:
     """A fixed map of an arbitrary model whose handles are device code: the posterior N(mean, V'V) over the nLin linear states, V
     lower (the DenseMagMap convention), as a SLAM filter or smoother run with the same DeviceHandles returns it (xl_max, P_max /
@@ -2770,8 +2798,8 @@ class LocalizationSession:
         self._stepped_pass_in_device_map("map", outs)
 
     def _stepped_pass_in_device_map(self, family, outs):
-        """A pass of rbpf_loc_generic_<family>_* (map: t = 0 .. N_T-2; marginal: t = N_T-2 .. 0) whose every step takes the `mean`
-        handle's mu and cov(dt, Q); the library names the step."""
+        """A pass of rbpf_loc_generic_<family>_* (map: t = 0 .. N_T-2; marginal and pair_stats: t = N_T-2 .. 0) whose every step takes
+        the `mean` handle's mu and cov(dt, Q); the library names the step."""
         lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
         torch, T, N, nN = drv.torch, prob.N_T, prob.N_P, self.nN
         begin, particles, step, finish = (getattr(lib, f"rbpf_loc_generic_{family}_{f}")
@@ -2823,6 +2851,34 @@ class LocalizationSession:
             self._stepped_pass_in_device_map("marginal", outs)
         else:
             check(self.lib.rbpf_loc_marginal_smooth(self.ctx, *outs))
+        return b
+
+    def transition_statistics(self, want=("S", "m", "pair_mass", "w_smooth", "mean")):
+        """rbpf_loc_pair_stats_smooth: the marginal smoother, and with its weights the two-slice (pairwise) smoothed moments of the
+        transition residual (keep_history and trace, every step done).  With xi_t(i, j) = w_t(i) p(X[t+1][:, j] | X[t][:, i])
+        w_{t+1|T}(j) / D_t(j), which sums to 1 over all pairs, and r_ij the UN-WHITENED residual of the transition density
+        ([p~ - (p_i + dx); phi] in a DenseMagMap; in a DeviceMap the wrapped differences and logq of the quaternion error, in the
+        order of the DeviceTransition's cov), returns a dict of what `want` names: S [n_res x n_res x (N_T-1)] = sum_ij xi r r',
+        m [n_res x (N_T-1)] = sum_ij xi r, pair_mass [N_T-1] = sum_ij xi (1 in exact arithmetic); page t belongs to the steps
+        (t, t+1).  The outputs of smoothed_marginals (w_smooth, mean, cov, ess, mass) may be named too and are bit for bit what it
+        returns.  xi is never stored.  transition_noise_estimate turns S (and m) into an estimate of Q.  In a DeviceMap without a
+        DeviceTransition the call is refused."""
+        if self.driver is not None and self.map.transition is None:
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, _NO_BACKWARD_IN_DEVICE_MAP)
+        names = ("w_smooth", "mean", "cov", "ess", "mass", "S", "m", "pair_mass")
+        unknown = set(want) - set(names)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        T, N, nN = self.prob.N_T, self.prob.N_P, self.nN
+        n_res = 6 if self.driver is None else self.map.transition.layout(nN)[3]
+        shapes = dict(w_smooth=(N, T), mean=(nN, T), cov=(nN, nN, T), ess=(T,), mass=(T,), S=(n_res, n_res, T - 1), m=(n_res, T - 1),
+                      pair_mass=(T - 1,))
+        b = {k: np.empty(shapes[k], order="F") for k in names if k in want}
+        outs = tuple(_dp(b[k]) if k in b else None for k in names)
+        if self.driver is not None:
+            self._stepped_pass_in_device_map("pair_stats", outs)
+        else:
+            check(self.lib.rbpf_loc_pair_stats_smooth(self.ctx, *outs))
         return b
 
     def close(self):
@@ -2938,6 +2994,90 @@ def particleMarginalSmootherLocalization(dynModel, measModel, odometry, y, x0_no
         fwd.update(cov=out["cov"], ess=out["ess"], mass=out["mass"])
         return out["mean"], out["w_smooth"], fwd
     return out["mean"], out["w_smooth"]
+
+
+def loc_pair_stats_workspace_bytes(N_P, N_T):
+    """rbpf_loc_pair_stats_workspace_bytes (no device access)."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_pair_stats_workspace_bytes(int(N_P), int(N_T), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def loc_pair_stats_step(xn, logw, xs_next, logws_next, odo, dt, Q, reps=1):
+    """rbpf_loc_pair_stats_step, the kernel-level probe: loc_marginal_step, and behind it the two-slice statistics of that step with
+    its own mass -> (D [M], lws [N] un-normalised, S [6 x 6], m [6], pair_mass, median ms of the marginal step, the normalisation and
+    the statistics pass together)."""
+    lib = load_library()
+    xn = np.asfortranarray(np.asarray(xn, dtype=np.float64).reshape(7, -1))
+    xs_next = np.asfortranarray(np.asarray(xs_next, dtype=np.float64).reshape(7, -1))
+    N, M = xn.shape[1], xs_next.shape[1]
+    logw = np.ascontiguousarray(np.asarray(logw, dtype=np.float64).ravel())
+    logws_next = np.ascontiguousarray(np.asarray(logws_next, dtype=np.float64).ravel())
+    odo = np.ascontiguousarray(np.asarray(odo, dtype=np.float64).ravel())
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(6, 6))
+    if logw.size != N or logws_next.size != M or odo.size != 7:
+        raise ValueError("logw must be [N], logws_next [M] and odo [7]")
+    D, lws, S, m, pm = np.empty(M), np.empty(N), np.empty((6, 6), order="F"), np.empty(6), np.empty(1)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_pair_stats_step(N, M, _dp(xn), _dp(logw), _dp(xs_next), _dp(logws_next), _dp(odo), float(dt), _dp(Q), _dp(D), _dp(lws),
+                                       _dp(S), _dp(m), _dp(pm), int(reps), C.byref(ms)))
+    return D, lws, S, m, float(pm[0]), ms.value
+
+
+def particleTransitionStatisticsLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, dt, *, rng=None, extras=False):
+    """The two-slice statistics of localisation in a fixed map: particleFilterLocalization, then LocalizationSession.transition_statistics
+    on its stored particles -> (S [n_res x n_res x (N_T-1)], m [n_res x (N_T-1)], pair_mass [N_T-1][, extras]).  dynModel / measModel, R
+    and rng as particleMarginalSmootherLocalization takes them.  extras: the filter's outputs and `w_smooth`, `mean`, `cov`, `ess`,
+    `mass` of the marginal smoother."""
+    import warnings
+    mp = _device_map(dynModel, measModel)
+    if mp is not None and mp.transition is None:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleTransitionStatisticsLocalization: " + _NO_BACKWARD_IN_DEVICE_MAP)
+    if mp is None:
+        mp = _recognise_map(dynModel, measModel)
+    with LocalizationSession(mp, odometry, y, x0_nonLin, Q, N_P, dt, rng=rng, keep_history=True, trace=True) as s:
+        s.advance(s.prob.N_T)
+        fwd = s.finish(extras=extras)
+        if fwd["first_degenerate_step"] >= 0:
+            warnings.warn(f"Weights filter close to zero at t={fwd['first_degenerate_step'] + 1} !!!", RuntimeWarning, stacklevel=2)
+        stats = ("S", "m", "pair_mass")
+        out = s.transition_statistics(want=stats + (("w_smooth", "mean", "cov", "ess", "mass") if extras else ()))
+    if extras:
+        fwd.update({k: v for k, v in out.items() if k not in stats})
+        return out["S"], out["m"], out["pair_mass"], fwd
+    return out["S"], out["m"], out["pair_mass"]
+
+
+def transition_noise_estimate(S, dt, m=None):
+    """The M-step of EM for a transition noise of the form cov(dt, Q) = dt Q, from the statistics of
+    LocalizationSession.transition_statistics, in plain numpy: S [n x n x P] (page t: the steps (t, t+1)), dt a scalar or [P] (or
+    longer: the first P entries are read, the way the passes read dt) ->
+        Q_hat = mean_t S_t / dt_t                                       (m None)
+        (Q_hat, bias) = (mean_t (S_t - m_t m_t') / dt_t, mean_t m_t)    (m [n x P]: the centred form, and the mean smoothed
+                                                                         residual: the odometry bias per step)
+    For a DeviceTransition whose cov(dt, Q) is dt Q on the residual rows this is the maximiser of the expected complete-data
+    likelihood under the smoothing weights of the current Q.  In a DenseMagMap it estimates the covariance per unit time of the
+    residual [p~ - (p + dx); phi], of which the two diagonal 3 x 3 blocks mean something: the map's dynModel draws its noise with
+    the ELEMENT-WISE sqrt(dt Q) of those two blocks of Q as factors S_pos and S_rot, so what it realises is S_pos S_pos' and
+    S_rot S_rot', equal to dt Q for diagonal blocks only -- compare the estimate's blocks with those products over dt.  The
+    off-diagonal block (position against orientation) is a diagnostic: the model has none."""
+    S = np.asarray(S, dtype=np.float64)
+    if S.ndim == 2:
+        S = S[:, :, None]
+    n, P = S.shape[0], S.shape[2]
+    if S.shape[1] != n or P < 1:
+        raise ValueError("S must be [n x n x P] with P >= 1")
+    dt = np.atleast_1d(np.asarray(dt, dtype=np.float64)).ravel()
+    dt = np.full(P, dt[0]) if dt.size == 1 else dt[:P]
+    if dt.size != P or not np.all(dt > 0.0):
+        raise ValueError("dt must be a positive scalar or hold one positive entry per page of S")
+    if m is None:
+        return np.mean(S / dt[None, None, :], axis=2)
+    m = np.asarray(m, dtype=np.float64).reshape(n, -1)
+    if m.shape[1] != P:
+        raise ValueError("m must be [n x P]")
+    return np.mean((S - m[:, None, :] * m[None, :, :]) / dt[None, None, :], axis=2), np.mean(m, axis=1)
 
 
 def loc_backward_workspace_bytes(N_P, N_T, n_traj):

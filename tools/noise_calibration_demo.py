@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""Calibrating the odometry noise of examples/mag-localization-mapping by EM on the device path, with synthetic data whose true Q is
+known (the recorded robot data set is not part of this repository): draw a field and a 'bean_6D' path with odometry noise Q, build
+the map by batch regression (DenseMagMap.from_data), then iterate from a Q that is a factor off:
+
+    filter with Q_k  ->  LocalizationSession.transition_statistics (the two-slice moments S_t, m_t of the transition residual)
+                     ->  Q_hat = transition_noise_estimate(S, dt)  ->  Q_{k+1} = diag(diag(Q_hat))
+
+(the map's dynModel reads the diagonal blocks of Q through an element-wise sqrt, and the true Q is diagonal: only the diagonal is fed
+back).  The filter starts from the true initial state; every iteration uses the same Philox seed.
+
+    python tools/noise_calibration_demo.py [factor=9] [iterations=5] [N_P=2048] [N_T=120] [m=1000] [seed=1]
+
+Prints one JSON line per iteration: diag(Q_k) / diag(Q_true) going in, diag(Q_hat) / diag(Q_true) coming out, the mean smoothed
+residual (the odometry bias) in units of the true standard deviation per step, the smallest effective sample size of the smoothed
+weights and the largest |pair_mass - 1|.  It is a demo: nothing is asserted on these numbers."""
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+rbpf = importlib.import_module("rao-blackwellized-slam-smoothing_amd")
+dg = importlib.import_module("rao-blackwellized-slam-smoothing_amd.datagen")
+
+Q_TRUE = np.diag(np.concatenate((10 ** 2 * np.array([0.05 ** 2, 0.05 ** 2, 0.01 ** 2]), (np.array([0.01, 0.01, 0.3]) * np.pi / 180) ** 2)))
+THETA = np.array([650.0, 1.2, 200.0, 10.0])
+
+
+def main():
+    a = sys.argv[1:]
+    factor = float(a[0]) if len(a) > 0 else 9.0
+    iters = int(a[1]) if len(a) > 1 else 5
+    N_P = int(a[2]) if len(a) > 2 else 2048
+    N_T = int(a[3]) if len(a) > 3 else 120
+    m = int(a[4]) if len(a) > 4 else 1000
+    seed = int(a[5]) if len(a) > 5 else 1
+    dt = 0.01
+    d = dg.bean_6D(N_T, Q_TRUE, THETA, dt, seed=seed, m_sim=2000)
+    model = rbpf.dense_mag_prior(m, d["LL"], THETA)[0]
+    y_nav = np.stack([dg._quat2rmat(d["quat"][t]) @ d["y"][t] for t in range(N_T)])
+    mp = rbpf.DenseMagMap.from_data(model, d["pos"].T, y_nav, THETA)
+    q_true = np.diag(Q_TRUE)
+    Q = factor * Q_TRUE
+    for k in range(iters):
+        rec = dict(iteration=k, factor=factor, N_P=N_P, N_T=N_T, Q_in_over_true=[float(v) for v in np.diag(Q) / q_true])
+        try:
+            with rbpf.LocalizationSession(mp, d["dx"], d["y"], d["initState"], Q, N_P, dt, rng=rbpf.PhiloxRNG(seed), keep_history=True,
+                                          trace=True) as s:
+                s.advance(N_T)
+                out = s.transition_statistics(want=("S", "m", "pair_mass", "ess"))
+        except rbpf.RBPFError as e:
+            rec["refused"] = str(e)
+            print(json.dumps(rec), flush=True)
+            break
+        Q_hat, bias = rbpf.transition_noise_estimate(out["S"], dt, out["m"])
+        Q_plain = rbpf.transition_noise_estimate(out["S"], dt)
+        rec.update(Q_hat_over_true=[float(v) for v in np.diag(Q_plain) / q_true],
+                   Q_hat_centred_over_true=[float(v) for v in np.diag(Q_hat) / q_true],
+                   bias_in_true_sd_per_step=[float(v) for v in bias / np.sqrt(dt * q_true)],
+                   largest_off_diagonal_correlation=float(np.max(np.abs(Q_plain / np.sqrt(np.outer(np.diag(Q_plain), np.diag(Q_plain))) - np.eye(6)))),
+                   min_ess=float(np.min(out["ess"])), worst_pair_mass_error=float(np.max(np.abs(out["pair_mass"] - 1.0))))
+        print(json.dumps(rec), flush=True)
+        Q = np.diag(np.diag(Q_plain))
+
+
+if __name__ == "__main__":
+    main()
