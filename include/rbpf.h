@@ -936,6 +936,45 @@ int rbpf_loc_pair_stats_step(int32_t N, int32_t M, const double* xn, const doubl
                              const double* odo, double dt, const double* Q, double* D, double* lws, double* S, double* m, double* pair_mass,
                              int32_t reps, double* ms);
 
+/* ---- running two-slice statistics of a localisation run: forward-only smoothing -----------------------
+ * The forward-only form of FFBSm for an additive functional (Del Moral, Doucet & Singh 2010): what rbpf_loc_pair_stats_smooth
+ * gives after the run, accumulated over the steps and available WHILE the run goes on, at one all-pairs step per new time step.
+ * Every particle carries tau(:, i, t), the conditional expectation of the functional accumulated so far:
+ *     D(j)          = log sum_i w(i, t) p(X(:, j, t+1) | X(:, i, t))
+ *     omega(i, j)   = w(i, t) p(X(:, j, t+1) | X(:, i, t)) / exp(D(j))                  (sums to 1 over i)
+ *     tau(j, t+1)   = sum_i omega(i, j) (tau(i, t) + s(i, j)),     tau(:, 1) = 0,     s = [r r' / dt(t); r]
+ *     S_run(:, :, k), m_run(:, k) = sum_j w(j, k+1) tau(j, k+1),     mass_run(k) = sum_j w(j, k+1) sum_i omega(i, j)     (= 1)
+ * r the un-whitened residual of rbpf_loc_pair_stats_smooth.  Page k (k = 1 .. T_done-1) is the FFBSm estimate of
+ * sum_{s<=k} E[r r'/dt(s) | y(1:k+1)] and sum_{s<=k} E[r | y(1:k+1)] from the steps 1 .. k+1 only; once every step is done the last
+ * page equals sum_t S(:, :, t) / dt(t) and sum_t m(:, t) of rbpf_loc_pair_stats_smooth (the same estimator, another order of sums).
+ * THE CARRY IS PERSISTENT STATE OF THE CONTEXT: tau [27 x N_P] (twice), the pages [N_T-1][43], the number of pairs of steps folded
+ * in and the kernels' workspace are taken from the context's pool at the first call, kept across calls and across further
+ * rbpf_loc_advance, and handed back by rbpf_loc_forward_stats_reset or rbpf_destroy.  A call folds in every stored pair of steps
+ * (t, t+1) not yet folded, ascending; not every step has to be done, but at least 2, and keep_history = 1 and trace = 1.  The other
+ * passes run beside a living carry as before.  Fixed summation order (a function of N_P), fp64, no atomics; a pair whose log omega
+ * lies below -746 contributes exactly 0.
+ * Outputs (NULL pointers are skipped): S_run [6 x 6 x (T_done-1)], m_run [6 x (T_done-1)], mass_run [T_done-1] (all pages, T_done =
+ * the steps done), tau_S [6 x 6 x N_P] (both triangles) and tau_m [6 x N_P], the carry of the latest step.                        */
+int rbpf_loc_forward_stats_update(rbpf_ctx* ctx, double* S_run, double* m_run, double* mass_run, double* tau_S, double* tau_m);
+/* Hands the carry back to the pool; the next update starts again at the first pair of steps.  No carry: nothing happens.         */
+int rbpf_loc_forward_stats_reset(rbpf_ctx* ctx);
+/* Bytes of device memory the carry holds while it lives (no device access).  With rows = 7, n_res = 6, KF = n_res (n_res + 3) / 2,
+ * C = max(256, ceil(ceil(N_P / max(1, ceil(1024 / ceil(N_P / 256)))) / 256) * 256) and nchunks = ceil(N_P / C), in doubles:
+ *   (rows + 1) N_P                        the predecessors of a step
+ * + 2 P,  P = what rbpf_loc_marginal_workspace_bytes counts per array of chunk partials (the normaliser pass's)
+ * + 4 N_P                                 zeros, D, what the normaliser's merge writes next to D, reach
+ * + nchunks (KF + 1) N_P                  the carry pass's chunk partials
+ * + 2 KF N_P                              tau, ping-pong
+ * + max(N_T - 1, 1) (n_res^2 + n_res + 1) the pages.                                                                              */
+int rbpf_loc_forward_stats_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes);
+/* One step on the caller's arrays, the kernel-level probe: xn [7 x N], logw [N], xs_next [7 x M], odo [7], dt, Q as
+ * rbpf_loc_marginal_step; tau_S [6 x 6 x N] (the lower triangle is read), tau_m [6 x N] the incoming carry -> D [M], tau_S_next
+ * [6 x 6 x M], tau_m_next [6 x M], reach [M] = sum_i omega(i, j).  *ms = median time of the normaliser pass, the carry pass, its
+ * merge and the reducer together (the reducer with uniform weights).                                                             */
+int rbpf_loc_forward_stats_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* tau_S,
+                                const double* tau_m, const double* odo, double dt, const double* Q, double* D, double* tau_S_next,
+                                double* tau_m_next, double* reach, int32_t reps, double* ms);
+
 /* ---- localisation in the fixed map of a generic device-code model --------------------------------
  * particleFilter.m:100-161 with the map frozen: xl = mean and P = V'V (V lower n_lin x n_lin, column-major, lower triangle read:
  * the rbpf_loc_map convention) are the same for every particle and never updated (:163-204 are left out).  The model is the
@@ -1124,6 +1163,32 @@ int rbpf_loc_generic_pair_stats_step(int32_t N, int32_t M, int32_t n_nonlin, int
                                      int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* logws_next,
                                      const double* cov, double* D, double* lws, double* S, double* m, double* pair_mass, int32_t reps,
                                      double* ms);
+
+/* ---- running two-slice statistics in the fixed map of a generic device-code model ----------------------
+ * The statistics of rbpf_loc_forward_stats_update on a context of rbpf_loc_generic_create or rbpf_loc_landmark_create, driven as
+ * the rbpf_loc_generic_pair_stats_* family is (same rows, angle_mask, quat_pos, checks; mu and cov for every step; the library names
+ * the step), but FORWARDS: the steps ascend from the first pair not yet folded in, t = folded .. T_done-2, and not every step of
+ * the run has to be done (at least 2).  _step_device takes s_scale = 1 / dt(t) next to cov: what the S part of the functional is
+ * scaled by (the library does not know dt).  The carry is persistent state of the context as in the dense-mag map; _begin takes it
+ * at the first call, and with other rows than the carry was built with it is refused (RBPF_ERR_STATE: _reset first).  Between _begin
+ * and _finish the stepping counts as a fifth kind of open pass: only one of the five can be open at once.  _finish closes the
+ * stepping and keeps the carry: with every stored pair folded it returns S_run [n_res x n_res x (T_done-1)], m_run [n_res x
+ * (T_done-1)], mass_run [T_done-1], tau_S [n_res x n_res x N_P], tau_m [n_res x N_P] in the CALLER's residual order (NULL pointers
+ * are skipped); with pairs left (a handle failed) it refuses unless every pointer is NULL, and the carry stays where the last
+ * complete step put it: a later _begin resumes there.  _reset (not while the stepping is open) hands the carry back.
+ * _workspace_bytes: the sum stated at rbpf_loc_forward_stats_workspace_bytes with rows = n_sel and n_res = n_sel (n_sel - 1 with a
+ * quaternion block).  _step is the probe: the arguments of rbpf_loc_generic_marginal_step without logws_next, the incoming carry
+ * and s_scale -> D [M], tau_S_next [n_res x n_res x M], tau_m_next [n_res x M], reach [M].                                          */
+int rbpf_loc_generic_forward_stats_begin(rbpf_ctx* ctx, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos);
+int rbpf_loc_generic_forward_stats_particles_device(rbpf_ctx* ctx, int32_t* t, const double** xn_dev);
+int rbpf_loc_generic_forward_stats_step_device(rbpf_ctx* ctx, const double* mu_dev, const double* cov, double s_scale);
+int rbpf_loc_generic_forward_stats_finish(rbpf_ctx* ctx, double* S_run, double* m_run, double* mass_run, double* tau_S, double* tau_m);
+int rbpf_loc_generic_forward_stats_reset(rbpf_ctx* ctx);
+int rbpf_loc_generic_forward_stats_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, size_t* bytes);
+int rbpf_loc_generic_forward_stats_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                        int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* tau_S,
+                                        const double* tau_m, const double* cov, double s_scale, double* D, double* tau_S_next,
+                                        double* tau_m_next, double* reach, int32_t reps, double* ms);
 
 /* ---- backward simulation by rejection sampling, in every fixed map -----------------------------------
  * The law of rbpf_loc_backward_simulate / rbpf_loc_generic_backward_*, drawn without the all-pairs pass where a proposal is

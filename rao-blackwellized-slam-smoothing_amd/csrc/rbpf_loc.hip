@@ -541,6 +541,8 @@ int rbpf_loc_create(const rbpf_loc_map* map, const rbpf_loc_problem* prob, const
   if (opt) c->opt = *opt;
   c->N = N; c->T = T; c->mdl = M; c->rng_mode = rng->mode; c->seed = rng->seed;
   L->n = n; L->sigma2 = map->sigma2; L->s_pages = s_pages; L->x0_cols = prob->x0_cols;
+  c->h_dt.assign(prob->dt, prob->dt + (prob->dt_len > 1 ? T - 1 : 1));   // (the running statistics scale S by 1 / dt)
+  c->dt_len = (int)c->h_dt.size();
   const bool hist = c->opt.keep_history != 0, trace = c->opt.trace != 0;
   std::unique_ptr<rbpf_ctx, void (*)(rbpf_ctx*)> guard(c, [](rbpf_ctx* p) { ctx_free(p); });
   HIPCHK(hipGetDevice(&c->device));

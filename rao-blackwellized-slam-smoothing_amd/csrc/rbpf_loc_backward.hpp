@@ -18,7 +18,8 @@
 //                                       pair_far(head, h, x), and the kernels put the test between them (a cheap part that decides
 //                                       and a dear one: the dense-mag map's position and orientation terms)
 //     Term::NR, term.pair_res(head, h, x, bound, l, r)   pair (or pair_near, the test, pair_far) that also leaves the NR un-whitened
-//                                       residuals of a pair it does not skip in r, kernel order (rbpf_loc_pairstats.hpp)
+//                                       residuals of a pair it does not skip in r, kernel order (rbpf_loc_pairstats.hpp,
+//                                       rbpf_loc_forwardstats.hpp)
 //     term.gather(head, X, N, idx, xs, j) xs[j] <- all rows of particle idx
 // The terms are BsTerm (the dense-mag map, rbpf_loc_smooth.hip) and GsTerm<NR, ANG, QP> (a generic map's Gaussian transitions,
 // with or without a quaternion block, rbpf_loc_generic_smooth.hip); each file also has the prologue that writes Xhat.

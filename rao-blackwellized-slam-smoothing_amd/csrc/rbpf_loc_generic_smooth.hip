@@ -41,6 +41,11 @@
 // rbpf_loc_pairstats.hpp on the same Xhat, c and mass; GsTerm::pair_res hands out the un-whitened residual in kernel order, and the
 // host puts S and m back into the caller's order (LocGenLayout::perm) when it copies out.
 //
+// THE RUNNING STATISTICS (rbpf_loc_generic_forward_stats_*): the forward-only recursion of rbpf_loc_forwardstats.hpp on the same
+// prologues and terms, driven FORWARDS in time from the first pair of steps not yet folded in (begin / particles_device / step_device
+// / finish); its carry stays in the context (LocState::fs) between calls, and only between begin and finish does it count as an open
+// pass.
+//
 // REJECTION SAMPLING (rbpf_loc_generic_backward_reject_begin): the pass that rbpf_loc_reject.hpp puts in front of the all-pairs pass
 // at steps N_T-2 .. 0, on the same prologues and terms, driven by the same particles_device / step_device / finish.
 #include "../../include/rbpf.h"
@@ -52,6 +57,7 @@
 #include "rbpf_loc_viterbi.hpp"
 #include "rbpf_loc_marginal.hpp"
 #include "rbpf_loc_pairstats.hpp"
+#include "rbpf_loc_forwardstats.hpp"
 #include "rbpf_loc_reject.hpp"
 #include "rbpf_timed_reps.hpp"
 
@@ -422,6 +428,8 @@ static hipError_t gs_launch_reject_step(const LocGenLayout& y, const GsArgs& a, 
   });
 }
 
+static const char* const kFsOpen = "a running-statistics stepping is open on this context (rbpf_loc_generic_forward_stats_finish first)";
+
 static void gs_release(rbpf_ctx* c) {
   c->loc->gb.rw.release();
   c->loc->gb.ws.release();
@@ -477,6 +485,7 @@ static int gs_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed,
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
+  if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "backward simulation", who));
   const int N = c->N, T = c->T, M = n_traj, nN = L->nN;
   LocGenBackward& g = L->gb;
@@ -728,6 +737,7 @@ int rbpf_loc_generic_map_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, 
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
+  if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "the MAP trajectory", "rbpf_loc_generic_map_begin"));
   const int N = c->N, T = c->T;
   LocGenBackward& g = L->gv;
@@ -876,6 +886,7 @@ static int gm_begin(const GmKind& k, rbpf_ctx* c, int32_t n_sel, const int32_t* 
   RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
+  if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, k.reader, (std::string(k.fam) + "_begin").c_str()));
@@ -1057,6 +1068,180 @@ int rbpf_loc_generic_pair_stats_step(int32_t N, int32_t M, int32_t n_nonlin, int
                                      const double* cov, double* D, double* lws, double* S, double* m, double* pair_mass, int32_t reps,
                                      double* ms) {
   return gm_probe(N, M, n_nonlin, n_sel, rows, angle_mask, quat_pos, mu, logw, xs_next, logws_next, cov, D, lws, true, S, m, pair_mass, reps, ms);
+}
+
+// ---- the running two-slice statistics (rbpf_loc_forwardstats.hpp) ------------------------------------------------------------
+typedef ForwardStatsArgs<GsData> GfArgs;
+
+static hipError_t gs_launch_forward_stats(const LocGenLayout& y, const GmArgs& a, const GfArgs& b, const double* mu, const double* w,
+                                          const double* logw, const ForwardCarry& f, double* tau_next, const double* w_next, double* page,
+                                          hipStream_t s) {
+  gs_launch_prologue(y, a.N, mu, w, f.Xhat, s);
+  if (logw) {
+    const hipError_t e = hipMemcpyAsync(f.Xhat + (size_t)y.n_sel * a.N, logw, (size_t)a.N * sizeof(double), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return e;
+  }
+  return gs_pick(y, a.head.angle_mask, [&](auto tag) {
+    typedef typename decltype(tag)::Term Term;
+    return forward_stats_launch_step(a.with(Term{a.term}), b.with(Term{b.term}), f.zero, f.D, f.cj, tau_next, f.reach, w_next, page, s);
+  });
+}
+
+// the head, the sizes and the buffers of a step (xn_next, tau, s_scale and the term's W are the caller's)
+static void gs_forward_stats_args(const ForwardCarry& f, const LocGenLayout& lay, int nN, int N, int M, GmArgs& a, GfArgs& b) {
+  std::memset(&b, 0, sizeof(b));
+  forward_stats_set(f, N, M, a, b);
+  a.head.nN = nN; a.head.first = 0; a.head.angle_mask = lay.angle_mask;
+  for (int q = 0; q < lay.n_sel; ++q) a.head.rows[q] = lay.rows[q];
+  b.head = a.head; b.term = a.term;
+}
+
+static bool gs_same_layout(const LocGenLayout& p, const LocGenLayout& q) {
+  if (p.n_sel != q.n_sel || p.n_res != q.n_res || p.n_plain != q.n_plain || p.angle_mask != q.angle_mask) return false;
+  for (int k = 0; k < 8; ++k)
+    if (p.rows[k] != q.rows[k] || p.src[k] != q.src[k] || p.perm[k] != q.perm[k]) return false;
+  return true;
+}
+
+static int gf_not_open() {
+  set_error("no running-statistics stepping is open (rbpf_loc_generic_forward_stats_begin first)");
+  return RBPF_ERR_STATE;
+}
+
+int rbpf_loc_generic_forward_stats_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, size_t* bytes) {
+  RB_TRY(rbpf_loc_generic_marginal_workspace_bytes(n_nonlin, n_sel, quat_pos, N_P, N_T, bytes));   // its argument checks
+  *bytes = forward_stats_bytes((size_t)n_sel, (size_t)(quat_pos == -1 ? n_sel : n_sel - 1), (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_forward_stats_reset(rbpf_ctx* c) {
+  RB_TRY(gs_ctx_ok(c));
+  if (c->loc->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->loc->fs.release();
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_forward_stats_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenLayout lay;
+  RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
+  if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
+  if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
+  RB_TRY(forward_stats_check_forward(c, "rbpf_loc_generic_forward_stats_begin"));
+  ForwardCarry& f = L->fs;
+  if (f.alive && !gs_same_layout(f.lay, lay)) {
+    set_error("the carry of the running statistics was built with other rows (rbpf_loc_generic_forward_stats_reset first)");
+    return RBPF_ERR_STATE;
+  }
+  if (!f.alive) {
+    RB_TRY(forward_stats_take(f, c->pool, L->nN, lay.n_sel, lay.n_res, c->N, c->N, c->T - 1, c->stream));
+    f.lay = lay;
+  }
+  f.open = true;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_forward_stats_particles_device(rbpf_ctx* c, int32_t* t, const double** xn_dev) {
+  RB_TRY(gs_ctx_ok(c));
+  if (!t || !xn_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  const ForwardCarry& f = c->loc->fs;
+  if (!f.open) return gf_not_open();
+  if (f.folded + 1 >= c->t) { set_error("every stored pair of steps is folded in (rbpf_loc_generic_forward_stats_finish)"); return RBPF_ERR_STATE; }
+  *t = f.folded;
+  *xn_dev = c->X + (size_t)f.folded * c->loc->nN * c->N;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_forward_stats_step_device(rbpf_ctx* c, const double* mu_dev, const double* cov, double s_scale) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  ForwardCarry& f = L->fs;
+  if (!f.open) return gf_not_open();
+  if (f.folded + 1 >= c->t) { set_error("every stored pair of steps is folded in (rbpf_loc_generic_forward_stats_finish)"); return RBPF_ERR_STATE; }
+  if (!mu_dev || !cov) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (!(s_scale >= 0.0) || !std::isfinite(s_scale)) { set_error("s_scale (1 / dt of the step) must be finite and >= 0"); return RBPF_ERR_INVALID_ARG; }
+  const int N = c->N, nN = L->nN, t = f.folded;
+  const size_t KF = (size_t)forward_stats_carry(f.n_res);
+  GmArgs a;
+  GfArgs b;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, f.lay, a.term.W, " of step " + std::to_string(t)));
+  HIPCHK(hipSetDevice(c->device));
+  gs_forward_stats_args(f, f.lay, nN, N, N, a, b);
+  a.xn_next = b.xn_next = c->X + (size_t)(t + 1) * nN * N;
+  b.tau = f.tau + (size_t)f.cur * KF * N; b.s_scale = s_scale;
+  HIPCHK(gs_launch_forward_stats(f.lay, a, b, mu_dev, c->w + (size_t)t * N, nullptr, f, f.tau + (size_t)(f.cur ^ 1) * KF * N,
+                                 c->w + (size_t)(t + 1) * N, f.pages + (size_t)t * pair_stats_page(f.n_res), c->stream));
+  f.cur ^= 1;
+  f.folded = t + 1;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_forward_stats_finish(rbpf_ctx* c, double* S_run, double* m_run, double* mass_run, double* tau_S, double* tau_m) {
+  RB_TRY(gs_ctx_ok(c));
+  ForwardCarry& f = c->loc->fs;
+  if (!f.open) return gf_not_open();
+  f.open = false;                                                        // the stepping is closed whichever way this returns; the carry stays
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (f.folded + 1 < c->t) {
+    if (!S_run && !m_run && !mass_run && !tau_S && !tau_m) return RBPF_OK;     // the way out of a stepping that was given up
+    set_error("rbpf_loc_generic_forward_stats_finish: the pairs of steps from " + std::to_string(f.folded) + " on were not folded in");
+    return RBPF_ERR_STATE;
+  }
+  RB_TRY(ctx_check_flags(c));
+  return forward_stats_copy_out(f, c->N, f.lay.perm, S_run, m_run, mass_run, tau_S, tau_m);
+}
+
+int rbpf_loc_generic_forward_stats_step(int32_t N, int32_t M, int32_t n_nonlin, int32_t n_sel, const int32_t* rows, uint32_t angle_mask,
+                                        int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* tau_S,
+                                        const double* tau_m, const double* cov, double s_scale, double* D, double* tau_S_next,
+                                        double* tau_m_next, double* reach, int32_t reps, double* ms) {
+  if (!mu || !logw || !xs_next || !tau_S || !tau_m || !cov || !D || !tau_S_next || !tau_m_next || !reach || !rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles || M > kMaxParticles) { set_error("N or M above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  if (!(s_scale >= 0.0) || !std::isfinite(s_scale)) { set_error("s_scale (1 / dt of the step) must be finite and >= 0"); return RBPF_ERR_INVALID_ARG; }
+  LocGenLayout lay;
+  RB_TRY(gs_layout(n_nonlin, n_sel, rows, angle_mask, quat_pos, lay));
+  GmArgs a;
+  GfArgs b;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, lay, a.term.W, ""));
+  if (!have_device()) { set_error("no HIP device: the running statistics have no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  const int NR = lay.n_res;
+  const size_t KF = (size_t)forward_stats_carry(NR), ld = (size_t)std::max(N, M);
+  std::vector<double> xt((size_t)n_nonlin * M), tk(KF * N);               // the successors as the history holds them: [n_nonlin][M]
+  for (int j = 0; j < M; ++j)
+    for (int r = 0; r < n_nonlin; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * n_nonlin + r];
+  forward_stats_pack(NR, N, lay.perm, tau_S, tau_m, tk.data());
+  DevicePool tmp;
+  ForwardCarry f;
+  RB_TRY(forward_stats_take(f, tmp, n_nonlin, lay.n_sel, NR, N, M, 1, 0));
+  double *d_mu = nullptr, *d_lw = nullptr, *d_xs = nullptr, *d_wn = nullptr;
+  RB_TRY(tmp.upload(&d_mu, mu, (size_t)lay.n_sel * N));
+  RB_TRY(tmp.upload(&d_lw, logw, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)n_nonlin * M));
+  RB_TRY(tmp.alloc(&d_wn, (size_t)M));
+  HIPCHK(hipMemcpy(f.tau, tk.data(), tk.size() * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(forward_stats_fill_kernel, dim3((M + 255) / 256), dim3(256), 0, 0, M, 1.0 / M, d_wn);   // (the reducer's weights: uniform)
+  gs_forward_stats_args(f, lay, n_nonlin, N, M, a, b);
+  a.xn_next = b.xn_next = d_xs;
+  b.tau = f.tau; b.s_scale = s_scale;
+  double* tau_next = f.tau + KF * ld;
+  // (the prologue's last row is overwritten with the caller's log w: what it reads as w does not matter)
+  RB_TRY(timed_reps(reps, 0, [&] { return gs_launch_forward_stats(lay, a, b, d_mu, d_lw, d_lw, f, tau_next, d_wn, f.pages, 0); }, ms));
+  std::vector<double> tn(KF * M);
+  HIPCHK(hipMemcpy(D, f.D, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(reach, f.reach, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tn.data(), tau_next, tn.size() * sizeof(double), hipMemcpyDeviceToHost));
+  forward_stats_unpack(NR, M, lay.perm, tn.data(), tau_S_next, tau_m_next);
+  return RBPF_OK;
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@
 // and so do the marginal smoothing weights (rbpf_loc_marginal_smooth, rbpf_loc_marginal.hpp), backward simulation by rejection
 // sampling (rbpf_loc_backward_simulate_reject, rbpf_loc_reject.hpp) and the two-slice statistics of the transition residual
 // (rbpf_loc_pair_stats_smooth, rbpf_loc_pairstats.hpp: BsTerm::pair_res hands out r = [p~ - (p_i + dx); phi]).
+// The running statistics (rbpf_loc_forward_stats_update, rbpf_loc_forwardstats.hpp) walk the stored steps FORWARDS on the same
+// prologue and term and keep their carry in the context (LocState::fs) between calls.
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
@@ -26,6 +28,7 @@
 #include "rbpf_loc_viterbi.hpp"
 #include "rbpf_loc_marginal.hpp"
 #include "rbpf_loc_pairstats.hpp"
+#include "rbpf_loc_forwardstats.hpp"
 #include "rbpf_loc_reject.hpp"
 #include "rbpf_timed_reps.hpp"
 
@@ -616,6 +619,123 @@ int rbpf_loc_pair_stats_step(int32_t N, int32_t M, const double* xn, const doubl
                              const double* odo, double dt, const double* Q, double* D, double* lws, double* S, double* m, double* pair_mass,
                              int32_t reps, double* ms) {
   return bs_marginal_probe(N, M, xn, logw, xs_next, logws_next, odo, dt, Q, D, lws, true, S, m, pair_mass, reps, ms);
+}
+
+// ---- the running two-slice statistics (rbpf_loc_forwardstats.hpp) ------------------------------------------------------------
+int rbpf_loc_forward_stats_workspace_bytes(int32_t N_P, int32_t N_T, size_t* bytes) {
+  RB_TRY(rbpf_loc_marginal_workspace_bytes(N_P, N_T, bytes));           // its argument checks
+  *bytes = forward_stats_bytes(7, BsTerm::NR, (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_forward_stats_reset(rbpf_ctx* c) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (c->loc->generic) { set_error("a generic localisation context has rbpf_loc_generic_forward_stats_reset"); return RBPF_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->loc->fs.release();
+  return RBPF_OK;
+}
+
+int rbpf_loc_forward_stats_update(rbpf_ctx* c, double* S_run, double* m_run, double* mass_run, double* tau_S, double* tau_m) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (c->loc->generic) {
+    set_error("the running statistics need the transition density of dynModel: a generic map's dynModel is a sampler (its handles carry no density)");
+    return RBPF_ERR_UNSUPPORTED;
+  }
+  RB_TRY(forward_stats_check_forward(c, "rbpf_loc_forward_stats_update"));
+  LocState* L = c->loc;
+  ForwardCarry& f = L->fs;
+  const int N = c->N, T = c->T, Td = c->t;
+  std::vector<BsNoise> nz((size_t)L->s_pages);
+  {
+    std::vector<double> Sq((size_t)L->s_pages * 36);
+    HIPCHK(hipMemcpy(Sq.data(), L->d_S, Sq.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < L->s_pages; ++p) RB_TRY(bs_noise(Sq.data() + (size_t)p * 36, nz[p]));
+  }
+  for (int t = f.alive ? f.folded : 0; t + 1 < Td; ++t)
+    if (!(c->h_dt[c->dt_len > 1 ? t : 0] > 0.0)) { set_error("dt of step " + std::to_string(t) + " is not positive: S / dt does not exist"); return RBPF_ERR_INVALID_ARG; }
+  if (!f.alive) RB_TRY(forward_stats_take(f, c->pool, 7, 7, BsTerm::NR, N, N, T - 1, c->stream));
+  constexpr size_t KF = (size_t)forward_stats_carry(BsTerm::NR);
+  for (int t = f.folded; t + 1 < Td; ++t) {
+    MarginalArgs<BsTerm> a;
+    ForwardStatsArgs<BsTerm> b;
+    forward_stats_set(f, N, N, a, b);
+    a.head.first = 0; b.head = a.head;
+    a.xn_next = b.xn_next = c->X + (size_t)(t + 1) * 7 * N;
+    a.term.nz = b.term.nz = nz[L->s_pages > 1 ? t : 0];
+    b.tau = f.tau + (size_t)f.cur * KF * N;
+    b.s_scale = 1.0 / c->h_dt[c->dt_len > 1 ? t : 0];
+    hipLaunchKernelGGL(bs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, c->stream, N, c->X + (size_t)t * 7 * N, (size_t)N, (size_t)1,
+                       c->w + (size_t)t * N, c->d_odo + (size_t)t * 7, f.Xhat);
+    HIPCHK(forward_stats_launch_step(a, b, f.zero, f.D, f.cj, f.tau + (size_t)(f.cur ^ 1) * KF * N, f.reach, c->w + (size_t)(t + 1) * N,
+                                     f.pages + (size_t)t * pair_stats_page(BsTerm::NR), c->stream));
+    f.cur ^= 1;
+    f.folded = t + 1;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  RB_TRY(ctx_check_flags(c));
+  return forward_stats_copy_out(f, N, nullptr, S_run, m_run, mass_run, tau_S, tau_m);
+}
+
+// One step on the caller's arrays, the kernel-level probe
+int rbpf_loc_forward_stats_step(int32_t N, int32_t M, const double* xn, const double* logw, const double* xs_next, const double* tau_S,
+                                const double* tau_m, const double* odo, double dt, const double* Q, double* D, double* tau_S_next,
+                                double* tau_m_next, double* reach, int32_t reps, double* ms) {
+  if (!xn || !logw || !xs_next || !tau_S || !tau_m || !odo || !Q || !D || !tau_S_next || !tau_m_next || !reach) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1) { set_error("N and M must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles || M > kMaxParticles) { set_error("N or M above 1048576 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  if (!(dt > 0.0)) { set_error("dt must be positive"); return RBPF_ERR_INVALID_ARG; }
+  double Sq[36];
+  for (int q = 0; q < 36; ++q) Sq[q] = 0.0;
+  for (int b = 0; b < 2; ++b)
+    for (int cc = 0; cc < 3; ++cc)
+      for (int r = 0; r < 3; ++r) {
+        const int q = (3 * b + r) + 6 * (3 * b + cc);
+        const double v = dt * Q[q];
+        if (!(v >= 0.0)) { set_error("dt * Q has a negative entry in a diagonal block: the element-wise sqrt of dynModel would be complex"); return RBPF_ERR_INVALID_ARG; }
+        Sq[q] = std::sqrt(v);
+      }
+  MarginalArgs<BsTerm> a;
+  ForwardStatsArgs<BsTerm> b;
+  RB_TRY(bs_noise(Sq, a.term.nz));
+  if (!have_device()) { set_error("no HIP device: the running statistics have no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  constexpr int NR = BsTerm::NR;
+  constexpr size_t KF = (size_t)forward_stats_carry(NR);
+  const size_t ld = (size_t)std::max(N, M);
+  std::vector<double> xt((size_t)7 * M), tk(KF * N);                      // the successors as the history holds them: [7][M]
+  for (int j = 0; j < M; ++j)
+    for (int r = 0; r < 7; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * 7 + r];
+  forward_stats_pack(NR, N, nullptr, tau_S, tau_m, tk.data());
+  DevicePool tmp;
+  ForwardCarry f;
+  RB_TRY(forward_stats_take(f, tmp, 7, 7, NR, N, M, 1, 0));
+  double *d_xn = nullptr, *d_lw = nullptr, *d_xs = nullptr, *d_odo = nullptr, *d_wn = nullptr;
+  RB_TRY(tmp.upload(&d_xn, xn, (size_t)7 * N));
+  RB_TRY(tmp.upload(&d_lw, logw, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)7 * M));
+  RB_TRY(tmp.upload(&d_odo, odo, (size_t)7));
+  RB_TRY(tmp.alloc(&d_wn, (size_t)M));
+  HIPCHK(hipMemcpy(f.tau, tk.data(), tk.size() * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(forward_stats_fill_kernel, dim3((M + 255) / 256), dim3(256), 0, 0, M, 1.0 / M, d_wn);   // (the reducer's weights: uniform)
+  forward_stats_set(f, N, M, a, b);
+  a.head.first = 0; b.head = a.head;
+  a.xn_next = b.xn_next = d_xs;
+  b.term = a.term; b.tau = f.tau; b.s_scale = 1.0 / dt;
+  double* tau_next = f.tau + KF * ld;
+  RB_TRY(timed_reps(reps, 0, [&] {
+    hipLaunchKernelGGL(bs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, 0, N, d_xn, (size_t)1, (size_t)7, d_lw, d_odo, f.Xhat);
+    // the caller's log w over the prologue's last row (what it read as w does not matter)
+    const hipError_t e = hipMemcpyAsync(f.Xhat + (size_t)7 * N, d_lw, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0);
+    if (e != hipSuccess) return e;
+    return forward_stats_launch_step(a, b, f.zero, f.D, f.cj, tau_next, f.reach, d_wn, f.pages, 0);
+  }, ms));
+  std::vector<double> tn(KF * M);
+  HIPCHK(hipMemcpy(D, f.D, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(reach, f.reach, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tn.data(), tau_next, tn.size() * sizeof(double), hipMemcpyDeviceToHost));
+  forward_stats_unpack(NR, M, nullptr, tn.data(), tau_S_next, tau_m_next);
+  return RBPF_OK;
 }
 
 }  // extern "C"

@@ -161,6 +161,30 @@ struct LocGenBackward {
   RejectWorkspace rw;
 };
 
+// The device buffers of the running statistics' carry (rbpf_loc_forwardstats.hpp).  Persistent state of a localisation context
+// (LocState::fs): taken from rbpf_ctx::pool at the first call, kept across calls and further steps of the filter, handed back by the
+// reset entry points (and with the context).  The probes build one on a pool of their own.
+//   Xhat [rows + 1][N]; pm, ps [marginal_part_count(N, M)] the norm pass's chunk partials; zero [M] zeros (logws_next of the norm
+//   merge); D [M]; cj [M] (what the norm merge writes next to D, not read); part [nchunks][KF + 1][M]; tau [2][KF][max(N, M)] the
+//   carry, ping-pong; reach [M]; pages [P][NR * NR + NR + 1].
+struct ForwardCarry {
+  DevicePool* pool = nullptr;
+  bool alive = false;
+  bool open = false;               // generic family: between _begin and _finish
+  int folded = 0;                  // pairs of steps (t, t + 1), t = 0 .. folded - 1, are in the carry
+  int cur = 0;                     // which half of tau holds the carry of step `folded`
+  int nN = 0, rows = 0, n_res = 0;
+  LocGenLayout lay;                // generic family
+  double *Xhat = nullptr, *pm = nullptr, *ps = nullptr, *zero = nullptr, *D = nullptr, *cj = nullptr, *part = nullptr, *tau = nullptr,
+         *reach = nullptr, *pages = nullptr;
+  void release() {
+    if (pool)
+      for (void* p : {(void*)Xhat, (void*)pm, (void*)ps, (void*)zero, (void*)D, (void*)cj, (void*)part, (void*)tau, (void*)reach, (void*)pages})
+        pool->release(p);
+    *this = ForwardCarry();
+  }
+};
+
 struct LocState {
   DevicePool pool;                 // owns the device buffers below; the context-level arrays of a localisation session are in rbpf_ctx::pool
   int n = 0;
@@ -181,6 +205,7 @@ struct LocState {
   LocGenBackward gv;               // the MAP trajectory with one (rbpf_loc_generic_map_begin .. _finish): t counts up, M = N_P; never open with gb
   LocGenBackward gm;               // marginal smoothing with one (rbpf_loc_generic_marginal_begin .. _finish): t counts down from N_T-2, M = N_P; never open with gb or gv
   LocGenBackward gp;               // two-slice statistics with one (rbpf_loc_generic_pair_stats_begin .. _finish): as gm; never open with gb, gv or gm
+  ForwardCarry fs;                 // the running statistics' carry (rbpf_loc_forward_stats_*, rbpf_loc_generic_forward_stats_*); while fs.open: a fifth kind of open pass
   // landmark map (rbpf_loc_landmark_create): the handle's yhat is the prediction and the outputs observed at a step are selected
   bool landmark = false;
   int *d_ind = nullptr;            // [N_T][32]: the observed outputs of every step, ascending

@@ -2148,6 +2148,38 @@ def device_map_pair_stats_workspace_bytes(n_nonlin, n_sel, N_P, N_T, quat_pos=-1
     return int(nbytes.value)
 
 
+def device_map_forward_stats_step(mu, logw, xs_next, tau_S, tau_m, cov, rows=None, angle_rows=(), quat_rows=None, s_scale=1.0, reps=1):
+    """rbpf_loc_generic_forward_stats_step, the kernel-level probe: one step of the running two-slice statistics with a Gaussian
+    transition on the caller's arrays.  mu, logw, xs_next, cov, rows, angle_rows and quat_rows as in device_map_marginal_step;
+    tau_S [n_res x n_res x N] (the lower triangle is read) and tau_m [n_res x N] the incoming carry in the order of cov; s_scale =
+    1 / dt of the step -> (D [M], tau_S_next [n_res x n_res x M], tau_m_next [n_res x M], reach [M] = sum_i omega(i, j), median ms
+    of the normaliser pass, the carry pass, its merge and the reducer together)."""
+    lib = load_library()
+    mu, xs_next, cov, rows_a, mask, qpos = _transition_probe_args(mu, xs_next, cov, rows, angle_rows, quat_rows)
+    (n_sel, N), (nN, M) = mu.shape, xs_next.shape
+    n = cov.shape[0]
+    logw = np.ascontiguousarray(np.asarray(logw, dtype=np.float64).ravel())
+    tau_S = np.asfortranarray(np.asarray(tau_S, dtype=np.float64).reshape(n, n, -1))
+    tau_m = np.asfortranarray(np.asarray(tau_m, dtype=np.float64).reshape(n, -1))
+    if logw.size != N or tau_S.shape[2] != N or tau_m.shape[1] != N:
+        raise ValueError("logw must be [N], tau_S [n_res x n_res x N] and tau_m [n_res x N]")
+    D, tS, tm, reach = np.empty(M), np.empty((n, n, M), order="F"), np.empty((n, M), order="F"), np.empty(M)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_generic_forward_stats_step(N, M, nN, n_sel, _ip(rows_a), mask, qpos, _dp(mu), _dp(logw), _dp(xs_next), _dp(tau_S),
+                                                  _dp(tau_m), _dp(cov), float(s_scale), _dp(D), _dp(tS), _dp(tm), _dp(reach), int(reps),
+                                                  C.byref(ms)))
+    return D, tS, tm, reach, ms.value
+
+
+def device_map_forward_stats_workspace_bytes(n_nonlin, n_sel, N_P, N_T, quat_pos=-1):
+    """rbpf_loc_generic_forward_stats_workspace_bytes (no device access): what the carry of the running statistics holds while it
+    lives; n_sel = len(rows), quat_pos the position of a quaternion block in rows or -1."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_generic_forward_stats_workspace_bytes(int(n_nonlin), int(n_sel), int(quat_pos), int(N_P), int(N_T), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
 class DeviceMap:
     """A fixed map of an arbitrary model whose handles are device code: the posterior N(mean, V'V) over the nLin linear states, V
     lower (the DenseMagMap convention), as a SLAM filter or smoother run with the same DeviceHandles returns it (xl_max, P_max /
@@ -2881,6 +2913,80 @@ class LocalizationSession:
             check(self.lib.rbpf_loc_pair_stats_smooth(self.ctx, *outs))
         return b
 
+    def running_statistics(self, want=("S_run", "m_run")):
+        """rbpf_loc_forward_stats_update: the two-slice statistics of transition_statistics, accumulated over the steps and available
+        WHILE the run goes on -- the forward-only form of FFBSm for an additive functional (Del Moral, Doucet & Singh 2010).  Needs
+        keep_history and trace and at least 2 steps done, NOT every step.  Returns a dict of what `want` names, with P = tell() - 1:
+        S_run [n_res x n_res x P] and m_run [n_res x P], page k the FFBSm estimate from the steps 0 .. k+1 alone of
+        sum_{s<=k} E[r r' / dt_s] and sum_{s<=k} E[r] (r as in transition_statistics); mass_run [P] (1 in exact arithmetic);
+        tau_S [n_res x n_res x N_P] and tau_m [n_res x N_P], the per-particle carry of the latest step.  Once every step is done the
+        last page equals sum_t S_t / dt_t and sum_t m_t of transition_statistics.  The carry is kept in the session: a call folds
+        in only the pairs of steps stored since the last one (one all-pairs step each), and holds its device memory until
+        reset_running_statistics() or close().  In a DeviceMap the `mean` handle is called once per newly folded step, ascending;
+        without a DeviceTransition the call is refused.  running_noise_estimate turns the pages into a running estimate of Q."""
+        if self.driver is not None and self.map.transition is None:
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, _NO_BACKWARD_IN_DEVICE_MAP)
+        names = ("S_run", "m_run", "mass_run", "tau_S", "tau_m")
+        unknown = set(want) - set(names)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        N, nN, P = self.prob.N_P, self.nN, max(self.tell() - 1, 0)
+        n_res = 6 if self.driver is None else self.map.transition.layout(nN)[3]
+        shapes = dict(S_run=(n_res, n_res, P), m_run=(n_res, P), mass_run=(P,), tau_S=(n_res, n_res, N), tau_m=(n_res, N))
+        b = {k: np.empty(shapes[k], order="F") for k in names if k in want}
+        outs = tuple(_dp(b[k]) if k in b else None for k in names)
+        if self.driver is not None:
+            self._forward_pass_in_device_map(outs)
+        else:
+            check(self.lib.rbpf_loc_forward_stats_update(self.ctx, *outs))
+        return b
+
+    def reset_running_statistics(self):
+        """rbpf_loc_forward_stats_reset: hands the carry of running_statistics back; the next call starts again at the first step."""
+        if self.driver is not None:
+            check(self.lib.rbpf_loc_generic_forward_stats_reset(self.ctx))
+        else:
+            check(self.lib.rbpf_loc_forward_stats_reset(self.ctx))
+
+    def _forward_pass_in_device_map(self, outs):
+        """The forward variant of _stepped_pass_in_device_map for rbpf_loc_generic_forward_stats_*: the steps ascend from the first
+        pair not yet folded in to tell() - 2, every one with the `mean` handle's mu, cov(dt, Q) and 1 / dt.  A failed handle closes
+        the stepping and leaves the carry where the last complete step put it."""
+        lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
+        torch, N, nN = drv.torch, prob.N_P, self.nN
+        rows_a, mask, qpos, n_sel, covs, page = self._transition_pages()
+        check(lib.rbpf_loc_generic_forward_stats_begin(self.ctx, n_sel, _ip(rows_a), mask, qpos))
+        try:
+            with torch.cuda.stream(drv.stream):
+                while True:
+                    t, xn = C.c_int32(0), C.c_void_p()
+                    st = lib.rbpf_loc_generic_forward_stats_particles_device(self.ctx, C.byref(t), C.byref(xn))
+                    if st == _ffi.RBPF_ERR_STATE:                 # (the stepping is open: every stored pair is folded in)
+                        break
+                    check(st)
+                    t = t.value
+                    X = drv._view(torch, xn, (nN, N), drv.device)
+                    Q = drv.Q[page(drv.Q.shape[0], t)]
+                    dt = float(drv.dt[page(drv.dt.size, t)])
+                    mu = tr.mean(X, drv.odo[t], dt, Q)
+                    if not torch.is_tensor(mu) or tuple(mu.shape) != (n_sel, N) or mu.dtype != torch.float64 or not mu.is_cuda:
+                        what = f"{tuple(mu.shape)} {mu.dtype} on {mu.device}" if torch.is_tensor(mu) else type(mu).__name__
+                        raise ValueError(f"mean returned {what}, expected a float64 device tensor of shape {(n_sel, N)}")
+                    if not dt > 0.0:
+                        raise ValueError(f"dt of step {t} is not positive: S / dt does not exist")
+                    mu = mu.contiguous()
+                    self._keep_mu = mu                            # read in stream order by the step just enqueued
+                    check(lib.rbpf_loc_generic_forward_stats_step_device(self.ctx, C.c_void_p(mu.data_ptr()),
+                                                                         _dp(covs[(page(prob._dt.size, t), page(prob._Q.shape[2], t))]), 1.0 / dt))
+        except BaseException:
+            lib.rbpf_loc_generic_forward_stats_finish(self.ctx, None, None, None, None, None)
+            self._keep_mu = None
+            raise
+        try:
+            check(lib.rbpf_loc_generic_forward_stats_finish(self.ctx, *outs))
+        finally:
+            self._keep_mu = None
+
     def close(self):
         if self.ctx:
             self.lib.rbpf_destroy(self.ctx)
@@ -3078,6 +3184,91 @@ def transition_noise_estimate(S, dt, m=None):
     if m.shape[1] != P:
         raise ValueError("m must be [n x P]")
     return np.mean((S - m[:, None, :] * m[None, :, :]) / dt[None, None, :], axis=2), np.mean(m, axis=1)
+
+
+def loc_forward_stats_workspace_bytes(N_P, N_T):
+    """rbpf_loc_forward_stats_workspace_bytes (no device access): what the carry of the running statistics holds while it lives."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_forward_stats_workspace_bytes(int(N_P), int(N_T), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def loc_forward_stats_step(xn, logw, xs_next, tau_S, tau_m, odo, dt, Q, reps=1):
+    """rbpf_loc_forward_stats_step, the kernel-level probe: one step of the running two-slice statistics in the dense-mag map on the
+    caller's arrays.  xn [7 x N], logw [N], xs_next [7 x M], odo [7], dt, Q as loc_marginal_step; tau_S [6 x 6 x N] (the lower
+    triangle is read) and tau_m [6 x N] the incoming carry -> (D [M], tau_S_next [6 x 6 x M], tau_m_next [6 x M], reach [M] =
+    sum_i omega(i, j), median ms of the normaliser pass, the carry pass, its merge and the reducer together)."""
+    lib = load_library()
+    xn = np.asfortranarray(np.asarray(xn, dtype=np.float64).reshape(7, -1))
+    xs_next = np.asfortranarray(np.asarray(xs_next, dtype=np.float64).reshape(7, -1))
+    N, M = xn.shape[1], xs_next.shape[1]
+    logw = np.ascontiguousarray(np.asarray(logw, dtype=np.float64).ravel())
+    odo = np.ascontiguousarray(np.asarray(odo, dtype=np.float64).ravel())
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(6, 6))
+    tau_S = np.asfortranarray(np.asarray(tau_S, dtype=np.float64).reshape(6, 6, -1))
+    tau_m = np.asfortranarray(np.asarray(tau_m, dtype=np.float64).reshape(6, -1))
+    if logw.size != N or odo.size != 7 or tau_S.shape[2] != N or tau_m.shape[1] != N:
+        raise ValueError("logw must be [N], odo [7], tau_S [6 x 6 x N] and tau_m [6 x N]")
+    D, tS, tm, reach = np.empty(M), np.empty((6, 6, M), order="F"), np.empty((6, M), order="F"), np.empty(M)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_forward_stats_step(N, M, _dp(xn), _dp(logw), _dp(xs_next), _dp(tau_S), _dp(tau_m), _dp(odo), float(dt), _dp(Q), _dp(D),
+                                          _dp(tS), _dp(tm), _dp(reach), int(reps), C.byref(ms)))
+    return D, tS, tm, reach, ms.value
+
+
+def particleRunningStatisticsLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, dt, *, rng=None, every=1, extras=False):
+    """The running two-slice statistics of localisation in a fixed map: the filter of particleFilterLocalization, and
+    LocalizationSession.running_statistics folded in every `every` steps while it runs -> (S_run [n_res x n_res x (N_T-1)],
+    m_run [n_res x (N_T-1)], mass_run [N_T-1][, extras]).  The pages do not depend on `every`.  dynModel / measModel, R and rng as
+    particleTransitionStatisticsLocalization takes them.  extras: the filter's outputs and `tau_S`, `tau_m` of the last step."""
+    import warnings
+    mp = _device_map(dynModel, measModel)
+    if mp is not None and mp.transition is None:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleRunningStatisticsLocalization: " + _NO_BACKWARD_IN_DEVICE_MAP)
+    if mp is None:
+        mp = _recognise_map(dynModel, measModel)
+    every = max(int(every), 1)
+    with LocalizationSession(mp, odometry, y, x0_nonLin, Q, N_P, dt, rng=rng, keep_history=True, trace=True) as s:
+        T = s.prob.N_T
+        while s.tell() < T:
+            s.advance(min(every, T - s.tell()))
+            if 2 <= s.tell() < T:
+                s.running_statistics(want=())
+        fwd = s.finish(extras=extras)
+        if fwd["first_degenerate_step"] >= 0:
+            warnings.warn(f"Weights filter close to zero at t={fwd['first_degenerate_step'] + 1} !!!", RuntimeWarning, stacklevel=2)
+        out = s.running_statistics(want=("S_run", "m_run", "mass_run") + (("tau_S", "tau_m") if extras else ()))
+    if extras:
+        fwd.update(tau_S=out["tau_S"], tau_m=out["tau_m"])
+        return out["S_run"], out["m_run"], out["mass_run"], fwd
+    return out["S_run"], out["m_run"], out["mass_run"]
+
+
+def running_noise_estimate(S_run, m_run=None):
+    """The running M-step for a transition noise of the form cov(dt, Q) = dt Q, from the pages of
+    LocalizationSession.running_statistics, in plain numpy: S_run [n x n x P] (page k: the steps 0 .. k+1, already divided by dt
+    step by step) ->
+        Q_hat[:, :, k] = S_run[:, :, k] / (k + 1)                        (m_run None)
+        (Q_hat, bias), bias[:, k] = m_run[:, k] / (k + 1)                (m_run [n x P]: the running smoothed odometry bias per step)
+    Page k is what transition_noise_estimate would give (un-centred) on a run that ended at step k+1.  The caveat of
+    transition_noise_estimate holds: in a DenseMagMap this estimates the covariance per unit time of the residual
+    [p~ - (p + dx); phi], of which the two diagonal 3 x 3 blocks mean something -- the map's dynModel draws its noise with the
+    ELEMENT-WISE sqrt(dt Q) of those blocks as factors S_pos and S_rot, so what it realises is S_pos S_pos' and S_rot S_rot', equal to
+    dt Q for diagonal blocks only; the off-diagonal block is a diagnostic."""
+    S = np.asarray(S_run, dtype=np.float64)
+    if S.ndim == 2:
+        S = S[:, :, None]
+    n, P = S.shape[0], S.shape[2]
+    if S.shape[1] != n or P < 1:
+        raise ValueError("S_run must be [n x n x P] with P >= 1")
+    k1 = np.arange(1, P + 1, dtype=np.float64)
+    if m_run is None:
+        return S / k1[None, None, :]
+    m = np.asarray(m_run, dtype=np.float64).reshape(n, -1)
+    if m.shape[1] != P:
+        raise ValueError("m_run must be [n x P]")
+    return S / k1[None, None, :], m / k1[None, :]
 
 
 def loc_backward_workspace_bytes(N_P, N_T, n_traj):

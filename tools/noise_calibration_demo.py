@@ -9,11 +9,16 @@ the map by batch regression (DenseMagMap.from_data), then iterate from a Q that 
 (the map's dynModel reads the diagonal blocks of Q through an element-wise sqrt, and the true Q is diagonal: only the diagonal is fed
 back).  The filter starts from the true initial state; every iteration uses the same Philox seed.
 
-    python tools/noise_calibration_demo.py [factor=9] [iterations=5] [N_P=2048] [N_T=120] [m=1000] [seed=1]
+    python tools/noise_calibration_demo.py [factor=9] [iterations=5] [N_P=2048] [N_T=120] [m=1000] [seed=1] [--running[=EVERY]]
 
 Prints one JSON line per iteration: diag(Q_k) / diag(Q_true) going in, diag(Q_hat) / diag(Q_true) coming out, the mean smoothed
 residual (the odometry bias) in units of the true standard deviation per step, the smallest effective sample size of the smoothed
-weights and the largest |pair_mass - 1|.  It is a demo: nothing is asserted on these numbers."""
+weights and the largest |pair_mass - 1|.  It is a demo: nothing is asserted on these numbers.
+
+--running[=EVERY] (default EVERY = N_T / 6): no EM; ONE run with the fixed Q = factor Q_true, and while it goes on, every EVERY steps,
+LocalizationSession.running_statistics (the forward-only form: one all-pairs step per new time step, nothing is walked backwards)
+and running_noise_estimate of its latest page, one JSON line each; at the end the offline estimate of the whole run
+(transition_statistics, transition_noise_estimate) next to the last page, which is the same estimator."""
 import importlib
 import json
 import os
@@ -31,7 +36,8 @@ THETA = np.array([650.0, 1.2, 200.0, 10.0])
 
 
 def main():
-    a = sys.argv[1:]
+    running = [x for x in sys.argv[1:] if x.startswith("--running")]
+    a = [x for x in sys.argv[1:] if not x.startswith("--")]
     factor = float(a[0]) if len(a) > 0 else 9.0
     iters = int(a[1]) if len(a) > 1 else 5
     N_P = int(a[2]) if len(a) > 2 else 2048
@@ -45,6 +51,24 @@ def main():
     mp = rbpf.DenseMagMap.from_data(model, d["pos"].T, y_nav, THETA)
     q_true = np.diag(Q_TRUE)
     Q = factor * Q_TRUE
+    if running:
+        every = int(running[0].split("=")[1]) if "=" in running[0] else max(N_T // 6, 1)
+        with rbpf.LocalizationSession(mp, d["dx"], d["y"], d["initState"], Q, N_P, dt, rng=rbpf.PhiloxRNG(seed), keep_history=True, trace=True) as s:
+            while s.tell() < N_T:
+                s.advance(min(every, N_T - s.tell()))
+                if s.tell() < 2:
+                    continue
+                out = s.running_statistics(want=("S_run", "m_run", "mass_run"))
+                Q_run, bias = rbpf.running_noise_estimate(out["S_run"], out["m_run"])
+                print(json.dumps(dict(steps_done=s.tell(), factor=factor, N_P=N_P, N_T=N_T,
+                                      Q_running_over_true=[float(v) for v in np.diag(Q_run[:, :, -1]) / q_true],
+                                      bias_in_true_sd_per_step=[float(v) for v in bias[:, -1] / np.sqrt(dt * q_true)],
+                                      worst_mass_error=float(np.max(np.abs(out["mass_run"] - 1.0))))), flush=True)
+            off = s.transition_statistics(want=("S", "m"))
+        Q_off = rbpf.transition_noise_estimate(off["S"], dt)
+        print(json.dumps(dict(offline=True, Q_hat_over_true=[float(v) for v in np.diag(Q_off) / q_true],
+                              last_page_against_offline=float(np.max(np.abs(Q_run[:, :, -1] - Q_off)) / np.max(np.abs(Q_off))))), flush=True)
+        return
     for k in range(iters):
         rec = dict(iteration=k, factor=factor, N_P=N_P, N_T=N_T, Q_in_over_true=[float(v) for v in np.diag(Q) / q_true])
         try:
