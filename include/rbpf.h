@@ -975,6 +975,48 @@ int rbpf_loc_forward_stats_step(int32_t N, int32_t M, const double* xn, const do
                                 const double* tau_m, const double* odo, double dt, const double* Q, double* D, double* tau_S_next,
                                 double* tau_m_next, double* reach, int32_t reps, double* ms);
 
+/* ---- fixed-lag smoothing of the state: forward-only, while the run goes on -------------------------------
+ * E[x(s) | y(1 : s+lag)] and its covariance for every step s, at one all-pairs pass per new time step whatever the lag: the
+ * forward-only form of FFBSm (the estimator of rbpf_loc_marginal_smooth) for the per-step functionals of the last `lag` steps.
+ * With D and omega as at rbpf_loc_forward_stats_update, n = 7 state rows, c(:, s) the filter mean of step s and d = x - c(:, s),
+ *     h(s)(x)        = d                                  (moments = 1, H = n columns)
+ *                    = [d; lower triangle by rows of d d'] (moments = 2, H = n (n + 3) / 2 columns)
+ *     T0(i, t)       = h(t)(X(:, i, t))
+ *     T(l)(j, t+1)   = sum_i omega(i, j) T(l-1)(i, t),     l = 1 .. lag                (one pass over lag H columns)
+ *     est(l, t+1)    = sum_j w(j, t+1) T(l)(j, t+1)  =  E[h(t+1-l)(x(t+1-l)) | y(1 : t+1)],     l = 0 .. lag
+ *     mass(t+1)      = sum_j w(j, t+1) sum_i omega(i, j)                                (= 1)
+ * est(l, t) is the FFBSm estimate from the steps up to t alone: what rbpf_loc_marginal_smooth gives for step t-l on a run that
+ * ended at t, in another order of sums.  mean = c + E[d], cov = E[d d'] - E[d] E[d]': centred at the filter mean, nothing cancels.
+ * Plain weighted moments of all rows: quaternion rows get no special handling.  Lags that reach before the first step carry zeros.
+ * THE CARRY IS PERSISTENT STATE OF THE CONTEXT, with the life cycle of the running statistics' (and beside it, if both live): taken
+ * from the context's pool at the first call, which fixes lag (1 .. 64) and moments; kept across calls and further
+ * rbpf_loc_advance; handed back by rbpf_loc_fixed_lag_reset or rbpf_destroy.  A call with another lag or moments is refused
+ * (RBPF_ERR_STATE: reset first).  A call folds in every stored step not yet folded, ascending; keep_history = 1, trace = 1 and at
+ * least 2 steps done (not every step).  Fixed summation order (a function of N_P), fp64, no atomics; a column's value depends
+ * neither on lag nor on moments nor on its place in the carry; a pair whose log omega lies below -746 contributes exactly 0.
+ * Outputs (NULL pointers are skipped), T_done = the steps done: pages [((lag + 1) H + 1) x T_done], column t: est(0 .. lag, t)
+ * (H values each, 0 where t - l < 0), then mass(t) (mass(1) = 1); means [7 x T_done] = c.                                          */
+int rbpf_loc_fixed_lag_update(rbpf_ctx* ctx, int32_t lag, int32_t moments, double* pages, double* means);
+/* Hands the carry back to the pool; the next update starts again at the first step.  No carry: nothing happens.                    */
+int rbpf_loc_fixed_lag_reset(rbpf_ctx* ctx);
+/* Bytes of device memory the carry holds while it lives (no device access).  With rows = n = 7, H as above, K = lag H, and C,
+ * nchunks, P as at rbpf_loc_forward_stats_workspace_bytes, in doubles:
+ *   (rows + 1) N_P                        the predecessors of a step
+ * + 2 P                                   the normaliser pass's chunk partials
+ * + 4 N_P                                 zeros, D, what the normaliser's merge writes next to D, reach
+ * + nchunks (K + 1) N_P                   the carry pass's chunk partials
+ * + 2 (K + H) N_P                         the carry, ping-pong
+ * + N_T (K + H + 1)                       the pages
+ * + N_T n                                 the filter means.                                                                       */
+int rbpf_loc_fixed_lag_workspace_bytes(int32_t N_P, int32_t N_T, int32_t lag, int32_t moments, size_t* bytes);
+/* One pass on the caller's arrays, the kernel-level probe: xn, logw, xs_next, odo, dt, Q as rbpf_loc_marginal_step; tau [K][N]
+ * (column k contiguous over the particles), any K >= 1, the incoming columns -> D [M], tau_next [K][M], reach [M] = sum_i omega(i,
+ * j).  *ms = median time of the normaliser pass and its merge, the carry pass, its merge, the enter kernel (with `moments`, on the
+ * successors) and the reducers together (uniform weights); the outputs do not depend on moments.                                   */
+int rbpf_loc_fixed_lag_step(int32_t N, int32_t M, int32_t K, int32_t moments, const double* xn, const double* logw, const double* xs_next,
+                            const double* tau, const double* odo, double dt, const double* Q, double* D, double* tau_next, double* reach,
+                            int32_t reps, double* ms);
+
 /* ---- localisation in the fixed map of a generic device-code model --------------------------------
  * particleFilter.m:100-161 with the map frozen: xl = mean and P = V'V (V lower n_lin x n_lin, column-major, lower triangle read:
  * the rbpf_loc_map convention) are the same for every particle and never updated (:163-204 are left out).  The model is the
@@ -1189,6 +1231,31 @@ int rbpf_loc_generic_forward_stats_step(int32_t N, int32_t M, int32_t n_nonlin, 
                                         int32_t quat_pos, const double* mu, const double* logw, const double* xs_next, const double* tau_S,
                                         const double* tau_m, const double* cov, double s_scale, double* D, double* tau_S_next,
                                         double* tau_m_next, double* reach, int32_t reps, double* ms);
+
+/* ---- fixed-lag smoothing in the fixed map of a generic device-code model --------------------------------
+ * The estimates of rbpf_loc_fixed_lag_update on a context of rbpf_loc_generic_create or rbpf_loc_landmark_create, over all n =
+ * n_nonlin state rows, driven as the rbpf_loc_generic_forward_stats_* family is: FORWARDS, t = (steps folded) - 1 .. T_done-2, mu
+ * and cov for every step, the library names the step; not every step of the run has to be done (at least 2).  _begin takes the
+ * carry at the first call, which fixes lag, moments and the rows; with others it is refused (RBPF_ERR_STATE: _reset first).
+ * Between _begin and _finish the stepping counts as a sixth kind of open pass: only one of the six can be open at once.  _finish
+ * closes the stepping and keeps the carry: with every stored step folded it returns pages and means [n_nonlin x T_done] as
+ * rbpf_loc_fixed_lag_update does (NULL pointers are skipped); with steps left (a handle failed) it refuses unless both pointers are
+ * NULL, and the carry stays where the last complete step put it: a later _begin resumes there.  _reset (not while the stepping is
+ * open) hands the carry back.  _workspace_bytes: the sum stated at rbpf_loc_fixed_lag_workspace_bytes with rows = n_sel and n =
+ * n_nonlin.  _step is the probe: the arguments of rbpf_loc_generic_marginal_step without logws_next, K, moments and tau [K][N] ->
+ * D [M], tau_next [K][M], reach [M].                                                                                              */
+int rbpf_loc_generic_fixed_lag_begin(rbpf_ctx* ctx, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos, int32_t lag,
+                                     int32_t moments);
+int rbpf_loc_generic_fixed_lag_particles_device(rbpf_ctx* ctx, int32_t* t, const double** xn_dev);
+int rbpf_loc_generic_fixed_lag_step_device(rbpf_ctx* ctx, const double* mu_dev, const double* cov);
+int rbpf_loc_generic_fixed_lag_finish(rbpf_ctx* ctx, double* pages, double* means);
+int rbpf_loc_generic_fixed_lag_reset(rbpf_ctx* ctx);
+int rbpf_loc_generic_fixed_lag_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, int32_t lag,
+                                               int32_t moments, size_t* bytes);
+int rbpf_loc_generic_fixed_lag_step(int32_t N, int32_t M, int32_t K, int32_t moments, int32_t n_nonlin, int32_t n_sel, const int32_t* rows,
+                                    uint32_t angle_mask, int32_t quat_pos, const double* mu, const double* logw, const double* xs_next,
+                                    const double* tau, const double* cov, double* D, double* tau_next, double* reach, int32_t reps,
+                                    double* ms);
 
 /* ---- backward simulation by rejection sampling, in every fixed map -----------------------------------
  * The law of rbpf_loc_backward_simulate / rbpf_loc_generic_backward_*, drawn without the all-pairs pass where a proposal is

@@ -23,6 +23,8 @@ from .host import (particleFilter, particleSmoother, particleSmootherInformation
                    device_map_pair_stats_workspace_bytes, transition_noise_estimate,
                    particleRunningStatisticsLocalization, loc_forward_stats_step, loc_forward_stats_workspace_bytes,
                    device_map_forward_stats_step, device_map_forward_stats_workspace_bytes, running_noise_estimate,
+                   particleFixedLagSmootherLocalization, loc_fixed_lag_step, loc_fixed_lag_workspace_bytes, device_map_fixed_lag_step,
+                   device_map_fixed_lag_workspace_bytes, fixed_lag_assemble,
                    loc_backward_reject_step, loc_backward_reject_workspace_bytes, device_map_backward_reject_step, reject_default_max_tries)
 
 

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "librbpf_hip.so")
 SOURCES = ["rbpf_kernels.hip", "rbpf_step_wide_28.hip", "rbpf_step_wide_47.hip", "rbpf_step_wide_56.hip", "rbpf_step_sym.hip", "rbpf_api.hip", "rbpf_smoother.hip", "rbpf_shard.hip", "rbpf_multi.hip", "rbpf_plan.hip", "rbpf_resample.hip", "rbpf_sparse.hip", "rbpf_sparse_ext.hip", "rbpf_sparse_ext_anc.hip", "rbpf_loc.hip", "rbpf_loc_generic.hip", "rbpf_loc_landmark.hip", "rbpf_loc_smooth.hip", "rbpf_loc_generic_smooth.hip", "rbpf_ekf.hip", "rbpf_external.hip"]
-HEADERS = ["rbpf_model_dev.hpp", "rbpf_chol64.hpp", "rbpf_chol_small.hpp", "rbpf_chol_sweep.hpp", "rbpf_internal.hpp", "rbpf_device.hpp", "rbpf_ctx.hpp", "rbpf_devmem.hpp", "rbpf_loc_state.hpp", "rbpf_loc_backward.hpp", "rbpf_loc_viterbi.hpp", "rbpf_loc_marginal.hpp", "rbpf_loc_pairstats.hpp", "rbpf_loc_forwardstats.hpp", "rbpf_loc_reject.hpp", "rbpf_timed_reps.hpp", "rbpf_plan.hpp", "rbpf_shard_state.hpp", "rbpf_sparse.hpp", "rbpf_step_full.hpp", "rbpf_step_sym_body.inc"]
+HEADERS = ["rbpf_model_dev.hpp", "rbpf_chol64.hpp", "rbpf_chol_small.hpp", "rbpf_chol_sweep.hpp", "rbpf_internal.hpp", "rbpf_device.hpp", "rbpf_ctx.hpp", "rbpf_devmem.hpp", "rbpf_loc_state.hpp", "rbpf_loc_backward.hpp", "rbpf_loc_viterbi.hpp", "rbpf_loc_marginal.hpp", "rbpf_loc_pairstats.hpp", "rbpf_loc_forwardstats.hpp", "rbpf_loc_fixedlag.hpp", "rbpf_loc_reject.hpp", "rbpf_timed_reps.hpp", "rbpf_plan.hpp", "rbpf_shard_state.hpp", "rbpf_sparse.hpp", "rbpf_step_full.hpp", "rbpf_step_sym_body.inc"]
 
 
 def _stale() -> bool:

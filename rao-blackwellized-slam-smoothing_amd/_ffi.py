@@ -182,6 +182,10 @@ EXPORTS = [
     "rbpf_loc_generic_forward_stats_begin", "rbpf_loc_generic_forward_stats_particles_device", "rbpf_loc_generic_forward_stats_step_device",
     "rbpf_loc_generic_forward_stats_finish", "rbpf_loc_generic_forward_stats_reset", "rbpf_loc_generic_forward_stats_workspace_bytes",
     "rbpf_loc_generic_forward_stats_step",
+    "rbpf_loc_fixed_lag_update", "rbpf_loc_fixed_lag_reset", "rbpf_loc_fixed_lag_workspace_bytes", "rbpf_loc_fixed_lag_step",
+    "rbpf_loc_generic_fixed_lag_begin", "rbpf_loc_generic_fixed_lag_particles_device", "rbpf_loc_generic_fixed_lag_step_device",
+    "rbpf_loc_generic_fixed_lag_finish", "rbpf_loc_generic_fixed_lag_reset", "rbpf_loc_generic_fixed_lag_workspace_bytes",
+    "rbpf_loc_generic_fixed_lag_step",
     "rbpf_loc_backward_simulate_reject", "rbpf_loc_backward_reject_workspace_bytes", "rbpf_loc_backward_reject_step",
     "rbpf_loc_generic_backward_reject_begin", "rbpf_loc_generic_backward_reject_stats", "rbpf_loc_generic_backward_reject_workspace_bytes",
     "rbpf_loc_generic_backward_reject_step",
@@ -401,6 +405,21 @@ def load_library(build_if_missing: bool = True):
     lib.rbpf_loc_generic_forward_stats_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, C.c_int32, c_double_p,
                                                         c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p,
                                                         c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_fixed_lag_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_double_p, c_double_p]
+    lib.rbpf_loc_fixed_lag_reset.argtypes = [C.c_void_p]
+    lib.rbpf_loc_fixed_lag_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_fixed_lag_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                            C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
+    lib.rbpf_loc_generic_fixed_lag_begin.argtypes = [C.c_void_p, C.c_int32, c_int32_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32]
+    lib.rbpf_loc_generic_fixed_lag_particles_device.argtypes = [C.c_void_p, c_int32_p, C.POINTER(C.c_void_p)]
+    lib.rbpf_loc_generic_fixed_lag_step_device.argtypes = [C.c_void_p, C.c_void_p, c_double_p]
+    lib.rbpf_loc_generic_fixed_lag_finish.argtypes = [C.c_void_p, c_double_p, c_double_p]
+    lib.rbpf_loc_generic_fixed_lag_reset.argtypes = [C.c_void_p]
+    lib.rbpf_loc_generic_fixed_lag_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                               C.POINTER(C.c_size_t)]
+    lib.rbpf_loc_generic_fixed_lag_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_uint32, C.c_int32,
+                                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                    C.c_int32, c_double_p]
     lib.rbpf_loc_landmark_create.argtypes = lib.rbpf_loc_generic_create.argtypes
     lib.rbpf_loc_landmark_map_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), c_int32_p]
     lib.rbpf_loc_landmark_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]

@@ -46,6 +46,9 @@
 // / finish); its carry stays in the context (LocState::fs) between calls, and only between begin and finish does it count as an open
 // pass.
 //
+// THE FIXED-LAG SMOOTHER (rbpf_loc_generic_fixed_lag_*): the recursion of rbpf_loc_fixedlag.hpp driven the same way, FORWARDS; its
+// carry is LocState::fl, and between begin and finish it counts as one more kind of open pass.
+//
 // REJECTION SAMPLING (rbpf_loc_generic_backward_reject_begin): the pass that rbpf_loc_reject.hpp puts in front of the all-pairs pass
 // at steps N_T-2 .. 0, on the same prologues and terms, driven by the same particles_device / step_device / finish.
 #include "../../include/rbpf.h"
@@ -58,6 +61,7 @@
 #include "rbpf_loc_marginal.hpp"
 #include "rbpf_loc_pairstats.hpp"
 #include "rbpf_loc_forwardstats.hpp"
+#include "rbpf_loc_fixedlag.hpp"
 #include "rbpf_loc_reject.hpp"
 #include "rbpf_timed_reps.hpp"
 
@@ -428,6 +432,7 @@ static hipError_t gs_launch_reject_step(const LocGenLayout& y, const GsArgs& a, 
   });
 }
 
+static const char* const kFlOpen = "a fixed-lag stepping is open on this context (rbpf_loc_generic_fixed_lag_finish first)";
 static const char* const kFsOpen = "a running-statistics stepping is open on this context (rbpf_loc_generic_forward_stats_finish first)";
 
 static void gs_release(rbpf_ctx* c) {
@@ -486,6 +491,7 @@ static int gs_begin(rbpf_ctx* c, int32_t n_traj, const double* u, uint64_t seed,
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
   if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
+  if (L->fl.open) { set_error(kFlOpen); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "backward simulation", who));
   const int N = c->N, T = c->T, M = n_traj, nN = L->nN;
   LocGenBackward& g = L->gb;
@@ -738,6 +744,7 @@ int rbpf_loc_generic_map_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, 
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
   if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
+  if (L->fl.open) { set_error(kFlOpen); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, "the MAP trajectory", "rbpf_loc_generic_map_begin"));
   const int N = c->N, T = c->T;
   LocGenBackward& g = L->gv;
@@ -887,6 +894,7 @@ static int gm_begin(const GmKind& k, rbpf_ctx* c, int32_t n_sel, const int32_t* 
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
   if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
+  if (L->fl.open) { set_error(kFlOpen); return RBPF_ERR_STATE; }
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
   if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
   RB_TRY(backward_check_forward(c, k.reader, (std::string(k.fam) + "_begin").c_str()));
@@ -1129,6 +1137,7 @@ int rbpf_loc_generic_forward_stats_begin(rbpf_ctx* c, int32_t n_sel, const int32
   LocGenLayout lay;
   RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
   if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
+  if (L->fl.open) { set_error(kFlOpen); return RBPF_ERR_STATE; }
   if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
   if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
   if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
@@ -1241,6 +1250,183 @@ int rbpf_loc_generic_forward_stats_step(int32_t N, int32_t M, int32_t n_nonlin, 
   HIPCHK(hipMemcpy(reach, f.reach, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(tn.data(), tau_next, tn.size() * sizeof(double), hipMemcpyDeviceToHost));
   forward_stats_unpack(NR, M, lay.perm, tn.data(), tau_S_next, tau_m_next);
+  return RBPF_OK;
+}
+
+// ---- the fixed-lag smoother (rbpf_loc_fixedlag.hpp) ------------------------------------------------------------------------------
+typedef FixedLagArgs<GsData> GlArgs;
+
+static hipError_t gs_launch_fixed_lag(const LocGenLayout& y, const GmArgs& a, const GlArgs& b, const double* mu, const double* w,
+                                      const double* logw, const FixedLagCarry& f, int moments, const double* X_next, const double* w_next,
+                                      double* T_next, double* c_next, double* page, hipStream_t s) {
+  gs_launch_prologue(y, a.N, mu, w, f.Xhat, s);
+  if (logw) {
+    const hipError_t e = hipMemcpyAsync(f.Xhat + (size_t)y.n_sel * a.N, logw, (size_t)a.N * sizeof(double), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return e;
+  }
+  return gs_pick(y, a.head.angle_mask, [&](auto tag) {
+    typedef typename decltype(tag)::Term Term;
+    return fixed_lag_launch_step(a.with(Term{a.term}), b.with(Term{b.term}), f, moments, X_next, w_next, T_next, c_next, page, s);
+  });
+}
+
+// the head, the sizes and the buffers of a step (xn_next, tau and the term's W are the caller's)
+static void gs_fixed_lag_args(const FixedLagCarry& f, const LocGenLayout& lay, int nN, int N, int M, GmArgs& a, GlArgs& b) {
+  std::memset(&b, 0, sizeof(b));
+  fixed_lag_set(f, N, M, a, b);
+  a.head.nN = nN; a.head.first = 0; a.head.angle_mask = lay.angle_mask;
+  for (int q = 0; q < lay.n_sel; ++q) a.head.rows[q] = lay.rows[q];
+  b.head = a.head; b.term = a.term;
+}
+
+static int gl_not_open() {
+  set_error("no fixed-lag stepping is open (rbpf_loc_generic_fixed_lag_begin first)");
+  return RBPF_ERR_STATE;
+}
+
+int rbpf_loc_generic_fixed_lag_workspace_bytes(int32_t n_nonlin, int32_t n_sel, int32_t quat_pos, int32_t N_P, int32_t N_T, int32_t lag,
+                                               int32_t moments, size_t* bytes) {
+  RB_TRY(rbpf_loc_generic_marginal_workspace_bytes(n_nonlin, n_sel, quat_pos, N_P, N_T, bytes));   // its argument checks
+  RB_TRY(fixed_lag_check_lag(lag, moments));
+  *bytes = fixed_lag_bytes((size_t)n_nonlin, (size_t)n_sel, (size_t)lag, (size_t)moments, (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_fixed_lag_reset(rbpf_ctx* c) {
+  RB_TRY(gs_ctx_ok(c));
+  if (c->loc->fl.open) { set_error(kFlOpen); return RBPF_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->loc->fl.release();
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_fixed_lag_begin(rbpf_ctx* c, int32_t n_sel, const int32_t* rows, uint32_t angle_mask, int32_t quat_pos, int32_t lag,
+                                     int32_t moments) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  LocGenLayout lay;
+  RB_TRY(gs_layout(L->nN, n_sel, rows, angle_mask, quat_pos, lay));
+  RB_TRY(fixed_lag_check_lag(lag, moments));
+  if (L->fl.open) { set_error(kFlOpen); return RBPF_ERR_STATE; }
+  if (L->fs.open) { set_error(kFsOpen); return RBPF_ERR_STATE; }
+  if (L->gm.open) { set_error("a marginal pass is open on this context (rbpf_loc_generic_marginal_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gp.open) { set_error("a statistics pass is open on this context (rbpf_loc_generic_pair_stats_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gb.open) { set_error("a backward pass is open on this context (rbpf_loc_generic_backward_finish first)"); return RBPF_ERR_STATE; }
+  if (L->gv.open) { set_error("a MAP pass is open on this context (rbpf_loc_generic_map_finish first)"); return RBPF_ERR_STATE; }
+  RB_TRY(forward_stats_check_forward(c, "rbpf_loc_generic_fixed_lag_begin"));
+  FixedLagCarry& f = L->fl;
+  if (f.alive) {
+    RB_TRY(fixed_lag_same(f, lag, moments, "rbpf_loc_generic_fixed_lag_reset"));
+    if (!gs_same_layout(f.lay, lay)) {
+      set_error("the carry of the fixed-lag smoother was built with other rows (rbpf_loc_generic_fixed_lag_reset first)");
+      return RBPF_ERR_STATE;
+    }
+  } else {
+    const int H = fixed_lag_columns(L->nN, moments);
+    RB_TRY(fixed_lag_take(f, c->pool, L->nN, lay.n_sel, lag * H, H, c->N, c->N, c->T, c->stream));
+    f.lay = lay; f.lag = lag; f.moments = moments;
+  }
+  if (f.entered == 0) {                                                  // step 0 enters: no all-pairs work
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(fixed_lag_launch_enter(f, moments, c->N, c->X, c->w, f.T + (size_t)f.cur * (f.K + f.H) * c->N, nullptr, f.cs, f.pages, c->stream));
+    f.entered = 1;
+  }
+  f.open = true;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_fixed_lag_particles_device(rbpf_ctx* c, int32_t* t, const double** xn_dev) {
+  RB_TRY(gs_ctx_ok(c));
+  if (!t || !xn_dev) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  const FixedLagCarry& f = c->loc->fl;
+  if (!f.open) return gl_not_open();
+  if (f.entered >= c->t) { set_error("every stored step is folded in (rbpf_loc_generic_fixed_lag_finish)"); return RBPF_ERR_STATE; }
+  *t = f.entered - 1;
+  *xn_dev = c->X + (size_t)(f.entered - 1) * c->loc->nN * c->N;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_fixed_lag_step_device(rbpf_ctx* c, const double* mu_dev, const double* cov) {
+  RB_TRY(gs_ctx_ok(c));
+  LocState* L = c->loc;
+  FixedLagCarry& f = L->fl;
+  if (!f.open) return gl_not_open();
+  if (f.entered >= c->t) { set_error("every stored step is folded in (rbpf_loc_generic_fixed_lag_finish)"); return RBPF_ERR_STATE; }
+  if (!mu_dev || !cov) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  const int N = c->N, nN = L->nN, t = f.entered - 1;
+  const size_t half = (size_t)(f.K + f.H) * N, page = (size_t)f.K + f.H + 1;
+  GmArgs a;
+  GlArgs b;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, f.lay, a.term.W, " of step " + std::to_string(t)));
+  HIPCHK(hipSetDevice(c->device));
+  gs_fixed_lag_args(f, f.lay, nN, N, N, a, b);
+  a.xn_next = b.xn_next = c->X + (size_t)(t + 1) * nN * N;
+  b.tau = f.T + (size_t)f.cur * half;
+  HIPCHK(gs_launch_fixed_lag(f.lay, a, b, mu_dev, c->w + (size_t)t * N, nullptr, f, f.moments, c->X + (size_t)(t + 1) * nN * N,
+                             c->w + (size_t)(t + 1) * N, f.T + (size_t)(f.cur ^ 1) * half, f.cs + (size_t)(t + 1) * nN,
+                             f.pages + (size_t)(t + 1) * page, c->stream));
+  f.cur ^= 1;
+  f.entered = t + 2;
+  return RBPF_OK;
+}
+
+int rbpf_loc_generic_fixed_lag_finish(rbpf_ctx* c, double* pages, double* means) {
+  RB_TRY(gs_ctx_ok(c));
+  FixedLagCarry& f = c->loc->fl;
+  if (!f.open) return gl_not_open();
+  f.open = false;                                                        // the stepping is closed whichever way this returns; the carry stays
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (f.entered < c->t) {
+    if (!pages && !means) return RBPF_OK;                                // the way out of a stepping that was given up
+    set_error("rbpf_loc_generic_fixed_lag_finish: the steps from " + std::to_string(f.entered) + " on were not folded in");
+    return RBPF_ERR_STATE;
+  }
+  RB_TRY(ctx_check_flags(c));
+  return fixed_lag_copy_out(f, pages, means);
+}
+
+int rbpf_loc_generic_fixed_lag_step(int32_t N, int32_t M, int32_t K, int32_t moments, int32_t n_nonlin, int32_t n_sel, const int32_t* rows,
+                                    uint32_t angle_mask, int32_t quat_pos, const double* mu, const double* logw, const double* xs_next,
+                                    const double* tau, const double* cov, double* D, double* tau_next, double* reach, int32_t reps,
+                                    double* ms) {
+  if (!mu || !logw || !xs_next || !tau || !cov || !D || !tau_next || !reach || !rows) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1 || K < 1) { set_error("N, M and K must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles || M > kMaxParticles || K > kFixedLagMaxLag * fixed_lag_columns(kBackwardMaxRows, 2)) { set_error("N or M above 1048576 or K above 64 x 44 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  RB_TRY(fixed_lag_check_lag(1, moments));
+  LocGenLayout lay;
+  RB_TRY(gs_layout(n_nonlin, n_sel, rows, angle_mask, quat_pos, lay));
+  GmArgs a;
+  GlArgs b;
+  std::memset(&a, 0, sizeof(a));
+  RB_TRY(gs_factor_layout(cov, lay, a.term.W, ""));
+  if (!have_device()) { set_error("no HIP device: the fixed-lag smoother has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  const int H = fixed_lag_columns(n_nonlin, moments);
+  const size_t ld = (size_t)std::max(N, M);
+  std::vector<double> xt((size_t)n_nonlin * M);                           // the successors as the history holds them: [n_nonlin][M]
+  for (int j = 0; j < M; ++j)
+    for (int r = 0; r < n_nonlin; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * n_nonlin + r];
+  DevicePool tmp;
+  FixedLagCarry f;
+  RB_TRY(fixed_lag_take(f, tmp, n_nonlin, lay.n_sel, K, H, N, M, 1, 0));
+  double *d_mu = nullptr, *d_lw = nullptr, *d_xs = nullptr, *d_wn = nullptr;
+  RB_TRY(tmp.upload(&d_mu, mu, (size_t)lay.n_sel * N));
+  RB_TRY(tmp.upload(&d_lw, logw, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)n_nonlin * M));
+  RB_TRY(tmp.alloc(&d_wn, (size_t)M));
+  HIPCHK(hipMemcpy(f.T, tau, (size_t)K * N * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(forward_stats_fill_kernel, dim3((M + 255) / 256), dim3(256), 0, 0, M, 1.0 / M, d_wn);   // (the reducer's weights: uniform)
+  gs_fixed_lag_args(f, lay, n_nonlin, N, M, a, b);
+  a.xn_next = b.xn_next = d_xs;
+  b.tau = f.T;
+  double* T_next = f.T + (size_t)(K + H) * ld;
+  // (the prologue's last row is overwritten with the caller's log w: what it reads as w does not matter)
+  RB_TRY(timed_reps(reps, 0, [&] { return gs_launch_fixed_lag(lay, a, b, d_mu, d_lw, d_lw, f, moments, d_xs, d_wn, T_next, f.cs, f.pages, 0); }, ms));
+  HIPCHK(hipMemcpy(D, f.D, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(reach, f.reach, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tau_next, T_next + (size_t)H * M, (size_t)K * M * sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 

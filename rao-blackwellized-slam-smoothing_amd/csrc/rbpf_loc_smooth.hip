@@ -19,6 +19,8 @@
 // (rbpf_loc_pair_stats_smooth, rbpf_loc_pairstats.hpp: BsTerm::pair_res hands out r = [p~ - (p_i + dx); phi]).
 // The running statistics (rbpf_loc_forward_stats_update, rbpf_loc_forwardstats.hpp) walk the stored steps FORWARDS on the same
 // prologue and term and keep their carry in the context (LocState::fs) between calls.
+// The fixed-lag smoother (rbpf_loc_fixed_lag_update, rbpf_loc_fixedlag.hpp) does the same with the moments of the last `lag` states
+// (LocState::fl).
 #include "../../include/rbpf.h"
 #include "rbpf_internal.hpp"
 #include "rbpf_device.hpp"
@@ -29,6 +31,7 @@
 #include "rbpf_loc_marginal.hpp"
 #include "rbpf_loc_pairstats.hpp"
 #include "rbpf_loc_forwardstats.hpp"
+#include "rbpf_loc_fixedlag.hpp"
 #include "rbpf_loc_reject.hpp"
 #include "rbpf_timed_reps.hpp"
 
@@ -735,6 +738,128 @@ int rbpf_loc_forward_stats_step(int32_t N, int32_t M, const double* xn, const do
   HIPCHK(hipMemcpy(reach, f.reach, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(tn.data(), tau_next, tn.size() * sizeof(double), hipMemcpyDeviceToHost));
   forward_stats_unpack(NR, M, nullptr, tn.data(), tau_S_next, tau_m_next);
+  return RBPF_OK;
+}
+
+// ---- the fixed-lag smoother (rbpf_loc_fixedlag.hpp) ------------------------------------------------------------------------------
+int rbpf_loc_fixed_lag_workspace_bytes(int32_t N_P, int32_t N_T, int32_t lag, int32_t moments, size_t* bytes) {
+  RB_TRY(rbpf_loc_marginal_workspace_bytes(N_P, N_T, bytes));           // its argument checks
+  RB_TRY(fixed_lag_check_lag(lag, moments));
+  *bytes = fixed_lag_bytes(7, 7, (size_t)lag, (size_t)moments, (size_t)N_P, (size_t)N_T);
+  return RBPF_OK;
+}
+
+int rbpf_loc_fixed_lag_reset(rbpf_ctx* c) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (c->loc->generic) { set_error("a generic localisation context has rbpf_loc_generic_fixed_lag_reset"); return RBPF_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->loc->fl.release();
+  return RBPF_OK;
+}
+
+int rbpf_loc_fixed_lag_update(rbpf_ctx* c, int32_t lag, int32_t moments, double* pages, double* means) {
+  if (!c || !c->loc) { set_error("not a localisation context"); return RBPF_ERR_INVALID_ARG; }
+  if (c->loc->generic) {
+    set_error("the fixed-lag smoother needs the transition density of dynModel: a generic map's dynModel is a sampler (its handles carry no density)");
+    return RBPF_ERR_UNSUPPORTED;
+  }
+  RB_TRY(fixed_lag_check_lag(lag, moments));
+  RB_TRY(forward_stats_check_forward(c, "rbpf_loc_fixed_lag_update"));
+  LocState* L = c->loc;
+  FixedLagCarry& f = L->fl;
+  if (f.alive) RB_TRY(fixed_lag_same(f, lag, moments, "rbpf_loc_fixed_lag_reset"));
+  const int N = c->N, T = c->T, Td = c->t;
+  std::vector<BsNoise> nz((size_t)L->s_pages);
+  {
+    std::vector<double> Sq((size_t)L->s_pages * 36);
+    HIPCHK(hipMemcpy(Sq.data(), L->d_S, Sq.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < L->s_pages; ++p) RB_TRY(bs_noise(Sq.data() + (size_t)p * 36, nz[p]));
+  }
+  if (!f.alive) {
+    const int H = fixed_lag_columns(7, moments);
+    RB_TRY(fixed_lag_take(f, c->pool, 7, 7, lag * H, H, N, N, T, c->stream));
+    f.lag = lag; f.moments = moments;
+  }
+  const size_t half = (size_t)(f.K + f.H) * N, page = (size_t)f.K + f.H + 1;
+  if (f.entered == 0) {
+    HIPCHK(fixed_lag_launch_enter(f, moments, N, c->X, c->w, f.T + (size_t)f.cur * half, nullptr, f.cs, f.pages, c->stream));
+    f.entered = 1;
+  }
+  for (int t = f.entered - 1; t + 1 < Td; ++t) {
+    MarginalArgs<BsTerm> a;
+    FixedLagArgs<BsTerm> b;
+    fixed_lag_set(f, N, N, a, b);
+    a.head.first = 0; b.head = a.head;
+    a.xn_next = b.xn_next = c->X + (size_t)(t + 1) * 7 * N;
+    a.term.nz = b.term.nz = nz[L->s_pages > 1 ? t : 0];
+    b.tau = f.T + (size_t)f.cur * half;
+    hipLaunchKernelGGL(bs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, c->stream, N, c->X + (size_t)t * 7 * N, (size_t)N, (size_t)1,
+                       c->w + (size_t)t * N, c->d_odo + (size_t)t * 7, f.Xhat);
+    HIPCHK(fixed_lag_launch_step(a, b, f, moments, c->X + (size_t)(t + 1) * 7 * N, c->w + (size_t)(t + 1) * N, f.T + (size_t)(f.cur ^ 1) * half,
+                                 f.cs + (size_t)(t + 1) * 7, f.pages + (size_t)(t + 1) * page, c->stream));
+    f.cur ^= 1;
+    f.entered = t + 2;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  RB_TRY(ctx_check_flags(c));
+  return fixed_lag_copy_out(f, pages, means);
+}
+
+// One step on the caller's arrays, the kernel-level probe
+int rbpf_loc_fixed_lag_step(int32_t N, int32_t M, int32_t K, int32_t moments, const double* xn, const double* logw, const double* xs_next,
+                            const double* tau, const double* odo, double dt, const double* Q, double* D, double* tau_next, double* reach,
+                            int32_t reps, double* ms) {
+  if (!xn || !logw || !xs_next || !tau || !odo || !Q || !D || !tau_next || !reach) { set_error("NULL argument"); return RBPF_ERR_INVALID_ARG; }
+  if (N < 1 || M < 1 || K < 1) { set_error("N, M and K must be >= 1"); return RBPF_ERR_INVALID_ARG; }
+  if (N > kMaxParticles || M > kMaxParticles || K > kFixedLagMaxLag * fixed_lag_columns(kBackwardMaxRows, 2)) { set_error("N or M above 1048576 or K above 64 x 44 is not supported"); return RBPF_ERR_UNSUPPORTED; }
+  RB_TRY(fixed_lag_check_lag(1, moments));
+  if (!(dt > 0.0)) { set_error("dt must be positive"); return RBPF_ERR_INVALID_ARG; }
+  double Sq[36];
+  for (int q = 0; q < 36; ++q) Sq[q] = 0.0;
+  for (int b = 0; b < 2; ++b)
+    for (int cc = 0; cc < 3; ++cc)
+      for (int r = 0; r < 3; ++r) {
+        const int q = (3 * b + r) + 6 * (3 * b + cc);
+        const double v = dt * Q[q];
+        if (!(v >= 0.0)) { set_error("dt * Q has a negative entry in a diagonal block: the element-wise sqrt of dynModel would be complex"); return RBPF_ERR_INVALID_ARG; }
+        Sq[q] = std::sqrt(v);
+      }
+  MarginalArgs<BsTerm> a;
+  FixedLagArgs<BsTerm> b;
+  RB_TRY(bs_noise(Sq, a.term.nz));
+  if (!have_device()) { set_error("no HIP device: the fixed-lag smoother has no CPU fallback"); return RBPF_ERR_NO_DEVICE; }
+  const int H = fixed_lag_columns(7, moments);
+  const size_t ld = (size_t)std::max(N, M);
+  std::vector<double> xt((size_t)7 * M);                                  // the successors as the history holds them: [7][M]
+  for (int j = 0; j < M; ++j)
+    for (int r = 0; r < 7; ++r) xt[(size_t)r * M + j] = xs_next[(size_t)j * 7 + r];
+  DevicePool tmp;
+  FixedLagCarry f;
+  RB_TRY(fixed_lag_take(f, tmp, 7, 7, K, H, N, M, 1, 0));
+  double *d_xn = nullptr, *d_lw = nullptr, *d_xs = nullptr, *d_odo = nullptr, *d_wn = nullptr;
+  RB_TRY(tmp.upload(&d_xn, xn, (size_t)7 * N));
+  RB_TRY(tmp.upload(&d_lw, logw, (size_t)N));
+  RB_TRY(tmp.upload(&d_xs, xt.data(), (size_t)7 * M));
+  RB_TRY(tmp.upload(&d_odo, odo, (size_t)7));
+  RB_TRY(tmp.alloc(&d_wn, (size_t)M));
+  HIPCHK(hipMemcpy(f.T, tau, (size_t)K * N * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(forward_stats_fill_kernel, dim3((M + 255) / 256), dim3(256), 0, 0, M, 1.0 / M, d_wn);   // (the reducer's weights: uniform)
+  fixed_lag_set(f, N, M, a, b);
+  a.head.first = 0; b.head = a.head;
+  a.xn_next = b.xn_next = d_xs;
+  b.term = a.term; b.tau = f.T;
+  double* T_next = f.T + (size_t)(K + H) * ld;
+  RB_TRY(timed_reps(reps, 0, [&] {
+    hipLaunchKernelGGL(bs_prologue_kernel, dim3((N + 255) / 256), dim3(256), 0, 0, N, d_xn, (size_t)1, (size_t)7, d_lw, d_odo, f.Xhat);
+    // the caller's log w over the prologue's last row (what it read as w does not matter)
+    const hipError_t e = hipMemcpyAsync(f.Xhat + (size_t)7 * N, d_lw, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, 0);
+    if (e != hipSuccess) return e;
+    return fixed_lag_launch_step(a, b, f, moments, d_xs, d_wn, T_next, f.cs, f.pages, 0);
+  }, ms));
+  HIPCHK(hipMemcpy(D, f.D, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(reach, f.reach, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tau_next, T_next + (size_t)H * M, (size_t)K * M * sizeof(double), hipMemcpyDeviceToHost));
   return RBPF_OK;
 }
 

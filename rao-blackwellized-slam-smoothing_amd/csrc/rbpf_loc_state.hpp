@@ -185,6 +185,29 @@ struct ForwardCarry {
   }
 };
 
+// The device buffers of the fixed-lag smoother's carry (rbpf_loc_fixedlag.hpp).  Persistent state of a localisation context
+// (LocState::fl) with the life cycle of ForwardCarry; the probes build one on a pool of their own.
+//   Xhat, pm, ps, zero, D, cj as in ForwardCarry; part [nchunks][K + 1][M]; T [2][K + H][max(N, M)] the carry, ping-pong: slot l of
+//   a step in the rows l H .. (l + 1) H - 1; reach [M]; pages [P][K + H + 1]: est of every slot and the mass; cs [P][nN]: the filter
+//   mean of every step entered.  K = lag H columns move on in a pass, H enter.
+struct FixedLagCarry {
+  DevicePool* pool = nullptr;
+  bool alive = false;
+  bool open = false;               // generic family: between _begin and _finish
+  int entered = 0;                 // the steps 0 .. entered - 1 are in the carry and have their page
+  int cur = 0;                     // which half of T holds the carry of step entered - 1
+  int nN = 0, rows = 0, lag = 0, moments = 0, K = 0, H = 0;
+  LocGenLayout lay;                // generic family
+  double *Xhat = nullptr, *pm = nullptr, *ps = nullptr, *zero = nullptr, *D = nullptr, *cj = nullptr, *part = nullptr, *T = nullptr,
+         *reach = nullptr, *pages = nullptr, *cs = nullptr;
+  void release() {
+    if (pool)
+      for (void* p : {(void*)Xhat, (void*)pm, (void*)ps, (void*)zero, (void*)D, (void*)cj, (void*)part, (void*)T, (void*)reach, (void*)pages, (void*)cs})
+        pool->release(p);
+    *this = FixedLagCarry();
+  }
+};
+
 struct LocState {
   DevicePool pool;                 // owns the device buffers below; the context-level arrays of a localisation session are in rbpf_ctx::pool
   int n = 0;
@@ -206,6 +229,7 @@ struct LocState {
   LocGenBackward gm;               // marginal smoothing with one (rbpf_loc_generic_marginal_begin .. _finish): t counts down from N_T-2, M = N_P; never open with gb or gv
   LocGenBackward gp;               // two-slice statistics with one (rbpf_loc_generic_pair_stats_begin .. _finish): as gm; never open with gb, gv or gm
   ForwardCarry fs;                 // the running statistics' carry (rbpf_loc_forward_stats_*, rbpf_loc_generic_forward_stats_*); while fs.open: a fifth kind of open pass
+  FixedLagCarry fl;                // the fixed-lag smoother's carry (rbpf_loc_fixed_lag_*, rbpf_loc_generic_fixed_lag_*); while fl.open: a sixth kind of open pass
   // landmark map (rbpf_loc_landmark_create): the handle's yhat is the prediction and the outputs observed at a step are selected
   bool landmark = false;
   int *d_ind = nullptr;            // [N_T][32]: the observed outputs of every step, ascending

@@ -2180,6 +2180,69 @@ def device_map_forward_stats_workspace_bytes(n_nonlin, n_sel, N_P, N_T, quat_pos
     return int(nbytes.value)
 
 
+def device_map_fixed_lag_step(mu, logw, xs_next, tau, cov, rows=None, angle_rows=(), quat_rows=None, moments=1, reps=1):
+    """rbpf_loc_generic_fixed_lag_step, the kernel-level probe: one pass of the fixed-lag smoother with a Gaussian transition on the
+    caller's arrays.  mu, logw, xs_next, cov, rows, angle_rows and quat_rows as in device_map_marginal_step; tau [K x N], any
+    K >= 1, the incoming columns of the carry -> (D [M], tau_next [K x M], reach [M] = sum_i omega(i, j), median ms of the
+    normaliser pass, the carry pass, its merge, the enter kernel (with `moments`) and the reducers together)."""
+    lib = load_library()
+    mu, xs_next, cov, rows_a, mask, qpos = _transition_probe_args(mu, xs_next, cov, rows, angle_rows, quat_rows)
+    (n_sel, N), (nN, M) = mu.shape, xs_next.shape
+    logw = np.ascontiguousarray(np.asarray(logw, dtype=np.float64).ravel())
+    tau = np.asarray(tau, dtype=np.float64)
+    tau = np.ascontiguousarray(tau.reshape(1, -1) if tau.ndim == 1 else tau)
+    K = tau.shape[0]
+    if logw.size != N or tau.shape != (K, N):
+        raise ValueError("logw must be [N] and tau [K x N]")
+    D, tn, reach = np.empty(M), np.empty((K, M)), np.empty(M)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_generic_fixed_lag_step(N, M, K, int(moments), nN, n_sel, _ip(rows_a), mask, qpos, _dp(mu), _dp(logw), _dp(xs_next),
+                                              _dp(tau), _dp(cov), _dp(D), _dp(tn), _dp(reach), int(reps), C.byref(ms)))
+    return D, tn, reach, ms.value
+
+
+def device_map_fixed_lag_workspace_bytes(n_nonlin, n_sel, N_P, N_T, lag, moments=1, quat_pos=-1):
+    """rbpf_loc_generic_fixed_lag_workspace_bytes (no device access): what the carry of the fixed-lag smoother holds while it lives;
+    n_sel = len(rows), quat_pos the position of a quaternion block in rows or -1."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_generic_fixed_lag_workspace_bytes(int(n_nonlin), int(n_sel), int(quat_pos), int(N_P), int(N_T), int(lag), int(moments),
+                                                         C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def fixed_lag_assemble(pages, means, lag, moments):
+    """The estimates of LocalizationSession.fixed_lag_estimates from what the library keeps, in plain numpy: pages
+    [((lag + 1) H + 1) x Td] (column t: est(l, t) for l = 0 .. lag, H values each, then mass(t)) and means [n x Td] (c_s, the filter
+    mean of step s), H = n (moments = 1) or n (n + 3) / 2 (moments = 2: d, then the lower triangle by rows of d d') ->
+    dict(mean [n x Td], lag_of [Td], by_lag [n x (lag + 1) x Td], mass [Td][, cov [n x n x Td]]).  mean = c + E[d],
+    cov = E[d d'] - E[d] E[d]'; column s takes lag_of[s] = min(lag, Td - 1 - s) from page s + lag_of[s]; NaN where t - l < 0."""
+    means = np.asarray(means, dtype=np.float64)
+    pages = np.asarray(pages, dtype=np.float64)
+    n, Td = means.shape
+    lag, moments = int(lag), int(moments)
+    H = n if moments == 1 else n * (n + 3) // 2
+    if moments not in (1, 2) or lag < 1 or pages.shape != ((lag + 1) * H + 1, Td):
+        raise ValueError(f"pages must be [((lag + 1) H + 1) x Td] = {((lag + 1) * H + 1, Td)} with lag >= 1 and moments 1 or 2")
+    est = pages[:-1].reshape(lag + 1, H, Td)
+    by_lag = np.full((n, lag + 1, Td), np.nan)
+    for l in range(min(lag, Td - 1) + 1):
+        by_lag[:, l, l:] = means[:, :Td - l] + est[l, :n, l:]
+    s = np.arange(Td)
+    lag_of = np.minimum(lag, Td - 1 - s).astype(np.int64)
+    out = dict(mean=np.asfortranarray(by_lag[:, lag_of, s + lag_of]), lag_of=lag_of, by_lag=np.asfortranarray(by_lag), mass=pages[-1].copy())
+    if moments == 2:
+        e = est[lag_of, :, s + lag_of].T                                  # [H x Td]: the page column s takes
+        cov = np.empty((n, n, Td), order="F")
+        k = n
+        for p_ in range(n):
+            for q in range(p_ + 1):
+                cov[p_, q] = cov[q, p_] = e[k] - e[p_] * e[q]
+                k += 1
+        out["cov"] = cov
+    return out
+
+
 class DeviceMap:
     """A fixed map of an arbitrary model whose handles are device code: the posterior N(mean, V'V) over the nLin linear states, V
     lower (the DenseMagMap convention), as a SLAM filter or smoother run with the same DeviceHandles returns it (xl_max, P_max /
@@ -2987,6 +3050,88 @@ class LocalizationSession:
         finally:
             self._keep_mu = None
 
+    def fixed_lag_estimates(self, lag, want=("mean",)):
+        """rbpf_loc_fixed_lag_update: the state with a fixed delay, E[x_s | y_{0:s+lag}] and its covariance, available WHILE the run
+        goes on at one all-pairs pass per new time step whatever the lag -- the forward-only form of FFBSm (the estimator of
+        smoothed_marginals) for the moments of the last `lag` states.  Needs keep_history and trace and at least 2 steps done, NOT
+        every step.  Returns a dict of what `want` names, with Td = tell() and n the state rows (plain weighted moments of all of
+        them: quaternion and angle rows get no special handling):
+          mean [n x Td]              column s: E[x_s | y_{0:min(s+lag, Td-1)}]
+          cov [n x n x Td]           its covariance; naming it at the first call makes the carry hold second moments (moments = 2)
+          lag_of [Td]                the lag actually applied: `lag` except in the last `lag` columns
+          by_lag [n x (lag+1) x Td]  E[x_{t-l} | y_{0:t}] at [:, l, t], NaN where t - l < 0
+          mass [Td]                  1 in exact arithmetic, mass[0] = 1
+        Columns with lag_of == lag are final and bit-identical in every later call; the others are provisional.  The carry is kept
+        in the session: a call folds in only the steps stored since the last one, and holds its device memory until
+        reset_fixed_lag() or close().  Another lag, or cov after a first call without it, is refused: reset_fixed_lag() first.  In a
+        DeviceMap the `mean` handle is called once per newly folded step, ascending; without a DeviceTransition the call is
+        refused."""
+        if self.driver is not None and self.map.transition is None:
+            raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, _NO_BACKWARD_IN_DEVICE_MAP)
+        names = ("mean", "cov", "lag_of", "by_lag", "mass")
+        unknown = set(want) - set(names)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        lag = int(lag)
+        held = getattr(self, "_fixed_lag", None)
+        moments = 2 if "cov" in want or (held is not None and held == (lag, 2)) else 1
+        n, Td = self.nN, self.tell()
+        H = n if moments == 1 else n * (n + 3) // 2
+        pages, means = np.empty(((max(lag, 0) + 1) * H + 1, Td), order="F"), np.empty((n, Td), order="F")
+        if self.driver is not None:
+            self._fixed_lag_pass_in_device_map(lag, moments, (_dp(pages), _dp(means)))
+        else:
+            check(self.lib.rbpf_loc_fixed_lag_update(self.ctx, lag, moments, _dp(pages), _dp(means)))
+        self._fixed_lag = (lag, moments)
+        out = fixed_lag_assemble(pages, means, lag, moments)
+        return {k: out[k] for k in names if k in want}
+
+    def reset_fixed_lag(self):
+        """rbpf_loc_fixed_lag_reset: hands the carry of fixed_lag_estimates back; the next call starts again at the first step and
+        may name another lag."""
+        if self.driver is not None:
+            check(self.lib.rbpf_loc_generic_fixed_lag_reset(self.ctx))
+        else:
+            check(self.lib.rbpf_loc_fixed_lag_reset(self.ctx))
+        self._fixed_lag = None
+
+    def _fixed_lag_pass_in_device_map(self, lag, moments, outs):
+        """_forward_pass_in_device_map for rbpf_loc_generic_fixed_lag_*: the steps ascend from the last one folded in to tell() - 2,
+        every one with the `mean` handle's mu and cov(dt, Q).  A failed handle closes the stepping and leaves the carry where the
+        last complete step put it."""
+        lib, drv, tr, prob = self.lib, self.driver, self.map.transition, self.prob
+        torch, N, nN = drv.torch, prob.N_P, self.nN
+        rows_a, mask, qpos, n_sel, covs, page = self._transition_pages()
+        check(lib.rbpf_loc_generic_fixed_lag_begin(self.ctx, n_sel, _ip(rows_a), mask, qpos, lag, moments))
+        try:
+            with torch.cuda.stream(drv.stream):
+                while True:
+                    t, xn = C.c_int32(0), C.c_void_p()
+                    st = lib.rbpf_loc_generic_fixed_lag_particles_device(self.ctx, C.byref(t), C.byref(xn))
+                    if st == _ffi.RBPF_ERR_STATE:                 # (the stepping is open: every stored step is folded in)
+                        break
+                    check(st)
+                    t = t.value
+                    X = drv._view(torch, xn, (nN, N), drv.device)
+                    Q = drv.Q[page(drv.Q.shape[0], t)]
+                    dt = float(drv.dt[page(drv.dt.size, t)])
+                    mu = tr.mean(X, drv.odo[t], dt, Q)
+                    if not torch.is_tensor(mu) or tuple(mu.shape) != (n_sel, N) or mu.dtype != torch.float64 or not mu.is_cuda:
+                        what = f"{tuple(mu.shape)} {mu.dtype} on {mu.device}" if torch.is_tensor(mu) else type(mu).__name__
+                        raise ValueError(f"mean returned {what}, expected a float64 device tensor of shape {(n_sel, N)}")
+                    mu = mu.contiguous()
+                    self._keep_mu = mu                            # read in stream order by the step just enqueued
+                    check(lib.rbpf_loc_generic_fixed_lag_step_device(self.ctx, C.c_void_p(mu.data_ptr()),
+                                                                     _dp(covs[(page(prob._dt.size, t), page(prob._Q.shape[2], t))])))
+        except BaseException:
+            lib.rbpf_loc_generic_fixed_lag_finish(self.ctx, None, None)
+            self._keep_mu = None
+            raise
+        try:
+            check(lib.rbpf_loc_generic_fixed_lag_finish(self.ctx, *outs))
+        finally:
+            self._keep_mu = None
+
     def close(self):
         if self.ctx:
             self.lib.rbpf_destroy(self.ctx)
@@ -3269,6 +3414,67 @@ def running_noise_estimate(S_run, m_run=None):
     if m.shape[1] != P:
         raise ValueError("m_run must be [n x P]")
     return S / k1[None, None, :], m / k1[None, :]
+
+
+def loc_fixed_lag_workspace_bytes(N_P, N_T, lag, moments=1):
+    """rbpf_loc_fixed_lag_workspace_bytes (no device access): what the carry of the fixed-lag smoother holds while it lives."""
+    lib = load_library()
+    nbytes = C.c_size_t(0)
+    check(lib.rbpf_loc_fixed_lag_workspace_bytes(int(N_P), int(N_T), int(lag), int(moments), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def loc_fixed_lag_step(xn, logw, xs_next, tau, odo, dt, Q, moments=1, reps=1):
+    """rbpf_loc_fixed_lag_step, the kernel-level probe: one pass of the fixed-lag smoother in the dense-mag map on the caller's
+    arrays.  xn [7 x N], logw [N], xs_next [7 x M], odo [7], dt, Q as loc_marginal_step; tau [K x N], any K >= 1, the incoming
+    columns of the carry -> (D [M], tau_next [K x M], reach [M] = sum_i omega(i, j), median ms of the normaliser pass, the carry
+    pass, its merge, the enter kernel (with `moments`) and the reducers together)."""
+    lib = load_library()
+    xn = np.asfortranarray(np.asarray(xn, dtype=np.float64).reshape(7, -1))
+    xs_next = np.asfortranarray(np.asarray(xs_next, dtype=np.float64).reshape(7, -1))
+    N, M = xn.shape[1], xs_next.shape[1]
+    logw = np.ascontiguousarray(np.asarray(logw, dtype=np.float64).ravel())
+    odo = np.ascontiguousarray(np.asarray(odo, dtype=np.float64).ravel())
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(6, 6))
+    tau = np.asarray(tau, dtype=np.float64)
+    tau = np.ascontiguousarray(tau.reshape(1, -1) if tau.ndim == 1 else tau)
+    K = tau.shape[0]
+    if logw.size != N or odo.size != 7 or tau.shape != (K, N):
+        raise ValueError("logw must be [N], odo [7] and tau [K x N]")
+    D, tn, reach = np.empty(M), np.empty((K, M)), np.empty(M)
+    ms = C.c_double(0.0)
+    check(lib.rbpf_loc_fixed_lag_step(N, M, K, int(moments), _dp(xn), _dp(logw), _dp(xs_next), _dp(tau), _dp(odo), float(dt), _dp(Q), _dp(D),
+                                      _dp(tn), _dp(reach), int(reps), C.byref(ms)))
+    return D, tn, reach, ms.value
+
+
+def particleFixedLagSmootherLocalization(dynModel, measModel, odometry, y, x0_nonLin, Q, R, N_P, dt, lag, *, rng=None, every=1, extras=False):
+    """The fixed-lag smoother of localisation in a fixed map: the filter of particleFilterLocalization, and
+    LocalizationSession.fixed_lag_estimates folded in every `every` steps while it runs -> (mean [n x N_T], cov [n x n x N_T],
+    lag_of [N_T][, extras]); column s is E[x_s | y_{0:min(s+lag, N_T-1)}] and its covariance.  The estimates do not depend on
+    `every`.  dynModel / measModel, R and rng as particleRunningStatisticsLocalization takes them.  extras: the filter's outputs and
+    `by_lag`, `mass`."""
+    import warnings
+    mp = _device_map(dynModel, measModel)
+    if mp is not None and mp.transition is None:
+        raise RBPFError(_ffi.RBPF_ERR_UNSUPPORTED, "particleFixedLagSmootherLocalization: " + _NO_BACKWARD_IN_DEVICE_MAP)
+    if mp is None:
+        mp = _recognise_map(dynModel, measModel)
+    every = max(int(every), 1)
+    with LocalizationSession(mp, odometry, y, x0_nonLin, Q, N_P, dt, rng=rng, keep_history=True, trace=True) as s:
+        T = s.prob.N_T
+        while s.tell() < T:
+            s.advance(min(every, T - s.tell()))
+            if 2 <= s.tell() < T:
+                s.fixed_lag_estimates(lag, want=("cov",))
+        fwd = s.finish(extras=extras)
+        if fwd["first_degenerate_step"] >= 0:
+            warnings.warn(f"Weights filter close to zero at t={fwd['first_degenerate_step'] + 1} !!!", RuntimeWarning, stacklevel=2)
+        out = s.fixed_lag_estimates(lag, want=("mean", "cov", "lag_of") + (("by_lag", "mass") if extras else ()))
+    if extras:
+        fwd.update(by_lag=out["by_lag"], mass=out["mass"])
+        return out["mean"], out["cov"], out["lag_of"], fwd
+    return out["mean"], out["cov"], out["lag_of"]
 
 
 def loc_backward_workspace_bytes(N_P, N_T, n_traj):
